@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- sliding windows/s through the MI355X HIP path of MTAD_GAT.forward.
 
-    python bench.py --gpus N --steps K --warmup W [--mode infer|train]
+    python bench.py --gpus N --steps K --warmup W [--mode infer|train] [--dump-outputs DIR] [--full]
 
 A "step" is one full `MTAD_GAT.forward` (conv -> feature-GAT || temporal-GAT -> GRU ->
 forecasting + reconstruction heads; reference mtad_gat.py:64-79) over one batch of
@@ -21,6 +21,7 @@ Also in the line:
                    terms and padding); both families always under `roofline_valu` / `roofline_mfma`;
                    plus `hbm` with the algorithmic-bytes rate vs 8 TB/s that BASELINE.json
                    asks for (this path is compute-bound by ~100x).
+With --full only (measurements that take runs of their own; a plain run stops after the line above):
   cpu_baseline  -- the unmodified reference module (imported from $MTADGAT_REFERENCE or /root/reference,
                    kind "reference") when that tree exists on this host, else the oracle port of it
                    (oracle/, kind "port"), timed on this host's cores on a bounded sample, N=1 / rank 0 only.
@@ -35,6 +36,10 @@ forward + global-batch RMSE losses through one small statistics all-reduce + bac
 -- two collectives per step, no host read before the backward is enqueued;
 reference training.py:106-127) at the MSL shape, `--batch` windows per GPU (default 8192); the two collectives are timed
 separately with HIP events on the stream they run on.  Works at N = 1 (the collectives are skipped).
+
+--dump-outputs DIR writes, after the timed steps, what the timed path handed its caller in the last step (rank 0's shard) as
+DIR/<name>.npy: `preds` and `recons` of MTAD_GAT.forward (infer), or `loss_rmse` and the flat `params` after the optimizer
+step (train).  The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -187,6 +192,26 @@ def cpu_baseline(sd, kw, budget_s=10.0):
             "sample": f"{iters} x {b}-window batches (W={kw['window_size']},F={kw['n_features']}) in {el:.1f} s; {what}; "
                       f"threads picked by a 1-iteration sweep {{{', '.join(f'{k}: {v:.0f} w/s' for k, v in sweep.items())}}} "
                       f"on a host with {ncores} logical cores"}
+
+
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(d, arrays, rows):
+    """Write each array as d/<name>.npy (float64 stays float64, everything else float32).  When the arrays would take more
+    than DUMP_BYTES_MAX in all, those with one entry per window (leading dimension `rows`) are cut to a fixed, seeded
+    sample of windows (numpy default_rng(0), ascending window order)."""
+    arrays = {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in arrays.items()}
+    arrays = {k: v.astype(np.float64 if v.dtype == np.float64 else np.float32, copy=False) for k, v in arrays.items()}
+    per_row = sum(v.nbytes for v in arrays.values() if v.ndim and v.shape[0] == rows)
+    fixed = sum(v.nbytes for v in arrays.values()) - per_row
+    if per_row and fixed + per_row > DUMP_BYTES_MAX:
+        keep = max(1, (DUMP_BYTES_MAX - fixed) * rows // per_row)
+        sel = np.sort(np.random.default_rng(0).choice(rows, size=keep, replace=False))
+        arrays = {k: (v[sel] if v.ndim and v.shape[0] == rows else v) for k, v in arrays.items()}
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(v))
 
 
 def _timed(fn, dev, iters, warm=3):
@@ -441,6 +466,9 @@ def train_mode(args, model, kw, dev, world, rank):
     elapsed = max_over_ranks(time.perf_counter() - t0, dev)
     per_rank = per_rank_rates(mine, B * args.steps, dev)
     ar = {k: sum(a.elapsed_time(b) for a, b in v) / max(len(v), 1) for k, v in timings.items()}
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss_rmse": np.array([float(v) for v in rm], dtype=np.float64),
+                                         "params": torch.cat([p.detach().reshape(-1) for p in model.parameters()])}, B)
     if rank == 0:
         n_par = sum(p.numel() for p in model.parameters())
         res = {
@@ -507,13 +535,20 @@ def main():
                     help="process-group backend.  nccl (= RCCL) is the default and the only one whose numbers count; gloo is a TEST-ONLY escape "
                          "hatch that lets N ranks share the GPUs that exist (rank r on cuda:(r mod devices), collectives staged through host "
                          "memory) so that the N-rank code path can be exercised on a one-GPU box -- the line then says backend: gloo")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the sub-records (other batch sizes, precisions and configurations, each with "
+                         "runs of its own) and the CPU baseline; off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-profile", action="store_true")
-    ap.add_argument("--no-sub", action="store_true", help="skip the batch256 / train_step / bf16 sub-records")
+    ap.add_argument("--no-sub", action="store_true", help="with --full: skip the batch256 / train_step / bf16 sub-records")
     ap.add_argument("--precision", choices=["fp32", "fp32_strict", "bf16"], default="fp32",
                     help="arithmetic of the timed region: fp32 (the headline, <= 1e-5 parity: fp32 accumulation, products of the "
                          "large-batch kernels from split-bf16 operands), fp32_strict (fp32 MFMA only) or bf16 MFMA operands (<= 2e-2)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.batch <= 0:
         args.batch = 65536 if args.mode == "infer" else 8192
 
@@ -595,6 +630,8 @@ def main():
     elapsed = max_over_ranks(elapsed, dev)      # the slowest rank's time is the job's time
     per_rank = per_rank_rates(mine, B * args.steps, dev)
     assert torch.isfinite(preds).all() and torch.isfinite(recons).all()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"preds": preds, "recons": recons}, B)
 
     if rank == 0:
         total_windows = world * B * args.steps
@@ -714,12 +751,12 @@ def main():
         res["hbm"] = {"alg_bytes_per_window": alg_bytes, "achieved": round(gbs, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                       "frac": round(gbs / HBM_PEAK_GBS / world, 5),
                       "note": "whole-forward algorithmic bytes rate per GPU vs HBM peak; the path is compute-bound"}
-        if world == 1 and not args.no_sub:
+        if world == 1 and args.full and not args.no_sub:
             try:
                 res["sub"] = sub_records(model, kw, dev, args.precision)
             except Exception as e:
                 res["sub"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 res["cpu_baseline"] = cpu_baseline(sd, kw)
             except Exception as e:  # never lose the GPU number to a baseline problem

@@ -8,7 +8,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-python "$ROOT/bench.py" > "$OUT/bench_line.json" 2> "$OUT/bench_stderr.log"
+python "$ROOT/bench.py" --full > "$OUT/bench_line.json" 2> "$OUT/bench_stderr.log"
 # 1. kernel trace of the flagship forward (fp32), of the same workload with bf16 operands, and of the training step
 rm -rf /tmp/kt && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -- python "$ROOT/bench.py" --steps 5 --warmup 2 --no-cpu-baseline --no-sub > "$OUT/kt_bench_line.json" 2> /dev/null
 cp "$(find /tmp/kt -name '*kernel_stats.csv' | head -1)" "$OUT/kernel_stats.csv"

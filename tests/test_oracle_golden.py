@@ -1,5 +1,9 @@
 """The oracle (oracle/mtad_gat_oracle.py) pinned against outputs of the reference itself
 (tests/golden/*.npz, produced by tests/golden/make_golden.py from /root/reference)."""
+import os
+import subprocess
+import sys
+
 import pytest
 import torch
 
@@ -7,14 +11,44 @@ from helpers import ALL_CASES, Case
 from oracle import mtad_gat_oracle as oracle
 
 SMALL = [c for c in ALL_CASES if c != "syn_c4"]
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+_STAGES = r"""
+import sys
+sys.dont_write_bytecode = True
+sys.path[:0] = sys.argv[2:]
+import torch
+from helpers import ALL_CASES, Case
+from oracle import mtad_gat_oracle as oracle
+res = {}
+with torch.no_grad():
+    for name in ALL_CASES:
+        c = Case(name)
+        p, r, st = oracle.forward(c.x, c.state_dict(), alpha=c.kwargs["alpha"], return_stages=True)
+        res[name] = (p, r, {k: st[k] for k in ("xc", "h_feat", "h_temp", "h_end")})
+torch.save(res, sys.argv[1])
+"""
+
+
+@pytest.fixture(scope="module")
+def oracle_fp32(tmp_path_factory):
+    """The oracle's float32 forward of every golden case, in a child process with MKL_CBWR=COMPATIBLE.  smd_1_1's temporal
+    attention stage is ill-conditioned (its float32 and float64 values differ by 2e-3), so agreeing with the reference's
+    float32 stages at 2e-6 needs GEMMs that round as they did where the goldens were made.  MKL's default code paths differ
+    between CPU vendors (3.9e-6 on an AMD EPYC host); its COMPATIBLE path rounds the same on Intel and AMD.  The mode has to
+    be set before MKL starts, hence the child process."""
+    out = tmp_path_factory.mktemp("oracle_fp32") / "stages.pt"
+    root = os.path.dirname(HERE)
+    r = subprocess.run([sys.executable, "-B", "-c", _STAGES, str(out), HERE, os.path.join(root, "mtad-gat-pytorch_amd"), root],
+                       env=dict(os.environ, MKL_CBWR="COMPATIBLE"), capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return torch.load(out)
 
 
 @pytest.mark.parametrize("name", ALL_CASES)
-def test_oracle_forward_matches_reference(name):
+def test_oracle_forward_matches_reference(name, oracle_fp32):
     case = Case(name)
-    sd = case.state_dict()
-    with torch.no_grad():
-        p, r, st = oracle.forward(case.x, sd, alpha=case.kwargs["alpha"], return_stages=True)
+    p, r, st = oracle_fp32[name]
     # same ATen kernels, same op order as the reference: agreement at float32 rounding level
     assert (p - case.preds).abs().max().item() <= 2e-6
     assert (r - case.recons).abs().max().item() <= 2e-6
