@@ -1,16 +1,23 @@
-// k_attend: un-fused graph attention for node counts beyond the fused kernel (K > 128) + launcher
+// k_attend: graph attention of the layers beyond k_gat_wide (more than 512 nodes or node dimensions) + launcher
 #include "mtadgat_device.h"
 
 namespace mtadgat {
+
+namespace {
 
 #ifndef MTADGAT_ATTEND_DEPTH
 #define MTADGAT_ATTEND_DEPTH 2
 #endif
 
 // ---------------------------------------------------------------------------
-// attend: complete-graph attention scores + softmax + aggregation + sigmoid for
-// a block of query nodes of one window.  reference FeatureAttentionLayer.forward
-// (modules.py:65-95) / TemporalAttentionLayer.forward (modules.py:166-193).
+// attend: complete-graph attention of one layer through an (B, K, K) score matrix in memory,
+// reference FeatureAttentionLayer.forward (modules.py:65-95) / TemporalAttentionLayer.forward
+// (modules.py:166-193), in three launches:
+//   k_attend          scores e_ij (+ bias) of a block of IB query rows x 64 JPL keys of one window -> S
+//   k_attend_softmax  S <- softmax over j, in place, a wave per row (K <= 2048)
+//   k_bgemm           h = sigmoid(S V) on the fp32 matrix pipe (mtadgat_bwdw.hip, sigmoid epilogue)
+// Serves the feature layer of F > 512 (K = F up to 2048 keys, D = W) and the temporal layer of
+// F > 512 (K = W, D = F, E = 2F up to 4096 embedding columns); k_gat_wide keeps every layer up to 512.
 //
 // GATv2 score, re-associated:
 //   e_ij = c_i + d_j + sum_{k in P} |L'_ik + R'_jk| - sum_{k in N} |L'_ik + R'_jk| + bias_ij
@@ -18,10 +25,7 @@ namespace mtadgat {
 // [0,PT) = L', [PT,2PT) = R', 2PT = c, 2PT+1 = d of each node's row in LR).
 // GAT (v1): e_ij = LeakyReLU(c_i + d_j) + bias_ij (PT = 0).
 //
-// lane <-> key node j (JPL nodes per lane), the query node i is wave-uniform so
-// L'_i comes in through scalar loads and the inner loop is 2 VALU ops/element.
-// The softmax'd rows are staged through LDS into MFMA B-operand order and the
-// aggregation att @ V runs on the matrix pipe.
+// lane <-> key node j (JPL nodes per lane), the inner loop is 2 VALU ops/element.
 // ---------------------------------------------------------------------------
 // one 8-wide k tile of the pairwise term for all IB query rows.
 //   r[jj][e]  : R'[k0+e][j]  for this lane's key nodes j (one VGPR each)
@@ -53,29 +57,18 @@ __device__ __forceinline__ void attend_tile(float (&acc)[IB][JPL], const float (
 }
 
 template <int JPL, int IB>
-__global__ __launch_bounds__(64, (JPL <= 2 ? 3 : 2)) void k_attend(const AttendArgs a) {
-    __shared__ __attribute__((aligned(16))) float att_s[32][68];
+__global__ __launch_bounds__(64, 3) void k_attend(const AttendArgs a) {
     static_assert(IB % 2 == 0 && IB <= 32, "IB");
     constexpr int NL = IB / 2;
     const int lane = threadIdx.x;
-    // XCD-aware block -> (window, row block) map: dispatch ids b, b+8, b+16, ... run on the same
-    // XCD (b % 8), so giving them the row blocks of ONE window lets that window's R'^T / V tiles be
-    // fetched from HBM once and served to the other row blocks from that XCD's L2.
+    // block -> (window, key block, row block), row blocks fastest: the row blocks of one key block share its R'^T columns in L2
     const long blk = blockIdx.x;
-    long win;
-    int rb;
-    if (a.xcd_map) {
-        const long grp = blk / (8 * a.nblk);
-        const int within = (int)(blk - grp * (8 * a.nblk));
-        win = grp * 8 + (within & 7);
-        rb = within >> 3;
-    } else {
-        win = blk / a.nblk;
-        rb = (int)(blk - win * a.nblk);
-    }
-    if (win >= a.nwin) return;
-    const int i0 = rb * a.rows_per_blk;
-    const int nrows = min(a.rows_per_blk, a.K - i0);
+    const int nrb = (a.K + IB - 1) / IB, nkb = (a.K + 64 * JPL - 1) / (64 * JPL);
+    const long win = blk / ((long)nrb * nkb);
+    const int rem = (int)(blk - win * nrb * nkb);
+    const int kb = rem / nrb, rb = rem - kb * nrb;
+    const int i0 = rb * IB, j0 = kb * 64 * JPL;
+    const int nrows = min(IB, a.K - i0);
     const int K = a.K, ldl = a.ldl, PT = a.ord ? a.ord[1] : a.PT, Kp = a.Kp;
     const float* __restrict__ Lrow0 = a.LC + (win * K + i0) * (long)ldl;
     const float* __restrict__ RTw = a.RT + win * (long)a.rt_rows * Kp;
@@ -86,12 +79,13 @@ __global__ __launch_bounds__(64, (JPL <= 2 ? 3 : 2)) void k_attend(const AttendA
 #pragma unroll
         for (int jj = 0; jj < JPL; ++jj) acc[ib][jj] = 0.f;
 
+    int jc[JPL];                  // this lane's key nodes, clamped (results past K are dropped below)
     const float* Rp[JPL];
 #pragma unroll
     for (int jj = 0; jj < JPL; ++jj) {
-        int j = jj * 64 + lane;
-        j = j < K ? j : K - 1;
-        Rp[jj] = RTw + j;
+        const int j = j0 + jj * 64 + lane;
+        jc[jj] = j < K ? j : K - 1;
+        Rp[jj] = RTw + jc[jj];
     }
     // rows past the end of the block are clamped duplicates; their results are dropped below
     int loff[NL];
@@ -104,9 +98,8 @@ __global__ __launch_bounds__(64, (JPL <= 2 ? 3 : 2)) void k_attend(const AttendA
         }
     }
     if (PT > 0) {
-        // 3-deep register ring over the k tiles: tile t+2 is requested before tile t is consumed, so two
-        // tiles of VALU work (~2.5k cycles) plus the other resident waves cover the HBM/L2 latency
-        constexpr int DEPTH = JPL <= 2 ? MTADGAT_ATTEND_DEPTH : 2;   // JPL >= 4: the tiles themselves fill the register file
+        // register ring over the k tiles: tile t+DEPTH-1 is requested before tile t is consumed
+        constexpr int DEPTH = MTADGAT_ATTEND_DEPTH;
         float rr[DEPTH][JPL][8], lr[DEPTH][NL];
         const int ntile = PT >> 3;
         auto fetch = [&](int st, int tile) {
@@ -136,173 +129,77 @@ __global__ __launch_bounds__(64, (JPL <= 2 ? 3 : 2)) void k_attend(const AttendA
         }
     }
 
-    // scores -> softmax over j (reference modules.py:85-89 / :184-188); branch-free over rows
+    // e_ij = c_i + d_j + pair term (GATv2) / LeakyReLU(c_i + d_j) (GAT v1), + bias_ij
     float dj[JPL];
 #pragma unroll
     for (int jj = 0; jj < JPL; ++jj) dj[jj] = Rp[jj][(long)PT * Kp];
     const float cvec = Lrow0[(long)(lane < nrows ? lane : nrows - 1) * ldl + PT];   // lane ib holds c_ib
-    float bv[IB][JPL];
-#pragma unroll
-    for (int ib = 0; ib < IB; ++ib) {
-        const int irow = i0 + (ib < nrows ? ib : nrows - 1);
-#pragma unroll
-        for (int jj = 0; jj < JPL; ++jj) {
-            int j = jj * 64 + lane;
-            j = j < K ? j : K - 1;
-            bv[ib][jj] = a.bias ? a.bias[(long)irow * K + j] : 0.f;
-        }
-    }
+    float* __restrict__ Sw = a.S + (win * K + i0) * (long)K;
 #pragma unroll
     for (int ib = 0; ib < IB; ++ib) {
         const float ci = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, cvec), ib));
-        float e[JPL];
-        float m = -INFINITY;
+        const int irow = i0 + (ib < nrows ? ib : nrows - 1);
 #pragma unroll
         for (int jj = 0; jj < JPL; ++jj) {
-            const int j = jj * 64 + lane;
             float v = acc[ib][jj] + ci + dj[jj];
             if (a.v1) v = fmaxf(v, 0.f) + a.alpha * fminf(v, 0.f);
-            v += bv[ib][jj];
-            v = j < K ? v : -INFINITY;
-            e[jj] = v;
-            m = fmaxf(m, v);
-        }
-        m = wave_max(m);
-        float sum = 0.f;
-#pragma unroll
-        for (int jj = 0; jj < JPL; ++jj) {
-            e[jj] = (jj * 64 + lane < K) ? soft_exp(e[jj] - m) : 0.f;
-            sum += e[jj];
-        }
-        sum = wave_sum(sum);
-        const float inv = soft_rcp(sum);
-#pragma unroll
-        for (int jj = 0; jj < JPL; ++jj) acc[ib][jj] = ib < nrows ? e[jj] * inv : 0.f;
-    }
-    if (a.ATT) {  // optional dump of the attention matrix (tests)
-#pragma unroll
-        for (int ib = 0; ib < IB; ++ib)
-            if (ib < nrows)
-#pragma unroll
-                for (int jj = 0; jj < JPL; ++jj) {
-                    const int j = jj * 64 + lane;
-                    if (j < K) a.ATT[(win * K + i0 + ib) * (long)K + j] = acc[ib][jj];
-                }
-    }
-
-    // aggregation h_i = sigmoid(sum_j att_ij * V_j) on the matrix pipe (modules.py:93 / :191)
-    const int i = lane & 31, g = lane >> 5;
-    if (IB < 32) {
-        for (int r = IB + g; r < 32; r += 2)
-            for (int c = i; c < 68; c += 32) att_s[r][c] = 0.f;
-    }
-    const int DT = (a.D + 31) >> 5;
-    const float* __restrict__ Vw = a.V + win * (long)K * a.ldv;
-    for (int dt0 = 0; dt0 < DT; dt0 += 2) {
-        f32x16 o[2];
-#pragma unroll
-        for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[nb][r] = 0.f;
-        int dcl[2];
-        bool dok[2];
-#pragma unroll
-        for (int nb = 0; nb < 2; ++nb) {
-            const int d = 32 * (dt0 + nb) + i;
-            dok[nb] = d < a.D;
-            dcl[nb] = dok[nb] ? d : a.D - 1;
-        }
-#pragma unroll
-        for (int jj = 0; jj < JPL; ++jj) {
-            if (jj * 64 < K) {
-                __syncthreads();
-#pragma unroll
-                for (int ib = 0; ib < IB; ++ib) att_s[ib][lane] = acc[ib][jj];
-                __syncthreads();
-                // rolled loop over the chunks of this 64-node block, operands of chunk q+1 fetched before
-                // chunk q's MFMAs (att is 0 past K; V loads are clamped + masked, no divergent control flow)
-                const int jn = min(64, K - jj * 64);
-                const int nq = (jn + 7) >> 3;
-                auto fetch = [&](int q, f32x4& bq, f32x4 (&av)[2]) {
-                    bq = *reinterpret_cast<const f32x4*>(&att_s[i][8 * q + 4 * g]);
-                    const int jb = jj * 64 + 8 * q + 4 * g;
-#pragma unroll
-                    for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                        for (int s = 0; s < 4; ++s) {
-                            const int jc = jb + s < K ? jb + s : K - 1;
-                            const float v = Vw[(long)jc * a.ldv + dcl[nb]];
-                            av[nb][s] = (jb + s < K && dok[nb]) ? v : 0.f;
-                        }
-                };
-                f32x4 bq, av[2];
-                fetch(0, bq, av);
-#pragma unroll 1
-                for (int q = 0; q < nq; ++q) {
-                    f32x4 bn, an[2];
-                    fetch(q + 1 < nq ? q + 1 : q, bn, an);
-                    o[0] = mfma4(av[0], bq, o[0]);
-                    o[1] = mfma4(av[1], bq, o[1]);
-                    bq = bn; av[0] = an[0]; av[1] = an[1];
-                }
-            }
-        }
-#pragma unroll
-        for (int nb = 0; nb < 2; ++nb) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int d = 32 * (dt0 + nb) + (r & 3) + 8 * (r >> 2) + 4 * g;
-                if (i < nrows && d < a.D)
-                    a.out[win * a.so_w + (long)(i0 + i) * a.so_i + (long)d * a.so_d] = gate_sigmoid(o[nb][r]);
-            }
+            if (a.bias) v += a.bias[(long)irow * K + jc[jj]];
+            const int j = j0 + jj * 64 + lane;
+            if (ib < nrows && j < K) Sw[(long)ib * K + j] = v;
         }
     }
 }
 
-// Split the K query nodes of a window into nblk blocks of <= rows_per_blk rows, one wave each,
-// and pick the kernel's unrolled row count IB >= rows_per_blk that wastes the fewest rows.
-void attend_plan(int K, int* rows_per_blk, int* nblk, int* IB) {
-    const int jpl = (K + 63) / 64;
-    const int ibmax = jpl <= 1 ? 32 : (jpl <= 2 ? 20 : (jpl <= 4 ? 16 : 8));   // register budget (no spills)
-    const int step = jpl <= 2 ? 4 : 8;
-    const int nb0 = (K + ibmax - 1) / ibmax;
-    long best = -1;
-    for (int nb = nb0; nb <= nb0 + 3; ++nb) {
-        const int rows = (K + nb - 1) / nb;
-        int ib = ((rows + step - 1) / step) * step;
-        if (ib < 8) ib = 8;
-        const long cost = (long)ib * nb;
-        if (best < 0 || cost < best) {
-            best = cost;
-            *rows_per_blk = rows;
-            *nblk = (K + rows - 1) / rows;
-            *IB = ib;
-        }
+// softmax over the keys of each score row (reference modules.py:85-89 / :184-188), in place; one wave per row,
+// the row in registers (32 per lane: K <= 2048)
+__global__ __launch_bounds__(256) void k_attend_softmax(float* __restrict__ S, long rows, int K) {
+    constexpr int NJ = 32;
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    float* __restrict__ p = S + row * K;
+    float e[NJ];
+    float m = -INFINITY;
+#pragma unroll
+    for (int q = 0; q < NJ; ++q) {
+        const int j = q * 64 + lane;
+        e[q] = j < K ? p[j] : -INFINITY;
+        m = fmaxf(m, e[q]);
+    }
+    m = wave_max(m);
+    float sum = 0.f;
+#pragma unroll
+    for (int q = 0; q < NJ; ++q) {
+        e[q] = (q * 64 + lane < K) ? soft_exp(e[q] - m) : 0.f;
+        sum += e[q];
+    }
+    sum = wave_sum(sum);
+    const float inv = soft_rcp(sum);
+#pragma unroll
+    for (int q = 0; q < NJ; ++q) {
+        const int j = q * 64 + lane;
+        if (j < K) p[j] = e[q] * inv;
     }
 }
 
-#define ATTEND_CASE(J, I)                                                             \
-    if (jpl == J && IB == I) {                                                        \
-        hipLaunchKernelGGL((k_attend<J, I>), dim3(grid), dim3(64), 0, s, a);          \
-        launched = true;                                                              \
-    }
+}  // namespace
 
-int launch_attend(const AttendArgs& a, int IB, hipStream_t s) {
-    if (a.total_blocks <= 0) return 0;
-    int jpl = (a.K + 63) / 64;
-    if (jpl == 3) jpl = 4;
-    if (jpl > 4 && jpl <= 8) jpl = 8;
-    const unsigned grid = (unsigned)a.total_blocks;
-    bool launched = false;
-    ATTEND_CASE(1, 8) ATTEND_CASE(1, 12) ATTEND_CASE(1, 16) ATTEND_CASE(1, 20)
-    ATTEND_CASE(1, 24) ATTEND_CASE(1, 28) ATTEND_CASE(1, 32)
-    ATTEND_CASE(2, 8) ATTEND_CASE(2, 12) ATTEND_CASE(2, 16) ATTEND_CASE(2, 20)
-    ATTEND_CASE(2, 24) ATTEND_CASE(2, 28) ATTEND_CASE(2, 32)
-    ATTEND_CASE(4, 8) ATTEND_CASE(4, 16)
-    ATTEND_CASE(8, 8)
-    if (!launched) return -2;
+int launch_attend(const AttendArgs& a, const DropArgs* drop, unsigned drop_stream, hipStream_t s) {
+    if (a.nwin <= 0) return 0;
+    if (a.K < 1 || a.K > MTADGAT_ATTEND_MAX_K) return -2;
+    constexpr int JPL = 2, IB = 16;
+    const long nrb = (a.K + IB - 1) / IB, nkb = (a.K + 64 * JPL - 1) / (64 * JPL);
+    const long grid = a.nwin * nrb * nkb;
+    if (grid > 0x7fffffffL) return -2;
+    hipLaunchKernelGGL((k_attend<JPL, IB>), dim3((unsigned)grid), dim3(64), 0, s, a);
     LAUNCH_CHECK();
-    return 0;
+    const long rows = a.nwin * a.K;
+    if ((rows + 3) / 4 > 0x7fffffffL) return -2;
+    hipLaunchKernelGGL(k_attend_softmax, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, a.S, rows, a.K);
+    LAUNCH_CHECK();
+    // h_i = sigmoid(sum_j att'_ij V_j), att' = dropout(att) (same counter stream as k_gat_wide): C_b(i, d) = out[b so_w + i so_i + d so_d]
+    return launch_bgemm_sigmoid(a.S, (long)a.K * a.K, a.K, 1, a.V, (long)a.K * a.ldv, a.ldv, 1, a.out, a.so_w, a.so_i, a.so_d,
+                                a.K, a.D, a.K, a.nwin, drop, drop_stream, a.K, s);
 }
 
 }  // namespace mtadgat

@@ -47,16 +47,17 @@ __global__ __launch_bounds__(256) void k_bw_ds(const float* __restrict__ H, cons
 // ---- batched GEMM on the fp32 matrix unit: C_b (M x N) = A_b (M x Kc) B_b (Kc x N), arbitrary element strides for A and B
 //   A_b(m, k) = A[b sAb + m sAm + k sAk]   (optionally times the dropout keep factor of attention element (k, m): A = att^T)
 //   B_b(k, n) = B[b sBb + k sBk + n sBn]
-//   C_b(m, n) = C[b sCb + m ldc + n]
+//   C_b(m, n) = C[b sCb + m ldc + n sCn]   (sig: sigmoid of the product, the forward aggregation of k_attend's layers)
 // One workgroup = a 64 x 64 block of C for one b; wave (wm, wn) owns a 32 x 32 quadrant on v_mfma_f32_32x32x2_f32; the
 // operands go through LDS 16 columns of the contraction at a time (clamped unconditional loads, zero where out of range).
 struct BGemmArgs {
     const float* A; long sAb, sAm, sAk;
     const float* B; long sBb, sBk, sBn;
-    float* C; long sCb, ldc;
+    float* C; long sCb, ldc, sCn;
+    int sig;
     int M, N, Kc;
     long nb;
-    int adrop;                 // 1: A_b(m, k) *= keep(k * dropK + m) ? keep_scale : 0
+    int adrop;                 // 1: A_b(m, k) *= keep(k * dropK + m) ? keep_scale : 0;  2: keep(m * dropK + k) (A = att, not transposed)
     int dropK;
     DropArgs drop;
     unsigned drop_stream;
@@ -92,7 +93,10 @@ __global__ __launch_bounds__(256) void k_bgemm(const BGemmArgs a) {
             const int gm = m0 + am, gk = k0 + ak;
             const int cm = gm < a.M ? gm : a.M - 1, ck = gk < a.Kc ? gk : a.Kc - 1;
             float v = Ab[cm * a.sAm + ck * a.sAk];
-            if (a.adrop && a.drop.thresh) v *= drop_keep(key, (unsigned)(ck * a.dropK + cm), a.drop.thresh) ? a.drop.keep_scale : 0.f;
+            if (a.adrop && a.drop.thresh) {
+                const unsigned di = a.adrop == 2 ? (unsigned)(cm * a.dropK + ck) : (unsigned)(ck * a.dropK + cm);
+                v *= drop_keep(key, di, a.drop.thresh) ? a.drop.keep_scale : 0.f;
+            }
             av[n] = (gm < a.M && gk < a.Kc) ? v : 0.f;
             const int bk = b_n_fast ? u / 64 : u % KS, bn = b_n_fast ? u % 64 : u / KS;
             const int hk = k0 + bk, hn = n0 + bn;
@@ -122,12 +126,13 @@ __global__ __launch_bounds__(256) void k_bgemm(const BGemmArgs a) {
 #pragma unroll
         for (int s4 = 0; s4 < 4; ++s4) {
             const int row = m0 + wm * 32 + 8 * q + 4 * g + s4;
-            if (row < a.M && col < a.N) Cb[row * a.ldc + col] = acc[4 * q + s4];
+            if (row < a.M && col < a.N) Cb[row * a.ldc + col * a.sCn] = a.sig ? gate_sigmoid(acc[4 * q + s4]) : acc[4 * q + s4];
         }
 }
 
 // ---- softmax backward, in place: DE holds d att' (the gradient of the dropped attention matrix) on entry, d e on exit.
-// One wave per row (K <= 512: eight elements per lane).
+// One wave per row, NJ elements per lane (K <= 64 NJ).
+template <int NJ>
 __global__ __launch_bounds__(256) void k_bw_softmax(const float* __restrict__ ATT, float* __restrict__ DE, long nwin, int K, DropArgs drop,
                                                     unsigned drop_stream) {
     const int lane = threadIdx.x & 63;
@@ -138,10 +143,10 @@ __global__ __launch_bounds__(256) void k_bw_softmax(const float* __restrict__ AT
     const unsigned key = drop_window_key(drop, drop_stream, win);
     const float* __restrict__ ap = ATT + row * K;
     float* __restrict__ dp = DE + row * K;
-    float av[8], dv[8];
+    float av[NJ], dv[NJ];
     float csum = 0.f;
 #pragma unroll
-    for (int n = 0; n < 8; ++n) {
+    for (int n = 0; n < NJ; ++n) {
         const int j = lane + 64 * n;
         const int jc = j < K ? j : K - 1;
         float sc = 1.f;
@@ -152,7 +157,7 @@ __global__ __launch_bounds__(256) void k_bw_softmax(const float* __restrict__ AT
     }
     csum = wave_sum(csum);
 #pragma unroll
-    for (int n = 0; n < 8; ++n) {
+    for (int n = 0; n < NJ; ++n) {
         const int j = lane + 64 * n;
         if (j < K) dp[j] = av[n] * (dv[n] - csum);
     }
@@ -191,11 +196,17 @@ __global__ __launch_bounds__(32 * G) void k_bw_pair(const BwPairArgs a) {
     const long win = blockIdx.x / nkb;
     const int kb = (int)(blockIdx.x - win * nkb);
     const int tid = threadIdx.x, k = tid & 31, q = tid >> 5;
-    const int j0 = q * JB;                                            // this group's keys: [j0, j0 + JB)
     const float* __restrict__ lr = a.LR + (win * K) * (long)a.ldlr + 32 * kb + k;
     const float* __restrict__ de = a.DE + win * (long)K * K;
     float* __restrict__ dlr = a.DLR + (win * K) * (long)a.ldlr + 32 * kb + k;
     const float alpha = a.alpha;
+    const float ak = a.avec[32 * kb + k];
+    float da = 0.f;
+    // keys in segments of G JB (one segment up to 512 keys); the rows' dl of a segment are added to those of the earlier ones in
+    // memory by the same thread, and scaled by a_k after the last
+    for (int s0 = 0; s0 < K; s0 += G * JB) {
+    const bool last = s0 + G * JB >= K;
+    const int j0 = s0 + q * JB;                                       // this group's keys: [j0, j0 + JB)
     float R[JB], dr[JB];
 #pragma unroll
     for (int jj = 0; jj < JB; ++jj) {
@@ -204,7 +215,6 @@ __global__ __launch_bounds__(32 * G) void k_bw_pair(const BwPairArgs a) {
         R[jj] = j < K ? v : 0.f;
         dr[jj] = 0.f;
     }
-    float da = 0.f;
     for (int i0 = 0; i0 < K; i0 += IB) {
         __syncthreads();                                   // the previous batch's readers of des / red are done
         // the batch's rows of d e (coalesced; rows and keys past K as zeros) and this thread's L values
@@ -214,7 +224,7 @@ __global__ __launch_bounds__(32 * G) void k_bw_pair(const BwPairArgs a) {
             for (int n = 0; n < IB * KP / NT; ++n) {
                 const int u = tid + n * NT;
                 const int r = u / KP, sl = u - r * KP;
-                const int j = (sl / JBP) * JB + (sl % JBP);            // slot -> key (positions JB .. JBP - 1 of a group: padding)
+                const int j = s0 + (sl / JBP) * JB + (sl % JBP);       // slot -> key (positions JB .. JBP - 1 of a group: padding)
                 const int ic = i0 + r < K ? i0 + r : K - 1, jc = j < K ? j : K - 1;
                 v[n] = de[(long)ic * K + jc];
             }
@@ -222,7 +232,7 @@ __global__ __launch_bounds__(32 * G) void k_bw_pair(const BwPairArgs a) {
             for (int n = 0; n < IB * KP / NT; ++n) {
                 const int u = tid + n * NT;
                 const int r = u / KP, sl = u - r * KP;
-                const int j = (sl / JBP) * JB + (sl % JBP);
+                const int j = s0 + (sl / JBP) * JB + (sl % JBP);
                 des[u] = (i0 + r < K && sl % JBP < JB && j < K) ? v[n] : 0.f;
             }
         }
@@ -254,11 +264,12 @@ __global__ __launch_bounds__(32 * G) void k_bw_pair(const BwPairArgs a) {
             for (int g2 = 0; g2 < G; ++g2) dl += red[(g2 * IB + r) * 32 + k];
             if (i0 + r < K) {
                 da = __builtin_fmaf(Lb[tid], dl, da);
-                dlr[(long)(i0 + r) * a.ldlr] = dl * a.avec[32 * kb + k];
+                float* o = &dlr[(long)(i0 + r) * a.ldlr];
+                const float t = s0 == 0 ? dl : *o + dl;
+                *o = last ? t * ak : t;
             }
         }
     }
-    const float ak = a.avec[32 * kb + k];
 #pragma unroll
     for (int jj = 0; jj < JB; ++jj) {
         const int j = j0 + jj;
@@ -266,6 +277,7 @@ __global__ __launch_bounds__(32 * G) void k_bw_pair(const BwPairArgs a) {
             da = __builtin_fmaf(R[jj], dr[jj], da);
             dlr[(long)j * a.ldlr + a.Ep] = dr[jj] * ak;
         }
+    }
     }
     __syncthreads();
     red[q * 32 + k] = da;
@@ -281,11 +293,12 @@ __global__ __launch_bounds__(32 * G) void k_bw_pair(const BwPairArgs a) {
 // ---- GAT (v1) score backward of a wide layer, one workgroup (256 threads) per window.  Vn: node rows (win K + node) ldv, D columns.
 //   c_i = u1 . v_i + ub1, d_j = u2 . v_j + ub2;  d s_ij = d e_ij [c_i + d_j > 0 ? 1 : alpha];  dc_i = sum_j d s_ij, dd_j = sum_i d s_ij
 //   d V[node] += dc u1 + dd u2;  part = [sum_i dc_i v_i | sum_j dd_j v_j | sum dc, sum dd]
-// LDS: cq[K] | dk[K] | dc[K] | dd[K] (K <= 512)
+// LDS: cq[K] | dk[K] | dc[K] | dd[K] (K <= 64 NH)
+template <int NH>
 __global__ __launch_bounds__(256) void k_bw_v1(const float* __restrict__ Vn, long ldv, int D, int K, const float* __restrict__ u,
                                                const float* __restrict__ DE, float alpha, float* __restrict__ DV, int lddv,
                                                float* __restrict__ part) {
-    __shared__ float cq[512], dk[512], dc[512], dd[512];
+    __shared__ float cq[64 * NH], dk[64 * NH], dc[64 * NH], dd[64 * NH];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long win = blockIdx.x;
     const float* __restrict__ vw = Vn + win * K * ldv;
@@ -300,14 +313,14 @@ __global__ __launch_bounds__(256) void k_bw_v1(const float* __restrict__ Vn, lon
     __syncthreads();
     // d s: a wave per query row, lanes over the keys; row sums by a wave reduction, column sums per lane (keys lane + 64 h)
     const float* __restrict__ de = DE + win * (long)K * K;
-    float colacc[8];
+    float colacc[NH];
 #pragma unroll
-    for (int h = 0; h < 8; ++h) colacc[h] = 0.f;
+    for (int h = 0; h < NH; ++h) colacc[h] = 0.f;
     for (int i = wave; i < K; i += 4) {
         const float ci = cq[i];
         float rs = 0.f;
 #pragma unroll
-        for (int h = 0; h < 8; ++h) {
+        for (int h = 0; h < NH; ++h) {
             const int j = lane + 64 * h;
             if (j < K) {
                 const float ds = de[(long)i * K + j] * (ci + dk[j] > 0.f ? 1.f : alpha);
@@ -321,7 +334,7 @@ __global__ __launch_bounds__(256) void k_bw_v1(const float* __restrict__ Vn, lon
     for (int w = 0; w < 4; ++w) {
         if (wave == w) {
 #pragma unroll
-            for (int h = 0; h < 8; ++h)
+            for (int h = 0; h < NH; ++h)
                 if (lane + 64 * h < K) dd[lane + 64 * h] += colacc[h];
         }
         __syncthreads();
@@ -361,6 +374,7 @@ int launch_bgemm(const float* A, long sAb, long sAm, long sAk, const float* B, l
     if (nb <= 0 || M <= 0 || N <= 0) return 0;
     BGemmArgs a{};
     a.A = A; a.sAb = sAb; a.sAm = sAm; a.sAk = sAk; a.B = B; a.sBb = sBb; a.sBk = sBk; a.sBn = sBn; a.C = C; a.sCb = sCb; a.ldc = ldc;
+    a.sCn = 1;
     a.M = M; a.N = N; a.Kc = Kc; a.nb = nb;
     if (drop) { a.adrop = 1; a.drop = *drop; a.drop_stream = drop_stream; a.dropK = dropK; }
     const long blocks = nb * ((M + 63) / 64) * ((N + 63) / 64);
@@ -370,11 +384,30 @@ int launch_bgemm(const float* A, long sAb, long sAm, long sAk, const float* B, l
     return 0;
 }
 
+int launch_bgemm_sigmoid(const float* A, long sAb, long sAm, long sAk, const float* B, long sBb, long sBk, long sBn, float* C, long sCb,
+                         long sCm, long sCn, int M, int N, int Kc, long nb, const DropArgs* drop, unsigned drop_stream, int dropK,
+                         hipStream_t s) {
+    if (nb <= 0 || M <= 0 || N <= 0) return 0;
+    BGemmArgs a{};
+    a.A = A; a.sAb = sAb; a.sAm = sAm; a.sAk = sAk; a.B = B; a.sBb = sBb; a.sBk = sBk; a.sBn = sBn; a.C = C; a.sCb = sCb; a.ldc = sCm;
+    a.sCn = sCn; a.sig = 1;
+    if (drop) { a.adrop = 2; a.drop = *drop; a.drop_stream = drop_stream; a.dropK = dropK; }
+    a.M = M; a.N = N; a.Kc = Kc; a.nb = nb;
+    const long blocks = nb * ((M + 63) / 64) * ((N + 63) / 64);
+    if (blocks > 0x7fffffffL) return -2;
+    hipLaunchKernelGGL(k_bgemm, dim3((unsigned)blocks), dim3(256), 0, s, a);
+    LAUNCH_CHECK();
+    return 0;
+}
+
 int launch_bw_softmax(const float* ATT, float* DE, long nwin, int K, const DropArgs& drop, unsigned drop_stream, hipStream_t s) {
     if (nwin <= 0) return 0;
-    if (K > 512) return -2;
+    if (K > 2048) return -2;
     const long rows = nwin * K;
-    hipLaunchKernelGGL(k_bw_softmax, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, ATT, DE, nwin, K, drop, drop_stream);
+    if (K <= 512)
+        hipLaunchKernelGGL(k_bw_softmax<8>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, ATT, DE, nwin, K, drop, drop_stream);
+    else
+        hipLaunchKernelGGL(k_bw_softmax<32>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, ATT, DE, nwin, K, drop, drop_stream);
     LAUNCH_CHECK();
     return 0;
 }
@@ -382,7 +415,7 @@ int launch_bw_softmax(const float* ATT, float* DE, long nwin, int K, const DropA
 int launch_bw_pair(const float* LR, int ldlr, int Ep, const float* avec, const float* DE, int K, float alpha, float* DLR, float* DAp,
                    long nwin, hipStream_t s) {
     if (nwin <= 0) return 0;
-    if ((Ep & 31) != 0 || K > 512 || K < 1) return -2;
+    if ((Ep & 31) != 0 || K > 2048 || K < 1) return -2;
     BwPairArgs a{};
     a.LR = LR; a.ldlr = ldlr; a.Ep = Ep; a.avec = avec; a.DE = DE; a.K = K; a.alpha = alpha; a.DLR = DLR; a.DAp = DAp; a.nwin = nwin;
     const long blocks = nwin * (Ep / 32);
@@ -395,6 +428,8 @@ int launch_bw_pair(const float* LR, int ldlr, int Ep, const float* avec, const f
 #undef BWP_CASE
             default: return -2;
         }
+    } else if (K > 512) {                                  // 32 key groups, segments of 512 keys
+        hipLaunchKernelGGL((k_bw_pair<16, 32>), dim3((unsigned)blocks), dim3(1024), 0, s, a);
     } else {                                               // 32 key groups
         switch ((K + 31) / 32) {
 #define BWP_CASE(N) case N: hipLaunchKernelGGL((k_bw_pair<N, 32>), dim3((unsigned)blocks), dim3(1024), 0, s, a); break;
@@ -410,8 +445,11 @@ int launch_bw_pair(const float* LR, int ldlr, int Ep, const float* avec, const f
 int launch_bw_v1(const float* Vn, long ldv, int D, int K, const float* u, const float* DE, float alpha, float* DV, int lddv, float* part,
                  long nwin, hipStream_t s) {
     if (nwin <= 0) return 0;
-    if (K > 512 || D < 1) return -2;
-    hipLaunchKernelGGL(k_bw_v1, dim3((unsigned)nwin), dim3(256), 0, s, Vn, ldv, D, K, u, DE, alpha, DV, lddv, part);
+    if (K > 2048 || D < 1) return -2;
+    if (K <= 512)
+        hipLaunchKernelGGL(k_bw_v1<8>, dim3((unsigned)nwin), dim3(256), 0, s, Vn, ldv, D, K, u, DE, alpha, DV, lddv, part);
+    else
+        hipLaunchKernelGGL(k_bw_v1<32>, dim3((unsigned)nwin), dim3(256), 0, s, Vn, ldv, D, K, u, DE, alpha, DV, lddv, part);
     LAUNCH_CHECK();
     return 0;
 }

@@ -275,8 +275,9 @@ int run_proj(Model& m, const GatPlan& g, const float* rows, long ld, int64_t nro
 }
 
 int run_attend(Model& m, const GatPlan& g, const float* lc, const float* rt, const float* v, int ldv, int64_t n, float* out,
-               long so_w, long so_i, long so_d, hipStream_t s, float* att = nullptr, const DropArgs* drop = nullptr, unsigned drop_stream = 0) {
-    Scope sc(m, S_ATTEND, s);
+               long so_w, long so_i, long so_d, float* sc, hipStream_t s, float* att = nullptr, const DropArgs* drop = nullptr,
+               unsigned drop_stream = 0) {
+    Scope sc_(m, S_ATTEND, s);
     if (g.K <= 512 && g.D <= 512) {
         // LDS-tiled pair grid of the fused kernel over the HBM-resident projections (BASELINE config 4 shapes)
         K_TRY(launch_gat_wide(lc, rt, g.ldl, g.rt_rows, g.Kp, pt_by_value(m, g), p8_by_value(m, g), m.packed_dev + g.bias_off, v, ldv, g.D, g.K, out, so_w,
@@ -285,21 +286,20 @@ int run_attend(Model& m, const GatPlan& g, const float* lc, const float* rt, con
               "wide gat attention");
         return 0;
     }
-    if (att || drop) return fail(MTADGAT_ERR_UNSUPPORTED, "training forward of an attention layer with more than 512 nodes / features");
+    if (att) sc = att;       // training forward: the softmax rows are built in the tape's attention matrix
+    if (!sc) return fail(MTADGAT_ERR_INVALID, "internal: no score scratch for an attention layer with more than 512 nodes / features");
     AttendArgs a{};
     a.LC = lc; a.RT = rt; a.ldl = g.ldl; a.rt_rows = g.rt_rows; a.Kp = g.Kp; a.PT = pt_by_value(m, g); a.P8 = p8_by_value(m, g);
     a.ord = m.cfg.use_gatv2 ? reinterpret_cast<const int*>(m.packed_dev + g.ord_off) : nullptr;
     a.bias = m.packed_dev + g.bias_off;
     a.V = v; a.ldv = ldv; a.D = g.D;
     a.out = out; a.so_w = so_w; a.so_i = so_i; a.so_d = so_d;
-    a.K = g.K; a.rows_per_blk = g.rows_per_blk; a.nblk = g.nblk;
+    a.K = g.K;
     a.nwin = n;
-    a.xcd_map = 1;
-    a.total_blocks = ((n + 7) / 8 * 8) * g.nblk;
     a.v1 = m.cfg.use_gatv2 ? 0 : 1;
     a.alpha = m.cfg.alpha;
-    a.ATT = nullptr;
-    K_TRY(launch_attend(a, g.IB, s), "gat attention");
+    a.S = sc;
+    K_TRY(launch_attend(a, drop, drop_stream, s), "gat attention (score matrix)");
     return 0;
 }
 
@@ -395,11 +395,11 @@ bool fused_conv_args(const Model& m, const XSource& src, int64_t c0, int64_t n, 
 
 // one graph-attention layer from its node rows, fused when the plan allows
 int run_gat_layer(Model& m, const GatPlan& g, const float* v, int ldv, int64_t n, float* lc, float* rt, float* out, long so_w,
-                  long so_i, long so_d, hipStream_t s) {
+                  long so_i, long so_d, float* sc, hipStream_t s) {
     if (use_fused(g)) return run_gat_fused(m, g, v, ldv, 0, n, out, so_w, so_i, so_d, s);
     int rc = run_proj(m, g, v, ldv, n * g.K, lc, rt, s);
     if (rc) return rc;
-    return run_attend(m, g, lc, rt, v, ldv, n, out, so_w, so_i, so_d, s);
+    return run_attend(m, g, lc, rt, v, ldv, n, out, so_w, so_i, so_d, sc, s);
 }
 
 // the small-batch fp32 recurrence kernels apply to a single-layer stack whose weights fit a wave's registers
@@ -748,7 +748,9 @@ int mtadgat_create(const mtadgat_config* cfg, mtadgat_handle* out) {
         const bool unfused = !(h->m.temp.fused && h->m.feat.fused);
         if (unfused) budget = std::min(budget, 6.0 * 1024 * 1024 * 1024);   // projections through HBM: a few hundred windows fill the machine
         int64_t c = (int64_t)(budget / per_window);
-        const int64_t gran = unfused ? 128 : 2048;
+        // (more than 512 features: score matrices of up to 16 MB and projections of up to 4 096 columns per window, ~70 MB of
+        // scratch per window at F = 2048, W = 512 -- fewer than 128 windows fit the budget)
+        const int64_t gran = unfused ? (h->m.F > 512 ? 8 : 128) : 2048;
         c = c / gran * gran;
         h->m.chunk = c < gran ? gran : (c > 65536 ? 65536 : c);
     }
@@ -1304,9 +1306,9 @@ static int forward_impl(mtadgat_handle h, const XSource& src, int64_t batch, flo
         } else {
             if ((rc = run_conv(m, src, c0, n, xc, xct, hcat, nullptr, s))) return rc;
             // temporal layer: nodes = time steps, rows of xc
-            if ((rc = run_gat_layer(m, m.temp, xc, m.Fp, n, ws + o.lct, ws + o.rtt, hcat + 2 * F, (long)W * m.Dp, m.Dp, 1, s))) return rc;
+            if ((rc = run_gat_layer(m, m.temp, xc, m.Fp, n, ws + o.lct, ws + o.rtt, hcat + 2 * F, (long)W * m.Dp, m.Dp, 1, ws + o.sc, s))) return rc;
             // feature layer: nodes = features, rows of xc^T
-            if ((rc = run_gat_layer(m, m.feat, xct, m.Wp, n, ws + o.lcf, ws + o.rtf, hcat + F, (long)W * m.Dp, 1, m.Dp, s))) return rc;
+            if ((rc = run_gat_layer(m, m.feat, xct, m.Wp, n, ws + o.lcf, ws + o.rtf, hcat + F, (long)W * m.Dp, 1, m.Dp, ws + o.sc, s))) return rc;
         }
         float* hend = ws + o.hend;
         const long ldh = m.gru.back().Hp;
@@ -1393,10 +1395,10 @@ int mtadgat_gat(mtadgat_handle h, int which, const float* xc_in, int64_t batch, 
         float* o_c = out + c0 * (int64_t)W * F;
         if (which == 1) {
             K_TRY(launch_copy2d(xin, F, ws + o.xc, m.Fp, n * W, F, s), "pad copy");
-            if ((rc = run_gat_layer(m, m.temp, ws + o.xc, m.Fp, n, ws + o.lct, ws + o.rtt, o_c, (long)W * F, F, 1, s))) return rc;
+            if ((rc = run_gat_layer(m, m.temp, ws + o.xc, m.Fp, n, ws + o.lct, ws + o.rtt, o_c, (long)W * F, F, 1, ws + o.sc, s))) return rc;
         } else {
             K_TRY(launch_transpose_win(xin, F, ws + o.xct, m.Wp, n, W, F, s), "transpose");
-            if ((rc = run_gat_layer(m, m.feat, ws + o.xct, m.Wp, n, ws + o.lcf, ws + o.rtf, o_c, (long)W * F, 1, F, s))) return rc;
+            if ((rc = run_gat_layer(m, m.feat, ws + o.xct, m.Wp, n, ws + o.lcf, ws + o.rtf, o_c, (long)W * F, 1, F, ws + o.sc, s))) return rc;
         }
     }
     return 0;
@@ -1705,14 +1707,14 @@ int mtadgat_forward_train(mtadgat_handle h, const float* x, int64_t batch, int64
         if ((rc = run_gat_fused(m, m.temp, hcat, m.Dp, 0, n, hcat + 2 * F, (long)W * m.Dp, m.Dp, 1, s, T + t.att_t, &drop, DROP_TEMP, vmax))) return rc;
     } else {
         if ((rc = run_proj(m, m.temp, hcat, m.Dp, n * W, T + t.lct, T + t.rtt, s))) return rc;
-        if ((rc = run_attend(m, m.temp, T + t.lct, T + t.rtt, hcat, m.Dp, n, hcat + 2 * F, (long)W * m.Dp, m.Dp, 1, s, T + t.att_t, &drop, DROP_TEMP))) return rc;
+        if ((rc = run_attend(m, m.temp, T + t.lct, T + t.rtt, hcat, m.Dp, n, hcat + 2 * F, (long)W * m.Dp, m.Dp, 1, nullptr, s, T + t.att_t, &drop, DROP_TEMP))) return rc;
     }
     if (use_fused(m.feat)) {
         if ((rc = run_gat_fused(m, m.feat, hcat, m.Dp, 1, n, hcat + F, (long)W * m.Dp, 1, m.Dp, s, T + t.att_f, &drop, DROP_FEAT, vmax))) return rc;
     } else {
         const float* xct = T + t.xct;
         if ((rc = run_proj(m, m.feat, xct, m.Wp, n * F, T + t.lcf, T + t.rtf, s))) return rc;
-        if ((rc = run_attend(m, m.feat, T + t.lcf, T + t.rtf, xct, m.Wp, n, hcat + F, (long)W * m.Dp, 1, m.Dp, s, T + t.att_f, &drop, DROP_FEAT))) return rc;
+        if ((rc = run_attend(m, m.feat, T + t.lcf, T + t.rtf, xct, m.Wp, n, hcat + F, (long)W * m.Dp, 1, m.Dp, nullptr, s, T + t.att_f, &drop, DROP_FEAT))) return rc;
     }
     // GRU stack (modules.py:235-238): every layer keeps its gates and states; between stacked layers nn.GRU's dropout
     // (training only; reference modules.py:232-233): the dropped sequence is what the next layer reads and is kept as well

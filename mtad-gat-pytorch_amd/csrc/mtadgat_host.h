@@ -27,8 +27,7 @@ struct GatPlan {
     size_t w_off = 0, b_off = 0, bias_off = 0;   // offsets (floats) into the packed buffer
     size_t ord_off = 0;     // [P8, PT, npos, 0] as ints in the packed buffer: what the kernels read (the device-side re-pack rewrites it)
     int PTcap = 0;          // upper bound of PT: E rounded up to 8, + 8
-    int rows_per_blk = 0, nblk = 0, IB = 0;      // attend launch plan (un-fused path)
-    // fused per-window kernel (k_gat) plan; fused == false -> k_rowgemm + k_attend through HBM
+    // fused per-window kernel (k_gat) plan; fused == false -> k_rowgemm + k_gat_wide (K, D <= 512) / k_attend through HBM
     bool fused = false;
     int f_nw = 0, f_IBL = 0, f_JPL = 0, f_RJ = 16, f_vld = 0, f_lr = 0;
     size_t f_lds_bytes = 0;
@@ -242,6 +241,7 @@ struct Workspace {
     size_t vmax;         // one word: bits of the largest convolution output of the chunk (range guard of the fp16 operand pieces)
     size_t winflag;      // one byte per window: the fused convolution's per-window range flag (k_gath CONV build -> k_gat)
     size_t cf, el, er;   // convolution rows shared by stride-1 windows of a series (run_conv_shared): segment rows, edge rows
+    size_t sc;           // (n, K, K) score matrix of a layer with more than 512 nodes / node dimensions (k_attend)
 };
 
 // activations kept between the training forward and the backward (caller-owned "tape"), offsets in floats

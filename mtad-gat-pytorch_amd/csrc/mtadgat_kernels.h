@@ -80,6 +80,8 @@ struct ConvArgs {
     const f32x4* Wp3;    // split-bf16 pack [tile][taps Fq / 16][3][64] (k_conv_x3; Fq = F rounded up to 16)
 };
 
+// graph attention of a layer beyond k_gat_wide (K or D above 512): scores through the (B, K, K) matrix S (mtadgat_attend.hip)
+constexpr int MTADGAT_ATTEND_MAX_K = 2048;   // k_attend_softmax keeps a row in registers, 32 per lane
 struct AttendArgs {
     const float* LC;     // (B*K, ldl) per query node: [L'(PT) | c | pad]
     const float* RT;     // (B, rt_rows, Kp) per window, key-node-minor: rows [0,PT) = R', row PT = d
@@ -90,13 +92,11 @@ struct AttendArgs {
     int ldv, D;
     float* out;          // out[win*so_w + i*so_i + d*so_d]
     long so_w, so_i, so_d;
-    int K, rows_per_blk, nblk;
-    long total_blocks;   // round_up(B, 8) * nblk
+    int K;
     long nwin;           // B
-    int xcd_map;         // 1: XCD-aware block -> (window, row block) map
     int v1;
     float alpha;
-    float* ATT;          // optional (B, K, K) dump of the attention matrix
+    float* S;            // (B, K, K): the scores, then the attention matrix (scratch, or the training tape)
 };
 
 // the window convolution computed inside the temporal layer's k_gath workgroup (mtadgat_gath.hip, CONV build): what k_conv_win
@@ -359,8 +359,8 @@ void set_gemm_lds_off(int off);
 int launch_conv(const ConvArgs& a, hipStream_t s);
 bool conv_win_applies(const ConvArgs& a);
 int launch_conv_win(const ConvArgs& a, hipStream_t s);
-void attend_plan(int K, int* rows_per_blk, int* nblk, int* IB);
-int launch_attend(const AttendArgs& a, int IB, hipStream_t s);
+// training forward (drop set): S is the tape's attention matrix and keeps the softmax rows before dropout
+int launch_attend(const AttendArgs& a, const DropArgs* drop, unsigned drop_stream, hipStream_t s);
 int launch_gat(const GatArgs& a, int IBL, int JPL, int rj, int nw, size_t lds_bytes, hipStream_t s);
 int launch_gath(const GatArgs& a, int IBL, int JPL, int rj, int nw, size_t lds_bytes, bool conv, hipStream_t s);
 bool gath_conv_applies(const GatArgs& a, int nw, int F, int W);
@@ -375,6 +375,11 @@ int launch_gat_colorder(const float* a_dev, int E, double alpha, int* colk_dev, 
 int launch_bw_ds(const float* H, const float* dH, long so_w, long so_i, long so_d, long nwin, int K, int D, float* dS, int ldS, hipStream_t s);
 int launch_bgemm(const float* A, long sAb, long sAm, long sAk, const float* B, long sBb, long sBk, long sBn, float* C, long sCb, long ldc,
                  int M, int N, int Kc, long nb, const DropArgs* drop, unsigned drop_stream, int dropK, hipStream_t s);
+// C_b(m, n) = sigmoid((A_b B_b)(m, n)) stored at C[b sCb + m sCm + n sCn]; drop: A_b(m, k) gets the dropout keep factor of
+// attention element (m, k) of window b (index m dropK + k)
+int launch_bgemm_sigmoid(const float* A, long sAb, long sAm, long sAk, const float* B, long sBb, long sBk, long sBn, float* C, long sCb,
+                         long sCm, long sCn, int M, int N, int Kc, long nb, const DropArgs* drop, unsigned drop_stream, int dropK,
+                         hipStream_t s);
 int launch_bw_softmax(const float* ATT, float* DE, long nwin, int K, const DropArgs& drop, unsigned drop_stream, hipStream_t s);
 // GAT (v1) score backward of a wide layer: k_gat_bwd_v1's outputs with the node rows read from memory (K <= 512)
 int launch_bw_v1(const float* Vn, long ldv, int D, int K, const float* u, const float* DE, float alpha, float* DV, int lddv, float* part,

@@ -18,11 +18,11 @@ size_t align64(size_t v) { return (v + 63) / 64 * 64; }
 
 // tile format: [NT][Q][64 lanes][4]; lane (j = lane&31, g = lane>>5), element s holds
 // M[32n + j][8q + 4g + s] (zero outside the matrix)
-template <class Get>
-void pack_tiles(float* out, int NT, int Q, Get get) {
+template <class T, class Get>
+void pack_tiles(T* out, int NT, int Q, Get get) {
     for (int n = 0; n < NT; ++n)
         for (int q = 0; q < Q; ++q) {
-            float* o = out + ((size_t)n * Q + q) * 256;
+            T* o = out + ((size_t)n * Q + q) * 256;
             for (int lane = 0; lane < 64; ++lane)
                 for (int s = 0; s < 4; ++s) o[lane * 4 + s] = get(32 * n + (lane & 31), 8 * q + 4 * (lane >> 5) + s);
         }
@@ -82,7 +82,8 @@ std::string validate_and_plan(Model& m) {
     if (c.n_features < 1 || c.window_size < 1 || c.out_dim < 1) return "n_features, window_size and out_dim must be >= 1";
     if (c.kernel_size < 1 || (c.kernel_size & 1) == 0) return "kernel_size must be odd (the reference's ConvLayer shortens the window otherwise)";
     if (c.feat_embed < 1 || c.time_embed < 1) return "embedding dims must be >= 1";
-    if (c.n_features > 512 || c.window_size > 512) return "n_features and window_size up to 512 nodes are supported";
+    if (c.n_features > 2048) return "n_features up to 2048 are supported";
+    if (c.window_size > 512) return "window_size up to 512 nodes is supported";
     if (c.gru_n_layers < 1 || c.gru_n_layers > MTADGAT_MAX_LAYERS) return "gru_n_layers out of range";
     if (c.recon_n_layers < 1 || c.recon_n_layers > MTADGAT_MAX_LAYERS) return "recon_n_layers out of range";
     if (c.forecast_n_linear < 1 || c.forecast_n_linear > MTADGAT_MAX_LAYERS) return "forecast_n_linear out of range";
@@ -128,7 +129,6 @@ std::string validate_and_plan(Model& m) {
         g.NT_L = g.ldl / 32;
         g.NT = 2 * g.NT_L;
         g.PT = g.P8 = 0;
-        attend_plan(K, &g.rows_per_blk, &g.nblk, &g.IB);
         // fused plan: one workgroup (f_nw waves) per window, tiles of the layer resident in LDS.
         // A wave owns 4*IBL query rows, a lane JPL key nodes (16*JPL >= K); see k_gat.
         g.fused = false;
@@ -361,12 +361,8 @@ std::string validate_and_plan(Model& m) {
         gl.rec_fc_w = gtake((int64_t)c.out_dim * c.recon_hid_dim); gl.rec_fc_b = gtake(c.out_dim);
         gl.total = go;
 
+        // wide layers go through the generic kernels of mtadgat_bwdw.hip: GATv2 and (round 6) GAT v1, up to 2048 nodes / node dimensions
         b.supported = true;
-        for (const GatPlan* g : {&m.feat, &m.temp})
-            if (!g->fused) {
-                // wide layers go through the generic kernels of mtadgat_bwdw.hip: GATv2 and (round 6) GAT v1, up to 512 nodes / node dimensions
-                if (g->K > 512 || g->D > 512) { b.supported = false; b.why = "graph-attention layers with more than 512 nodes / features"; }
-            }
         if (b.supported) {
             for (int which = 0; which < 2; ++which) {
                 const GatPlan& g = which == 0 ? m.feat : m.temp;
@@ -486,6 +482,10 @@ void plan_workspace(const Model& m, int64_t n, Workspace& ws) {
     ws.cf = take(both_fused ? (N + m.W) * m.Fp : 0);
     ws.el = take(both_fused ? N * 2 * m.pad * m.Fp : 0);
     ws.er = take(both_fused ? N * 2 * m.pad * m.Fp : 0);
+    size_t kk = 0;       // layers beyond k_gat_wide (more than 512 nodes / node dimensions) run through a score matrix, one at a time
+    for (const GatPlan* g : {&m.feat, &m.temp})
+        if (!g->fused && (g->K > 512 || g->D > 512)) kk = std::max(kk, (size_t)g->K * g->K);
+    ws.sc = take(N * kk);
     ws.total = off;
 }
 
@@ -1010,24 +1010,36 @@ std::string build_device_tables(Model& m) {
     if (m.precision == 1) return "device-side re-packing covers the fp32 image only";
     t.fo = flat_offsets(m);
     if (t.fo.total != m.bw.gl.total) return "internal: flat parameter layout mismatch";
-    if (t.fo.total >= (1 << 24)) return "model too large for the index-encoded gather table";
-    std::vector<float> synth((size_t)t.fo.total);
-    for (int64_t i = 0; i < t.fo.total; ++i) synth[(size_t)i] = (float)(i + 1);
-    mtadgat_params p;
-    params_from_flat(m, t.fo, synth.data(), p);
-    const int keep[4] = {m.feat.PT, m.feat.P8, m.temp.PT, m.temp.P8};
-    const int keep_np[2] = {m.feat.npos, m.temp.npos};
-    const bool keep_bf = m.bf16_packed;
-    std::vector<float> img;
-    std::string err = pack_weights(m, p, img);
-    m.feat.PT = keep[0]; m.feat.P8 = keep[1]; m.temp.PT = keep[2]; m.temp.P8 = keep[3];
-    m.feat.npos = keep_np[0]; m.temp.npos = keep_np[1];
-    m.bf16_packed = keep_bf;
-    if (!err.empty()) return err;
+    if (t.fo.total >= ((int64_t)1 << 31)) return "model too large for the index-encoded gather table";
+    // fp32 holds integers exactly below 2^24 only: models of more than 2^24 parameters (F > 512) are encoded in two runs of the
+    // packer, the low 22 bits of the index and the rest
+    const int64_t LOW = (int64_t)1 << 22;
+    const int runs = t.fo.total < ((int64_t)1 << 24) ? 1 : 2;
+    std::vector<float> img[2];
+    for (int r = 0; r < runs; ++r) {
+        std::vector<float> synth((size_t)t.fo.total);
+        for (int64_t i = 0; i < t.fo.total; ++i) synth[(size_t)i] = (float)(runs == 1 ? i + 1 : (r == 0 ? (i & (LOW - 1)) : (i >> 22)) + 1);
+        mtadgat_params p;
+        params_from_flat(m, t.fo, synth.data(), p);
+        const int keep[4] = {m.feat.PT, m.feat.P8, m.temp.PT, m.temp.P8};
+        const int keep_np[2] = {m.feat.npos, m.temp.npos};
+        const bool keep_bf = m.bf16_packed;
+        std::string err = pack_weights(m, p, img[r]);
+        m.feat.PT = keep[0]; m.feat.P8 = keep[1]; m.temp.PT = keep[2]; m.temp.P8 = keep[3];
+        m.feat.npos = keep_np[0]; m.temp.npos = keep_np[1];
+        m.bf16_packed = keep_bf;
+        if (!err.empty()) return err;
+    }
     t.gidx.assign(m.packed_floats, -1);
+    auto code = [](float v, int64_t hi) -> int64_t { return (v >= 1.f && v <= (float)hi && v == std::floor(v)) ? (int64_t)v - 1 : -1; };
     for (size_t i = 0; i < m.packed_floats; ++i) {
-        const float v = img[i];
-        if (v >= 1.f && v <= (float)t.fo.total && v == std::floor(v)) t.gidx[i] = (int)v - 1;
+        if (runs == 1) {
+            t.gidx[i] = (int)code(img[0][i], t.fo.total);
+        } else {
+            const int64_t lo = code(img[0][i], LOW), hi = code(img[1][i], (t.fo.total >> 22) + 1);
+            const int64_t idx = hi * LOW + lo;
+            if (lo >= 0 && hi >= 0 && idx < t.fo.total) t.gidx[i] = (int)idx;
+        }
     }
     auto exclude = [&](size_t off, size_t n) { std::fill(t.gidx.begin() + off, t.gidx.begin() + off + n, -1); };
     for (int which = 0; which < 2; ++which) {
@@ -1035,10 +1047,8 @@ std::string build_device_tables(Model& m) {
         exclude(g.w_off, (size_t)g.NT * g.Q * 256);
         exclude(g.b_off, (size_t)g.NT * 32);
         const int D = g.D, NC = 2 * g.ldl;
-        std::vector<float> code((size_t)g.NT * g.Q * 256, 0.f);
-        pack_tiles(code.data(), g.NT, g.Q, [&](int n, int k) -> float { return (n < NC && k <= D) ? (float)((size_t)n * (D + 1) + k + 1) : 0.f; });
-        t.gatcode[which].assign(code.size(), 0);
-        for (size_t i = 0; i < code.size(); ++i) t.gatcode[which][i] = (int)code[i];
+        t.gatcode[which].assign((size_t)g.NT * g.Q * 256, 0);
+        pack_tiles(t.gatcode[which].data(), g.NT, g.Q, [&](int n, int k) -> int { return (n < NC && k <= D) ? n * (D + 1) + k + 1 : 0; });
     }
     auto gru_excl = [&](const GruPlan& g) {
         exclude(g.b_off, (size_t)4 * g.Hp);
