@@ -262,6 +262,34 @@ int mtadgat_heads(mtadgat_handle h, const float* hend_dev, int64_t batch,
                   float* preds_dev, float* recons_dev,
                   void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ---- attention maps ----------------------------------------------------------------------------
+ * The post-softmax matrices of the two graph-attention layers -- `attention` of FeatureAttentionLayer.forward
+ * (modules.py:85-89, nodes = features) and of TemporalAttentionLayer.forward (modules.py:184-188, nodes = time steps) --
+ * in eval mode (no dropout): row i = softmax over the keys j.  Only the convolution and the attention layers run.
+ *   att_feat_dev (batch, F, F) and att_temp_dev (batch, W, W), float32, out.  Either may be NULL: that layer does not run.
+ * Arithmetic: the fp32 builds the training forward keeps its softmax rows with, in EVERY precision mode -- the maps do not
+ * depend on mtadgat_set_precision, and a handle in mode 1 is served like one in mode 0.  The call leaves no state behind:
+ * a later mtadgat_forward on the handle returns what it returned before, bit for bit.
+ * The batch is walked in chunks of mtadgat_chunk_windows() windows.  batch < 1 returns MTADGAT_ERR_INVALID.
+ * Workspace: mtadgat_attention_workspace_bytes(h, batch, 0), 16-byte aligned. */
+size_t mtadgat_attention_workspace_bytes(mtadgat_handle h, int64_t batch, int reduce);
+int mtadgat_attention(mtadgat_handle h, const float* x_dev, int64_t batch, float* att_feat_dev, float* att_temp_dev,
+                      void* workspace_dev, size_t workspace_bytes, void* stream);
+/* The same for the windows of mtadgat_forward_series (series_dev (n_rows, F), starts_dev or start0 + w * stride): the windows
+ * are gathered from the series, not materialised. */
+int mtadgat_attention_series(mtadgat_handle h, const float* series_dev, int64_t n_rows, const int64_t* starts_dev, int64_t start0,
+                             int64_t stride, int64_t batch, float* att_feat_dev, float* att_temp_dev, void* workspace_dev,
+                             size_t workspace_bytes, void* stream);
+/* Mean over the call's windows only: mean_feat_dev (F, F), mean_temp_dev (W, W).  The per-window maps pass through the
+ * workspace a chunk at a time (chunks of at most mtadgat_chunk_windows() windows and 2^26 map floats), so the workspace --
+ * mtadgat_attention_workspace_bytes(h, batch, 1) -- is bounded by one chunk.  The reduction is a fixed-order compensated fp32
+ * sum without atomics (k_att_mean_part / k_att_mean_final): identical calls give identical bits for a given chunk size. */
+int mtadgat_attention_mean(mtadgat_handle h, const float* x_dev, int64_t batch, float* mean_feat_dev, float* mean_temp_dev,
+                           void* workspace_dev, size_t workspace_bytes, void* stream);
+int mtadgat_attention_series_mean(mtadgat_handle h, const float* series_dev, int64_t n_rows, const int64_t* starts_dev,
+                                  int64_t start0, int64_t stride, int64_t batch, float* mean_feat_dev, float* mean_temp_dev,
+                                  void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* ---- training step --------------------------------------------------------------------------------
  * Replaces what autograd does for the reference around MTAD_GAT.forward in Trainer.fit
  * (training.py:106-127: preds, recons = model(x); loss.backward()): a forward that keeps the

@@ -101,6 +101,12 @@ def load_library():
     lib.mtadgat_gat.argtypes = [vp, ctypes.c_int, vp, i64, vp, vp, sz, vp]
     lib.mtadgat_gru.argtypes = [vp, vp, i64, vp, vp, sz, vp]
     lib.mtadgat_heads.argtypes = [vp, vp, i64, vp, vp, vp, sz, vp]
+    lib.mtadgat_attention_workspace_bytes.argtypes = [vp, i64, ctypes.c_int]
+    lib.mtadgat_attention_workspace_bytes.restype = sz
+    lib.mtadgat_attention.argtypes = [vp, vp, i64, vp, vp, vp, sz, vp]
+    lib.mtadgat_attention_mean.argtypes = [vp, vp, i64, vp, vp, vp, sz, vp]
+    lib.mtadgat_attention_series.argtypes = [vp, vp, i64, vp, i64, i64, i64, vp, vp, vp, sz, vp]
+    lib.mtadgat_attention_series_mean.argtypes = [vp, vp, i64, vp, i64, i64, i64, vp, vp, vp, sz, vp]
     u64, f32 = ctypes.c_uint64, ctypes.c_float
     lib.mtadgat_backward_supported.argtypes = [vp]
     lib.mtadgat_tape_bytes.argtypes = [vp, i64]
@@ -486,9 +492,8 @@ class Engine:
                    _dev_ptr(ws, "workspace"), need)
         return (preds, recons, hend) if want_hend else (preds, recons)
 
-    def forward_series(self, series, starts=None, start0=0, stride=1, count=None, want_recons=True, want_last=False):
-        """Windows gathered on the GPU from the device-resident series (n_rows, F); returns
-        (preds, recons or None, recons[:, -1] or None)."""
+    def _series_windows(self, series, starts, start0, stride, count):
+        """(series pointer, n_rows, starts pointer or None, window count) of a series call, checked on the host."""
         c = self.cfg
         if series.dim() != 2 or series.shape[1] != c.n_features:
             raise RuntimeError(f"series must have shape (n_rows, {c.n_features}), got {tuple(series.shape)}")
@@ -504,6 +509,13 @@ class Engine:
         else:
             b = count if count is not None else max(0, (n_rows - c.window_size - start0) // max(stride, 1) + 1)
             stp = None
+        return sp, n_rows, stp, b
+
+    def forward_series(self, series, starts=None, start0=0, stride=1, count=None, want_recons=True, want_last=False):
+        """Windows gathered on the GPU from the device-resident series (n_rows, F); returns
+        (preds, recons or None, recons[:, -1] or None)."""
+        c = self.cfg
+        sp, n_rows, stp, b = self._series_windows(series, starts, start0, stride, count)
         dev = series.device
         preds = _empty((b, c.out_dim), dtype=torch.float32, device=dev)
         recons = _empty((b, c.window_size, c.out_dim), dtype=torch.float32, device=dev) if want_recons else None
@@ -513,6 +525,48 @@ class Engine:
                    _dev_ptr(preds, "preds"), _dev_ptr(recons, "recons") if want_recons else None,
                    _dev_ptr(last, "recons_last") if want_last else None, _dev_ptr(ws, "workspace") if b else None, need)
         return preds, recons, last
+
+    # -- attention maps (eval mode, fp32 in every precision mode) -----------------------------------------
+    def _attention_ws(self, batch, reduce, device):
+        """Scratch of an attention call: its own buffer (the forward's workspace is sized differently), poisoned like it."""
+        need = self.lib.mtadgat_attention_workspace_bytes(self.handle, batch, 1 if reduce else 0)
+        return _empty((need + 3) // 4, dtype=torch.float32, device=device), need
+
+    def _attention_out(self, b, reduce, feat, temp, device):
+        c = self.cfg
+        lead = () if reduce else (b,)
+        af = _empty(lead + (c.n_features, c.n_features), dtype=torch.float32, device=device) if feat else None
+        at = _empty(lead + (c.window_size, c.window_size), dtype=torch.float32, device=device) if temp else None
+        return af, at
+
+    def attention(self, x, reduce=False, feat=True, temp=True):
+        """Attention matrices of the windows x (b, W, F): per window ((b, F, F), (b, W, W)) or, reduce=True, their means
+        ((F, F), (W, W)); a layer not asked for (feat / temp False) comes back as None."""
+        c = self.cfg
+        b = x.shape[0]
+        xp = _dev_ptr(x, "x", (b, c.window_size, c.n_features))
+        af, at = self._attention_out(b, reduce, feat, temp, x.device)
+        if b == 0 and not reduce:
+            return af, at
+        ws, need = self._attention_ws(b, reduce, x.device)
+        fn = self.lib.mtadgat_attention_mean if reduce else self.lib.mtadgat_attention
+        self._call(fn, "attention", x.device, xp, b, _dev_ptr(af, "att_feat") if feat else None,
+                   _dev_ptr(at, "att_temp") if temp else None, _dev_ptr(ws, "workspace"), need)
+        return af, at
+
+    def attention_series(self, series, starts=None, start0=0, stride=1, count=None, reduce=True, feat=True, temp=True):
+        """attention() over the windows of forward_series(), gathered from the device-resident series."""
+        sp, n_rows, stp, b = self._series_windows(series, starts, start0, stride, count)
+        dev = series.device
+        af, at = self._attention_out(b, reduce, feat, temp, dev)
+        if b == 0 and not reduce:
+            return af, at
+        ws, need = self._attention_ws(b, reduce, dev)
+        fn = self.lib.mtadgat_attention_series_mean if reduce else self.lib.mtadgat_attention_series
+        self._call(fn, "attention_series", dev, sp, n_rows, stp, int(start0), int(stride), b,
+                   _dev_ptr(af, "att_feat") if feat else None, _dev_ptr(at, "att_temp") if temp else None,
+                   _dev_ptr(ws, "workspace") if b else None, need)
+        return af, at
 
     def conv(self, x):
         c = self.cfg

@@ -36,6 +36,13 @@ def _drop(t, p, training, mask=None):
 
 def graph_attention(v, layer, training, mask=None):
     """v (b, K, D) node rows -> sigmoid(softmax(e) @ v), e as in modules.py:74-93 / :174-191."""
+    att = attention_matrix(v, layer)
+    att = _drop(att, layer.dropout, training, mask)
+    return torch.sigmoid(att @ v)
+
+
+def attention_matrix(v, layer):
+    """v (b, K, D) node rows -> softmax(e) (b, K, K), the layer's attention before dropout (modules.py:74-89 / :174-188)."""
     alpha = layer.alpha
     if layer.use_gatv2:
         d = v.shape[2]
@@ -54,9 +61,7 @@ def graph_attention(v, layer, training, mask=None):
         e = F.leaky_relu((p @ a[:e_dim]).unsqueeze(2) + (p @ a[e_dim:]).unsqueeze(1), alpha)
     if layer.use_bias:
         e = e + layer.bias
-    att = torch.softmax(e, dim=2)
-    att = _drop(att, layer.dropout, training, mask)
-    return torch.sigmoid(att @ v)
+    return torch.softmax(e, dim=2)
 
 
 def conv_stage(model, x):
@@ -121,6 +126,15 @@ def recon_stage(model, h_end, masks=None):
         with _no_miopen_rnn(rep):
             dec, _ = model.recon_model.decoder.rnn(rep)
     return model.recon_model.fc(dec)
+
+
+def attention_maps(model, x, feat=True, temp=True):
+    """Eval-mode attention matrices of the two layers for windows x (b, W, F): (feature (b, F, F) or None, temporal (b, W, W)
+    or None) -- what MTAD_GAT.attention_maps returns for CPU tensors."""
+    xc = conv_stage(model, x)
+    att_f = attention_matrix(xc.permute(0, 2, 1), model.feature_gat) if feat else None
+    att_t = attention_matrix(xc, model.temporal_gat) if temp else None
+    return att_f, att_t
 
 
 def forward(model, x, masks=None):

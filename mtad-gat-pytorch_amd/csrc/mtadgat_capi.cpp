@@ -1449,6 +1449,148 @@ int mtadgat_heads(mtadgat_handle h, const float* hend, int64_t batch, float* pre
     return 0;
 }
 
+// ---- attention maps (the post-softmax `attention` of modules.py:85-89 / :184-188, eval mode) -------------------------------
+// Scratch of one chunk: h_cat (the convolution in [:, :F], the layers' outputs behind it), x_c^T and the projections of un-fused
+// layers -- as in the training forward's tape --, and in the mean mode the chunk's maps of one layer at a time plus the running
+// (sum, compensation) slabs of k_att_mean_part.
+struct AttPlan {
+    int64_t chunk;
+    size_t hcat, xct, lct, rtt, lcf, rtf, maps, ps_f, pc_f, ps_t, pc_t, total;
+    int slabs_f, slabs_t;
+};
+// mean mode: at most 2^26 floats (256 MB) of per-window maps per chunk (MSL's temporal layer: 6 710 windows of 100 x 100)
+static constexpr int64_t ATT_MAPS_FLOATS = int64_t(1) << 26;
+static void plan_attention(const Model& m, int64_t batch, bool reduce, AttPlan& p) {
+    size_t off = 0;
+    auto take = [&](size_t cnt) {
+        size_t o = off;
+        off = (off + cnt + 63) / 64 * 64;
+        return o;
+    };
+    const int64_t kk = std::max<int64_t>((int64_t)m.F * m.F, (int64_t)m.W * m.W);
+    p.chunk = reduce ? std::min<int64_t>(m.chunk, std::max<int64_t>(1, ATT_MAPS_FLOATS / kk)) : m.chunk;
+    const int64_t n = std::min<int64_t>(batch, p.chunk);
+    const size_t N = (size_t)n;
+    p.hcat = take(N * m.W * m.Dp);
+    p.xct = take(m.feat.fused ? 0 : N * m.F * m.Wp);
+    p.lct = take(m.temp.fused ? 0 : N * m.W * m.temp.ldl);
+    p.rtt = take(m.temp.fused ? 0 : N * m.temp.rt_rows * m.temp.Kp);
+    p.lcf = take(m.feat.fused ? 0 : N * m.F * m.feat.ldl);
+    p.rtf = take(m.feat.fused ? 0 : N * m.feat.rt_rows * m.feat.Kp);
+    p.slabs_f = reduce ? att_mean_slabs(n, m.F) : 0;
+    p.slabs_t = reduce ? att_mean_slabs(n, m.W) : 0;
+    p.maps = take(reduce ? N * (size_t)kk : 0);
+    p.ps_f = take((size_t)p.slabs_f * m.F * m.F);
+    p.pc_f = take((size_t)p.slabs_f * m.F * m.F);
+    p.ps_t = take((size_t)p.slabs_t * m.W * m.W);
+    p.pc_t = take((size_t)p.slabs_t * m.W * m.W);
+    p.total = off;
+}
+
+// The maps come from the fp32 builds the training forward keeps its softmax rows with (k_gat / k_gat_wide / k_attend, no
+// dropout), whatever precision mode the handle is in: the mode is set to 0 for the call and restored, and so is profiling --
+// the call leaves the handle as it found it.
+static int attention_impl(mtadgat_handle h, const XSource& src, int64_t batch, bool reduce, float* att_f, float* att_t, void* ws_,
+                          size_t ws_bytes, void* stream) {
+    if (!h) return fail(MTADGAT_ERR_INVALID, "null handle");
+    if (batch < 1) return fail(MTADGAT_ERR_INVALID, "attention maps need at least one window");
+    if (!h->m.have_weights) return fail(MTADGAT_ERR_NOWEIGHTS, "mtadgat_load_weights has not been called");
+    if (!src.x) return fail(MTADGAT_ERR_INVALID, "input is NULL");
+    if (!att_f && !att_t) return fail(MTADGAT_ERR_INVALID, "both attention outputs are NULL");
+    if (!ws_) return fail(MTADGAT_ERR_WORKSPACE, "workspace is NULL");
+    if (!aligned16(ws_)) return fail(MTADGAT_ERR_WORKSPACE, "workspace must be 16-byte aligned");
+    Model& m = h->m;
+    AttPlan p;
+    plan_attention(m, batch, reduce, p);
+    if (ws_bytes < p.total * sizeof(float)) return fail(MTADGAT_ERR_WORKSPACE, "workspace too small");
+    struct Restore {
+        Model& m; int precision; bool profile;
+        ~Restore() { m.precision = precision; m.profile = profile; }
+    } restore{m, m.precision, m.profile};
+    m.precision = 0;
+    m.profile = false;
+    hipStream_t s = (hipStream_t)stream;
+    float* ws = static_cast<float*>(ws_);
+    const int F = m.F, W = m.W;
+    float* hcat = ws + p.hcat;
+    int rc;
+    for (int64_t c0 = 0; c0 < batch; c0 += p.chunk) {
+        const int64_t n = std::min<int64_t>(p.chunk, batch - c0);
+        if ((rc = run_conv(m, src, c0, n, nullptr, (att_f && !m.feat.fused) ? ws + p.xct : nullptr, hcat, nullptr, s))) return rc;
+        // temporal layer: nodes = time steps, rows of h_cat[:, :F]
+        if (att_t) {
+            float* dst = reduce ? ws + p.maps : att_t + c0 * (int64_t)W * W;
+            if (use_fused(m.temp)) {
+                if ((rc = run_gat_fused(m, m.temp, hcat, m.Dp, 0, n, hcat + 2 * F, (long)W * m.Dp, m.Dp, 1, s, dst))) return rc;
+            } else {
+                if ((rc = run_proj(m, m.temp, hcat, m.Dp, n * W, ws + p.lct, ws + p.rtt, s))) return rc;
+                if ((rc = run_attend(m, m.temp, ws + p.lct, ws + p.rtt, hcat, m.Dp, n, hcat + 2 * F, (long)W * m.Dp, m.Dp, 1, nullptr, s, dst))) return rc;
+            }
+            if (reduce) K_TRY(launch_att_mean_part(dst, n, W, p.slabs_t, c0 == 0, ws + p.ps_t, ws + p.pc_t, s), "attention mean (temporal)");
+        }
+        // feature layer: nodes = features, columns of h_cat[:, :F] (fused) or rows of x_c^T
+        if (att_f) {
+            float* dst = reduce ? ws + p.maps : att_f + c0 * (int64_t)F * F;
+            if (use_fused(m.feat)) {
+                if ((rc = run_gat_fused(m, m.feat, hcat, m.Dp, 1, n, hcat + F, (long)W * m.Dp, 1, m.Dp, s, dst))) return rc;
+            } else {
+                const float* xct = ws + p.xct;
+                if ((rc = run_proj(m, m.feat, xct, m.Wp, n * F, ws + p.lcf, ws + p.rtf, s))) return rc;
+                if ((rc = run_attend(m, m.feat, ws + p.lcf, ws + p.rtf, xct, m.Wp, n, hcat + F, (long)W * m.Dp, 1, m.Dp, nullptr, s, dst))) return rc;
+            }
+            if (reduce) K_TRY(launch_att_mean_part(dst, n, F, p.slabs_f, c0 == 0, ws + p.ps_f, ws + p.pc_f, s), "attention mean (feature)");
+        }
+    }
+    if (reduce && att_t) K_TRY(launch_att_mean_final(ws + p.ps_t, ws + p.pc_t, W, p.slabs_t, batch, att_t, s), "attention mean (temporal)");
+    if (reduce && att_f) K_TRY(launch_att_mean_final(ws + p.ps_f, ws + p.pc_f, F, p.slabs_f, batch, att_f, s), "attention mean (feature)");
+    return 0;
+}
+
+static int attention_series(mtadgat_handle h, const float* series, int64_t n_rows, const int64_t* starts, int64_t start0,
+                            int64_t stride, int64_t batch, bool reduce, float* att_f, float* att_t, void* ws, size_t ws_bytes,
+                            void* stream) {
+    if (!h) return fail(MTADGAT_ERR_INVALID, "null handle");
+    if (n_rows < h->m.W) return fail(MTADGAT_ERR_INVALID, "series shorter than one window");
+    if (!starts && (stride < 0 || start0 < 0 || (batch > 0 && start0 + (batch - 1) * stride + h->m.W > n_rows)))
+        return fail(MTADGAT_ERR_INVALID, "windows start0 + w*stride .. +W do not lie inside the series");
+    XSource src;
+    src.x = series; src.gather = 1; src.starts = starts; src.start0 = start0; src.stride = stride;
+    return attention_impl(h, src, batch, reduce, att_f, att_t, ws, ws_bytes, stream);
+}
+
+size_t mtadgat_attention_workspace_bytes(mtadgat_handle h, int64_t batch, int reduce) {
+    if (!h || batch <= 0) return 0;
+    AttPlan p;
+    plan_attention(h->m, batch, reduce != 0, p);
+    return p.total * sizeof(float);
+}
+
+int mtadgat_attention(mtadgat_handle h, const float* x, int64_t batch, float* att_feat, float* att_temp, void* ws, size_t ws_bytes,
+                      void* stream) {
+    XSource src;
+    src.x = x;
+    return attention_impl(h, src, batch, false, att_feat, att_temp, ws, ws_bytes, stream);
+}
+
+int mtadgat_attention_mean(mtadgat_handle h, const float* x, int64_t batch, float* mean_feat, float* mean_temp, void* ws,
+                           size_t ws_bytes, void* stream) {
+    XSource src;
+    src.x = x;
+    return attention_impl(h, src, batch, true, mean_feat, mean_temp, ws, ws_bytes, stream);
+}
+
+int mtadgat_attention_series(mtadgat_handle h, const float* series, int64_t n_rows, const int64_t* starts, int64_t start0,
+                             int64_t stride, int64_t batch, float* att_feat, float* att_temp, void* ws, size_t ws_bytes,
+                             void* stream) {
+    return attention_series(h, series, n_rows, starts, start0, stride, batch, false, att_feat, att_temp, ws, ws_bytes, stream);
+}
+
+int mtadgat_attention_series_mean(mtadgat_handle h, const float* series, int64_t n_rows, const int64_t* starts, int64_t start0,
+                                  int64_t stride, int64_t batch, float* mean_feat, float* mean_temp, void* ws, size_t ws_bytes,
+                                  void* stream) {
+    return attention_series(h, series, n_rows, starts, start0, stride, batch, true, mean_feat, mean_temp, ws, ws_bytes, stream);
+}
+
 int mtadgat_profile_enable(mtadgat_handle h, int on) {
     if (!h) return fail(MTADGAT_ERR_INVALID, "null handle");
     h->m.profile = on != 0;

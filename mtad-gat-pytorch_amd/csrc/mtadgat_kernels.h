@@ -446,5 +446,11 @@ int launch_copy2d(const float* src, long lds, float* dst, long ldd, long R, int 
 int launch_conv_scatter(const float* cf, const float* el, const float* er, float* hcat, long n, int W, int F, int Fp, int Dp, int pad,
                         hipStream_t s);
 int launch_transpose_win(const float* src, long lds, float* dst, long ldd, long B, int R, int C, hipStream_t s);
+// mean of (n, K, K) attention maps over windows (mtadgat_attmean.hip): slabs of the first stage for a chunk of n windows; per chunk
+// the slabs' running (sum, compensation) pairs PS / PC (nslab, K, K) are written (first != 0) or added to; the final stage writes
+// out (K, K) = their sum / n_total
+int att_mean_slabs(long n, int K);
+int launch_att_mean_part(const float* A, long n, int K, int nslab, int first, float* PS, float* PC, hipStream_t s);
+int launch_att_mean_final(const float* PS, const float* PC, int K, int nslab, long n_total, float* out, hipStream_t s);
 
 }  // namespace mtadgat

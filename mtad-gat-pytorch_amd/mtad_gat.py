@@ -443,6 +443,66 @@ class MTAD_GAT(nn.Module):
             p, r, _ = self._checked(series.device, self._use_bf16(series), lambda eng: eng.forward_series(sf, starts, start, stride, count))
         return p, r
 
+    # -- the attention maps behind a score (the two graph-attention layers' softmax matrices) ----------------------------------
+    def attention_maps(self, x, reduce=None):
+        """The post-softmax attention matrices of the two graph-attention layers for windows x (b, window_size, n_features):
+        `attention` of the reference's FeatureAttentionLayer.forward (modules.py:85-89, nodes = features) and
+        TemporalAttentionLayer.forward (modules.py:184-188, nodes = time steps); row i is the softmax over the keys j.
+        Returns (att_feat (b, F, F), att_temp (b, W, W)), or with reduce="mean" their means over the windows ((F, F), (W, W)).
+
+        The maps are always the EVAL-mode maps (no dropout), in train() and eval() alike: this method runs under
+        torch.no_grad() and does not look at or change `self.training`.  x may be float32, bfloat16 or float16; the maps are
+        float32.  GPU tensors run the HIP kernels (fp32 arithmetic whatever `self.precision` says; the mean is reduced on the
+        device), CPU tensors the package's torch-op algebra (`_torchpath.py`)."""
+        if x.dim() != 3 or x.shape[1] != self.window_size or x.shape[2] != self.n_features:
+            raise RuntimeError(f"expected input of shape (b, {self.window_size}, {self.n_features}), got {tuple(x.shape)}")
+        mean = self._attention_reduce(reduce)
+        if mean and x.shape[0] == 0:
+            raise RuntimeError("the mean attention map needs at least one window")
+        with torch.no_grad():
+            if x.device.type != "cuda":
+                return self._attention_cpu(x.float(), mean)
+            xin = x.detach().contiguous().float()
+            return self._checked(x.device, False, lambda eng: eng.attention(xin, reduce=mean))
+
+    def attention_series(self, series, starts=None, start=0, stride=1, count=None, reduce="mean"):
+        """attention_maps() over sliding windows of a series (n_rows, F), with forward_series()'s window arguments: window
+        w = series[s_w : s_w + W], s_w = starts[w] or start + w*stride (count windows; default: as many as fit).  By default
+        the mean over the windows ((F, F), (W, W)); reduce=None gives the per-window maps.  On the GPU the windows are gathered
+        from the device-resident series and, for the mean, the per-window maps never exist in full: they pass through the
+        library's workspace a chunk at a time.  Eval-mode maps, under torch.no_grad(), `self.training` untouched."""
+        mean = self._attention_reduce(reduce)
+        W = self.window_size
+        if series.dim() != 2 or series.shape[1] != self.n_features:
+            raise RuntimeError(f"series must have shape (n_rows, {self.n_features}), got {tuple(series.shape)}")
+        with torch.no_grad():
+            if series.device.type != "cuda":
+                if starts is None:
+                    n = count if count is not None else max(0, (series.shape[0] - W - start) // max(stride, 1) + 1)
+                    starts = start + torch.arange(n, dtype=torch.int64) * stride
+                if starts.numel() and (int(starts.min()) < 0 or int(starts.max()) + W > series.shape[0]):
+                    raise RuntimeError("a window does not lie inside the series")
+                if mean and starts.numel() == 0:
+                    raise RuntimeError("the mean attention map needs at least one window")
+                x = series.float().unfold(0, W, 1)[starts.cpu()].permute(0, 2, 1)
+                return self._attention_cpu(x, mean)
+            sf = series.contiguous().float()
+            return self._checked(series.device, False,
+                                 lambda eng: eng.attention_series(sf, starts, start, stride, count, reduce=mean))
+
+    @staticmethod
+    def _attention_reduce(reduce):
+        if reduce not in (None, "mean"):
+            raise ValueError(f"reduce must be None or 'mean', got {reduce!r}")
+        return reduce == "mean"
+
+    def _attention_cpu(self, x, mean):
+        import _torchpath
+        att_f, att_t = _torchpath.attention_maps(self, x)
+        if mean:
+            return att_f.double().mean(0).float(), att_t.double().mean(0).float()
+        return att_f, att_t
+
     def score_series(self, values):
         """The model evaluations of `Predictor.get_score` (reference prediction.py:51-63) for a whole
         series (N, F), fused: for every i in [0, N-W)
