@@ -324,8 +324,44 @@ int mtadgat_backward(mtadgat_handle h, const float* x_dev, int64_t batch, int64_
                      float* grads_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 /* Gradient with respect to the input windows (the reference's autograd provides it when x.requires_grad: mtad_gat.py:64-79 under
  * training.py:126; none of its callers asks).  Call right after mtadgat_backward of the same chunk, on the same stream, with the
- * same workspace: the convolution's pre-activation gradients are still in it.  dx_dev: (batch, W, F) float32, overwritten. */
+ * same workspace: the convolution's pre-activation gradients are still in it.  dx_dev: (batch, W, F) float32, overwritten.
+ * Covers every window shape the training step takes: windows of at most 64 KB (W F floats) keep one window per workgroup in LDS
+ * (k_conv_dx); larger ones run d x as a forward-style convolution of the pre-activation gradients with the flipped, transposed
+ * kernel w'[i][o][j] = w[o][i][k-1-j] (no bias, no ReLU) on the fp32 MFMA (k_conv over a pack of w' kept for such models). */
 int mtadgat_backward_input(mtadgat_handle h, int64_t batch, const void* workspace_dev, size_t workspace_bytes, float* dx_dev, void* stream);
+/* The data-only backward: mtadgat_backward's data path for one chunk -- every data gradient through the heads, recurrences,
+ * attention layers and convolution, then the input gradient into dx_dev (batch, W, F), overwritten -- without a single
+ * weight-gradient GEMM, column sum or reduction, and without a gradient buffer.  dx is bit-identical to mtadgat_backward followed
+ * by mtadgat_backward_input on the same chunk.  Arguments as mtadgat_backward's (x_dev is not read and may be NULL); workspace:
+ * mtadgat_backward_workspace_bytes. */
+int mtadgat_backward_data(mtadgat_handle h, const float* x_dev, int64_t batch, int64_t window0, float dropout_p, uint64_t seed,
+                          const float* d_preds_dev, const float* d_recons_dev, const void* tape_dev, size_t tape_bytes, float* dx_dev,
+                          void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ---- score attribution -------------------------------------------------------------------------------------------------
+ * Which input rows and channels pushed an anomaly score up.  For a series (N, F), window W and score index i with
+ * 0 <= i < N - W (the index into the per-timestamp score of Predictor.get_score, prediction.py:65-91; the scored row is
+ * series[i + W]):
+ *   slice S = series[i : i+W+1] (W+1 rows); window A = S[0:W], window B = S[1:W+1], target y = S[W, dims]
+ *   a_i(S) = sum_d w_d * ( |yhat_A[d] - y[d]| + gamma * |r_B[W-1, d] - y[d]| ),  yhat_A = preds of A, r_B = recons of B
+ * w_d = 1 / n_dims, or with scaled scores 1 / (n_dims (1 + IQR_d)), IQR_d held constant (the caller computes it).  The model is the
+ * eval-mode function (no dropout); the arithmetic is fp32.
+ *   steps == 0 (gradient):            out = d a_i / d S                                   (W+1, F), sign(0) = 0
+ *   steps == m > 0 (Integrated Grad.): out = (S - b) * (1/m) sum_{k<m} d a_i / d S at b + alpha_k (S - b), alpha_k = (k + 1/2) / m
+ * Baseline b: baseline_kind 0 zeros (baseline_dev unused), 1 one (F) row for every step of the slice, 2 a (W+1, F) slice.
+ *   series_dev (n_rows, F) float32; idx_dev (count) int64 score indices, each in [0, n_rows - W) -- not checked on the device;
+ *   dims_dev (n_dims) int32 series column of each output dimension (n_dims == out_dim), each in [0, F); dim_w_dev (n_dims) float32 w_d;
+ *   out_dev (count, W+1, F) float32, overwritten.
+ * The 2 * count * max(steps, 1) windows are evaluated in chunks of at most mtadgat_chunk_windows() windows and ~4 GiB of scratch
+ * (training forward without dropout, then mtadgat_backward_data); the sum over the steps is added in step order by one thread per
+ * output element: no atomics, identical calls give identical bits.  The precision mode is set for the call -- 0 stays 0, 1 and 2
+ * run as 2 (fp32-class) -- and restored afterwards.  MTADGAT_ERR_UNSUPPORTED when mtadgat_backward_supported is 0.
+ * Workspace: mtadgat_score_attribution_workspace_bytes(h, count, steps), 16-byte aligned. */
+size_t mtadgat_score_attribution_workspace_bytes(mtadgat_handle h, int64_t count, int steps);
+int mtadgat_score_attribution(mtadgat_handle h, const float* series_dev, int64_t n_rows, const int64_t* idx_dev, int64_t count,
+                              const int32_t* dims_dev, int n_dims, const float* dim_w_dev, float gamma, int steps,
+                              const float* baseline_dev, int baseline_kind, float* out_dev, void* workspace_dev, size_t workspace_bytes,
+                              void* stream);
 /* Diagnostics for the tests: the keep-masks (1 / 0) the kernels apply -- mask_feat (batch, F, F), mask_temp
  * (batch, W, W), mask_fc (forecast_n_linear - 1, batch, forecast_hid_dim), any may be NULL -- and the offsets
  * (floats) of the tape / backward-workspace regions (order: see mtadgat_capi.cpp). */

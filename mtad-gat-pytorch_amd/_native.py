@@ -121,6 +121,11 @@ def load_library():
     lib.mtadgat_train_layout.argtypes = [vp, i64, ctypes.POINTER(i64), ctypes.c_int]
     lib.mtadgat_forward_train.argtypes = [vp, vp, i64, i64, f32, u64, vp, vp, vp, sz, vp]
     lib.mtadgat_backward.argtypes = [vp, vp, i64, i64, f32, u64, vp, vp, vp, sz, vp, vp, sz, vp]
+    lib.mtadgat_backward_data.argtypes = [vp, vp, i64, i64, f32, u64, vp, vp, vp, sz, vp, vp, sz, vp]
+    lib.mtadgat_score_attribution_workspace_bytes.argtypes = [vp, i64, ctypes.c_int]
+    lib.mtadgat_score_attribution_workspace_bytes.restype = sz
+    lib.mtadgat_score_attribution.argtypes = [vp, vp, i64, vp, i64, vp, ctypes.c_int, vp, f32, ctypes.c_int, vp, ctypes.c_int, vp,
+                                              vp, sz, vp]
     lib.mtadgat_dropout_masks.argtypes = [vp, i64, i64, f32, u64, vp, vp, vp, vp]
     lib.mtadgat_dropout_masks_rnn.argtypes = [vp, i64, i64, f32, u64, vp, vp, vp]
     lib.mtadgat_profile_enable.argtypes = [vp, ctypes.c_int]
@@ -262,6 +267,56 @@ class Engine:
         ws = self._buf("_bws", need_w, x_like.device, fresh=False)      # (mtadgat_backward's d pre-activations are read from it)
         self._call(self.lib.mtadgat_backward_input, "backward_input", x_like.device, b, _dev_ptr(ws, "workspace"), need_w, _dev_ptr(dx, "dx"))
         return dx
+
+    def backward_data(self, x, p, seed, d_preds, d_recons, tape, window0=0):
+        """The data-only backward of one chunk (mtadgat_backward_data): d loss / d x (b, W, F) from the tape of forward_train, with
+        no weight gradient computed and no gradient buffer; bit-identical to backward() + backward_input() on the same chunk."""
+        c = self.cfg
+        b = x.shape[0]
+        dx = _empty((b, c.window_size, c.n_features), dtype=torch.float32, device=x.device)
+        if b == 0:
+            return dx
+        xp = _dev_ptr(x, "x", (b, c.window_size, c.n_features))
+        need_t = self.lib.mtadgat_tape_bytes(self.handle, b)
+        need_w = self.lib.mtadgat_backward_workspace_bytes(self.handle, b)
+        ws = self._buf("_bws", need_w, x.device)
+        self._call(self.lib.mtadgat_backward_data, "backward_data", x.device, xp, b, int(window0), float(p), int(seed),
+                   _dev_ptr(d_preds, "d_preds", (b, c.out_dim)), _dev_ptr(d_recons, "d_recons", (b, c.window_size, c.out_dim)),
+                   _dev_ptr(tape, "tape"), need_t, _dev_ptr(dx, "dx"), _dev_ptr(ws, "workspace"), need_w)
+        return dx
+
+    def score_attribution_workspace_bytes(self, count, steps):
+        return int(self.lib.mtadgat_score_attribution_workspace_bytes(self.handle, int(count), int(steps)))
+
+    def score_attribution(self, series, idx, dims, dim_w, gamma, steps, baseline=None):
+        """Attribution of the anomaly scores at indices `idx` (int64, on the series' device) to the W + 1 rows each reads:
+        (count, W + 1, F).  dims (out_dim) int32 series columns, dim_w (out_dim) float32 weights w_d, steps 0 = gradient, else
+        Integrated Gradients with `steps` midpoint nodes from `baseline` (None = zeros, (F,) or (W + 1, F))."""
+        c = self.cfg
+        W, F = c.window_size, c.n_features
+        dev = series.device
+        sp = _dev_ptr(series, "series")
+        if series.dim() != 2 or series.shape[1] != F:
+            raise RuntimeError(f"series must have shape (n_rows, {F}), got {tuple(series.shape)}")
+        for t, name, dt in ((idx, "indices", torch.int64), (dims, "dims", torch.int32)):
+            if t.dtype != dt or t.device != dev or not t.is_contiguous() or t.dim() != 1:
+                raise RuntimeError(f"{name} must be a contiguous 1-D {dt} tensor on the series' device")
+        count = idx.shape[0]
+        out = _empty((count, W + 1, F), dtype=torch.float32, device=dev)
+        if count == 0:
+            return out
+        if not self.backward_supported():
+            raise RuntimeError("score attribution needs the HIP backward, which this configuration lacks: " + self.why_not())
+        kind, bp = 0, None
+        if baseline is not None:
+            kind = 1 if baseline.dim() == 1 else 2
+            bp = _dev_ptr(baseline, "baseline", (F,) if kind == 1 else (W + 1, F))
+        need = self.score_attribution_workspace_bytes(count, steps)
+        ws = _empty((need + 3) // 4, dtype=torch.float32, device=dev)
+        self._call(self.lib.mtadgat_score_attribution, "score_attribution", dev, sp, series.shape[0], ctypes.c_void_p(idx.data_ptr()),
+                   count, ctypes.c_void_p(dims.data_ptr()), dims.shape[0], _dev_ptr(dim_w, "dim_w", (dims.shape[0],)), float(gamma),
+                   int(steps), bp, kind, _dev_ptr(out, "out"), _dev_ptr(ws, "workspace"), need)
+        return out
 
     def dropout_masks(self, batch, p, seed, device, window0=0):
         """The keep-masks the kernels apply: {"feat": (b,F,F), "temp": (b,W,W), "fc": [(b,hid)] * hidden layers}."""

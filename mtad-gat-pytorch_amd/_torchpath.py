@@ -149,3 +149,67 @@ def forward(model, x, masks=None):
     recons = recon_stage(model, h_end, masks.get("rec"))
     return preds, recons
 
+
+
+@contextlib.contextmanager
+def _eval_mode(model):
+    """Every sub-module in eval mode for the block (nn.GRU's inter-layer dropout included), the flags restored afterwards."""
+    flags = [(mod, mod.training) for mod in model.modules()]
+    try:
+        for mod, _ in flags:
+            mod.training = False
+        yield
+    finally:
+        for mod, t in flags:
+            mod.training = t
+
+
+def per_dim_scores(model, values, dims, gamma, chunk=256):
+    """|y_hat_i - y_i| + gamma |recon_i - y_i| per output dimension for every score index i of a series (N, F) -- the per-dimension
+    scores of MTAD_GAT.anomaly_scores, eval mode, from torch ops: (N - W, out_dim)."""
+    W = model.window_size
+    n = values.shape[0] - W
+    out = []
+    with torch.no_grad(), _eval_mode(model), torch.backends.cudnn.flags(enabled=False):
+        for lo in range(0, n, chunk):
+            hi = min(n, lo + chunk)
+            S = values.unfold(0, W + 1, 1)[lo:hi].permute(0, 2, 1)
+            preds, _ = forward(model, S[:, :W])
+            _, recons = forward(model, S[:, 1:])
+            y = S[:, W][:, dims]
+            out.append((preds - y).abs() + gamma * (recons[:, -1] - y).abs())
+    return torch.cat(out)
+
+
+def score_attribution(model, values, indices, dims, dim_w, gamma, steps, baseline=None, chunk=64):
+    """MTAD_GAT.score_attribution from torch ops: for each index i the slice S = values[i : i+W+1] and
+        a_i(S) = sum_d dim_w[d] * (|preds(S[0:W])[d] - S[W, dims[d]]| + gamma * |recons(S[1:W+1])[W-1, d] - S[W, dims[d]]|)
+    in eval mode; steps == 0: d a_i / d S, else (S - b) * (1/steps) sum_k d a_i / d S at b + (k + 1/2)/steps (S - b).
+    Gradients are taken with torch.autograd.grad with respect to the slices only: no parameter's .grad is touched.
+    Returns (len(indices), W + 1, F) in values' dtype."""
+    W = model.window_size
+    idx = [int(i) for i in indices]
+    dims = list(dims)
+    m = max(int(steps), 1)
+    out = []
+    with _eval_mode(model), torch.enable_grad(), torch.backends.cudnn.flags(enabled=False):
+        def grad_at(Z):
+            Z = Z.detach().requires_grad_(True)
+            preds, _ = forward(model, Z[:, :W])
+            _, recons = forward(model, Z[:, 1:])
+            y = Z[:, W][:, dims]
+            a = (dim_w * ((preds - y).abs() + gamma * (recons[:, -1] - y).abs())).sum()
+            return torch.autograd.grad(a, Z)[0]
+
+        for lo in range(0, len(idx), chunk):
+            S = torch.stack([values[i:i + W + 1] for i in idx[lo:lo + chunk]])
+            if steps == 0:
+                out.append(grad_at(S))
+                continue
+            b = torch.zeros_like(S) if baseline is None else baseline.to(S.dtype).expand_as(S)
+            total = None
+            for k in range(m):
+                g = grad_at(b + ((k + 0.5) / m) * (S - b))
+                total = g if total is None else total + g
+            out.append((S - b) * (total / m))
+    return torch.cat(out) if out else values.new_zeros((0, W + 1, values.shape[1]))

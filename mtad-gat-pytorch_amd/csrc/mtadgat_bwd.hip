@@ -809,7 +809,7 @@ __global__ void k_gat_v1_prep(const float* __restrict__ Wm, const float* __restr
     }
 }
 
-// one workgroup (256 threads) per window.  LDS: Vs [K][D + 1] | cq[K] | dk[K] | dc[K] | dd[K]
+// one workgroup (256 threads) per window.  LDS: Vs [K][D + 1] | cq[K] | dk[K] | dc[K] | dd[K] | ddw[4][K]
 __global__ __launch_bounds__(256) void k_gat_bwd_v1(const float* __restrict__ V, int ldv, int D, int K, int vt, const float* __restrict__ u,
                                                     const float* __restrict__ DE, float alpha, float* __restrict__ DV, int lddv,
                                                     float* __restrict__ part) {
@@ -822,6 +822,7 @@ __global__ __launch_bounds__(256) void k_gat_bwd_v1(const float* __restrict__ V,
     float* __restrict__ dk = cq + K;
     float* __restrict__ dc = dk + K;
     float* __restrict__ dd = dc + K;
+    float* __restrict__ ddw = dd + K;               // the four waves' column sums, added in wave order (no float atomics)
     {
         const float* __restrict__ vsrc = V + win * (long)(vt ? D : K) * ldv;
         if (!vt) {
@@ -858,7 +859,9 @@ __global__ __launch_bounds__(256) void k_gat_bwd_v1(const float* __restrict__ V,
     }
 #pragma unroll
     for (int h = 0; h < 2; ++h)
-        if (lane + 64 * h < K) atomicAdd(&dd[lane + 64 * h], colacc[h]);
+        if (lane + 64 * h < K) ddw[wave * K + lane + 64 * h] = colacc[h];
+    __syncthreads();
+    for (int j = tid; j < K; j += 256) dd[j] = ((ddw[j] + ddw[K + j]) + ddw[2 * K + j]) + ddw[3 * K + j];
     __syncthreads();
     for (int x = tid; x < K * D; x += 256) {
         const int node = x / D, col = x - node * D;
@@ -897,7 +900,7 @@ __global__ void k_gat_v1_finish(const float* __restrict__ P, const float* __rest
     }
 }
 
-size_t gat_bwd_v1_lds(int K, int D) { return ((size_t)K * (D + 1) + 4 * (size_t)K) * sizeof(float); }
+size_t gat_bwd_v1_lds(int K, int D) { return ((size_t)K * (D + 1) + 8 * (size_t)K) * sizeof(float); }
 
 int launch_gat_v1_prep(const float* Wm, const float* bv, const float* av, int E, int D, float* u, hipStream_t s) {
     hipLaunchKernelGGL(k_gat_v1_prep, dim3((unsigned)((D + 2 + 255) / 256)), dim3(256), 0, s, Wm, bv, av, E, D, u);
@@ -953,11 +956,11 @@ int launch_xdec(const float* hend, long ldh, int H, int T, long B, float* X, lon
 
 // adjoint of the decoder input x_t[j] = h_end[(t H + j) / T] (modules.py:279): d h_end[m] += sum of the T consecutive entries
 // m T .. m T + T - 1 of the window's flattened (T, H) block.  One workgroup per window: coalesced reads of the block into LDS,
-// then one thread per entry sums its T values (blocks beyond 60 KB: sums through LDS float atomics instead); H <= 256.
+// then one thread per entry sums its T values (blocks beyond 60 KB: the same sums in the same order, read from memory); H <= 256.
+// No float atomics: the result does not depend on scheduling.
 template <bool STAGED>
 __global__ __launch_bounds__(256) void k_xdec_bwd(const float* __restrict__ dX, long ldx, int H, int T, long B, float* __restrict__ dhend, long ldh) {
     extern __shared__ float xs[];                   // STAGED: the window's T x H block, flattened without the row padding
-    __shared__ float acc[256];
     const long b = blockIdx.x;
     const int tid = threadIdx.x;
     const float* __restrict__ src = dX + b * T * ldx;
@@ -971,24 +974,22 @@ __global__ __launch_bounds__(256) void k_xdec_bwd(const float* __restrict__ dX, 
             dhend[b * ldh + tid] += v;
         }
     } else {
-        acc[tid] = 0.f;
-        __syncthreads();
-        for (int f0 = 0; f0 < total; f0 += 256) {
-            const int f = f0 + tid;
-            if (f < total) {
-                const int t = f / H, j = f - t * H;
-                atomicAdd(&acc[f / T], src[(long)t * ldx + j]);
+        (void)total;
+        if (tid < H) {
+            float v = 0.f;
+            for (int k = 0; k < T; ++k) {
+                const int f = tid * T + k, t = f / H, j = f - t * H;
+                v += src[(long)t * ldx + j];
             }
+            dhend[b * ldh + tid] += v;
         }
-        __syncthreads();
-        if (tid < H) dhend[b * ldh + tid] += acc[tid];
     }
 }
 int launch_xdec_bwd(const float* dX, long ldx, int H, int T, long B, float* dhend, long ldh, hipStream_t s) {
     if (B <= 0) return 0;
     if (H > 256) return -2;
     const size_t lds = (size_t)T * H * sizeof(float);
-    if (lds <= 60 * 1024)       // (with the 1 KiB of acc below the 64 KiB that need no opt-in)
+    if (lds <= 60 * 1024)
         hipLaunchKernelGGL(k_xdec_bwd<true>, dim3((unsigned)B), dim3(256), lds, s, dX, ldx, H, T, B, dhend, ldh);
     else
         hipLaunchKernelGGL(k_xdec_bwd<false>, dim3((unsigned)B), dim3(256), 0, s, dX, ldx, H, T, B, dhend, ldh);

@@ -1,6 +1,7 @@
 // C ABI (include/mtadgat.h) over the gfx950 kernels: handle lifetime, weight upload,
 // the forward() launch sequence and the per-stage entry points.
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -1962,13 +1963,23 @@ int mtadgat_forward_train(mtadgat_handle h, const float* x, int64_t batch, int64
     return 0;
 }
 
-int mtadgat_backward(mtadgat_handle h, const float* x, int64_t batch, int64_t window0, float dropout_p, uint64_t seed,
-                     const float* d_preds, const float* d_recons, const void* tape_, size_t tape_bytes, float* grads,
-                     void* ws_, size_t ws_bytes, void* stream) {
+}  // extern "C"
+
+namespace {
+
+// The backward of one chunk.  grads == nullptr: the data path only (mtadgat_backward_data) -- the same kernels in the same order
+// produce every data gradient, so the convolution's pre-activation gradients (and the input gradient from them) are those of
+// the full backward bit for bit; no weight-gradient GEMM, column sum or reduction is issued and no gradient buffer is touched.
+// (Kernels that produce a weight-only partial beside their data output -- k_bw_pair's d a', k_gat_bwd_v1 / k_bw_v1's per-window
+// sums -- still run: their data outputs are what the layer below reads; the partials stay in the workspace.)
+int backward_impl(mtadgat_handle h, const float* x, int64_t batch, int64_t window0, float dropout_p, uint64_t seed,
+                  const float* d_preds, const float* d_recons, const void* tape_, size_t tape_bytes, float* grads,
+                  void* ws_, size_t ws_bytes, void* stream) {
     int rc = check_train(h, batch, dropout_p);
     if (rc) return rc;
     if (batch == 0) return 0;
-    if (!x || !d_preds || !d_recons || !tape_ || !grads || !ws_) return fail(MTADGAT_ERR_INVALID, "null tensor");
+    if (!d_preds || !d_recons || !tape_ || !ws_ || (grads && !x)) return fail(MTADGAT_ERR_INVALID, "null tensor");
+    const bool wg = grads != nullptr;
     Model& m = h->m;
     const BwdPlan& b = m.bw;
     const GradLayout& gl = b.gl;
@@ -2005,7 +2016,7 @@ int mtadgat_backward(mtadgat_handle h, const float* x, int64_t batch, int64_t wi
             const long lda = i > 0 ? (long)m.fc[i - 1].NT * 32 : g.Hp;
             WgradIn in;
             in.A = dy; in.lda = lddy; in.B = act; in.ldb = lda; in.R = n; in.T = 1;
-            if ((rc = run_wgrad(m, b.fc_wg[i], in, wpart, grads + gl.fc_w[i], grads + gl.fc_b[i], s))) return rc;
+            if (wg && (rc = run_wgrad(m, b.fc_wg[i], in, wpart, grads + gl.fc_w[i], grads + gl.fc_b[i], s))) return rc;
             float* y = i > 0 ? ws + ((i & 1) ? w.dz1 : w.dz0) : dhend;
             const long ldy = i > 0 ? (long)b.fcT[i].NT * 32 : g.Hp;
             if ((rc = run_rowgemm_T(m, b.fcT[i], dy, lddy, n, y, ldy, (int)ldy, false, i > 0 ? act : nullptr, lda, drop.keep_scale, s))) return rc;
@@ -2043,6 +2054,7 @@ int mtadgat_backward(mtadgat_handle h, const float* x, int64_t batch, int64_t wi
             ga.DA = da; ga.Hp = q.Hp; ga.H = q.H; ga.T = W; ga.NCG = q.NCG; ga.B = n;
             K_TRY(launch_gru_bwd(ga, s), what);
         }
+        if (!wg) return 0;
         int rc2;
         WgradIn hh;
         hh.A = da + q.Hp; hh.lda = 4L * q.Hp; hh.bshift = 1; hh.B = seq; hh.ldb = q.Hp; hh.R = RW; hh.T = W;
@@ -2058,7 +2070,7 @@ int mtadgat_backward(mtadgat_handle h, const float* x, int64_t batch, int64_t wi
         if ((rc = run_rowgemm_T(m, b.recfcT, d_recons, od, RW, dhdec, r.Hp, r.Hp, false, nullptr, 0, 1.f, s))) return rc;
         WgradIn in;
         in.A = d_recons; in.lda = od; in.B = seq_top; in.ldb = r.Hp; in.R = RW; in.T = W;
-        if ((rc = run_wgrad(m, b.recfc_wg, in, wpart, grads + gl.rec_fc_w, grads + gl.rec_fc_b, s))) return rc;
+        if (wg && (rc = run_wgrad(m, b.recfc_wg, in, wpart, grads + gl.rec_fc_w, grads + gl.rec_fc_b, s))) return rc;
         for (int l = Ld - 1; l >= 0; --l) {
             const GruPlan& q = m.rec[l];
             const float* gates = T + (l == 0 ? t.gates_d : t.gates_du[l - 1]);
@@ -2137,6 +2149,7 @@ int mtadgat_backward(mtadgat_handle h, const float* x, int64_t batch, int64_t wi
                 const float* av = m.packed_dev + gb.a_off;
                 K_TRY(launch_gat_v1_prep(Wm, bv, av, E, D, u, s), "attention backward (v1 vectors)");
                 K_TRY(launch_bw_v1(Vn, ldv, D, K, u, de, m.cfg.alpha, dv, lddv, dlr, n, s), "attention backward (v1 scores, wide)");
+                if (!wg) continue;
                 HIP_TRY(hipMemsetAsync(P, 0, (size_t)PV * sizeof(float), s));
                 K_TRY(launch_sum_rows(dlr, PV, n, PV, ws + w.sums, P, s), "attention backward (v1 sums)");
                 K_TRY(launch_gat_v1_finish(P, Wm, bv, av, E, D, grads + gl.lin_w[which], grads + gl.lin_b[which], grads + gl.a[which], s),
@@ -2151,9 +2164,9 @@ int mtadgat_backward(mtadgat_handle h, const float* x, int64_t batch, int64_t wi
             if ((rc = run_rowgemm_T(m, gb.lrT, dlr, 2L * Ep, RK, dv, lddv, gp.D, true, nullptr, 0, 1.f, s))) return rc;
             WgradIn in;
             in.A = dlr; in.lda = 2L * Ep; in.R = RK; in.T = 1; in.B = Vn; in.ldb = ldv;
-            if ((rc = run_wgrad(m, gb.wg, in, wpart, grads + gl.lin_w[which], grads + gl.lin_b[which], s))) return rc;
-            if ((rc = run_sum_rows_queued(de, (long)K * K, n, K * K, ws + w.sums_q[2 * which], grads + gl.bias[which], wpart, s))) return rc;
-            if ((rc = run_sum_rows_queued(dap, Ep, n, gp.E, ws + w.sums_q[2 * which + 1], grads + gl.a[which], wpart, s))) return rc;
+            if (wg && (rc = run_wgrad(m, gb.wg, in, wpart, grads + gl.lin_w[which], grads + gl.lin_b[which], s))) return rc;
+            if (wg && (rc = run_sum_rows_queued(de, (long)K * K, n, K * K, ws + w.sums_q[2 * which], grads + gl.bias[which], wpart, s))) return rc;
+            if (wg && (rc = run_sum_rows_queued(dap, Ep, n, gp.E, ws + w.sums_q[2 * which + 1], grads + gl.a[which], wpart, s))) return rc;
             continue;
         }
         GatBwdAttArgs aa{};
@@ -2174,6 +2187,7 @@ int mtadgat_backward(mtadgat_handle h, const float* x, int64_t batch, int64_t wi
             const float* av = m.packed_dev + gb.a_off;
             K_TRY(launch_gat_v1_prep(Wm, bv, av, E, D, u, s), "attention backward (v1 vectors)");
             K_TRY(launch_gat_bwd_v1(hcat, m.Dp, D, K, aa.vt, u, de, m.cfg.alpha, dv, lddv, dlr, n, s), "attention backward (v1 scores)");
+            if (!wg) continue;
             HIP_TRY(hipMemsetAsync(P, 0, (size_t)PV * sizeof(float), s));
             K_TRY(launch_sum_rows(dlr, PV, n, PV, ws + w.sums, P, s), "attention backward (v1 sums)");
             K_TRY(launch_gat_v1_finish(P, Wm, bv, av, E, D, grads + gl.lin_w[which], grads + gl.lin_b[which], grads + gl.a[which], s),
@@ -2193,9 +2207,9 @@ int mtadgat_backward(mtadgat_handle h, const float* x, int64_t batch, int64_t wi
         WgradIn in;
         in.A = dlr; in.lda = 2L * gb.Ep; in.R = RK; in.T = 1;
         if (which == 0) { in.B = T + t.xct; in.ldb = m.Wp; } else { in.B = hcat; in.ldb = m.Dp; }
-        if ((rc = run_wgrad(m, gb.wg, in, wpart, grads + gl.lin_w[which], grads + gl.lin_b[which], s))) return rc;
-        if ((rc = run_sum_rows_queued(de, (long)K * K, n, K * K, ws + w.sums_q[2 * which], grads + gl.bias[which], wpart, s))) return rc;
-        if ((rc = run_sum_rows_queued(dap, gb.Ep, n, gp.E, ws + w.sums_q[2 * which + 1], grads + gl.a[which], wpart, s))) return rc;
+        if (wg && (rc = run_wgrad(m, gb.wg, in, wpart, grads + gl.lin_w[which], grads + gl.lin_b[which], s))) return rc;
+        if (wg && (rc = run_sum_rows_queued(de, (long)K * K, n, K * K, ws + w.sums_q[2 * which], grads + gl.bias[which], wpart, s))) return rc;
+        if (wg && (rc = run_sum_rows_queued(dap, gb.Ep, n, gp.E, ws + w.sums_q[2 * which + 1], grads + gl.a[which], wpart, s))) return rc;
     }
     // ---- 5. convolution (modules.py:18-22)
     {
@@ -2203,9 +2217,53 @@ int mtadgat_backward(mtadgat_handle h, const float* x, int64_t batch, int64_t wi
         K_TRY(launch_dxc(hcat, dhcat, m.Dp, ws + w.dv_t, m.Fp, ws + w.dv_f, m.Wp, n, W, F, dpre, m.Fp, s), "conv pre-activation gradient");
         WgradIn in;
         in.A = dpre; in.lda = m.Fp; in.B = x; in.bmode = 1; in.R = RW; in.T = W;
-        if ((rc = run_wgrad(m, b.conv_wg, in, wpart, grads + gl.conv_w, grads + gl.conv_b, s))) return rc;
+        if (wg && (rc = run_wgrad(m, b.conv_wg, in, wpart, grads + gl.conv_w, grads + gl.conv_b, s))) return rc;
     }
     return wpart.flush();            // every weight-gradient reduction of the step, one launch
+}
+
+// d x of the chunk whose backward left its convolution pre-activation gradients in `ws`: k_conv_dx (the window in LDS) up to
+// 64 KB per window, above that the convolution of d pre with the flipped, transposed kernel (conv_wT_off) on k_conv
+int input_gradient(Model& m, int64_t batch, const float* ws, const BwdWorkspace& w, float* dx, hipStream_t s) {
+    if (!conv_dx_wide(m)) {
+        K_TRY(launch_conv_dx(ws + w.dpre, m.Fp, m.packed_dev + m.conv_wraw_off, batch, m.W, m.F, m.taps, m.pad, dx, s), "input gradient");
+        return 0;
+    }
+    if (m.taps != 2 * m.pad + 1 || !m.conv_wT_off) return fail(MTADGAT_ERR_UNSUPPORTED, "input gradient of wide windows needs an odd kernel size");
+    ConvArgs a{};
+    a.X = ws + w.dpre; a.ldx = m.Fp;
+    a.B = batch; a.W = m.W; a.F = m.F; a.Fp = m.Fp; a.Fq = m.Fp; a.taps = m.taps; a.pad = m.pad;
+    a.Wp = reinterpret_cast<const f32x4*>(m.packed_dev + m.conv_wT_off);
+    a.NT = m.convNT;
+    a.Y = dx; a.linear = 1;
+    K_TRY(launch_conv_dx_gemm(a, s), "input gradient (wide windows)");
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mtadgat_backward(mtadgat_handle h, const float* x, int64_t batch, int64_t window0, float dropout_p, uint64_t seed,
+                     const float* d_preds, const float* d_recons, const void* tape_, size_t tape_bytes, float* grads,
+                     void* ws_, size_t ws_bytes, void* stream) {
+    if (int rc = check_train(h, batch, dropout_p)) return rc;
+    if (batch > 0 && (!x || !grads)) return fail(MTADGAT_ERR_INVALID, "null tensor");
+    return backward_impl(h, x, batch, window0, dropout_p, seed, d_preds, d_recons, tape_, tape_bytes, grads, ws_, ws_bytes, stream);
+}
+
+int mtadgat_backward_data(mtadgat_handle h, const float* x, int64_t batch, int64_t window0, float dropout_p, uint64_t seed,
+                          const float* d_preds, const float* d_recons, const void* tape_, size_t tape_bytes, float* dx,
+                          void* ws_, size_t ws_bytes, void* stream) {
+    int rc = check_train(h, batch, dropout_p);
+    if (rc) return rc;
+    if (batch == 0) return 0;
+    if (!dx) return fail(MTADGAT_ERR_INVALID, "null tensor");
+    if ((rc = backward_impl(h, x, batch, window0, dropout_p, seed, d_preds, d_recons, tape_, tape_bytes, nullptr, ws_, ws_bytes, stream)))
+        return rc;
+    BwdWorkspace w;
+    plan_bwd_workspace(h->m, batch, w);
+    return input_gradient(h->m, batch, static_cast<const float*>(ws_), w, dx, (hipStream_t)stream);
 }
 
 /* The keep-masks of nn.GRU's dropout between stacked layers (reference modules.py:233 / :253): mask_gru (gru_n_layers - 1, batch, W, H),
@@ -2219,9 +2277,113 @@ int mtadgat_backward_input(mtadgat_handle h, int64_t batch, const void* ws_, siz
     BwdWorkspace w;
     plan_bwd_workspace(m, batch, w);
     if (!aligned16(ws_) || ws_bytes < w.total * sizeof(float)) return fail(MTADGAT_ERR_WORKSPACE, "backward workspace too small or misaligned");
-    if ((size_t)m.W * m.F * sizeof(float) > 64 * 1024) return fail(MTADGAT_ERR_UNSUPPORTED, "input gradient: window too large for one workgroup's LDS");
-    const float* ws = static_cast<const float*>(ws_);
-    K_TRY(launch_conv_dx(ws + w.dpre, m.Fp, m.packed_dev + m.conv_wraw_off, batch, m.W, m.F, m.taps, m.pad, dx, (hipStream_t)stream), "input gradient");
+    return input_gradient(m, batch, static_cast<const float*>(ws_), w, dx, (hipStream_t)stream);
+}
+
+/* ---- score attribution --------------------------------------------------------------------------------------------------- */
+// Per chunk: the A / B windows of `units` (index, step) units -- A windows first --, the heads' outputs and their seeds, the
+// units' targets and d a / d y, d x of every window, and the training tape / backward workspace of 2 * units windows.
+struct AttrPlan {
+    int64_t units;
+    size_t x, y, preds, recons, dpreds, drecons, gy, dx, tape, bws, total;
+    size_t tape_floats, bws_floats;
+};
+// the chunk's scratch stays below 4 GiB (MSL shape: ~2 300 windows; BASELINE config 4: ~190), and below mtadgat_chunk_windows()
+static constexpr double ATTR_WS_BYTES = 4.0 * 1024 * 1024 * 1024;
+static void plan_attribution(const Model& m, int64_t count, int steps, AttrPlan& p) {
+    const int W = m.W, F = m.F, od = m.cfg.out_dim;
+    const int64_t U = count * std::max(steps, 1);
+    Tape t64;
+    plan_tape(m, 64, t64);
+    BwdWorkspace w64;
+    plan_bwd_workspace(m, 64, w64);
+    const double per_window = ((double)(t64.total + w64.total) / 64 + 2.0 * W * F + 2.0 * (W + 1) * od + 2.0 * od) * sizeof(float);
+    int64_t win = std::min<int64_t>(m.chunk, (int64_t)(ATTR_WS_BYTES / per_window));
+    win = std::max<int64_t>(2, win / 2 * 2);
+    p.units = std::max<int64_t>(1, std::min<int64_t>(U, win / 2));
+    const size_t n = (size_t)(2 * p.units), nu = (size_t)p.units;
+    size_t off = 0;
+    auto take = [&](size_t cnt) {
+        size_t o = off;
+        off = (off + cnt + 63) / 64 * 64;
+        return o;
+    };
+    p.x = take(n * W * F);
+    p.y = take(nu * od);
+    p.preds = take(n * od);
+    p.recons = take(n * W * od);
+    p.dpreds = take(n * od);
+    p.drecons = take(n * W * od);
+    p.gy = take(nu * od);
+    p.dx = take(n * W * F);
+    Tape t;
+    plan_tape(m, (int64_t)n, t);
+    BwdWorkspace w;
+    plan_bwd_workspace(m, (int64_t)n, w);
+    p.tape_floats = t.total;
+    p.bws_floats = w.total;
+    p.tape = take(t.total);
+    p.bws = take(w.total);
+    p.total = off;
+}
+
+size_t mtadgat_score_attribution_workspace_bytes(mtadgat_handle h, int64_t count, int steps) {
+    if (!h || count < 1 || steps < 0 || !h->m.bw.supported) return 0;
+    AttrPlan p;
+    plan_attribution(h->m, count, steps, p);
+    return p.total * sizeof(float);
+}
+
+int mtadgat_score_attribution(mtadgat_handle h, const float* series, int64_t n_rows, const int64_t* idx, int64_t count,
+                              const int32_t* dims, int n_dims, const float* dim_w, float gamma, int steps, const float* baseline,
+                              int baseline_kind, float* out, void* ws_, size_t ws_bytes, void* stream) {
+    if (!h) return fail(MTADGAT_ERR_INVALID, "null handle");
+    Model& m = h->m;
+    if (!m.have_weights) return fail(MTADGAT_ERR_NOWEIGHTS, "mtadgat_load_weights has not been called");
+    if (!m.bw.supported) return fail(MTADGAT_ERR_UNSUPPORTED, "score attribution needs the HIP backward, which this configuration lacks: " + m.bw.why);
+    if (count < 0) return fail(MTADGAT_ERR_INVALID, "negative index count");
+    if (steps < 0) return fail(MTADGAT_ERR_INVALID, "steps must be >= 0 (0 = gradient)");
+    if (n_dims != m.cfg.out_dim) return fail(MTADGAT_ERR_INVALID, "n_dims must equal out_dim (one series column per output dimension)");
+    if (baseline_kind < 0 || baseline_kind > 2) return fail(MTADGAT_ERR_INVALID, "baseline_kind must be 0 (zeros), 1 (F) or 2 (W+1, F)");
+    if (baseline_kind != 0 && !baseline) return fail(MTADGAT_ERR_INVALID, "baseline is NULL");
+    if (!(std::isfinite(gamma))) return fail(MTADGAT_ERR_INVALID, "gamma must be finite");
+    if (count == 0) return 0;
+    if (n_rows < (int64_t)m.W + 1) return fail(MTADGAT_ERR_INVALID, "series shorter than window_size + 1");
+    if (!series || !idx || !dims || !dim_w || !out) return fail(MTADGAT_ERR_INVALID, "null tensor");
+    if (!ws_) return fail(MTADGAT_ERR_WORKSPACE, "workspace is NULL");
+    if (!aligned16(ws_)) return fail(MTADGAT_ERR_WORKSPACE, "workspace must be 16-byte aligned");
+    AttrPlan p;
+    plan_attribution(m, count, steps, p);
+    if (ws_bytes < p.total * sizeof(float)) return fail(MTADGAT_ERR_WORKSPACE, "workspace too small");
+    // fp32 arithmetic of the training step: mode 0 stays 0, modes 1 and 2 run as 2; restored (with profiling) on return
+    struct Restore {
+        Model& m; int precision; bool profile;
+        ~Restore() { m.precision = precision; m.profile = profile; }
+    } restore{m, m.precision, m.profile};
+    m.precision = m.precision == 0 ? 0 : 2;
+    m.profile = false;
+    hipStream_t s = (hipStream_t)stream;
+    float* ws = static_cast<float*>(ws_);
+    AttrArgs a{};
+    a.series = series; a.idx = reinterpret_cast<const long*>(idx); a.dims = dims; a.dim_w = dim_w;
+    a.base = baseline; a.base_kind = baseline_kind;
+    a.W = m.W; a.F = m.F; a.od = m.cfg.out_dim; a.steps = steps; a.gamma = gamma;
+    a.X = ws + p.x; a.Y = ws + p.y; a.preds = ws + p.preds; a.recons = ws + p.recons; a.dpreds = ws + p.dpreds; a.drecons = ws + p.drecons;
+    a.gy = ws + p.gy; a.dx = ws + p.dx; a.out = out;
+    const int64_t U = count * std::max(steps, 1);
+    int rc;
+    for (int64_t u0 = 0; u0 < U; u0 += p.units) {
+        const int64_t nu = std::min<int64_t>(p.units, U - u0);
+        a.u0 = u0; a.nu = nu;
+        K_TRY(launch_attr_gather(a, s), "attribution (gather)");
+        if ((rc = mtadgat_forward_train(h, a.X, 2 * nu, 0, 0.f, 0, ws + p.preds, ws + p.recons, ws + p.tape, p.tape_floats * sizeof(float), stream)))
+            return rc;
+        K_TRY(launch_attr_seed(a, s), "attribution (seed)");
+        if ((rc = mtadgat_backward_data(h, a.X, 2 * nu, 0, 0.f, 0, ws + p.dpreds, ws + p.drecons, ws + p.tape, p.tape_floats * sizeof(float),
+                                        ws + p.dx, ws + p.bws, p.bws_floats * sizeof(float), stream)))
+            return rc;
+        K_TRY(launch_attr_combine(a, s), "attribution (combine)");
+    }
     return 0;
 }
 

@@ -192,6 +192,8 @@ struct Model {
     size_t conv_w16_off = 0;
     size_t conv_wf16_off = 0;        // fp32 tiles in the 16-channel geometry (source of the split-bf16 pack)
     size_t conv_wraw_off = 0;        // conv.weight as the reference stores it, (F, F, taps): the input gradient of mtadgat_backward_input
+    size_t conv_wT_off = 0;          // windows of more than 64 KB only (else 0): the flipped, transposed kernel w'[i][o][j] = w[o][i][taps-1-j]
+                                     // in conv_w_off's tile format -- the input gradient as a forward-style convolution (k_conv)
     size_t conv_w3_off = 0;          // three bf16 pieces of those tiles [tile][taps Fp16 / 16][3][64], derived on the device (k_conv_x3: wide models)
     size_t conv_w2h_off = 0, conv_scale_off = 0;   // k_conv_win: two fp16 pieces of S * W [tile][taps * Fp16 / 16][2][64], [bits of max |W|, S, 1 / S, 0]
     GatPlan feat, temp;
@@ -263,6 +265,8 @@ struct BwdWorkspace {
     size_t wpart_floats;
 };
 
+// the input gradient of a window of more than 64 KB (W F floats) is the k_conv convolution over conv_wT_off instead of k_conv_dx
+inline bool conv_dx_wide(const Model& m) { return (size_t)m.W * m.F * sizeof(float) > 64 * 1024; }
 std::string validate_and_plan(Model& m);                       // "" on success
 FlatOffsets flat_offsets(const Model& m);
 void params_from_flat(const Model& m, const FlatOffsets& fo, const float* flat, mtadgat_params& p);

@@ -78,6 +78,10 @@ struct ConvArgs {
     int Dp;
     float* Y;            // (B*W, F) plain output   or null
     const f32x4* Wp3;    // split-bf16 pack [tile][taps Fq / 16][3][64] (k_conv_x3; Fq = F rounded up to 16)
+    // k_conv only (launch_conv_dx_gemm, the input gradient of wide windows): row stride of X (0 = F) and a linear epilogue --
+    // no bias, no ReLU
+    long ldx;
+    int linear;
 };
 
 // graph attention of a layer beyond k_gat_wide (K or D above 512): scores through the (B, K, K) matrix S (mtadgat_attend.hip)
@@ -436,6 +440,36 @@ int launch_xdec_bwd(const float* dX, long ldx, int H, int T, long B, float* dhen
 // dpre[(b*T + t)*ldp + f] = xc > 0 ? dhcat[.., f] + dvt[(b*T + t)*ldt + f] + dvf[(b*F + f)*ldf + t] : 0   (xc = hcat[.., f])
 // d x of the convolution (the input gradient of mtadgat_backward_input): dx[b, t, i] = sum_{o, j} w[o, i, j] dpre[b, t - j + pad, o]
 int launch_conv_dx(const float* dpre, long ldp, const float* w, long B, int T, int F, int taps, int pad, float* dx, hipStream_t s);
+// the input gradient as a forward-style convolution of the pre-activation gradients (a.X, row stride a.ldx) with the flipped,
+// transposed kernel (a.Wp: conv_wT_off), no bias, no ReLU, into a.Y (B*W, F): k_conv on the fp32 MFMA, any window shape
+int launch_conv_dx_gemm(const ConvArgs& a, hipStream_t s);
+
+// ---- score attribution (mtadgat_attrib.hip) ----
+// unit u = p * msteps + k (p: attributed index, k: IG step; msteps = max(steps, 1)); a chunk holds units [u0, u0 + nu)
+struct AttrArgs {
+    const float* series;     // (n_rows, F)
+    const long* idx;         // (count) score indices: slice S_p = series[idx[p] .. idx[p] + W]
+    const int* dims;         // (od) feature column of each output dimension
+    const float* dim_w;      // (od) w_d
+    const float* base;       // baseline: kind 0 none (zeros), 1 (F), 2 (W+1, F)
+    int base_kind;
+    int W, F, od;
+    int steps;               // 0: gradient, else IG steps m
+    float gamma;
+    long u0, nu;
+    float* X;                // (2 nu, W, F): A windows then B windows
+    float* Y;                // (nu, od) targets
+    const float* preds;      // (2 nu, od)
+    const float* recons;     // (2 nu, W, od)
+    float* dpreds;           // (2 nu, od)
+    float* drecons;          // (2 nu, W, od)
+    float* gy;               // (nu, od): d a / d y
+    const float* dx;         // (2 nu, W, F)
+    float* out;              // (count, W+1, F)
+};
+int launch_attr_gather(const AttrArgs& a, hipStream_t s);
+int launch_attr_seed(const AttrArgs& a, hipStream_t s);
+int launch_attr_combine(const AttrArgs& a, hipStream_t s);
 int launch_dxc(const float* hcat, const float* dhcat, long ldh, const float* dvt, long ldt, const float* dvf, long ldf,
                long B, int T, int F, float* dpre, long ldp, hipStream_t s);
 // keep-mask (1 / 0) of a dropout stream: mask[w*n + idx] for windows win0 + w (test hook)

@@ -301,8 +301,9 @@ __global__ __launch_bounds__(64) void k_conv(const ConvArgs a) {
     const long win = rowc / a.W;
     const int t = (int)(rowc - win * a.W);
     // gather mode: the window is a view of the device-resident series (SlidingWindowDataset.__getitem__, utils.py:114-117)
+    const long ldx = a.ldx ? a.ldx : a.F;
     const float* __restrict__ xwin = a.gather ? a.X + (a.starts ? a.starts[win] : a.start0 + win * a.stride) * (long)a.F
-                                              : a.X + win * (long)a.W * a.F;
+                                              : a.X + win * (long)a.W * ldx;
     const int QF = a.Fp >> 3;
     const int Q = a.taps * QF;
     const f32x4* __restrict__ Wp = a.Wp;
@@ -311,7 +312,7 @@ __global__ __launch_bounds__(64) void k_conv(const ConvArgs a) {
         for (int c = 3 * a.F; c < a.Dp; ++c) a.HCAT[row * a.Dp + c] = 0.f;
     // unconditional loads from clamped addresses, masked afterwards (a guarded load is a branch with a full memory
     // round trip per chunk); one 16-byte load when the rows allow it
-    const bool xvec4 = (a.F & 3) == 0;
+    const bool xvec4 = (a.F & 3) == 0 && (ldx & 3) == 0;
     auto loadx = [&](int q) -> f32x4 {
         const int tap = q / QF;
         const int cb = q - tap * QF;
@@ -319,7 +320,7 @@ __global__ __launch_bounds__(64) void k_conv(const ConvArgs a) {
         const int c0 = 8 * cb + 4 * g;
         const bool tok = tt >= 0 && tt < a.W;
         const int ttc = tt < 0 ? 0 : (tt < a.W ? tt : a.W - 1);
-        const float* p = xwin + (long)ttc * a.F;
+        const float* p = xwin + (long)ttc * ldx;
         f32x4 v;
         if (xvec4) {
             const int cc = c0 + 3 < a.F ? c0 : a.F - 4;
@@ -368,11 +369,11 @@ __global__ __launch_bounds__(64) void k_conv(const ConvArgs a) {
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
                 const int col = 32 * (n0 + nb) + 8 * m + 4 * g;
-                const f32x4 bv = *reinterpret_cast<const f32x4*>(a.bias + col);
+                const f32x4 bv = a.linear ? f32x4{0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const f32x4*>(a.bias + col);
 #pragma unroll
                 for (int s = 0; s < 4; ++s) {
                     const int o = col + s;
-                    const float v = fmaxf(acc[nb][4 * m + s] + bv[s], 0.f);
+                    const float v = a.linear ? acc[nb][4 * m + s] : fmaxf(acc[nb][4 * m + s] + bv[s], 0.f);
                     if (row < R && o < a.F) {
                         if (a.XC) a.XC[row * a.Fp + o] = v;
                         if (a.XCT) a.XCT[(win * a.F + o) * (long)a.Wpad + t] = v;
@@ -996,6 +997,19 @@ int launch_conv(const ConvArgs& a, hipStream_t s) {
         else
             hipLaunchKernelGGL(k_conv<1>, dim3(grid), dim3(64), 0, s, a);
     }
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_conv_dx_gemm(const ConvArgs& a, hipStream_t s) {
+    const long R = a.B * a.W;
+    if (R <= 0) return 0;
+    if (!a.linear || a.gather || !a.Y || a.XC || a.XCT || a.HCAT || a.vmax) return -1;
+    const unsigned grid = (unsigned)((R + 31) / 32);
+    if (a.NT >= 2)
+        hipLaunchKernelGGL(k_conv<2>, dim3(grid), dim3(64), 0, s, a);
+    else
+        hipLaunchKernelGGL(k_conv<1>, dim3(grid), dim3(64), 0, s, a);
     LAUNCH_CHECK();
     return 0;
 }

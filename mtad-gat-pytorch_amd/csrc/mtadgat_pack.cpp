@@ -118,6 +118,7 @@ std::string validate_and_plan(Model& m) {
         m.conv_w3_off = take((size_t)m.convNT * (m.taps * m.Fp16 / 16) * 3 * 256);
         m.conv_w2h_off = take((size_t)m.convNT * (m.taps * m.Fp16 / 16) * 2 * 256);
         m.conv_scale_off = take(4);
+        m.conv_wT_off = conv_dx_wide(m) ? take((size_t)m.convNT * Q * 256) : 0;
     }
     // GAT layers
     auto plan_gat = [&](GatPlan& g, int K, int D, int E) {
@@ -786,6 +787,11 @@ std::string pack_weights(Model& m, const mtadgat_params& p, std::vector<float>& 
         });
         for (int n = 0; n < F; ++n) out[m.conv_b_off + n] = p.conv_bias[n];
         for (size_t k = 0; k < (size_t)F * F * taps; ++k) out[m.conv_wraw_off + k] = p.conv_weight[k];
+        if (m.conv_wT_off)           // input gradient of wide windows: dx[t][i] = sum_{o,j} w[o][i][taps-1-j] dpre[t+j-pad][o] (odd taps)
+            pack_tiles(out.data() + m.conv_wT_off, m.convNT, taps * Fp / 8, [&](int n, int k) -> float {
+                const int tap = k / Fp, ch = k % Fp;
+                return (n < F && ch < F && tap < taps) ? p.conv_weight[((size_t)ch * F + n) * taps + (taps - 1 - tap)] : 0.f;
+            });
         const int Fp16 = m.Fp16;
         pack_tiles(out.data() + m.conv_wf16_off, m.convNT, taps * Fp16 / 8, [&](int n, int k) -> float {
             const int tap = k / Fp16, ch = k % Fp16;

@@ -546,6 +546,77 @@ class MTAD_GAT(nn.Module):
             a = (a - q[1]) / (1.0 + (q[2] - q[0]))
         return a.mean(dim=1), a
 
+    # -- which inputs pushed a score up: gradient attribution of anomaly_scores ---------------------------------------------------
+    def score_attribution(self, values, indices, target_dims=None, gamma=1.0, scale_scores=False, method="gradient", steps=32,
+                          baseline=None):
+        """Attribution of the anomaly scores at `indices` to the input rows and channels they read: (len(indices), W+1, F) float32
+        on values' device (a float64 series on the CPU, with a float64 model, is attributed in float64).
+
+        For a series `values` (N, F), window W and score index i with 0 <= i < N - W (the index into anomaly_scores' output; the
+        scored row is values[i+W]):
+          slice S = values[i : i+W+1] (W+1 rows); window A = S[0:W], window B = S[1:W+1], target y = S[W, dims]
+          a_i(S) = sum_d w_d * ( |yhat_A[d] - y[d]| + gamma * |r_B[W-1, d] - y[d]| ),  yhat_A = preds of A, r_B = recons of B
+        which equals anomaly_scores(values, target_dims, gamma, scale_scores)[0][i] (reference prediction.py:65-91).
+          w_d = 1/|dims|; with scale_scores=True w_d = 1/(|dims| (1 + IQR_d)), IQR_d from the whole series' per-dimension scores as
+          anomaly_scores computes them, held constant (the median drops out of the gradient).
+        The model is the eval-mode function (no dropout) whatever self.training is; the arithmetic is fp32.
+          method="gradient":   attr = d a_i / d S, shape (W+1, F), including the direct dependence through the target row
+                               (sign(0) = 0, as torch's abs backward)
+          method="integrated": attr = (S - b) * (1/m) sum_{k<m} d a_i / d S at b + alpha_k (S - b), alpha_k = (k + 1/2)/m, m = steps
+        baseline b: None (zeros), an (F,) vector or a (W+1, F) slice; the interpolation covers the whole slice, target row included.
+
+        GPU tensors run the HIP library (mtadgat_score_attribution: training forward without dropout and the data-only backward,
+        chunked, under no_grad); self.training, the precision setting and every p.grad are left as they were.  CPU tensors go
+        through the torch-op algebra with torch.autograd.grad with respect to the slices only."""
+        W, F = self.window_size, self.n_features
+        if values.dim() != 2 or values.shape[1] != F:
+            raise RuntimeError(f"values must have shape (N, {F}), got {tuple(values.shape)}")
+        if method not in ("gradient", "integrated"):
+            raise ValueError(f"method must be 'gradient' or 'integrated', got {method!r}")
+        m = 0
+        if method == "integrated":
+            m = int(steps)
+            if m < 1 or m != steps:
+                raise ValueError(f"steps must be a positive integer, got {steps!r}")
+        n = values.shape[0] - W
+        idx = torch.as_tensor(indices, dtype=torch.int64).reshape(-1).cpu()
+        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= n):
+            raise IndexError(f"score indices must lie in [0, {max(n, 0)}) for a series of {values.shape[0]} rows and window {W}")
+        dims = list(range(F)) if target_dims is None else ([target_dims] if isinstance(target_dims, int) else [int(d) for d in target_dims])
+        if len(dims) != self.out_dim:
+            raise RuntimeError(f"target_dims select {len(dims)} columns but the model has out_dim={self.out_dim}")
+        if any(d < 0 or d >= F for d in dims):
+            raise IndexError(f"target_dims must lie in [0, {F})")
+        dev = values.device
+        gpu = dev.type == "cuda"
+        dtype = values.dtype if (not gpu and values.dtype == torch.float64) else torch.float32
+        if baseline is not None:
+            baseline = torch.as_tensor(baseline)
+            if tuple(baseline.shape) not in ((F,), (W + 1, F)):
+                raise RuntimeError(f"baseline must have shape ({F},) or ({W + 1}, {F}), got {tuple(baseline.shape)}")
+            baseline = baseline.to(device=dev, dtype=dtype).contiguous()
+        if idx.numel() == 0:
+            return torch.zeros((0, W + 1, F), dtype=torch.float32, device=dev)
+        vf = values.detach().to(dtype).contiguous()
+        dim_w = torch.full((len(dims),), 1.0 / len(dims), dtype=torch.float64)
+        if scale_scores:
+            if gpu:
+                per_dim = self.anomaly_scores(vf, dims, gamma, False)[1]
+            else:
+                import _torchpath
+                per_dim = _torchpath.per_dim_scores(self, vf, dims, gamma)
+            qs = torch.tensor([0.25, 0.75], device=per_dim.device, dtype=per_dim.dtype)
+            q = torch.stack([_column_quantiles(per_dim[:, d], qs) for d in range(per_dim.shape[1])], dim=1)
+            dim_w = dim_w / (1.0 + (q[1] - q[0]).double().cpu())
+        if not gpu:
+            import _torchpath
+            return _torchpath.score_attribution(self, vf, idx.tolist(), dims, dim_w.to(dtype), gamma, m, baseline)
+        with torch.no_grad():
+            idx_d = idx.to(dev)
+            dims_d = torch.tensor(dims, dtype=torch.int32, device=dev)
+            w_d = dim_w.to(device=dev, dtype=torch.float32)
+            return self._checked(dev, False, lambda eng: eng.score_attribution(vf, idx_d, dims_d, w_d, gamma, m, baseline))
+
 
 def _column_quantiles(col, qs):
     """Linear-interpolation quantiles of a 1-D tensor of any length (sort based: no 16 M element limit)."""
