@@ -360,6 +360,10 @@ int run_gat_fused(Model& m, const GatPlan& g, const float* v, int ldv, int vt, i
         if (cv) a.winflag = cv->flag;    // per-window range guard: k_gat serves exactly the windows k_gath flagged
     } else if (cv) {
         return fail(MTADGAT_ERR_INVALID, "internal: fused convolution without k_gath");
+    } else if (m.cfg.use_gatv2) {
+        // without k_gath in front, k_gat would take the fp16 pieces itself -- but a GATv2 layer's fp16-piece pack is in k_gath's
+        // compact column order (launch_split2h_gath), not the 8-padded one k_gat's tiles walk: k_gat keeps the bf16 pieces
+        a.vmax = nullptr; a.Wp2 = nullptr; a.scale2 = nullptr;
     }
     K_TRY(launch_gat(a, g.f_IBL, g.f_JPL, g.f_RJ, g.f_nw, g.f_lds_bytes, s), "fused gat");
     return 0;

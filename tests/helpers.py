@@ -188,3 +188,143 @@ def training_loss(preds, recons, x, y, target_dims):
         y = y.squeeze(1)
     mse = torch.nn.MSELoss()
     return torch.sqrt(mse(y, preds)), torch.sqrt(mse(x, recons))
+
+
+# ---- float64 per-window references of large GPU calls (tests/test_gpu_large_batch_gradients.py) ---------------------------------
+# The check of a call of b windows evaluates only a sample of them: under the window-separable loss
+#     L = sum_w <cp_w, preds_w> + <cr_w, recons_w>
+# (seeded random cotangents cp, cr) d L / d x_w depends on window w alone, so the reference of a sampled window is exact.
+WINDOW_ABS, WINDOW_REL, WINDOW_NOISE_REL = 1e-6, 1e-4, 1e-5     # the global gates of the existing gradient tests, per window
+KINK_REL = 1e-6
+
+
+def model64(model):
+    """A float64 copy of `model` on the CPU in eval mode (dropout only through explicit masks)."""
+    import copy
+    return copy.deepcopy(model).cpu().double().eval()
+
+
+def separable_cotangents(b, window, out_dim, seed, device="cpu"):
+    """(cp (b, out_dim), cr (b, window, out_dim)) float32 normal cotangents of the window-separable loss."""
+    g = torch.Generator(device=device).manual_seed(seed)
+    cp = torch.randn(b, out_dim, generator=g, device=device)
+    cr = torch.randn(b, window, out_dim, generator=g, device=device)
+    return cp, cr
+
+
+def separable_input_grad(model, x, cp, cr, masks=None):
+    """d/dx of sum_w <cp_w, preds_w> + <cr_w, recons_w> through the torch-op algebra (_torchpath.forward) in model's dtype."""
+    import _torchpath
+    dt = next(model.parameters()).dtype
+    x = x.detach().to(dt).requires_grad_(True)
+    with torch.enable_grad():
+        pr, rc = _torchpath.forward(model, x, masks)
+        return torch.autograd.grad((pr * cp.to(dt)).sum() + (rc * cr.to(dt)).sum(), x)[0]
+
+
+def masks_at(eng, windows, p, seed, device, dtype=torch.float64):
+    """The library's keep-masks (Engine.dropout_masks) of the given GLOBAL windows, stacked, on the CPU in `dtype`; None for p = 0."""
+    if p <= 0.0:
+        return None
+    parts = [eng.dropout_masks(1, p, seed, device, window0=int(w)) for w in windows]
+
+    def cat(ms):
+        return torch.cat([m.cpu() for m in ms]).to(dtype)
+    out = {"feat": cat([q["feat"] for q in parts]), "temp": cat([q["temp"] for q in parts]),
+           "fc": [cat([q["fc"][i] for q in parts]) for i in range(len(parts[0]["fc"]))]}
+    for key in ("gru", "rec"):
+        if key in parts[0]:
+            out[key] = [cat([q[key][i] for q in parts]) for i in range(len(parts[0][key]))]
+    return out
+
+
+def _near_zero(t, rel):
+    """bool per window (dim 0): some entry of t within rel * (the window's max |entry|) of zero."""
+    t = t.flatten(1).abs()
+    return (t < rel * t.amax(1, keepdim=True)).any(1) if t.shape[1] else torch.zeros(t.shape[0], dtype=torch.bool)
+
+
+def kink_windows(m64, x, masks=None, rel=KINK_REL, gatv2_pairs=False):
+    """bool (k,): windows whose float64 evaluation puts a convolution ReLU, a forecasting ReLU or a GAT (v1) LeakyReLU argument
+    within `rel` of zero, relative to that layer's largest |argument| in the window.  Either side's rounding can put such a point
+    on the other side of the kink: a property of the input, not of the kernels.  gatv2_pairs: also the GATv2 LeakyReLU arguments
+    u_ij = W_l v_i + b + W_r v_j (K * K * E per layer and window) -- one sign flip there moves a sum of parameter gradients over
+    thousands of windows by more than the summation's rounding does."""
+    import torch.nn.functional as F
+    import _torchpath as tp
+    masks = masks or {}
+    with torch.no_grad():
+        x = x.to(torch.float64)
+        conv = m64.conv.conv
+        pad = (conv.kernel_size[0] - 1) // 2
+        pre = F.conv1d(F.pad(x.permute(0, 2, 1), (pad, pad)), conv.weight, conv.bias)
+        bad = _near_zero(pre, rel)
+        xc = F.relu(pre).permute(0, 2, 1)
+        for layer, v in ((m64.feature_gat, xc.permute(0, 2, 1)), (m64.temporal_gat, xc)):
+            if not layer.use_gatv2:
+                e_dim = layer.lin.weight.shape[0]
+                pv = layer.lin(v)
+                a = layer.a.squeeze(1)
+                bad |= _near_zero((pv @ a[:e_dim]).unsqueeze(2) + (pv @ a[e_dim:]).unsqueeze(1), rel)
+            elif gatv2_pairs:
+                d = v.shape[2]
+                left = F.linear(v, layer.lin.weight[:, :d], layer.lin.bias)
+                right = F.linear(v, layer.lin.weight[:, d:])
+                bad |= _near_zero(left.unsqueeze(2) + right.unsqueeze(1), rel)
+        hf = tp.feature_gat_stage(m64, xc, False, masks.get("feat"))
+        ht = tp.temporal_gat_stage(m64, xc, False, masks.get("temp"))
+        y = tp.gru_stage(m64, torch.cat([xc, hf, ht], dim=2), masks.get("gru"))
+        layers = m64.forecasting_model.layers
+        for i, lin in enumerate(layers[:-1]):
+            pre = lin(y)
+            bad |= _near_zero(pre, rel)
+            y = F.relu(pre)
+            if masks.get("fc") is not None:
+                y = y * masks["fc"][i] * (1.0 / (1.0 - m64.forecasting_model.dropout.p))
+    return bad
+
+
+def sample_windows(b, edges=(), n=32, seed=0, groups=(16, 32)):
+    """<= n window indices of a b-window call: 0, 1, the last two, both sides of every edge e (windows e - 1, e) inside the call,
+    of the last `groups`-window group edges, then seeded random windows."""
+    must = [0, 1, b - 2, b - 1]
+    for e in list(edges) + [(b - 1) // gsz * gsz for gsz in groups]:
+        must += [e - 1, e]
+    must = sorted({w for w in must if 0 <= w < b})[:n]
+    g = torch.Generator().manual_seed(seed)
+    rest = [w for w in torch.randperm(b, generator=g)[: n + len(must)].tolist() if w not in must][: n - len(must)]
+    return sorted(must + rest)
+
+
+def window_gate(ours, ref64, ref32_of, what=""):
+    """Per window w of (k, ...) tensors, s_w = max |ref64_w|: pass when max |ours_w - ref64_w| <= 1e-6 + 1e-4 s_w; otherwise only
+    when it is within the fp32 torch-op route's own distance from float64 for that window + 1e-6 + 1e-5 s_w (helpers.gate's rule).
+    ref32_of(rows) evaluates the fp32 route for the window rows it is given.  Returns the worst err / (1e-6 + 1e-4 s_w)."""
+    ours = ours.detach().cpu().double().flatten(1)
+    ref = ref64.detach().cpu().double().flatten(1)
+    assert ours.shape == ref.shape, (what, ours.shape, ref.shape)
+    assert torch.isfinite(ours).all(), f"{what}: non-finite values"
+    err, s = (ours - ref).abs().amax(1), ref.abs().amax(1)
+    bound = WINDOW_ABS + WINDOW_REL * s
+    over = (err > bound).nonzero().flatten().tolist()
+    if over:
+        ref32 = ref32_of(over).detach().cpu().double().flatten(1)
+        noise = (ref32 - ref[over]).abs().amax(1)
+        for j, r in enumerate(over):
+            lim = noise[j].item() + WINDOW_ABS + WINDOW_NOISE_REL * s[r].item()
+            assert err[r].item() <= lim, (f"{what}: row {r}: |ours - ref64| = {err[r].item():.3e} > fp32 route's {noise[j].item():.3e} "
+                                          f"+ 1e-6 + 1e-5 * {s[r].item():.3e}")
+    return (err / bound).max().item() if err.numel() else 0.0
+
+
+def attribution_chunks(count, steps, units):
+    """(u0, nu) of the chunks mtadgat_score_attribution walks: count * max(steps, 1) (index, step) units, index-major, `units` per
+    chunk."""
+    total = count * max(steps, 1)
+    return [(u0, min(units, total - u0)) for u0 in range(0, total, units)]
+
+
+def straddling_indices(count, steps, units):
+    """Positions p whose step range [p m, (p + 1) m) (m = max(steps, 1)) crosses a chunk boundary of attribution_chunks."""
+    m = max(steps, 1)
+    return [p for p in range(count) if (p * m) // units != ((p + 1) * m - 1) // units]
