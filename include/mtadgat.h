@@ -24,7 +24,10 @@
  *   - every launch goes to the HIP stream the caller passes (a hipStream_t cast
  *     to void*; NULL = the null stream) and nothing synchronises the device.
  *   - the library keeps no per-call state besides the packed weights held by
- *     the handle; one handle may be used from one thread at a time.
+ *     the handle.  A handle may be used from several streams one after
+ *     another (weight packs one call derives on the device are waited for by
+ *     later calls on other streams; the caller still orders its own buffers
+ *     and weight uploads), but not from two host threads at once.
  *   - gfx950 only.  There is no CPU implementation behind this ABI.
  */
 #ifndef MTADGAT_H
@@ -139,7 +142,8 @@ int64_t mtadgat_selfcheck_gather_table(mtadgat_handle h, const mtadgat_params* p
  * `stream` -- the tests compare the device-side re-pack with the host packer through it. */
 int64_t mtadgat_packed_floats(mtadgat_handle h);
 /* (offset, length) pairs in floats of the image regions that are derived on the device from other regions of the image
- * (the split-bf16 packs); returns their number (at most max_pairs are written) */
+ * (the split packs); returns their number (at most max_pairs are written).  out_pairs == NULL with max_pairs == 0 returns
+ * the number only. */
 int mtadgat_derived_regions(mtadgat_handle h, int64_t* out_pairs, int max_pairs);
 int mtadgat_read_packed(mtadgat_handle h, float* dst_host, int64_t n_floats, void* stream);
 

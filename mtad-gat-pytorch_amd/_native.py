@@ -435,10 +435,11 @@ class Engine:
         return out
 
     def derived_regions(self):
-        """(offset, length) pairs in floats of the image regions derived on the device from other regions (split-bf16 packs)."""
-        buf = (ctypes.c_int64 * 64)()
-        n = self.lib.mtadgat_derived_regions(self.handle, buf, 32)
-        return [(int(buf[2 * i]), int(buf[2 * i + 1])) for i in range(min(n, 32))]
+        """(offset, length) pairs in floats of the image regions derived on the device from other regions (split packs)."""
+        n = self.lib.mtadgat_derived_regions(self.handle, None, 0)
+        buf = (ctypes.c_int64 * (2 * n))()
+        n = self.lib.mtadgat_derived_regions(self.handle, buf, n)
+        return [(int(buf[2 * i]), int(buf[2 * i + 1])) for i in range(n)]
 
     def load_weights(self, sd, device, allow_device_pack=True):
         """sd: reference-format state_dict (any device).  The first load packs on the host and uploads on the current

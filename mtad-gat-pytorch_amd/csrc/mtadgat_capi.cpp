@@ -84,80 +84,40 @@ static bool conv_win_selected(const Model& m, int64_t n) {
 // Round 6: the split packs are derived LAZILY, by the first launch that reads them after an upload.  Rounds 2-5 re-derived all of
 // them behind every upload -- ~30 launches of a few microseconds each (ranges, scales, splits) after every optimizer step, although a
 // training step of the reference's batch size (256 windows) reads none of them: 0.15-0.2 ms of a 2.3 ms step.  An upload now only
-// bumps weights_version; ensure_*_split() derive on the stream of the consumer.  Calls that fork onto the second lane derive
-// everything on the caller's stream first (ensure_all_split in forward_impl), so the lanes never race for a derivation.
-int ensure_gru_split(Model& m, const GruPlan& g, hipStream_t s) {
-    if (g.split_ver == m.weights_version) return 0;
-    // the layer's power-of-two weight scale (fp16 range of the recurrent pieces), from the largest weight, on the device
-    const long outer_x = (long)(g.xmode == 1 ? m.W : 1) * g.NCG;
-    float* sc = m.packed_dev + g.scale_off;
-    HIP_TRY(hipMemsetAsync(sc, 0, 4 * sizeof(float), s));
-    K_TRY(launch_absmax(m.packed_dev + g.wx_off, outer_x * g.Qxp * 3 * 256, sc, s), "weight range");
-    K_TRY(launch_absmax(m.packed_dev + g.wh_off, (long)g.NCG * (4 * g.NCG + 2) * 3 * 256, sc, s), "weight range");
-    K_TRY(launch_scale_from_max(sc, s), "weight scale");
-    K_TRY(launch_split_x(m.packed_dev + g.wx_off, m.packed_dev + g.wx3_off, outer_x, g.Qxp, g.Qxp16, g.qb3, sc + 1, s), "split input weights");
-    if (g.wx2_off && g.qb3 > 0)
-        K_TRY(launch_split_x(m.packed_dev + g.wx_off, m.packed_dev + g.wx2_off, outer_x, g.Qxp, g.Qxp16, 0, sc + 1, s), "split input weights (fp16)");
-    K_TRY(launch_split2h(m.packed_dev + g.wh_off, m.packed_dev + g.wh3_off, g.NCG, 4 * g.NCG + 2, 2 * g.NCG + 2, 3, sc + 1, s),
-          "split-fp16 recurrent weights");
-    if (g.wxq_off)       // chunk-major copy of the two-piece input pack (k_gru_cm)
-        K_TRY(launch_reorder_xq(m.packed_dev + ((g.wx2_off && g.qb3 > 0) ? g.wx2_off : g.wx3_off), m.packed_dev + g.wxq_off, g.NCG, g.Qxp16, s),
-              "chunk-major input weights");
-    g.split_ver = m.weights_version;
-    return 0;
-}
-int ensure_conv_split(Model& m, hipStream_t s) {
-    if (m.split_ver_conv == m.weights_version) return 0;
-    // the window convolution's pack: two fp16 pieces of S * W in the 16-channel geometry; three bf16 pieces for the wide models' k_conv_x3
-    float* sc = m.packed_dev + m.conv_scale_off;
-    const int q8 = m.taps * m.Fp16 / 8;
-    HIP_TRY(hipMemsetAsync(sc, 0, 4 * sizeof(float), s));
-    K_TRY(launch_absmax(m.packed_dev + m.conv_wf16_off, (long)m.convNT * q8 * 256, sc, s), "convolution weight range");
-    K_TRY(launch_scale_from_max(sc, s), "convolution weight scale");
-    K_TRY(launch_split2h(m.packed_dev + m.conv_wf16_off, m.packed_dev + m.conv_w2h_off, m.convNT, q8, q8 / 2, 1, sc + 1, s), "split-fp16 convolution weights");
-    K_TRY(launch_split3(m.packed_dev + m.conv_wf16_off, m.packed_dev + m.conv_w3_off, m.convNT, m.taps * m.Fp16 / 8, m.taps * m.Fp16 / 16, 1, nullptr, s),
-          "split-bf16 convolution weights");
-    m.split_ver_conv = m.weights_version;
-    return 0;
-}
-int ensure_gat_split(Model& m, const GatPlan& g, hipStream_t s) {
-    const int which = &g == &m.feat ? 0 : 1;
-    if (m.split_ver_gat[which] == m.weights_version) return 0;
-    if (!g.fused && g.uQ16 > 0)
-        K_TRY(launch_split3(m.packed_dev + g.w_off, m.packed_dev + g.uw3_off, g.NT, g.Q, g.uQ16, 1, nullptr, s), "split-bf16 projection weights (row GEMM)");
-    if (g.fused) {
-        K_TRY(launch_split3(m.packed_dev + g.w_off, m.packed_dev + g.w3_off, g.NT, g.Q, g.Q16, 1, nullptr, s), "split-bf16 projection weights");
-        float* sc = m.packed_dev + g.gscale_off;
-        HIP_TRY(hipMemsetAsync(sc, 0, 4 * sizeof(float), s));
-        K_TRY(launch_absmax(m.packed_dev + g.w_off, (long)g.NT * g.Q * 256, sc, s), "projection weight range");
-        K_TRY(launch_scale_from_max(sc, s), "projection weight scale");
-        if (m.cfg.use_gatv2)     // k_gath's pack: the compact column order (non-negative group padded to 2, not 8)
-            K_TRY(launch_split2h_gath(m.packed_dev + g.w_off, m.packed_dev + g.w2h_off, g.NT_L, g.Q, g.Q16,
-                                      reinterpret_cast<const int*>(m.packed_dev + g.ord_off), g.E, sc + 1, s), "split-fp16 projection weights (compact)");
-        else
-            K_TRY(launch_split2h(m.packed_dev + g.w_off, m.packed_dev + g.w2h_off, g.NT, g.Q, g.Q16, 1, sc + 1, s), "split-fp16 projection weights");
+// bumps weights_version; each consumer calls ensure() on the group it reads (SplitTable, mtadgat_host.h), which derives the group on
+// the consumer's stream when it is stale.  A group that is current but was derived on another stream is waited for through the event
+// recorded after its last step: a handle may be used from several streams one after another.  Calls that fork onto the second lane
+// derive everything on the caller's stream first (ensure_all_split in forward_impl), so the lanes never race for a derivation.
+int ensure(Model& m, int group, hipStream_t s) {
+    SplitGroup& g = m.split.groups[group];
+    if (g.version == m.weights_version) {
+        if (s != g.stream) HIP_TRY(hipStreamWaitEvent(s, g.done, 0));
+        return 0;
     }
-    m.split_ver_gat[which] = m.weights_version;
-    return 0;
-}
-int ensure_lin_split(Model& m, const LinPlan& p, hipStream_t s) {
-    if (!p.w3_off || p.Q16 <= 0 || p.w3_version == m.weights_version) return 0;
-    K_TRY(launch_split3(m.packed_dev + p.w_off, m.packed_dev + p.w3_off, p.NT, p.Q, p.Q16, 1, nullptr, s), "split-bf16 Linear weights");
-    p.w3_version = m.weights_version;
+    float* P = m.packed_dev;
+    for (const SplitStep& t : g.steps) {
+        float* sc = P + t.scale;
+        switch (t.op) {
+        case SplitStep::ZERO_SCALE: HIP_TRY(hipMemsetAsync(sc, 0, 4 * sizeof(float), s)); break;
+        case SplitStep::ABSMAX: K_TRY(launch_absmax(P + t.src, t.n, sc, s), "weight range"); break;
+        case SplitStep::SCALE_FROM_MAX: K_TRY(launch_scale_from_max(sc, s), "weight scale"); break;
+        case SplitStep::SPLIT3: K_TRY(launch_split3(P + t.src, P + t.dst, t.n, t.Qs, t.Qd, 1, nullptr, s), "split-bf16 weights"); break;
+        case SplitStep::SPLIT2H: K_TRY(launch_split2h(P + t.src, P + t.dst, t.n, t.Qs, t.Qd, t.arg, sc + 1, s), "split-fp16 weights"); break;
+        case SplitStep::SPLIT2H_GATH:
+            K_TRY(launch_split2h_gath(P + t.src, P + t.dst, (int)t.n, t.Qs, t.Qd, reinterpret_cast<const int*>(P + t.ord), t.arg, sc + 1, s), "split-fp16 weights"); break;
+        case SplitStep::SPLIT_X: K_TRY(launch_split_x(P + t.src, P + t.dst, t.n, t.Qs, t.Qd, t.arg, sc + 1, s), "split input weights"); break;
+        case SplitStep::REORDER_XQ: K_TRY(launch_reorder_xq(P + t.src, P + t.dst, (int)t.n, t.Qd, s), "chunk-major input weights"); break;
+        }
+    }
+    HIP_TRY(hipEventRecord(g.done, s));
+    g.version = m.weights_version;
+    g.stream = s;
     return 0;
 }
 // everything an inference call may read, on ONE stream (no-ops while the weights are unchanged)
 int ensure_all_split(Model& m, hipStream_t s) {
-    int rc;
-    for (const GruPlan& g : m.gru) {
-        if ((rc = ensure_gru_split(m, g, s))) return rc;
-        if (g.has_xproj && (rc = ensure_lin_split(m, g.xproj, s))) return rc;
-    }
-    for (const GruPlan& g : m.rec)
-        if ((rc = ensure_gru_split(m, g, s))) return rc;
-    if ((rc = ensure_lin_split(m, m.rec_fc, s))) return rc;
-    if ((rc = ensure_conv_split(m, s))) return rc;
-    if ((rc = ensure_gat_split(m, m.feat, s)) || (rc = ensure_gat_split(m, m.temp, s))) return rc;
+    for (int i = 0; i < m.split.n_infer; ++i)
+        if (int rc = ensure(m, i, s)) return rc;
     return 0;
 }
 // geo (optional): the rows are cut into `geo_W`-row windows instead of the model's W-row ones (run_conv_shared)
@@ -198,7 +158,7 @@ int run_conv(Model& m, const XSource& src, int64_t c0, int64_t n, float* xc, flo
     if (conv_win_selected(m, n) && !geo_W && hcat && !xc && !xct && !y) {
         ConvArgs b = a;
         b.Fq = m.Fp16;
-        if (int rc_ = ensure_conv_split(m, s)) return rc_;
+        if (int rc_ = ensure(m, m.conv_split, s)) return rc_;
         b.Wp = reinterpret_cast<const f32x4*>(m.packed_dev + m.conv_w2h_off);
         b.wscale = m.packed_dev + m.conv_scale_off + 1;
         if (conv_win_applies(b)) {
@@ -209,7 +169,7 @@ int run_conv(Model& m, const XSource& src, int64_t c0, int64_t n, float* xc, flo
     // wide models (rows too long for the LDS-staged kernels): the straight-from-memory kernel on three bf16 pieces per operand
     if (m.precision == 2 && !a.bf16 && !src.x_bf16 && m.conv_kernel != 1 && (n * Wk >= 65536 || m.conv_kernel == 2) &&
         (size_t)(32 + m.taps - 1) * (m.Fp + 4) * sizeof(float) > 20 * 1024) {
-        if (int rc_ = ensure_conv_split(m, s)) return rc_;
+        if (int rc_ = ensure(m, m.conv_split, s)) return rc_;
         a.Wp3 = reinterpret_cast<const f32x4*>(m.packed_dev + m.conv_w3_off);
         a.Fq = m.Fp16;
     }
@@ -267,7 +227,7 @@ int run_proj(Model& m, const GatPlan& g, const float* rows, long ld, int64_t nro
     a.R = nrows; a.NT = g.NT; a.relu = 0;
     a.NT_rm = g.NT_L; a.YT = rt; a.group = g.K; a.YT_rows = g.rt_rows; a.YT_ld = g.Kp;
     if (m.precision == 2 && g.uw3_off && g.uQ16 > 0 && m.rowgemm_kernel != 1 && (nrows >= 65536 || m.rowgemm_kernel == 2)) {       // wide layers: three bf16 pieces per operand
-        if (int rc_ = ensure_gat_split(m, g, s)) return rc_;
+        if (int rc_ = ensure(m, g.split, s)) return rc_;
         a.x3 = 1; a.Q16 = g.uQ16;
         a.Wp3 = reinterpret_cast<const f32x4*>(m.packed_dev + g.uw3_off);
     }
@@ -326,7 +286,7 @@ int run_gat_fused(Model& m, const GatPlan& g, const float* v, int ldv, int vt, i
         // beside the pair grid of the other waves (the fp32 MFMA does not: profiles/r02_mfma_valu_overlap.txt).  Measured at
         // (W=100, F=55): feature layer 5.90 -> 5.09 ms, temporal layer 7.40 -> 6.94 ms (two weight chunks in registers; with
         // four the temporal layer's larger pair-grid block spilled and lost)
-        if (int rc_ = ensure_gat_split(m, g, s)) return rc_;
+        if (int rc_ = ensure(m, g.split, s)) return rc_;
         a.bf16 = 2; a.Q = g.Q16;
         a.Wp = reinterpret_cast<const f32x4*>(m.packed_dev + g.w3_off);
         // two fp16 pieces instead when the convolution that produced the node values recorded a maximum below 2^15
@@ -420,7 +380,7 @@ int run_gat_layer(Model& m, const GatPlan& g, const float* v, int ldv, int64_t n
 // launches per 896-window chunk, 42 of its 268 ms per 8 192 windows).
 int lin_split_operands(Model& m, const LinPlan& p, long rows, RowGemmArgs& a, hipStream_t s) {
     if (!p.w3_off || p.Q16 <= 0 || m.precision != 2 || m.rowgemm_kernel == 1 || !(rows >= 65536 || m.rowgemm_kernel == 2)) return 0;
-    if (int rc_ = ensure_lin_split(m, p, s)) return rc_;
+    if (int rc_ = ensure(m, p.split, s)) return rc_;
     a.x3 = 1; a.Q16 = p.Q16;
     a.Wp3 = reinterpret_cast<const f32x4*>(m.packed_dev + p.w3_off);
     return 0;
@@ -534,7 +494,7 @@ int run_gru_layer(Model& m, int slot, const GruPlan& g, const float* x, long ldx
         a.bf16 = 1;
     }
     if (x3 || sp_train) {
-        if (int rc_ = ensure_gru_split(m, g, s)) return rc_;
+        if (int rc_ = ensure(m, g.split, s)) return rc_;
     }
     if (x3) {
         a.Wx = reinterpret_cast<const f32x4*>(m.packed_dev + g.wx3_off);
@@ -803,6 +763,20 @@ static void free_lane(Model& m) {
     m.lane_device = -1;
 }
 
+// the packed image and the split groups' events (created with it) belong to the device they were allocated on
+static void free_image(Model& m) {
+    if (!m.packed_dev) return;
+    int cur = 0;
+    const bool sw = hipGetDevice(&cur) == hipSuccess && cur != m.packed_device;
+    if (sw) (void)hipSetDevice(m.packed_device);
+    for (SplitGroup& g : m.split.groups)
+        if (g.done) { (void)hipEventDestroy(g.done); g.done = nullptr; }
+    (void)hipFree(m.packed_dev);
+    if (sw) (void)hipSetDevice(cur);
+    m.packed_dev = nullptr;
+    m.have_weights = false;
+}
+
 int mtadgat_destroy(mtadgat_handle h) {
     if (!h) return 0;
     free_device_tables(h->m);
@@ -812,20 +786,13 @@ int mtadgat_destroy(mtadgat_handle h) {
     }
     free_lane(h->m);
     if (h->m.staging_pinned) (void)hipHostFree(h->m.staging_pinned);
-    if (h->m.packed_dev) (void)hipFree(h->m.packed_dev);
+    free_image(h->m);
     for (auto& v : h->m.ev)
         for (auto& p : v) {
             (void)hipEventDestroy(p.first);
             (void)hipEventDestroy(p.second);
         }
     delete h;
-    return 0;
-}
-
-// split-bf16 packs of the large-batch recurrences, derived on the device from the fp32 packs of the image
-// an upload happened: every derived pack is stale from here on
-static int run_split3(Model& m, hipStream_t) {
-    ++m.weights_version;
     return 0;
 }
 
@@ -839,17 +806,15 @@ int mtadgat_load_weights(mtadgat_handle h, const mtadgat_params* p, void* stream
     // another GPU gets a fresh allocation there
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
-    if (m.packed_dev && m.packed_device != dev) {
-        int cur = dev;
-        (void)hipSetDevice(m.packed_device);
-        (void)hipFree(m.packed_dev);
-        (void)hipSetDevice(cur);
-        m.packed_dev = nullptr;
-        m.have_weights = false;
-    }
+    if (m.packed_dev && m.packed_device != dev) free_image(m);
     if (!m.packed_dev) {
         HIP_TRY(hipMalloc(reinterpret_cast<void**>(&m.packed_dev), m.packed_floats * sizeof(float)));
         m.packed_device = dev;
+        for (SplitGroup& g : m.split.groups)
+            if (hipError_t e = hipEventCreateWithFlags(&g.done, hipEventDisableTiming)) {
+                free_image(m);
+                return hip_fail(e, "hipEventCreateWithFlags");
+            }
     }
     hipStream_t s = (hipStream_t)stream;
     // Stream-ordered upload without a device synchronisation: the packed image goes through a pinned staging
@@ -868,7 +833,7 @@ int mtadgat_load_weights(mtadgat_handle h, const mtadgat_params* p, void* stream
     std::memcpy(m.staging_pinned, host.data(), m.packed_floats * sizeof(float));
     HIP_TRY(hipMemcpyAsync(m.packed_dev, m.staging_pinned, m.packed_floats * sizeof(float), hipMemcpyHostToDevice, s));
     HIP_TRY(hipEventRecord(m.upload_ev, s));
-    { int rc = run_split3(m, s); if (rc) return rc; }
+    ++m.weights_version;                 // every split pack is stale from here on
     m.have_weights = true;
     return 0;
 }
@@ -951,7 +916,7 @@ int mtadgat_update_weights_device(mtadgat_handle h, const float* flat_dev, int64
         a.prefix = t.foldsum_dev;
         K_TRY(launch_pack_fold(a, s), "decoder input fold");
     }
-    { int rc = run_split3(m, s); if (rc) return rc; }      // the split packs follow the fp32 packs they are derived from
+    ++m.weights_version;                 // the split packs follow the fp32 packs they are derived from
     m.bf16_packed = false;
     return 0;
 }
@@ -975,52 +940,16 @@ int mtadgat_params_fingerprint(const void* const* tensors_dev, const int64_t* n_
     return 0;
 }
 
-/* (offset, length) pairs, in floats, of the regions of the packed image that are derived on the device from other
- * regions (the split-bf16 packs); returns the number of pairs */
+/* (offset, length) pairs, in floats, of the regions of the packed image reserved for split packs (derived on the device from
+ * other regions); at most max_pairs are written, the number of regions is returned */
 int mtadgat_derived_regions(mtadgat_handle h, int64_t* out, int max_pairs) {
-    if (!h || !out) return 0;
-    const Model& m = h->m;
-    int n = 0;
-    auto add = [&](size_t off, size_t len) {
-        if (n < max_pairs) { out[2 * n] = (int64_t)off; out[2 * n + 1] = (int64_t)len; }
-        ++n;
-    };
-    auto one = [&](const GruPlan& g) {
-        add(g.wx3_off, (size_t)(g.xmode == 1 ? m.W : 1) * g.NCG * g.Qxp16 * 9 * 256);
-        add(g.wh3_off, (size_t)g.NCG * (2 * g.NCG + 2) * 6 * 256 + 3 * 256);
-        add(g.scale_off, 4);
-        if (g.wx2_off) add(g.wx2_off, (size_t)g.NCG * g.Qxp16 * 6 * 256 + 3 * 256);
-        if (g.wxq_off) add(g.wxq_off, (size_t)g.NCG * g.Qxp16 * 6 * 256 + 3 * 256);
-    };
-    for (const GruPlan& g : m.gru) one(g);
-    for (const GruPlan& g : m.rec) one(g);
-    add(m.feat.w3_off, (size_t)m.feat.NT * m.feat.Q16 * 3 * 256);
-    add(m.temp.w3_off, (size_t)m.temp.NT * m.temp.Q16 * 3 * 256);
-    if (m.bw.supported) {
-        for (const GruBwdPlan& gb : m.bw.gru) add(gb.wihT.w3_off, (size_t)gb.wihT.NT * gb.wihT.Q16 * 3 * 256);
-        for (const GruBwdPlan& gb : m.bw.rec) add(gb.wihT.w3_off, (size_t)gb.wihT.NT * gb.wihT.Q16 * 3 * 256);
-        for (size_t l = 0; l < m.bw.gru.size(); ++l)
-            if (m.bw.gru[l].whT3_off) add(m.bw.gru[l].whT3_off, (size_t)m.gru[l].NCG * 6 * m.gru[l].NCG * 3 * 256);
-        for (size_t l = 0; l < m.bw.rec.size(); ++l)
-            if (m.bw.rec[l].whT3_off) add(m.bw.rec[l].whT3_off, (size_t)m.rec[l].NCG * 6 * m.rec[l].NCG * 3 * 256);
-        for (const LinTPlan& p : m.bw.fcT) add(p.w3_off, (size_t)p.NT * p.Q16 * 3 * 256);
-        add(m.bw.recfcT.w3_off, (size_t)m.bw.recfcT.NT * m.bw.recfcT.Q16 * 3 * 256);
-        for (int k = 0; k < 2; ++k) add(m.bw.gat[k].lrT.w3_off, (size_t)m.bw.gat[k].lrT.NT * m.bw.gat[k].lrT.Q16 * 3 * 256);
-        for (int k = 0; k < 2; ++k)
-            if (m.bw.gat[k].wu3_off) add(m.bw.gat[k].wu3_off, (size_t)2 * m.bw.gat[k].NTu * (((k == 0 ? m.feat : m.temp).Q + 1) / 2) * 3 * 256);
+    if (!h || (!out && max_pairs > 0)) return 0;
+    const std::vector<std::pair<size_t, size_t>>& r = h->m.split.regions;
+    for (int i = 0; i < max_pairs && i < (int)r.size(); ++i) {
+        out[2 * i] = (int64_t)r[i].first;
+        out[2 * i + 1] = (int64_t)r[i].second;
     }
-    for (const GruPlan& g : m.gru)
-        if (g.has_xproj && g.xproj.w3_off) add(g.xproj.w3_off, (size_t)g.xproj.NT * g.xproj.Q16 * 3 * 256);
-    if (m.rec_fc.w3_off) add(m.rec_fc.w3_off, (size_t)m.rec_fc.NT * m.rec_fc.Q16 * 3 * 256);
-    add(m.conv_w3_off, (size_t)m.convNT * (m.taps * m.Fp16 / 16) * 3 * 256);
-    for (const GatPlan* g : {&m.feat, &m.temp}) add(g->uw3_off, (size_t)g->NT * g->uQ16 * 3 * 256);
-    add(m.conv_w2h_off, (size_t)m.convNT * (m.taps * m.Fp16 / 16) * 2 * 256);
-    add(m.conv_scale_off, 4);
-    for (const GatPlan* g : {&m.feat, &m.temp}) {
-        add(g->w2h_off, (size_t)g->NT * g->Q16 * 2 * 256);
-        add(g->gscale_off, 4);
-    }
-    return n;
+    return (int)r.size();
 }
 
 /* Host-only self check of the device-side re-pack's gather table (no GPU needed): packs `p` with the host packer, builds
@@ -1676,10 +1605,7 @@ int run_rowgemm_T(Model& m, const LinTPlan& p, const float* X, long ldx, long R,
     // split-bf16 operands from 64 Ki rows on (batches of >= 656 windows at W = 100: below that the product is a few tens of
     // microseconds either way and the pack would have to be re-split after every optimizer step for nothing)
     if (p.w3_off && ((m.precision == 2 && m.rowgemm_kernel != 1 && R >= 65536) || m.rowgemm_kernel == 2)) {
-        if (p.w3_version != m.weights_version) {
-            K_TRY(launch_split3(m.packed_dev + p.w_off, m.packed_dev + p.w3_off, p.NT, p.Q, p.Q16, 1, nullptr, s), "split-bf16 transposed weights");
-            p.w3_version = m.weights_version;
-        }
+        if (int rc_ = ensure(m, p.split, s)) return rc_;
         a.x3 = 1; a.Q16 = p.Q16;
         a.Wp3 = reinterpret_cast<const f32x4*>(m.packed_dev + p.w3_off);
     }
@@ -1697,12 +1623,8 @@ int run_bwd_projection(Model& m, const GatPlan& gp, const GatBwdPlan& gb, const 
     r.Y = LR; r.ldy = 2L * gb.Ep; r.Nvalid = 2 * gb.Ep; r.vec_store = 1;
     r.R = rows; r.NT = 2 * gb.NTu; r.NT_rm = 2 * gb.NTu; r.group = 1; r.relu = 0;
     if (gb.wu3_off && ((m.precision == 2 && m.rowgemm_kernel != 1 && rows >= 65536) || m.rowgemm_kernel == 2)) {
-        const int Q16 = (gp.Q + 1) / 2;
-        if (gb.wu3_version != m.weights_version) {
-            K_TRY(launch_split3(m.packed_dev + gb.wu_off, m.packed_dev + gb.wu3_off, 2 * gb.NTu, gp.Q, Q16, 1, nullptr, s), "split-bf16 projection weights (backward)");
-            gb.wu3_version = m.weights_version;
-        }
-        r.x3 = 1; r.Q16 = Q16;
+        if (int rc_ = ensure(m, gb.split, s)) return rc_;
+        r.x3 = 1; r.Q16 = (gp.Q + 1) / 2;
         r.Wp3 = reinterpret_cast<const f32x4*>(m.packed_dev + gb.wu3_off);
     }
     K_TRY(launch_rowgemm(r, s), "attention backward (projection)");
@@ -2047,11 +1969,7 @@ int backward_impl(mtadgat_handle h, const float* x, int64_t batch, int64_t windo
             ga.Gates = gates; ga.Seq = seq; ga.DHseq = dhseq; ga.lddh = q.Hp; ga.DHend = dhend_; ga.ldde = q.Hp;
             ga.WhT = reinterpret_cast<const f32x4*>(m.packed_dev + qb.whT_off);
             if (m.precision == 2 && qb.whT3_off) {       // default arithmetic: three bf16 pieces per operand (split on first use after an upload)
-                if (qb.whT3_version != m.weights_version) {
-                    K_TRY(launch_split3(m.packed_dev + qb.whT_off, m.packed_dev + qb.whT3_off, q.NCG, 12 * q.NCG, 6 * q.NCG, 1, nullptr, s),
-                          "split-bf16 transposed recurrent weights");
-                    qb.whT3_version = m.weights_version;
-                }
+                if (int rc_ = ensure(m, qb.split, s)) return rc_;
                 ga.WhT = reinterpret_cast<const f32x4*>(m.packed_dev + qb.whT3_off);
                 ga.x3 = 1;
             }

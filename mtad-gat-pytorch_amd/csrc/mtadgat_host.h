@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/mtadgat.h"
@@ -11,6 +12,32 @@
 namespace mtadgat {
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+
+// ---- split packs ---------------------------------------------------------------------------------------------------------------
+// Copies of fp32 packs of the image as two fp16 or three bf16 pieces, and power-of-two scale slots [bits of max |W|, S, 1 / S, 0],
+// read by the large-batch kernels.  validate_and_plan records every region it reserves for them and, per group, the steps that
+// derive them from the fp32 packs; the first call after an upload that reads a group derives it on the device (ensure,
+// mtadgat_capi.cpp).  Plans refer to their group by its index (-1: none).
+struct SplitStep {
+    enum Op : uint8_t { ZERO_SCALE, ABSMAX, SCALE_FROM_MAX, SPLIT3, SPLIT2H, SPLIT2H_GATH, SPLIT_X, REORDER_XQ } op;
+    size_t scale = 0;           // the group's scale slots: zeroed, ranged (ABSMAX), scaled; the fp16-piece kinds read S from them
+    size_t src = 0, dst = 0;    // offsets (floats) of the fp32 pack read and of the region written
+    long n = 0;                 // ABSMAX: floats of src; the others: outer count (tiles, column groups; SPLIT2H_GATH: NT_L)
+    int Qs = 0, Qd = 0;         // chunks per tile of src / dst
+    int arg = 0;                // SPLIT2H: G; SPLIT_X: leading chunks kept on three bf16 pieces; SPLIT2H_GATH: E
+    size_t ord = 0;             // SPLIT2H_GATH: the layer's column order [P8, PT, npos, 0]
+};
+struct SplitGroup {                 // derived together, in step order
+    std::vector<SplitStep> steps;
+    uint64_t version = 0;           // Model::weights_version the group was last derived from,
+    hipStream_t stream = nullptr;   // on this stream;
+    hipEvent_t done = nullptr;      // recorded there after the last step (created with the packed image, on its device)
+};
+struct SplitTable {
+    std::vector<std::pair<size_t, size_t>> regions;   // (offset, floats) of every region reserved for split packs, in image order
+    std::vector<SplitGroup> groups;
+    int n_infer = 0;                // groups [0, n_infer): what an inference call may read (the rest: the training backward's)
+};
 
 // Packed projection of one GAT layer (see mtadgat_pack.cpp / DESIGN.md section 3)
 struct GatPlan {
@@ -46,6 +73,7 @@ struct GatPlan {
     // un-fused path (projections through HBM, wide layers): split-bf16 pack of the row GEMM's tiles [tile][uQ16][3][64] (k_rowgemm_x3)
     int uQ16 = 0;
     size_t uw3_off = 0;
+    int split = -1;         // fused: w3, gscale, w2h; un-fused: uw3
 };
 
 struct LinPlan {
@@ -56,7 +84,7 @@ struct LinPlan {
     // recon_model.fc
     int Q16 = 0;
     size_t w3_off = 0;
-    mutable uint64_t w3_version = 0;
+    int split = -1;
 };
 
 struct GruPlan {
@@ -67,7 +95,7 @@ struct GruPlan {
     // rows (b*T, in_dim) -> (b*T, 3*Hp) [W_ir x + b_ir + b_hr | W_iz x + b_iz + b_hz | W_in x + b_in]
     bool has_xproj = false;
     LinPlan xproj;
-    mutable uint64_t split_ver = 0;   // Model::weights_version the layer's split packs (scale, wx3, wx2, wh3, wxq) were derived from
+    int split = -1;         // the layer's split packs: scale, wx3, wx2, wh3, wxq
     // bf16 operand packs (16-feature chunks, element order of mtadgat_device.h): same streams, half the bytes per feature
     int Qxp16 = 0;          // packed input chunks (1, or a multiple of 3)
     size_t wx16_off = 0, wh16_off = 0;
@@ -102,7 +130,7 @@ struct LinTPlan {
     size_t w_off = 0;
     int Q16 = 0;         // 16-feature chunks of the split-bf16 pack [tile][Q16][3 pieces][64], derived on the device (k_rowgemm_x3)
     size_t w3_off = 0;
-    mutable uint64_t w3_version = 0;   // the weight upload the split pack was derived from (derived on first use after an upload)
+    int split = -1;
 };
 // one weight-gradient GEMM: shapes, index maps into the flat gradient buffer (ints stored in the packed buffer)
 struct WgradPlan {
@@ -114,7 +142,7 @@ struct GatBwdPlan {
     int Ep = 0, NTu = 0;            // E rounded up to 32, tiles per side
     size_t wu_off = 0;              // un-scaled projection tiles [2*NTu][Q][64]
     size_t wu3_off = 0;             // ... as three bf16 pieces [2*NTu][(Q + 1) / 2][3][64], derived on first use after an upload (k_rowgemm_x3, GATv2)
-    mutable uint64_t wu3_version = 0;
+    int split = -1;                 // wu3
     size_t a_off = 0;               // a (Ep floats, zero padded)
     LinTPlan lrT;                   // d V += [dL | dR] [W_l ; W_r]
     WgradPlan wg;                   // lin.weight / lin.bias
@@ -129,7 +157,7 @@ struct GatBwdPlan {
 struct GruBwdPlan {
     size_t whT_off = 0;             // W_hh^T tiles for k_gru_bwd
     size_t whT3_off = 0;            // ... as three bf16 pieces [NCG][6*NCG][3][64], derived on first use after an upload (k_gru_bwd<true>)
-    mutable uint64_t whT3_version = 0;
+    int split = -1;                 // whT3
     LinTPlan wihT;                  // d x = d a W_ih
     WgradPlan wg_ih, wg_hh;
 };
@@ -196,6 +224,7 @@ struct Model {
                                      // in conv_w_off's tile format -- the input gradient as a forward-style convolution (k_conv)
     size_t conv_w3_off = 0;          // three bf16 pieces of those tiles [tile][taps Fp16 / 16][3][64], derived on the device (k_conv_x3: wide models)
     size_t conv_w2h_off = 0, conv_scale_off = 0;   // k_conv_win: two fp16 pieces of S * W [tile][taps * Fp16 / 16][2][64], [bits of max |W|, S, 1 / S, 0]
+    int conv_split = -1;             // conv_scale, conv_w2h, conv_w3
     GatPlan feat, temp;
     std::vector<GruPlan> gru, rec;
     std::vector<LinPlan> fc;
@@ -219,10 +248,8 @@ struct Model {
     int64_t chunk = 65536;
     int wgrad_kernel = 0;            // weight-gradient GEMMs of the training step (testing hook): 0 automatic (split-bf16 operands in mode 2), 1 fp32 MFMA, 2 split-bf16 always
     int conv_shared = 0;             // series scoring (testing hook): 1 keeps the shared-row convolution where the window-per-workgroup kernel would run
-    uint64_t weights_version = 0;    // counts weight uploads / device-side re-packs
-    // the split packs (two-fp16-piece / three-bf16-piece copies of the fp32 packs, power-of-two scales) are derived on the device
-    // on first use after an upload: the upload each of them was last derived from (ensure_*_split, mtadgat_capi.cpp)
-    uint64_t split_ver_conv = 0, split_ver_gat[2] = {0, 0};
+    uint64_t weights_version = 0;    // counts weight uploads / device-side re-packs: a split group of another version is stale
+    SplitTable split;
     int rowgemm_kernel = 0;          // data-gradient row GEMMs of mtadgat_backward in mode 2 (testing hook): 0 automatic (split-bf16 operands from 4096 rows), 1 fp32 MFMA, 2 split-bf16 always
     int conv_kernel = 0;             // convolution of the fused front end in mode 2 (testing hook): 0 automatic (k_conv_win from 4096 windows), 1 k_conv_lds, 2 k_conv_win at any batch size
     int gath_dbg = 0;                // measurement hook: GatArgs::dbg of k_gath (knock-out bits, profiles/gath_knockout.py)

@@ -105,6 +105,12 @@ std::string validate_and_plan(Model& m) {
         off = align64(off + n);
         return o;
     };
+    // split packs (SplitTable): take_split reserves a region for one, split_group records the steps that derive a group of them
+    using S = SplitStep;
+    m.split = SplitTable();
+    auto take_split = [&](size_t n) { const size_t o = take(n); m.split.regions.emplace_back(o, n); return o; };
+    auto split_group = [&](std::vector<SplitStep> st) { m.split.groups.push_back(SplitGroup{std::move(st)}); return (int)m.split.groups.size() - 1; };
+    auto lin_split = [&](auto& p) { p.split = split_group({{S::SPLIT3, 0, p.w_off, p.w3_off, p.NT, p.Q, p.Q16}}); };
     // conv
     m.convNT = (m.F + 31) / 32;
     {
@@ -115,10 +121,18 @@ std::string validate_and_plan(Model& m) {
         m.Fp16 = round_up(m.F, 16);
         m.conv_w16_off = take((size_t)m.convNT * (m.taps * m.Fp16 / 16) * 256);
         m.conv_wf16_off = take((size_t)m.convNT * (m.taps * m.Fp16 / 8) * 256);
-        m.conv_w3_off = take((size_t)m.convNT * (m.taps * m.Fp16 / 16) * 3 * 256);
-        m.conv_w2h_off = take((size_t)m.convNT * (m.taps * m.Fp16 / 16) * 2 * 256);
-        m.conv_scale_off = take(4);
+        m.conv_w3_off = take_split((size_t)m.convNT * (m.taps * m.Fp16 / 16) * 3 * 256);
+        m.conv_w2h_off = take_split((size_t)m.convNT * (m.taps * m.Fp16 / 16) * 2 * 256);
+        m.conv_scale_off = take_split(4);
         m.conv_wT_off = conv_dx_wide(m) ? take((size_t)m.convNT * Q * 256) : 0;
+        // k_conv_win's two fp16 pieces of S * W in the 16-channel geometry; three bf16 pieces for the wide models' k_conv_x3
+        const int q8 = m.taps * m.Fp16 / 8;
+        const size_t sc = m.conv_scale_off;
+        m.conv_split = split_group({{S::ZERO_SCALE, sc},
+                                    {S::ABSMAX, sc, m.conv_wf16_off, 0, (long)m.convNT * q8 * 256},
+                                    {S::SCALE_FROM_MAX, sc},
+                                    {S::SPLIT2H, sc, m.conv_wf16_off, m.conv_w2h_off, m.convNT, q8, q8 / 2, 1},
+                                    {S::SPLIT3, 0, m.conv_wf16_off, m.conv_w3_off, m.convNT, q8, q8 / 2}});
     }
     // GAT layers
     auto plan_gat = [&](GatPlan& g, int K, int D, int E) {
@@ -200,11 +214,37 @@ std::string validate_and_plan(Model& m) {
             if (const char* e_ = getenv("MTADGAT_GATH_PADLDS")) g.fh_lds_bytes = std::max<size_t>(g.fh_lds_bytes, (size_t)atoi(e_) * 1024);
         }
         g.w16_off = take((size_t)g.NT * g.Q16 * 256);
-        g.w3_off = take((size_t)g.NT * g.Q16 * 3 * 256);
-        g.w2h_off = take((size_t)g.NT * g.Q16 * 2 * 256);
-        g.gscale_off = take(4);
+        g.w3_off = take_split((size_t)g.NT * g.Q16 * 3 * 256);
+        g.w2h_off = take_split((size_t)g.NT * g.Q16 * 2 * 256);
+        g.gscale_off = take_split(4);
         g.uQ16 = g.fused ? 0 : (g.Q + 1) / 2;
-        g.uw3_off = take((size_t)g.NT * g.uQ16 * 3 * 256);
+        g.uw3_off = take_split((size_t)g.NT * g.uQ16 * 3 * 256);
+        const size_t sc = g.gscale_off;
+        if (g.fused)        // k_gat's bf16 pieces; the scale and k_gath's fp16 pieces (GATv2: compact column order, non-negative group padded to 2, not 8)
+            g.split = split_group({{S::SPLIT3, 0, g.w_off, g.w3_off, g.NT, g.Q, g.Q16},
+                                   {S::ZERO_SCALE, sc},
+                                   {S::ABSMAX, sc, g.w_off, 0, (long)g.NT * g.Q * 256},
+                                   {S::SCALE_FROM_MAX, sc},
+                                   c.use_gatv2 ? S{S::SPLIT2H_GATH, sc, g.w_off, g.w2h_off, g.NT_L, g.Q, g.Q16, g.E, g.ord_off}
+                                               : S{S::SPLIT2H, sc, g.w_off, g.w2h_off, g.NT, g.Q, g.Q16, 1}});
+        else if (g.uQ16 > 0)   // the row GEMM's pack (k_rowgemm_x3)
+            g.split = split_group({{S::SPLIT3, 0, g.w_off, g.uw3_off, g.NT, g.Q, g.uQ16}});
+    };
+    // a recurrence layer: the power-of-two scale from its largest weight, the input pack on three bf16 pieces (and on two fp16 pieces),
+    // the recurrent pack on two fp16 pieces, the chunk-major copy of the two-piece input pack (k_gru_cm)
+    auto gru_split = [&](GruPlan& g) {
+        const long outer_x = (long)(g.xmode == 1 ? m.W : 1) * g.NCG;
+        const size_t sc = g.scale_off;
+        const bool x2 = g.wx2_off && g.qb3 > 0;
+        std::vector<SplitStep> st = {{S::ZERO_SCALE, sc},
+                                     {S::ABSMAX, sc, g.wx_off, 0, outer_x * g.Qxp * 3 * 256},
+                                     {S::ABSMAX, sc, g.wh_off, 0, (long)g.NCG * (4 * g.NCG + 2) * 3 * 256},
+                                     {S::SCALE_FROM_MAX, sc},
+                                     {S::SPLIT_X, sc, g.wx_off, g.wx3_off, outer_x, g.Qxp, g.Qxp16, g.qb3}};
+        if (x2) st.push_back({S::SPLIT_X, sc, g.wx_off, g.wx2_off, outer_x, g.Qxp, g.Qxp16, 0});
+        st.push_back({S::SPLIT2H, sc, g.wh_off, g.wh3_off, g.NCG, 4 * g.NCG + 2, 2 * g.NCG + 2, 3});
+        if (g.wxq_off) st.push_back({S::REORDER_XQ, 0, x2 ? g.wx2_off : g.wx3_off, g.wxq_off, g.NCG, 0, g.Qxp16});
+        g.split = split_group(std::move(st));
     };
     plan_gat(m.feat, m.F, m.W, c.feat_embed);
     plan_gat(m.temp, m.W, m.F, c.time_embed);
@@ -235,14 +275,15 @@ std::string validate_and_plan(Model& m) {
         g.Qxp16 = round_up((g.Qx + 1) / 2, 6);       // whole turns of the bf16 weight ring (6 stages; k_gru_split: 3)
         g.wx16_off = take((size_t)g.NCG * g.Qxp16 * 3 * 256);
         g.wh16_off = take((size_t)g.NCG * (2 * g.NCG + 2) * 3 * 256);
-        g.wx3_off = take((size_t)g.NCG * g.Qxp16 * 9 * 256);
-        g.wh3_off = take((size_t)g.NCG * (2 * g.NCG + 2) * 6 * 256 + 3 * 256);
-        g.scale_off = take(4);
+        g.wx3_off = take_split((size_t)g.NCG * g.Qxp16 * 9 * 256);
+        g.wh3_off = take_split((size_t)g.NCG * (2 * g.NCG + 2) * 6 * 256 + 3 * 256);
+        g.scale_off = take_split(4);
         // layer 0 reads h_cat = [conv output (relu: unbounded) | h_feat | h_temp (sigmoids)]: the chunks that touch the
         // first F features keep three bf16 pieces; later layers read a previous layer's state, |h| <= 1
         g.qb3 = l == 0 ? std::min(g.Qxp16, round_up((m.F + 15) / 16, 2)) : 0;
-        if (l == 0) g.wx2_off = take((size_t)g.NCG * g.Qxp16 * 6 * 256 + 3 * 256);
-        g.wxq_off = take((size_t)g.NCG * g.Qxp16 * 6 * 256 + 3 * 256);
+        if (l == 0) g.wx2_off = take_split((size_t)g.NCG * g.Qxp16 * 6 * 256 + 3 * 256);
+        g.wxq_off = take_split((size_t)g.NCG * g.Qxp16 * 6 * 256 + 3 * 256);
+        gru_split(g);
         if (l == 0) {
             g.has_xproj = true;
             g.xproj.in_dim = g.in_dim; g.xproj.out_dim = 3 * g.Hp;
@@ -250,7 +291,8 @@ std::string validate_and_plan(Model& m) {
             g.xproj.w_off = take((size_t)g.xproj.NT * g.xproj.Q * 256);
             g.xproj.b_off = take((size_t)3 * g.Hp);
             g.xproj.Q16 = (g.in_dim + 15) / 16;
-            g.xproj.w3_off = take((size_t)g.xproj.NT * g.xproj.Q16 * 3 * 256);
+            g.xproj.w3_off = take_split((size_t)g.xproj.NT * g.xproj.Q16 * 3 * 256);
+            lin_split(g.xproj);
             plan16(g);
         }
     }
@@ -298,10 +340,11 @@ std::string validate_and_plan(Model& m) {
         g.Qxp16 = g.xmode == 1 ? (g.Qx == 1 ? 1 : round_up((g.Qx + 1) / 2, 6)) : round_up((g.Qx + 1) / 2, 6);
         g.wx16_off = take((size_t)(g.xmode == 1 ? m.W : 1) * g.NCG * g.Qxp16 * 3 * 256);
         g.wh16_off = take((size_t)g.NCG * (2 * g.NCG + 2) * 3 * 256);
-        g.wx3_off = take((size_t)(g.xmode == 1 ? m.W : 1) * g.NCG * g.Qxp16 * 9 * 256);
-        g.wh3_off = take((size_t)g.NCG * (2 * g.NCG + 2) * 6 * 256 + 3 * 256);
-        g.scale_off = take(4);
-        if (g.xmode == 0) g.wxq_off = take((size_t)g.NCG * g.Qxp16 * 6 * 256 + 3 * 256);
+        g.wx3_off = take_split((size_t)(g.xmode == 1 ? m.W : 1) * g.NCG * g.Qxp16 * 9 * 256);
+        g.wh3_off = take_split((size_t)g.NCG * (2 * g.NCG + 2) * 6 * 256 + 3 * 256);
+        g.scale_off = take_split(4);
+        if (g.xmode == 0) g.wxq_off = take_split((size_t)g.NCG * g.Qxp16 * 6 * 256 + 3 * 256);
+        gru_split(g);
         if (l == 0) plan16(g);
     }
     {
@@ -313,8 +356,10 @@ std::string validate_and_plan(Model& m) {
         p.w_off = take((size_t)p.NT * p.Q * 256);
         p.b_off = take((size_t)p.NT * 32);
         p.Q16 = (p.Q + 1) / 2;
-        p.w3_off = take((size_t)p.NT * p.Q16 * 3 * 256);
+        p.w3_off = take_split((size_t)p.NT * p.Q16 * 3 * 256);
+        lin_split(p);
     }
+    m.split.n_infer = (int)m.split.groups.size();
 
     // ---- backward (training) plans: transposed packs, un-scaled attention projections, gradient index maps
     {
@@ -325,7 +370,8 @@ std::string validate_and_plan(Model& m) {
             p.NT = (outdim + 31) / 32; p.Q = (kdim + 7) / 8;
             p.w_off = take((size_t)p.NT * p.Q * 256);
             p.Q16 = (kdim + 15) / 16;
-            p.w3_off = take((size_t)p.NT * p.Q16 * 3 * 256);
+            p.w3_off = take_split((size_t)p.NT * p.Q16 * 3 * 256);
+            lin_split(p);
         };
         auto wg = [&](WgradPlan& p, int M, int N, bool bias) {
             p.M = M; p.N = N; p.has_bias = bias;
@@ -362,6 +408,17 @@ std::string validate_and_plan(Model& m) {
         gl.rec_fc_w = gtake((int64_t)c.out_dim * c.recon_hid_dim); gl.rec_fc_b = gtake(c.out_dim);
         gl.total = go;
 
+        // GATv2: the un-scaled projection pack (and its three bf16 pieces), its bias, `a`, the transposed pack of d V, the weight gradient
+        // (round 6: the score backward's projections are a row GEMM for fused layers too)
+        auto gat_wu = [&](GatBwdPlan& gb, const GatPlan& g) {
+            gb.wu_off = take((size_t)2 * gb.NTu * g.Q * 256);
+            gb.wu3_off = take_split((size_t)2 * gb.NTu * ((g.Q + 1) / 2) * 3 * 256);
+            gb.split = split_group({{S::SPLIT3, 0, gb.wu_off, gb.wu3_off, 2 * gb.NTu, g.Q, (g.Q + 1) / 2}});
+            gb.bu_off = take((size_t)2 * gb.Ep);
+            gb.a_off = take((size_t)gb.Ep);
+            lint(gb.lrT, 2 * gb.Ep, g.D);
+            wg(gb.wg, 2 * gb.Ep, g.D, true);
+        };
         // wide layers go through the generic kernels of mtadgat_bwdw.hip: GATv2 and (round 6) GAT v1, up to 2048 nodes / node dimensions
         b.supported = true;
         if (b.supported) {
@@ -377,12 +434,7 @@ std::string validate_and_plan(Model& m) {
                     continue;
                 }
                 if (gb.wide) {
-                    gb.wu_off = take((size_t)2 * gb.NTu * g.Q * 256);
-                    gb.wu3_off = take((size_t)2 * gb.NTu * ((g.Q + 1) / 2) * 3 * 256);
-                    gb.bu_off = take((size_t)2 * gb.Ep);
-                    gb.a_off = take((size_t)gb.Ep);
-                    lint(gb.lrT, 2 * gb.Ep, g.D);
-                    wg(gb.wg, 2 * gb.Ep, g.D, true);
+                    gat_wu(gb, g);
                     continue;
                 }
                 gb.att_lds = gat_bwd_att_lds(g.K, g.D, g.f_vld, (g.K + 15) / 16);
@@ -395,17 +447,13 @@ std::string validate_and_plan(Model& m) {
                     if (gb.att_lds > 160 * 1024 || gb.pair_lds > 160 * 1024) { b.supported = false; b.why = "attention backward tiles exceed the LDS"; }
                     continue;
                 }
-                gb.wu_off = take((size_t)2 * gb.NTu * g.Q * 256);
-                gb.wu3_off = take((size_t)2 * gb.NTu * ((g.Q + 1) / 2) * 3 * 256);
-                gb.bu_off = take((size_t)2 * gb.Ep);         // (round 6: the score backward's projections are a row GEMM here too)
-                gb.a_off = take((size_t)gb.Ep);
-                lint(gb.lrT, 2 * gb.Ep, g.D);
-                wg(gb.wg, 2 * gb.Ep, g.D, true);
+                gat_wu(gb, g);
                 if (gb.att_lds > 160 * 1024) { b.supported = false; b.why = "attention backward tiles exceed the LDS"; }
             }
             auto gru_b = [&](GruBwdPlan& gb, const GruPlan& g) {
                 gb.whT_off = take((size_t)g.NCG * 12 * g.NCG * 256);
-                gb.whT3_off = take((size_t)g.NCG * 6 * g.NCG * 3 * 256);
+                gb.whT3_off = take_split((size_t)g.NCG * 6 * g.NCG * 3 * 256);
+                gb.split = split_group({{S::SPLIT3, 0, gb.whT_off, gb.whT3_off, g.NCG, 12 * g.NCG, 6 * g.NCG}});
                 lint(gb.wihT, 3 * g.Hp, g.in_dim);
                 wg(gb.wg_ih, 3 * g.Hp, g.in_dim, true);
                 wg(gb.wg_hh, 3 * g.Hp, g.H, true);

@@ -54,7 +54,9 @@ def test_device_repack_equals_the_host_packer(name, gpu_device):
         # attention columns are bit-identical; the folded decoder input sums the same terms in another order (host:
         # differences of prefix sums) -- last-bit differences only
         mism = img_dev.view(torch.int32) != img_host.view(torch.int32)
-        for off, n in eng.derived_regions():      # split-bf16 packs: produced from the fp32 packs by the same kernel on both paths
+        regions = eng.derived_regions()
+        assert len(regions) == eng.lib.mtadgat_derived_regions(eng.handle, None, 0)     # every one of them, however many
+        for off, n in regions:      # split packs: produced from the fp32 packs by the same kernel on both paths
             mism[off:off + n] = False
         assert mism.float().mean().item() < 0.02, (name, rnd, int(mism.sum()))
         if mism.any():
@@ -103,3 +105,52 @@ def test_training_loop_on_device_packed_weights_tracks_the_host_packed_loop(name
         assert abs(a - b) <= 1e-5, (l_dev, l_host)
     for a, b in zip(p_dev, p_host):
         assert (a - b).abs().max().item() <= 1e-5
+
+
+def _stream_sequence(gpu_device, side):
+    """Weights loaded on the current stream; then a 4 096-window forward, an 8 192-window training forward + backward, a device
+    re-pack and the forward again.  side=True: each on a stream of its own, ordered by the caller only where its own buffers and
+    the weight image ask for it -- the training step does NOT wait for the forward, whose stream derived the split packs it reads."""
+    import _native
+    from mtad_gat import MTAD_GAT
+    kw = CONFIGS["msl_shape"]
+    W, F = kw["window_size"], kw["n_features"]
+    torch.manual_seed(0)
+    model = MTAD_GAT(**kw).to(gpu_device)
+    eng = _native.Engine(model._native_cfg, gpu_device)
+    eng.set_precision(2)
+    g = torch.Generator(device=gpu_device).manual_seed(7)
+    x1 = torch.rand(4096, W, F, generator=g, device=gpu_device)
+    x2 = torch.rand(8192, W, F, generator=g, device=gpu_device)
+    dp = torch.randn(8192, kw["out_dim"], generator=g, device=gpu_device)
+    dr = torch.randn(8192, W, kw["out_dim"], generator=g, device=gpu_device)
+    grads = torch.zeros(eng.grad_layout()[1], device=gpu_device)
+    eng.load_weights(model.state_dict(), gpu_device, allow_device_pack=False)
+    _perturb(model, 3)
+    sd2 = model.state_dict()
+    torch.cuda.synchronize()
+    cur = torch.cuda.current_stream()
+    s1, s2, s3, s4 = (torch.cuda.Stream(gpu_device) for _ in range(4)) if side else (cur,) * 4
+    with torch.cuda.stream(s1):
+        p1, r1 = eng.forward(x1)
+    with torch.cuda.stream(s2):
+        pt, rt, tape = eng.forward_train(x2, 0.2, 1234)
+        eng.backward(x2, 0.2, 1234, dp, dr, tape, grads)
+    s3.wait_stream(s1)        # the re-pack rewrites the image both calls read
+    s3.wait_stream(s2)
+    with torch.cuda.stream(s3):
+        assert eng.update_weights_device(sd2, gpu_device)
+    s4.wait_stream(s3)        # (and the forward's workspace, last written on s1)
+    with torch.cuda.stream(s4):
+        p4, r4 = eng.forward(x1)
+    torch.cuda.synchronize()
+    return [t.cpu() for t in (p1, r1, pt, rt, grads, p4, r4)]
+
+
+def test_calls_on_several_streams_equal_the_one_stream_sequence(gpu_device):
+    """A handle used from several streams one after another: every output equals the same sequence on one stream, bit for bit."""
+    one = _stream_sequence(gpu_device, side=False)
+    several = _stream_sequence(gpu_device, side=True)
+    for what, a, b in zip(("preds", "recons", "train preds", "train recons", "grads", "preds after re-pack", "recons after re-pack"),
+                          one, several):
+        assert torch.equal(a, b), what
