@@ -146,6 +146,23 @@ int64_t mtadgat_packed_floats(mtadgat_handle h);
  * the number only. */
 int mtadgat_derived_regions(mtadgat_handle h, int64_t* out_pairs, int max_pairs);
 int mtadgat_read_packed(mtadgat_handle h, float* dst_host, int64_t n_floats, void* stream);
+/* Test hook (host only: needs neither a GPU nor loaded weights): which kernels run one recurrence layer.  stack 0: the GRU stack,
+ * 1: the reconstruction decoder; `layer` counts from the input; n: windows of the call (one piece of a forward(), or one training
+ * forward); compute_units: of the device the call would run on (256 on MI355X).  The answer is the one the library's own dispatch
+ * uses -- for a forward() that returns predictions and reconstructions, or a training forward -- under the handle's current
+ * mtadgat_set_precision mode and "gru_kernel" option.  Writes 8 ints:
+ *   out[0]  first kernel: 1 k_gru1 (window per workgroup), 2 k_gru16 (16-window groups), 3 k_gru_split (hidden-tile split),
+ *           4 k_gru_split on split operands, 5 k_gru_cm (chunk-major), 6 k_gru (tile-major)
+ *   out[1]  kernel launched behind it as the device-side range-guard fallback (same codes), 0 none
+ *   out[2]  operand build of the k_gru_split / k_gru named in out[0] / out[1]: 0 fp32, 1 bf16, 2 / 3 split-bf16 (hidden sizes
+ *           above / up to 128); 0 when neither is named
+ *   out[3]  k_gru takes two 32-window groups per wave
+ *   out[4]  the input products of all steps are hoisted into a launch in front
+ *   out[5]  the layer's split packs are needed (derived on first use after an upload)
+ *   out[6]  the per-step Linear of the decoder rides inside the recurrence
+ *   out[7]  the stack takes the small-batch kernels (what the heads and the backward ask; equals out[0] in {1, 2} for layer 0)
+ * Returns 0, or MTADGAT_ERR_INVALID. */
+int mtadgat_gru_route(mtadgat_handle h, int stack, int layer, int64_t n, int training, int compute_units, int* out);
 
 /* Arithmetic of the inference entry points (forward / forward_series / stage calls):
  *   0 (default of a new handle)  fp32 operands on the exact fp32 MFMA: <= 1e-5 of the reference's float32 forward

@@ -33,6 +33,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "libmtadgat.so")
 MAX_LAYERS = 8
 PROFILE_SLOTS = 6
+# mtadgat_gru_route: the integers it writes, the kernel codes (GruKernel) and operand builds (GruBuild) of csrc/mtadgat_host.h
+GRU_ROUTE_FIELDS = ("first", "fallback", "build", "two", "hoist", "split_packs", "fc_rides", "small_stack")
+GRU_KERNELS = ("none", "k_gru1", "k_gru16", "k_gru_split", "k_gru_split_x3", "k_gru_cm", "k_gru")
+GRU_BUILDS = ("fp32", "bf16", "x3_hi", "x3_lo")
 
 _c_float_p = ctypes.POINTER(ctypes.c_float)
 
@@ -85,6 +89,7 @@ def load_library():
     lib.mtadgat_packed_floats.restype = i64
     lib.mtadgat_read_packed.argtypes = [vp, vp, i64, vp]
     lib.mtadgat_derived_regions.argtypes = [vp, ctypes.POINTER(i64), ctypes.c_int]
+    lib.mtadgat_gru_route.argtypes = [vp, ctypes.c_int, ctypes.c_int, i64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
     lib.mtadgat_workspace_bytes.argtypes = [vp, i64]
     lib.mtadgat_workspace_bytes.restype = sz
     lib.mtadgat_set_precision.argtypes = [vp, ctypes.c_int]
@@ -440,6 +445,13 @@ class Engine:
         buf = (ctypes.c_int64 * (2 * n))()
         n = self.lib.mtadgat_derived_regions(self.handle, buf, n)
         return [(int(buf[2 * i]), int(buf[2 * i + 1])) for i in range(n)]
+
+    def gru_route(self, stack, layer, n, training=False, compute_units=256):
+        """Which kernels run recurrence layer `layer` of the GRU stack (stack 0) or the decoder (1) at n windows, under the current
+        precision and "gru_kernel" option (host only): dict of the eight integers of mtadgat_gru_route (include/mtadgat.h)."""
+        buf = (ctypes.c_int * 8)()
+        _check(self.lib.mtadgat_gru_route(self.handle, stack, layer, n, int(training), compute_units, buf), "mtadgat_gru_route")
+        return dict(zip(GRU_ROUTE_FIELDS, (int(v) for v in buf)))
 
     def load_weights(self, sd, device, allow_device_pack=True):
         """sd: reference-format state_dict (any device).  The first load packs on the host and uploads on the current

@@ -367,12 +367,6 @@ int run_gat_layer(Model& m, const GatPlan& g, const float* v, int ldv, int64_t n
     return run_attend(m, g, lc, rt, v, ldv, n, out, so_w, so_i, so_d, sc, s);
 }
 
-// the small-batch fp32 recurrence kernels apply to a single-layer stack whose weights fit a wave's registers
-// (inference in the bf16 mode uses k_gru1 up to 1024 windows -- faster there than the bf16 build of the throughput
-// kernels, and exact; the training step keeps the bf16 recurrences it was asked for)
-// the part of run_gru_layer's `cm_fit` that does not depend on the call: can the split-operand kernels (k_gru_cm / the X3H
-// build of k_gru_split) serve this layer at all?  (hidden sizes above 160, wide windows, input packs that need the range guard
-// without a fused front end cannot: such layers keep k_gru16 up to G16_MAX_WINDOWS)
 // A Linear over (window, step) rows in the default fp32 arithmetic: from 65 536 rows on the products come from three bf16 pieces per
 // operand on the 16-bit matrix pipe (k_rowgemm_x3 / _x3s: 2.7 x less matrix time than the fp32 MFMA, results <= 2e-7 apart), with the
 // split pack derived on first use after an upload -- as the wide attention layers' projections and the backward's data gradients
@@ -386,174 +380,143 @@ int lin_split_operands(Model& m, const LinPlan& p, long rows, RowGemmArgs& a, hi
     return 0;
 }
 
-bool split_kernels_fit(const Model& m, const GruPlan& g) {
-    if (m.W > 512 || !(g.Qxp16 == 1 || g.Qxp16 % 2 == 0)) return false;
-    if (g.xmode == 1) return g.Qxp16 == 1 && gru_cm_supported(g.NCG, 1, false, 0);
-    const bool guard = use_fused(m.temp) && use_fused(m.feat);           // the convolution records its output range only there
-    return gru_cm_supported(g.NCG, 0, false, 0) && g.wxq_off != 0 && g.Qx >= 3 && ((guard && g.wx2_off && g.qb3 > 0) || g.qb3 == 0);
+// The k_rowgemm arguments of a Linear over rows: Y = X W^T + b for `rows` rows of X (row stride ldx).  ldy == 0: Y is the caller's
+// dense (rows, out_dim) tensor, stored with vector stores when its rows are 16-byte aligned; otherwise an internal buffer with
+// 16-byte aligned rows of ldy floats, all of them written.  The caller adds what its site needs: ReLU, dropout, lin_split_operands.
+RowGemmArgs lin_rows(const Model& m, const LinPlan& p, const float* x, long ldx, long rows, float* y, long ldy = 0) {
+    RowGemmArgs a{};
+    a.X = x; a.ldx = ldx; a.Kvalid = p.in_dim; a.Q = p.Q;
+    a.Wp = reinterpret_cast<const f32x4*>(m.packed_dev + p.w_off);
+    a.bias = m.packed_dev + p.b_off;
+    a.R = rows; a.NT = p.NT; a.NT_rm = p.NT; a.group = 1;
+    a.Y = y;
+    if (ldy) {
+        a.ldy = ldy; a.Nvalid = (int)ldy; a.vec_store = 1;
+    } else {
+        a.ldy = p.out_dim; a.Nvalid = p.out_dim;
+        a.vec_store = (p.out_dim % 4 == 0 && aligned16(y)) ? 1 : 0;
+    }
+    return a;
 }
 
-bool use_g16(const Model& m, const std::vector<GruPlan>& stack, int64_t n, bool training = false) {
-    if (stack.size() != 1 || !stack[0].has16) return false;
-    if (m.precision == 1) return !training && n <= 1024;
-    // inference in the split-operand arithmetic: from SPLIT3_MIN_WINDOWS on the hidden-tile-split kernel's split-operand build
-    // is the faster one (run_gru_layer) -- where it applies; the measurement hook can force it at any size
-    if (m.precision == 2 && !training && stack[0].NCG >= 2 && split_kernels_fit(m, stack[0]) &&
-        (m.gru_kernel == 3 || (m.gru_kernel == 0 && n >= SPLIT3_MIN_WINDOWS))) return false;
-    return n <= G16_MAX_WINDOWS;
+// the buffers of one recurrence layer's call
+struct GruIo {
+    const float* x = nullptr;        // rows (n*T, ldx) for xmode 0, hin (n, ldx) for xmode 1
+    long ldx = 0;
+    int kx = 0;
+    float* hend = nullptr;           // (n, ldhe) last states, or null
+    long ldhe = 0;
+    float* seq = nullptr;            // (n*T, Hp) states of every step, or null
+    const LinPlan* fc = nullptr;     // a per-step Linear to run inside the recurrence, into yfc (all steps) / ylast (last step)
+    float* yfc = nullptr;
+    float* ylast = nullptr;
+    float* gates = nullptr;          // training forward: the gate activations of every step
+    float* xp = nullptr;             // room for the input products of all steps (n*T, 3 Hp), or null
+    const unsigned* vmax = nullptr;  // the convolution's recorded output range, or null
+};
+
+// The operand packs `k` reads, into a.  A split-operand kernel and the fallback behind it share one pack selection at inference
+// (the tile-major kernel reads the three-piece input pack the others' two-piece packs were split beside); the training forward's
+// fallback is the fp32 kernel.
+void gru_select_packs(const Model& m, const GruPlan& g, const GruRoute& r, GruKernel k, int xmode, const GruIo& io, GruArgs& a) {
+    auto at = [&](size_t off) { return reinterpret_cast<const f32x4*>(m.packed_dev + off); };
+    const bool train_x3 = io.gates && k == GRU_SPLIT_X3, infer_x3 = !io.gates && r.split_packs;
+    a.Wx = at(g.wx_off); a.Wh = at(g.wh_off); a.whs = 4 * g.NCG + 2; a.Qxp = g.Qxp;
+    a.bf16 = 0; a.x3 = 0; a.scale = nullptr; a.qb3 = 0; a.vmax = nullptr; a.Wx2 = nullptr; a.Wxq = nullptr;
+    if (m.precision == 1) {       // bf16 operand build: the same streams in 16-feature chunks (inference, and the bf16 training step)
+        a.Wx = at(g.wx16_off); a.Wh = at(g.wh16_off);
+    }
+    if (m.precision == 1 || train_x3 || infer_x3) {
+        a.whs = 2 * g.NCG + 2; a.Qxp = g.Qxp16; a.bf16 = 1;
+    }
+    if (train_x3) {
+        a.Wh = at(g.wh3_off); a.x3 = 1; a.scale = m.packed_dev + g.scale_off + 1;
+        a.vmax = r.guarded ? io.vmax : nullptr;                  // layer 0: the convolution's channels need the recorded range
+        a.Wxq = at(r.guarded ? g.wx2_off : g.wx3_off);
+    } else if (infer_x3) {
+        a.Wx = at(g.wx3_off); a.Wh = at(g.wh3_off); a.x3 = 1; a.scale = m.packed_dev + g.scale_off + 1;
+        a.qb3 = g.qb3;
+        if (r.guarded) {
+            a.vmax = io.vmax;
+            a.Wx2 = at(g.wx2_off);
+        }
+        if (r.first == GRU_SPLIT_X3) a.Wxq = (xmode == 0 && a.Wx2) ? a.Wx2 : a.Wx;      // the two-piece input pack in [tile][chunk] order
+        if (r.first == GRU_CM) a.Wxq = xmode == 1 ? a.Wx : at(g.wxq_off);
+    } else if (io.gates && r.fallback != GRU_NONE) {
+        a.vmax = io.vmax;                                        // the fp32 kernel serves the launch when the range is too large
+    }
 }
 
-// ... and below G1_MAX_WINDOWS a workgroup takes one window at a time
-bool use_g1(int64_t n) {
-    return n <= G1_MAX_WINDOWS;
+int launch_gru_kernel(const GruRoute& r, GruKernel k, const GruArgs& a, int ncg, int xmode, bool fc, hipStream_t s) {
+    switch (k) {
+        case GRU_SPLIT: K_TRY(launch_gru_split(a, ncg, xmode, fc, s), a.Gates ? "gru (training)" : "gru (hidden-tile split)"); return 0;
+        case GRU_SPLIT_X3: K_TRY(launch_gru_split_x3(a, ncg, xmode, fc, s), a.Gates ? "gru (training, split operands)" : "gru (hidden-tile split, split operands)"); return 0;
+        case GRU_CM: K_TRY(launch_gru_cm(a, ncg, xmode, fc, s), "gru (chunk-major)"); return 0;
+        case GRU_TILE: K_TRY(launch_gru_tile(a, ncg, xmode, fc, r.build, r.two, s), "gru (tile-major)"); return 0;
+        default: return fail(MTADGAT_ERR_INVALID, "internal: recurrence route names no throughput kernel");
+    }
 }
 
-// one GRU layer.  x: rows (n*T, ldx) for xmode 0, hin (n, ldx) for xmode 1
-int run_gru_layer(Model& m, int slot, const GruPlan& g, const float* x, long ldx, int kx, int64_t n, float* hend,
-                  long ldhe, float* seq, const LinPlan* fc, float* yfc, float* ylast, hipStream_t s, float* gates = nullptr,
-                  float* xp = nullptr, bool g16 = false, const unsigned* vmax = nullptr) {
+// one GRU layer of `stack`: the kernels gru_route names, in its order
+int run_gru_layer(Model& m, int slot, const std::vector<GruPlan>& stack, int layer, const GruIo& io, int64_t n, hipStream_t s) {
     Scope sc(m, slot, s);
+    const GruPlan& g = stack[layer];
+    GruCall c;
+    c.training = io.gates != nullptr;
+    c.fc = io.fc != nullptr; c.fc_out_dim = io.fc ? io.fc->out_dim : 0;
+    c.range = io.vmax != nullptr; c.xp = io.xp != nullptr;
+    c.hend_fits = io.hend == nullptr || io.ldhe >= g.Hp;
+    const GruRoute r = gru_route(m, stack, layer, n, cu_count(), c);
+    const float* x = io.x;
+    long ldx = io.ldx;
     int xmode = g.xmode;
-    if (g16) {
-        // small batch, fp32: input products of all steps ahead of the recurrence, 16-window groups with register-resident
-        // weights (mtadgat_gru16.hip); a per-step Linear is the caller's row GEMM over `seq`
-        if (!xp || !g.has16 || fc) return fail(MTADGAT_ERR_INVALID, "internal: k_gru16 without its buffers");
+    if (r.hoist) {
         if (g.xmode == 0) {
-            RowGemmArgs r{};
-            r.X = x; r.ldx = ldx; r.Kvalid = g.in_dim; r.Q = g.xproj.Q;
-            r.Wp = reinterpret_cast<const f32x4*>(m.packed_dev + g.xproj.w_off);
-            r.bias = m.packed_dev + g.xproj.b_off;
-            r.Y = xp; r.ldy = 3L * g.Hp; r.Nvalid = 3 * g.Hp; r.vec_store = 1;
-            r.R = n * m.W; r.NT = g.xproj.NT; r.NT_rm = g.xproj.NT; r.group = 1; r.relu = 0;
-            if (int rc_ = lin_split_operands(m, g.xproj, r.R, r, s)) return rc_;
-            K_TRY(launch_rowgemm(r, s), "gru input projection");
+            RowGemmArgs p = lin_rows(m, g.xproj, x, ldx, n * m.W, io.xp, 3L * g.Hp);
+            if (int rc_ = lin_split_operands(m, g.xproj, p.R, p, s)) return rc_;
+            K_TRY(launch_rowgemm(p, s), "gru input projection");
         } else {
-            K_TRY(launch_xproj_dec(x, ldx, kx, m.packed_dev + g.fold_off, reinterpret_cast<const int*>(m.packed_dev + g.m0_off),
-                                   m.packed_dev + g.b_off, g.Hp, m.W, n, xp, s), "decoder input projection");
+            K_TRY(launch_xproj_dec(x, ldx, io.kx, m.packed_dev + g.fold_off, reinterpret_cast<const int*>(m.packed_dev + g.m0_off),
+                                   m.packed_dev + g.b_off, g.Hp, m.W, n, io.xp, s), "decoder input projection");
         }
+        x = io.xp; ldx = 3L * g.Hp; xmode = 3;
+    }
+    if (r.small()) {
+        if (!g.has16 || io.fc) return fail(MTADGAT_ERR_INVALID, "internal: k_gru16 without its buffers");
         Gru16Args a{};
-        a.XP = xp; a.W16 = m.packed_dev + g.g16_off; a.bias = m.packed_dev + g.b_off;
+        a.XP = x; a.W16 = m.packed_dev + (r.first == GRU_WINDOW ? g.g1_off : g.g16_off); a.bias = m.packed_dev + g.b_off;
         a.Hp = g.Hp; a.KS = g.KS16; a.NT16 = g.NT16; a.T = m.W; a.B = n;
-        a.Hend = hend; a.ldhe = ldhe; a.ncol = (int)std::min<long>(ldhe, g.Hp); a.Seq = seq; a.Gates = gates; a.H = g.H;
-        if (use_g1(n)) {
-            a.W16 = m.packed_dev + g.g1_off;
-            K_TRY(launch_gru1(a, s), "gru (window per workgroup)");
-            return 0;
-        }
-        K_TRY(launch_gru16(a, s), "gru (16-window groups)");
+        a.Hend = io.hend; a.ldhe = io.ldhe; a.ncol = (int)std::min<long>(io.ldhe, g.Hp); a.Seq = io.seq; a.Gates = io.gates; a.H = g.H;
+        if (r.first == GRU_WINDOW) K_TRY(launch_gru1(a, s), "gru (window per workgroup)");
+        else K_TRY(launch_gru16(a, s), "gru (16-window groups)");
         return 0;
     }
-    // chunk-major recurrence (k_gru_cm): 32 windows per wave, the weight stream shared by a workgroup's waves through LDS.
-    // It needs two-piece (fp16) input operands: the decoder's and stacked layers' inputs always are; layer 0's when the
-    // convolution's recorded range allows -- decided on the device: both kernels are launched, each returns at once when
-    // the launch is the other's.  Measured against the kernels it replaces (MSL shape, GRU layer + decoder): 12 288 windows
-    // 5.9 -> 4.0 ms, 32 768: 7.3 -> 4.4, 65 536: 12.0 -> 9.1; from CM_MIN_WINDOWS on.
-    const bool cm_fit = m.precision == 2 && !gates && gru_cm_supported(g.NCG, g.xmode, fc != nullptr, fc ? fc->out_dim : 0) &&
-                        (g.Qxp16 == 1 || g.Qxp16 % 2 == 0) &&
-                        (g.xmode == 1 ? g.Qxp16 == 1 : (g.wxq_off != 0 && g.Qx >= 3 && ((vmax && g.wx2_off && g.qb3 > 0) || g.qb3 == 0))) &&
-                        (hend == nullptr || ldhe >= g.Hp) && m.W <= 512;
-    // ... and between CM_MIN_WINDOWS and SPLIT3_MAX_WINDOWS the split-operand build of the hidden-tile-split kernel (same
-    // packs, same range guard): there a 32-window wave per SIMD is a latency chain, five waves per 32 windows are not
-    const bool use_sp = cm_fit && g.NCG >= 2 && (m.gru_kernel == 3 || (m.gru_kernel == 0 && n >= SPLIT3_MIN_WINDOWS && n <= SPLIT3_MAX_WINDOWS));
-    const bool use_cm = cm_fit && !use_sp && m.gru_kernel != 1 && m.gru_kernel != 3 && (m.gru_kernel == 2 || n >= CM_MIN_WINDOWS);
-    // large batch, split-bf16 operands: fp32-class results from the bf16 matrix pipe (k_gru X3 build), from 1.25 32-window
-    // groups per CU on (measured: 12 320 windows 10.5 ms against 13.1 ms for the hidden-tile-split kernel at 12 288; 8 192 windows 7.4 ms there)
-    // training forward (gates kept for the backward): the same split-operand build of the hidden-tile-split kernel from
-    // SPLIT3_MIN_WINDOWS on -- the input part in the kernel (no pre-projection GEMM on the fp32 pipe), any per-step Linear
-    const bool sp_train = gates != nullptr && m.precision == 2 && g.NCG >= 2 && m.gru_kernel != 1 && n >= SPLIT3_MIN_WINDOWS &&
-                          (g.Qxp16 == 1 || g.Qxp16 % 6 == 0) &&
-                          (g.xmode == 1 ? g.Qxp16 == 1 : ((vmax && g.wx2_off && g.qb3 > 0) || g.qb3 == 0)) && (hend == nullptr || ldhe >= g.Hp) &&
-                          ((size_t)g.NCG * 1024 + (fc ? (size_t)g.NCG * fc->out_dim * 32 : 0)) * sizeof(float) <= 64 * 1024;
-    const bool x3 = m.precision == 2 && !gates && ((n + 31) / 32 > 5L * cu_count() / 4 || use_cm || use_sp) &&
-                    (g.Qxp16 == 1 || g.Qxp16 % 2 == 0);
-    if (sp_train) xp = nullptr;
-    if (!x3 && xp && g.has_xproj && g.xmode == 0) {
-        // small batch: all steps' input products as one throughput GEMM, the recurrence keeps only its h part
-        RowGemmArgs r{};
-        r.X = x; r.ldx = ldx; r.Kvalid = g.in_dim; r.Q = g.xproj.Q;
-        r.Wp = reinterpret_cast<const f32x4*>(m.packed_dev + g.xproj.w_off);
-        r.bias = m.packed_dev + g.xproj.b_off;
-        r.Y = xp; r.ldy = 3L * g.Hp; r.Nvalid = 3 * g.Hp; r.vec_store = 1;
-        r.R = n * m.W; r.NT = g.xproj.NT; r.NT_rm = g.xproj.NT; r.group = 1; r.relu = 0;
-        if (int rc_ = lin_split_operands(m, g.xproj, r.R, r, s)) return rc_;
-        K_TRY(launch_rowgemm(r, s), "gru input projection");
-        x = xp; ldx = 3L * g.Hp; xmode = 3;
-    }
-    GruArgs a{};
-    a.X = x; a.ldx = ldx; a.Kx = kx; a.Qx = g.Qx; a.Qxp = g.Qxp;
-    a.m0 = xmode == 1 ? reinterpret_cast<const int*>(m.packed_dev + g.m0_off) : nullptr;
-    a.Wx = reinterpret_cast<const f32x4*>(m.packed_dev + g.wx_off);
-    a.Wh = reinterpret_cast<const f32x4*>(m.packed_dev + g.wh_off);
-    a.bias = m.packed_dev + g.b_off;
-    a.whs = 4 * g.NCG + 2;
-    if (m.precision == 1) {       // bf16 operand build: the same streams in 16-feature chunks (inference, and the bf16 training step)
-        a.Wx = reinterpret_cast<const f32x4*>(m.packed_dev + g.wx16_off);
-        a.Wh = reinterpret_cast<const f32x4*>(m.packed_dev + g.wh16_off);
-        a.whs = 2 * g.NCG + 2;
-        a.Qxp = g.Qxp16;
-        a.bf16 = 1;
-    }
-    if (x3 || sp_train) {
+    if (r.split_packs) {
         if (int rc_ = ensure(m, g.split, s)) return rc_;
     }
-    if (x3) {
-        a.Wx = reinterpret_cast<const f32x4*>(m.packed_dev + g.wx3_off);
-        a.Wh = reinterpret_cast<const f32x4*>(m.packed_dev + g.wh3_off);
-        a.whs = 2 * g.NCG + 2;
-        a.Qxp = g.Qxp16;
-        a.bf16 = 1;
-        a.x3 = 1;
-        a.scale = m.packed_dev + g.scale_off + 1;
-        a.qb3 = g.qb3;
-        if (vmax && g.wx2_off && g.qb3 > 0) {
-            a.vmax = vmax;
-            a.Wx2 = reinterpret_cast<const f32x4*>(m.packed_dev + g.wx2_off);
-        }
-    }
+    GruArgs a{};
+    a.X = x; a.ldx = ldx; a.Kx = io.kx; a.Qx = g.Qx;
+    a.m0 = xmode == 1 ? reinterpret_cast<const int*>(m.packed_dev + g.m0_off) : nullptr;
+    a.bias = m.packed_dev + g.b_off;
     a.Hp = g.Hp; a.H = g.H; a.T = m.W; a.B = n;
-    a.Hend = hend; a.ldhe = ldhe;
-    a.Seq = seq; a.ldseq = g.Hp;
-    if (fc) {
-        a.Wfc = reinterpret_cast<const f32x4*>(m.packed_dev + fc->w_off);
-        a.bfc = m.packed_dev + fc->b_off;
-        a.NTfc = fc->NT;
-        a.Yfc = yfc;
-        a.Ylast = ylast;
-        a.out_dim = fc->out_dim;
+    a.Hend = io.hend; a.ldhe = io.ldhe;
+    a.Seq = io.seq; a.ldseq = g.Hp;
+    if (r.fc_rides) {
+        a.Wfc = reinterpret_cast<const f32x4*>(m.packed_dev + io.fc->w_off);
+        a.bfc = m.packed_dev + io.fc->b_off;
+        a.NTfc = io.fc->NT;
+        a.Yfc = io.yfc;
+        a.Ylast = io.ylast;
+        a.out_dim = io.fc->out_dim;
     }
-    if (gates) {     // training forward: keep the gate activations of every step
-        a.Gates = gates;
-        if (sp_train) {
-            GruArgs a3 = a;
-            a3.Wh = reinterpret_cast<const f32x4*>(m.packed_dev + g.wh3_off);
-            a3.whs = 2 * g.NCG + 2; a3.Qxp = g.Qxp16; a3.bf16 = 1; a3.x3 = 1;
-            a3.scale = m.packed_dev + g.scale_off + 1;
-            const bool guard = xmode == 0 && g.qb3 > 0;              // layer 0: the convolution's channels need the recorded range
-            a3.vmax = guard ? vmax : nullptr;
-            a3.Wxq = reinterpret_cast<const f32x4*>(m.packed_dev + (guard ? g.wx2_off : g.wx3_off));
-            K_TRY(launch_gru_split_x3(a3, g.NCG, xmode, fc != nullptr, s), "gru (training, split operands)");
-            if (!guard) return 0;
-            a.vmax = vmax; a.skip_xh = 1;                            // the fp32 kernel serves the launch when the range is too large
-        }
-        K_TRY(launch_gru_train(a, g.NCG, xmode, fc != nullptr, s), "gru (training)");
-        return 0;
-    }
-    if (use_sp) {
-        a.Wxq = (xmode == 0 && a.Wx2) ? a.Wx2 : a.Wx;         // the two-piece input pack in [tile][chunk] order
-        const size_t lds = ((size_t)g.NCG * 1024 + (fc ? (size_t)g.NCG * fc->out_dim * 32 : 0)) * sizeof(float);
-        if (lds <= 64 * 1024) {
-            K_TRY(launch_gru_split_x3(a, g.NCG, xmode, fc != nullptr, s), "gru (hidden-tile split, split operands)");
-            if (a.vmax == nullptr) return 0;
-            a.skip_xh = 1;
-        }
-    } else if (use_cm) {
-        a.Wxq = xmode == 1 ? a.Wx : reinterpret_cast<const f32x4*>(m.packed_dev + g.wxq_off);
-        K_TRY(launch_gru_cm(a, g.NCG, xmode, fc != nullptr, s), "gru (chunk-major)");
-        if (a.vmax == nullptr) return 0;
-        a.skip_xh = 1;
-    }
-    K_TRY(launch_gru(a, g.NCG, xmode, fc != nullptr, s), "gru");
-    return 0;
+    a.Gates = io.gates;
+    gru_select_packs(m, g, r, r.first, xmode, io, a);
+    if (int rc_ = launch_gru_kernel(r, r.first, a, g.NCG, xmode, r.fc_rides, s)) return rc_;
+    if (r.fallback == GRU_NONE) return 0;
+    // both kernels are launched, each returns at once when the launch is the other's (the device reads the recorded range)
+    gru_select_packs(m, g, r, r.fallback, xmode, io, a);
+    a.skip_xh = 1;
+    return launch_gru_kernel(r, r.fallback, a, g.NCG, xmode, r.fc_rides, s);
 }
 
 // hcat is the internal (n*W, Dp) buffer: 16-byte aligned rows whose pad columns are zero (the kernels read them unguarded)
@@ -566,11 +529,10 @@ int run_gru_stack(Model& m, const float* hcat, long ldx, int64_t n, float* hend,
     for (int l = 0; l < L; ++l) {
         const bool last = (l == L - 1);
         float* seq = last ? nullptr : ws + ((l & 1) ? o.seq1 : o.seq0);
-        const bool g16 = use_g16(m, m.gru, n) && o.has_xp;
-        float* xp = (l == 0 && o.has_xp && (g16 || n <= gru_split_max_windows())) ? ws + o.xp : nullptr;
-        int rc = run_gru_layer(m, S_GRU, m.gru[l], x, ld, kx, n, last ? hend : nullptr, ldhe, seq, nullptr, nullptr, nullptr, s, nullptr, xp, g16,
-                               l == 0 ? vmax : nullptr);
-        if (rc) return rc;
+        GruIo io;
+        io.x = x; io.ldx = ld; io.kx = kx; io.hend = last ? hend : nullptr; io.ldhe = ldhe; io.seq = seq;
+        if (l == 0) { io.xp = o.has_xp ? ws + o.xp : nullptr; io.vmax = vmax; }
+        if (int rc = run_gru_layer(m, S_GRU, m.gru, l, io, n, s)) return rc;
         x = seq; ld = m.gru[l].Hp; kx = m.gru[l].H;      // sequence buffers hold all Hp columns, padding lanes are exact zeros
     }
     return 0;
@@ -587,19 +549,8 @@ int run_heads(Model& m, const float* hend, long ldh, int64_t n, float* preds, fl
         for (int i = 0; i < nfc; ++i) {
             const LinPlan& p = m.fc[i];
             const bool last = (i == nfc - 1);
-            RowGemmArgs a{};
-            a.X = x; a.ldx = ld; a.Kvalid = p.in_dim; a.Q = p.Q;
-            a.Wp = reinterpret_cast<const f32x4*>(m.packed_dev + p.w_off);
-            a.bias = m.packed_dev + p.b_off;
-            a.R = n; a.NT = p.NT; a.NT_rm = p.NT; a.group = 1;
-            if (last) {
-                a.Y = preds; a.ldy = p.out_dim; a.Nvalid = p.out_dim;
-                a.vec_store = (p.out_dim % 4 == 0 && aligned16(preds)) ? 1 : 0;
-                a.relu = 0;
-            } else {
-                a.Y = ws + ((i & 1) ? o.fc1 : o.fc0); a.ldy = p.NT * 32; a.Nvalid = p.NT * 32; a.vec_store = 1;
-                a.relu = 1;   // eval mode: dropout is the identity (reference modules.py:309-310)
-            }
+            RowGemmArgs a = last ? lin_rows(m, p, x, ld, n, preds) : lin_rows(m, p, x, ld, n, ws + ((i & 1) ? o.fc1 : o.fc0), p.NT * 32);
+            a.relu = last ? 0 : 1;   // eval mode: dropout is the identity (reference modules.py:309-310)
             K_TRY(launch_rowgemm(a, s), "forecasting head");
             x = a.Y; ld = a.ldy;
         }
@@ -613,24 +564,18 @@ int run_heads(Model& m, const float* hend, long ldh, int64_t n, float* preds, fl
         // recon_model.fc (modules.py:282): with few outputs (target dims of MSL / SMAP) it rides inside the recurrence;
         // otherwise the last layer's states go to memory and the Linear is one throughput GEMM over the b*W rows --
         // inside the step loop it would sit on the latency chain with 4 * Qh matrix instructions per 32 outputs
-        if (use_g16(m, m.rec, n) && o.rec16) {
+        if (gru_stack_small(m, m.rec, n, false) && o.rec16) {
             // small batch: k_gru16 keeps the states (or, when only the last step is wanted, the last state) and
             // recon_model.fc is a row GEMM over them
             Scope sc(m, S_RECON, s);
             const GruPlan& g = m.rec[0];
             const LinPlan& p = m.rec_fc;
             float* seq = ws + o.rseq0;
-            int rc = run_gru_layer(m, S_RECON, g, x, ld, kx, n, recons ? nullptr : seq, g.Hp, recons ? seq : nullptr, nullptr, nullptr, nullptr, s,
-                                   nullptr, ws + o.xp, true);
-            if (rc) return rc;
-            RowGemmArgs a{};
-            a.X = seq; a.ldx = g.Hp; a.Kvalid = g.H; a.Q = p.Q;
-            a.Wp = reinterpret_cast<const f32x4*>(m.packed_dev + p.w_off);
-            a.bias = m.packed_dev + p.b_off;
-            float* y = recons ? recons : recons_last;
-            a.Y = y; a.ldy = p.out_dim; a.Nvalid = p.out_dim;
-            a.vec_store = (p.out_dim % 4 == 0 && aligned16(y)) ? 1 : 0;
-            a.R = recons ? n * (int64_t)m.W : n; a.NT = p.NT; a.NT_rm = p.NT; a.group = 1; a.relu = 0;
+            GruIo io;
+            io.x = x; io.ldx = ld; io.kx = kx; io.hend = recons ? nullptr : seq; io.ldhe = g.Hp; io.seq = recons ? seq : nullptr;
+            io.xp = ws + o.xp;
+            if (int rc = run_gru_layer(m, S_RECON, m.rec, 0, io, n, s)) return rc;
+            RowGemmArgs a = lin_rows(m, p, seq, g.Hp, recons ? n * (int64_t)m.W : n, recons ? recons : recons_last);
             // (the arithmetic is chosen by the size of the whole reconstruction, also when only its last step is wanted: score_series
             // equals forward() on the same windows bit for bit)
             if (int rc_ = lin_split_operands(m, p, n * (int64_t)m.W, a, s)) return rc_;
@@ -645,21 +590,16 @@ int run_heads(Model& m, const float* hend, long ldh, int64_t n, float* preds, fl
             const bool last = (l == L - 1);
             const bool fc_in = last && !hoist_fc;
             float* seq = (last && !hoist_fc) ? nullptr : ws + ((l & 1) ? o.rseq1 : o.rseq0);
-            int rc = run_gru_layer(m, S_RECON, m.rec[l], x, ld, kx, n, nullptr, 0, seq, fc_in ? &m.rec_fc : nullptr,
-                                   fc_in ? recons : nullptr, fc_in ? recons_last : nullptr, s);
-            if (rc) return rc;
+            GruIo io;
+            io.x = x; io.ldx = ld; io.kx = kx; io.seq = seq;
+            if (fc_in) { io.fc = &m.rec_fc; io.yfc = recons; io.ylast = recons_last; }
+            if (int rc = run_gru_layer(m, S_RECON, m.rec, l, io, n, s)) return rc;
             x = seq; ld = m.rec[l].Hp; kx = m.rec[l].H;
         }
         if (hoist_fc) {
             Scope sc(m, S_RECON, s);
             const LinPlan& p = m.rec_fc;
-            RowGemmArgs a{};
-            a.X = x; a.ldx = ld; a.Kvalid = kx; a.Q = p.Q;
-            a.Wp = reinterpret_cast<const f32x4*>(m.packed_dev + p.w_off);
-            a.bias = m.packed_dev + p.b_off;
-            a.Y = recons; a.ldy = p.out_dim; a.Nvalid = p.out_dim;
-            a.vec_store = (p.out_dim % 4 == 0 && aligned16(recons)) ? 1 : 0;
-            a.R = n * (int64_t)m.W; a.NT = p.NT; a.NT_rm = p.NT; a.group = 1; a.relu = 0;
+            RowGemmArgs a = lin_rows(m, p, x, ld, n * (int64_t)m.W, recons);
             if (int rc_ = lin_split_operands(m, p, a.R, a, s)) return rc_;
             K_TRY(launch_rowgemm(a, s), "reconstruction Linear");
             if (recons_last)
@@ -950,6 +890,22 @@ int mtadgat_derived_regions(mtadgat_handle h, int64_t* out, int max_pairs) {
         out[2 * i + 1] = (int64_t)r[i].second;
     }
     return (int)r.size();
+}
+
+/* Read-only test hook (no GPU, no weights): the recurrence route (gru_route) of layer `layer` of the GRU stack (stack 0) or the decoder
+ * (stack 1) for a whole forward() / training forward of n windows on a device of `compute_units` CUs, under the handle's current
+ * precision and "gru_kernel" option: out[0 .. 8) = first kernel, fallback kernel (GruKernel), operand build (GruBuild), two groups
+ * per wave, hoisted input products, split packs needed, per-step Linear inside, the stack takes the small-batch kernels */
+int mtadgat_gru_route(mtadgat_handle h, int stack, int layer, int64_t n, int training, int compute_units, int* out) {
+    if (!h || !out) return fail(MTADGAT_ERR_INVALID, "null argument");
+    const Model& m = h->m;
+    if (stack != 0 && stack != 1) return fail(MTADGAT_ERR_INVALID, "stack must be 0 (GRU) or 1 (decoder)");
+    const std::vector<GruPlan>& st = stack ? m.rec : m.gru;
+    if (layer < 0 || layer >= (int)st.size() || n < 1 || compute_units < 1) return fail(MTADGAT_ERR_INVALID, "layer, window count or compute units out of range");
+    const GruRoute r = gru_route(m, st, layer, n, compute_units, gru_call_facts(m, stack == 1, layer, n, training != 0));
+    const int v[8] = {r.first, r.fallback, r.build, r.two, r.hoist, r.split_packs, r.fc_rides, gru_stack_small(m, st, n, training != 0)};
+    std::copy(v, v + 8, out);
+    return 0;
 }
 
 /* Host-only self check of the device-side re-pack's gather table (no GPU needed): packs `p` with the host packer, builds
@@ -1799,8 +1755,10 @@ int mtadgat_forward_train(mtadgat_handle h, const float* x, int64_t batch, int64
             const bool last = l == Lg - 1;
             float* seq = T + (l == 0 ? t.seq_g : t.seq_gu[l - 1]);
             float* gates = T + (l == 0 ? t.gates_g : t.gates_gu[l - 1]);
-            if ((rc = run_gru_layer(m, S_GRU, gl_, xin, ldin, kx, n, last ? hend : nullptr, gl_.Hp, seq, nullptr, nullptr, nullptr, s, gates,
-                                    l == 0 ? T + t.xp : nullptr, l == 0 && use_g16(m, m.gru, n, true), l == 0 ? vmax : nullptr))) return rc;
+            GruIo io;
+            io.x = xin; io.ldx = ldin; io.kx = kx; io.hend = last ? hend : nullptr; io.ldhe = gl_.Hp; io.seq = seq; io.gates = gates;
+            if (l == 0) { io.xp = T + t.xp; io.vmax = vmax; }
+            if ((rc = run_gru_layer(m, S_GRU, m.gru, l, io, n, s))) return rc;
             if (!last) {
                 float* dr = T + t.drop_g[l];
                 K_TRY(launch_seq_dropout(seq, dr, n, W, gl_.H, gl_.Hp, drop, DROP_GRU0 + (unsigned)l, s), "gru inter-layer dropout");
@@ -1817,17 +1775,8 @@ int mtadgat_forward_train(mtadgat_handle h, const float* x, int64_t batch, int64
         for (int i = 0; i < nfc; ++i) {
             const LinPlan& p = m.fc[i];
             const bool last = (i == nfc - 1);
-            RowGemmArgs a{};
-            a.X = xin; a.ldx = ld; a.Kvalid = p.in_dim; a.Q = p.Q;
-            a.Wp = reinterpret_cast<const f32x4*>(m.packed_dev + p.w_off);
-            a.bias = m.packed_dev + p.b_off;
-            a.R = n; a.NT = p.NT; a.NT_rm = p.NT; a.group = 1;
-            if (last) {
-                a.Y = preds; a.ldy = p.out_dim; a.Nvalid = p.out_dim;
-                a.vec_store = (p.out_dim % 4 == 0 && aligned16(preds)) ? 1 : 0;
-                a.relu = 0;
-            } else {
-                a.Y = T + t.fc_act[i]; a.ldy = p.NT * 32; a.Nvalid = p.NT * 32; a.vec_store = 1;
+            RowGemmArgs a = last ? lin_rows(m, p, xin, ld, n, preds) : lin_rows(m, p, xin, ld, n, T + t.fc_act[i], p.NT * 32);
+            if (!last) {
                 a.relu = 1;
                 a.drop_thresh = drop.thresh; a.seed_lo = drop.seed_lo; a.seed_hi = drop.seed_hi; a.keep_scale = drop.keep_scale;
                 a.drop_stream = DROP_FC0 + (unsigned)i; a.row0 = window0;
@@ -1838,19 +1787,12 @@ int mtadgat_forward_train(mtadgat_handle h, const float* x, int64_t batch, int64
     }
     // reconstruction decoder, all steps kept
     const GruPlan& r = m.rec[0];
-    if (Ld == 1 && use_g16(m, m.rec, n, true)) {
-        if ((rc = run_gru_layer(m, S_RECON, r, hend, g.Hp, m.cfg.gru_hid_dim, n, nullptr, 0, T + t.seq_d, nullptr, nullptr, nullptr, s, T + t.gates_d,
-                                T + t.xp, true))) return rc;
+    if (gru_stack_small(m, m.rec, n, true)) {
+        GruIo io;
+        io.x = hend; io.ldx = g.Hp; io.kx = m.cfg.gru_hid_dim; io.seq = T + t.seq_d; io.gates = T + t.gates_d; io.xp = T + t.xp;
+        if ((rc = run_gru_layer(m, S_RECON, m.rec, 0, io, n, s))) return rc;
         Scope sc(m, S_RECON, s);
-        const LinPlan& p = m.rec_fc;
-        RowGemmArgs a{};
-        a.X = T + t.seq_d; a.ldx = r.Hp; a.Kvalid = r.H; a.Q = p.Q;
-        a.Wp = reinterpret_cast<const f32x4*>(m.packed_dev + p.w_off);
-        a.bias = m.packed_dev + p.b_off;
-        a.Y = recons; a.ldy = p.out_dim; a.Nvalid = p.out_dim;
-        a.vec_store = (p.out_dim % 4 == 0 && aligned16(recons)) ? 1 : 0;
-        a.R = n * (int64_t)W; a.NT = p.NT; a.NT_rm = p.NT; a.group = 1; a.relu = 0;
-        K_TRY(launch_rowgemm(a, s), "reconstruction Linear (training)");
+        K_TRY(launch_rowgemm(lin_rows(m, m.rec_fc, T + t.seq_d, r.Hp, n * (int64_t)W, recons), s), "reconstruction Linear (training)");
     } else {
         // layer 0 reads the repeated h_end (modules.py:279), the layers above the (dropped-out) states of the one below; the
         // per-step Linear (modules.py:282) rides in the last layer while its weights fit beside the state in 64 KB of LDS
@@ -1858,30 +1800,23 @@ int mtadgat_forward_train(mtadgat_handle h, const float* x, int64_t batch, int64
         const float* xin = hend;
         long ldin = g.Hp;
         int kx = m.cfg.gru_hid_dim;
-        const GruPlan& rlast = m.rec[Ld - 1];
-        const bool fc_rides = ((size_t)rlast.NCG * 1024 + (size_t)rlast.NCG * m.rec_fc.out_dim * 32) * sizeof(float) <= 64 * 1024;
+        const bool fc_rides = rec_fc_rides_train(m);
         for (int l = 0; l < Ld; ++l) {
             const GruPlan& rl = m.rec[l];
             const bool last = l == Ld - 1, fused = last && fc_rides;
             float* seq = T + (l == 0 ? t.seq_d : t.seq_du[l - 1]);
             float* gates = T + (l == 0 ? t.gates_d : t.gates_du[l - 1]);
-            if ((rc = run_gru_layer(m, S_RECON, rl, xin, ldin, kx, n, nullptr, 0, seq, fused ? &m.rec_fc : nullptr, fused ? recons : nullptr, nullptr, s,
-                                    gates))) return rc;
+            GruIo io;
+            io.x = xin; io.ldx = ldin; io.kx = kx; io.seq = seq; io.gates = gates;
+            if (fused) { io.fc = &m.rec_fc; io.yfc = recons; }
+            if ((rc = run_gru_layer(m, S_RECON, m.rec, l, io, n, s))) return rc;
             if (!last) {
                 float* dr = T + t.drop_d[l];
                 K_TRY(launch_seq_dropout(seq, dr, n, W, rl.H, rl.Hp, drop, DROP_REC0 + (unsigned)l, s), "decoder inter-layer dropout");
                 xin = dr; ldin = rl.Hp; kx = rl.H;
             } else if (!fused) {
                 Scope sc(m, S_RECON, s);
-                const LinPlan& p = m.rec_fc;
-                RowGemmArgs a{};
-                a.X = seq; a.ldx = rl.Hp; a.Kvalid = rl.H; a.Q = p.Q;
-                a.Wp = reinterpret_cast<const f32x4*>(m.packed_dev + p.w_off);
-                a.bias = m.packed_dev + p.b_off;
-                a.Y = recons; a.ldy = p.out_dim; a.Nvalid = p.out_dim;
-                a.vec_store = (p.out_dim % 4 == 0 && aligned16(recons)) ? 1 : 0;
-                a.R = n * (int64_t)W; a.NT = p.NT; a.NT_rm = p.NT; a.group = 1; a.relu = 0;
-                K_TRY(launch_rowgemm(a, s), "reconstruction Linear (training)");
+                K_TRY(launch_rowgemm(lin_rows(m, m.rec_fc, seq, rl.Hp, n * (int64_t)W, recons), s), "reconstruction Linear (training)");
             }
         }
     }
@@ -1959,7 +1894,7 @@ int backward_impl(mtadgat_handle h, const float* x, int64_t batch, int64_t windo
             Gru16BwdArgs ga{};
             ga.Gates = gates; ga.Seq = seq; ga.DHseq = dhseq; ga.lddh = q.Hp; ga.DHend = dhend_; ga.ldde = q.Hp;
             ga.W16T = m.packed_dev + q.g16T_off; ga.DA = da; ga.Hp = q.Hp; ga.KS = q.KS16; ga.NT16 = q.NT16; ga.T = W; ga.B = n; ga.H = q.H;
-            if (use_g1(n)) {
+            if (n <= G1_MAX_WINDOWS) {                       // as the forward (gru_route): one window per workgroup at a time
                 ga.W16T = m.packed_dev + q.g1T_off;
                 K_TRY(launch_gru1_bwd(ga, s), what);
             } else
@@ -1999,7 +1934,7 @@ int backward_impl(mtadgat_handle h, const float* x, int64_t batch, int64_t windo
             const float* seq = T + (l == 0 ? t.seq_d : t.seq_du[l - 1]);
             const float* xin = l == 0 ? T + t.xdec : T + t.drop_d[l - 1];
             const long ldxin = l == 0 ? m.gru.back().Hp : m.rec[l - 1].Hp;
-            if ((rc = layer_bwd(q, b.rec[l], Ld == 1 && use_g16(m, m.rec, n, true), gates, seq, dhdec, nullptr, xin, ldxin, gl.rec_wih[l],
+            if ((rc = layer_bwd(q, b.rec[l], gru_stack_small(m, m.rec, n, true), gates, seq, dhdec, nullptr, xin, ldxin, gl.rec_wih[l],
                                 gl.rec_whh[l], gl.rec_bih[l], gl.rec_bhh[l], "decoder backward"))) return rc;
             if (l > 0) {
                 // d (dropped states of the layer below), then through the dropout: the gradient of that layer's states
@@ -2022,7 +1957,7 @@ int backward_impl(mtadgat_handle h, const float* x, int64_t batch, int64_t windo
         const float* xin = l == 0 ? hcat : T + t.drop_g[l - 1];
         const long ldxin = l == 0 ? m.Dp : m.gru[l - 1].Hp;
         const bool top = l == Lg - 1;
-        if ((rc = layer_bwd(q, b.gru[l], Lg == 1 && use_g16(m, m.gru, n, true), gates, seq, top ? nullptr : dhdec, top ? dhend : nullptr, xin, ldxin,
+        if ((rc = layer_bwd(q, b.gru[l], gru_stack_small(m, m.gru, n, true), gates, seq, top ? nullptr : dhdec, top ? dhend : nullptr, xin, ldxin,
                             gl.gru_wih[l], gl.gru_whh[l], gl.gru_bih[l], gl.gru_bhh[l], "gru backward"))) return rc;
         if (l > 0) {
             const GruPlan& lo = m.gru[l - 1];

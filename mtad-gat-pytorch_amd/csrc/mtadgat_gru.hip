@@ -335,10 +335,10 @@ static void launch_split_x3(const GruArgs& a, unsigned grid, int ncg, size_t lds
     }
 }
 
-static int launch_gru_split(const GruArgs& a, int ncg, int xmode, bool fc, hipStream_t s) {
+static int launch_split(const GruArgs& a, int ncg, int xmode, bool fc, hipStream_t s) {
     const unsigned grid = (unsigned)((a.B + 31) / 32);
-    const size_t lds = ((size_t)ncg * 1024 + (fc ? (size_t)ncg * a.out_dim * 32 : 0)) * sizeof(float);
-    if (lds > 64 * 1024) return -2;
+    const size_t lds = gru_split_lds_bytes(ncg, fc ? a.out_dim : 0);
+    if (lds > GRU_SPLIT_LDS_MAX) return -2;
     const int xm = xmode == 3 ? 3 : (xmode == 0 ? 0 : (a.Qxp == 1 ? 1 : 2));
     const bool save = a.Gates != nullptr;
     if (a.x3 && (xm == 3 || a.Wxq == nullptr || a.scale == nullptr)) return -2;
@@ -357,53 +357,41 @@ static int launch_gru_split(const GruArgs& a, int ncg, int xmode, bool fc, hipSt
     return 0;
 }
 
-// training forward: the hidden-tile-split kernel at every batch size (it is the one that keeps the gates)
-int launch_gru_train(const GruArgs& a, int ncg, int xmode, bool fc, hipStream_t s) {
+// the input layouts the recurrence kernels read: 16-byte rows; packed input chunks 1 (decoder) or a multiple of 3
+static bool gru_input_ok(const GruArgs& a, int xmode) {
+    if (xmode == 3) return (a.ldx & 3) == 0;
+    if (xmode == 0) return (a.ldx & 3) == 0 && a.Qxp % 3 == 0;
+    return a.Qxp == 1 || a.Qxp % 3 == 0;
+}
+
+// hidden-tile-split kernel on fp32 / bf16 packs: inference, and the training forward at every batch size (it is the one that keeps
+// the gates); xmode 3: the input products come pre-projected
+int launch_gru_split(const GruArgs& a, int ncg, int xmode, bool fc, hipStream_t s) {
     if (a.B <= 0) return 0;
-    if (xmode == 0 && ((a.ldx & 3) != 0 || a.Qxp % 3 != 0)) return -2;
-    if (xmode == 3 && (a.ldx & 3) != 0) return -2;
-    if (xmode != 0 && xmode != 3 && a.Qxp != 1 && a.Qxp % 3 != 0) return -2;
-    if (ncg < 1) return -2;
-    return launch_gru_split(a, ncg, xmode, fc, s);
+    if (a.x3 || ncg < 1 || !gru_input_ok(a, xmode)) return -2;
+    return launch_split(a, ncg, xmode, fc, s);
 }
 
 // split-operand (two fp16 pieces) build of the hidden-tile-split kernel: a.x3 = 1, a.Wh the [gate][piece] pack, a.Wxq the
 // two-piece input pack in [tile][chunk] order, a.Qxp in 16-feature chunks (a multiple of 3, or 1 for the decoder)
 int launch_gru_split_x3(const GruArgs& a, int ncg, int xmode, bool fc, hipStream_t s) {
     if (a.B <= 0) return 0;
-    if (!a.x3 || ncg < 1 || xmode == 3) return -2;
-    if (xmode == 0 && ((a.ldx & 3) != 0 || a.Qxp % 3 != 0)) return -2;
-    if (xmode != 0 && a.Qxp != 1 && a.Qxp % 3 != 0) return -2;
-    return launch_gru_split(a, ncg, xmode, fc, s);
+    if (!a.x3 || ncg < 1 || xmode == 3 || !gru_input_ok(a, xmode)) return -2;
+    return launch_split(a, ncg, xmode, fc, s);
 }
 
-// windows up to which the hidden-tile-split kernel is the faster one (a 32-window group per CU x 2)
-long gru_split_max_windows() { return 64L * cu_count(); }
-
-int launch_gru(const GruArgs& a, int ncg, int xmode, bool fc, hipStream_t s) {
+// tile-major kernel (k_gru) in the build named: it must be the one a's packs are laid out for
+int launch_gru_tile(const GruArgs& a, int ncg, int xmode, bool fc, GruBuild build, bool two, hipStream_t s) {
     if (a.B <= 0) return 0;
-    if (xmode == 3) {                // pre-projected input: only the split kernel takes it
-        if ((a.ldx & 3) != 0 || ncg < 1) return -2;
-        return launch_gru_split(a, ncg, xmode, fc, s);
+    if (xmode == 3 || !gru_input_ok(a, xmode)) return -2;
+    const bool x3 = build == GRU_X3_HI || build == GRU_X3_LO;
+    if (x3 != (a.x3 != 0) || (!x3 && (build == GRU_BF16) != (a.bf16 != 0)) || (x3 && (build == GRU_X3_HI) != (ncg >= 5))) return -2;
+    switch (build) {
+        case GRU_X3_HI: return launch_gru_big_x3_hi(a, ncg, xmode, fc, two, s);
+        case GRU_X3_LO: return launch_gru_big_x3_lo(a, ncg, xmode, fc, two, s);
+        case GRU_BF16: return launch_gru_big_bf16(a, ncg, xmode, fc, two, s);
+        default: return launch_gru_big_f32(a, ncg, xmode, fc, two, s);
     }
-    if (xmode == 0 && ((a.ldx & 3) != 0 || a.Qxp % 3 != 0)) return -2;
-    if (xmode != 0 && a.Qxp != 1 && a.Qxp % 3 != 0) return -2;
-    // Small batches: spread the 32-window groups over ncg waves each (k_gru_split) -- k_gru needs ~2 groups
-    // per SIMD to fill the machine and leaves it mostly idle below that.  Measured on MI355X (W=100, F=55,
-    // H=150, GRU + decoder): 256 windows 12.0 -> 4.9 ms, 16 k windows 12.2 -> 9.9 ms, 32 k windows 12.2 vs 19.6
-    // (the 5 waves of a group land 2/1/1/1 on the SIMDs, so the split form loses once the machine is full).
-    const int n_cu = cu_count();
-    {
-        const long groups = (a.B + 31) / 32;
-        const size_t lds = ((size_t)ncg * 1024 + (fc ? (size_t)ncg * a.out_dim * 32 : 0)) * sizeof(float);
-        if (!a.x3 && ncg >= 2 && groups <= 2L * n_cu && lds <= 64 * 1024) return launch_gru_split(a, ncg, xmode, fc, s);
-    }
-    // two groups per wave once that still gives every SIMD a wave
-    const bool two = (a.B + 31) / 32 >= 8L * n_cu;
-    if (a.x3) {
-        return ncg >= 5 ? launch_gru_big_x3_hi(a, ncg, xmode, fc, two, s) : launch_gru_big_x3_lo(a, ncg, xmode, fc, two, s);
-    }
-    return a.bf16 ? launch_gru_big_bf16(a, ncg, xmode, fc, two, s) : launch_gru_big_f32(a, ncg, xmode, fc, two, s);
 }
 
 }  // namespace mtadgat

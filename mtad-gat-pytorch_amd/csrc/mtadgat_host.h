@@ -120,6 +120,52 @@ constexpr int64_t CM_MIN_WINDOWS = 4097;
 constexpr int64_t SPLIT3_MIN_WINDOWS = 2561, SPLIT3_MAX_WINDOWS = 8192;      // k_gru_cm (chunk-major recurrence, 128 windows per workgroup) from here on
 constexpr int64_t FORK_MAX_WINDOWS = 1024;   // up to here no launch of the forward fills the machine: independent stages run on two streams
 constexpr int64_t G1_MAX_WINDOWS = 1792;       // up to 7 windows per CU one after the other; beyond that 16-window groups pay
+// The hoisted input products of GRU layer 0 (GruPlan::xproj) serve inference batches of up to 64 windows per compute unit -- two
+// 32-window groups per CU, the band of the hidden-tile-split kernel; above that the recurrence kernels stream x themselves.  The
+// workspace reserves the buffer for what a 256-CU device can use (its layout does not depend on the device).
+constexpr int64_t XP_WINDOWS_PER_CU = 64;
+constexpr int XP_PLAN_CUS = 256;
+inline bool gru_xp_serves(int64_t n, int cu) { return n <= XP_WINDOWS_PER_CU * cu; }
+
+// ---- recurrence routes ---------------------------------------------------------------------------------------------------------
+// Which kernels run one GRU / decoder layer of one call.  gru_route (mtadgat_pack.cpp) is the only place that decides; run_gru_layer
+// (mtadgat_capi.cpp) launches what it names, the callers ask gru_stack_small for the stack-level question.  DESIGN.md section 4 has
+// the table of bands.
+enum GruKernel : int {
+    GRU_NONE = 0,
+    GRU_WINDOW = 1,       // k_gru1: one window per workgroup at a time (small batch, hoisted input products)
+    GRU_GROUP16 = 2,      // k_gru16: 16-window groups (small batch, hoisted input products)
+    GRU_SPLIT = 3,        // k_gru_split: a 32-window group over NCG waves, fp32 / bf16 packs (GruRoute::build)
+    GRU_SPLIT_X3 = 4,     // k_gru_split on split operands (two fp16 pieces)
+    GRU_CM = 5,           // k_gru_cm: chunk-major, 128 windows per workgroup, split operands
+    GRU_TILE = 6,         // k_gru: tile-major, one or two 32-window groups per wave (GruRoute::build, ::two)
+};
+struct GruCall {          // what the route depends on beside the model, the layer and the window count
+    bool training = false;    // the gates of every step are kept for the backward
+    bool fc = false;          // a per-step Linear is wanted inside the recurrence ...
+    int fc_out_dim = 0;       // ... with this many outputs
+    bool range = false;       // the convolution recorded its output range for this call (layer 0 of the GRU stack behind the fused front end)
+    bool xp = false;          // a buffer for the hoisted input products is available
+    bool hend_fits = true;    // no last-state output, or its row stride is at least Hp
+};
+struct GruRoute {
+    GruKernel first = GRU_NONE;
+    GruKernel fallback = GRU_NONE;   // launched behind `first`; serves the launch when the recorded range rules out fp16 pieces (decided on the device)
+    GruBuild build = GRU_F32;        // operand build of the GRU_SPLIT / GRU_TILE kernel named above (GRU_F32 when none is)
+    bool two = false;                // GRU_TILE: two groups per wave
+    bool hoist = false;              // the input products of all steps come from a row GEMM (decoder, small batch: k_xproj_dec) in front
+    bool split_packs = false;        // the layer's split packs must be current (ensure)
+    bool guarded = false;            // layer 0's input chunks of the convolution's channels go onto two fp16 pieces under the recorded range
+    bool fc_rides = false;           // the per-step Linear runs inside the recurrence
+    bool small() const { return first == GRU_WINDOW || first == GRU_GROUP16; }
+};
+struct Model;
+// does this stack take the small-batch kernels (k_gru1 / k_gru16) at n windows?  (layer 0's route is small exactly then, given its buffer)
+bool gru_stack_small(const Model& m, const std::vector<GruPlan>& stack, int64_t n, bool training);
+GruRoute gru_route(const Model& m, const std::vector<GruPlan>& stack, int layer, int64_t n, int cu, const GruCall& c);
+// the facts of layer `layer` of the GRU stack (decoder = false) or the decoder in a whole forward() (predictions and reconstructions
+// wanted, n windows in one piece) or training forward: what mtadgat_gru_route reports
+GruCall gru_call_facts(const Model& m, bool decoder, int layer, int64_t n, bool training);
 
 // ---- backward (training) plans -------------------------------------------------------------------------
 // transposed Linear for the data gradient d X = d Y W through k_rowgemm: rows of the pack = input features
@@ -255,7 +301,7 @@ struct Model {
     int gath_dbg = 0;                // measurement hook: GatArgs::dbg of k_gath (knock-out bits, profiles/gath_knockout.py)
     int conv_fused = 0;              // the convolution inside the temporal layer's k_gath workgroup: 0 automatic (wherever both kernels apply), 1 off
     int gat_kernel = 0;              // fused attention layers in the split-operand arithmetic (testing hook): 0 automatic (k_gath, the fp16-piece build, from 4096 windows), 1 k_gat only, 3 k_gath at any batch size
-    int gru_kernel = 0;              // large-batch recurrence: 0 automatic, 1 tile-major k_gru, 2 chunk-major k_gru_cm (testing hook: mtadgat_set_option)
+    int gru_kernel = 0;              // recurrence route (gru_route): 0 automatic, 1 tile-major k_gru, 2 chunk-major k_gru_cm, 3 hidden-tile split on split operands (testing hook: mtadgat_set_option)
     DevTables dt;
     // profiling
     bool profile = false;
@@ -265,7 +311,7 @@ struct Model {
 struct Workspace {
     // offsets in floats for a chunk of `n` windows
     size_t xc, xct, lct, rtt, lcf, rtf, hcat, hend, seq0, seq1, fc0, fc1, rseq0, rseq1, xp, total;
-    bool has_xp;         // room for the pre-projected GRU input (batches the hidden-tile-split kernel serves)
+    bool has_xp;         // room for the pre-projected GRU input (gru_xp_serves on XP_PLAN_CUS compute units)
     bool rec16;          // room for the decoder's pre-projected input and state sequence (k_gru16)
     size_t vmax;         // one word: bits of the largest convolution output of the chunk (range guard of the fp16 operand pieces)
     size_t winflag;      // one byte per window: the fused convolution's per-window range flag (k_gath CONV build -> k_gat)
@@ -294,6 +340,9 @@ struct BwdWorkspace {
 
 // the input gradient of a window of more than 64 KB (W F floats) is the k_conv convolution over conv_wT_off instead of k_conv_dx
 inline bool conv_dx_wide(const Model& m) { return (size_t)m.W * m.F * sizeof(float) > 64 * 1024; }
+// training forward: the per-step Linear (modules.py:282) rides in the last decoder layer while its partial sums fit beside the
+// state in the hidden-tile-split kernel's LDS; otherwise it is a row GEMM over the kept states
+inline bool rec_fc_rides_train(const Model& m) { return gru_split_lds_bytes(m.rec.back().NCG, m.rec_fc.out_dim) <= GRU_SPLIT_LDS_MAX; }
 std::string validate_and_plan(Model& m);                       // "" on success
 FlatOffsets flat_offsets(const Model& m);
 void params_from_flat(const Model& m, const FlatOffsets& fo, const float* flat, mtadgat_params& p);

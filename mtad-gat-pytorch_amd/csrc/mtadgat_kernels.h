@@ -390,13 +390,20 @@ int launch_bw_v1(const float* Vn, long ldv, int D, int K, const float* u, const 
                  long nwin, hipStream_t s);
 int launch_bw_pair(const float* LR, int ldlr, int Ep, const float* avec, const float* DE, int K, float alpha, float* DLR, float* DAp,
                    long nwin, hipStream_t s);
-int launch_gru(const GruArgs& a, int ncg, int xmode, bool fc, hipStream_t s);
-int launch_gru_train(const GruArgs& a, int ncg, int xmode, bool fc, hipStream_t s);     // always the hidden-tile-split kernel
+// The recurrence launchers launch exactly the kernel they name: which one a layer gets is decided by gru_route (mtadgat_host.h).
+// LDS of a hidden-tile-split workgroup (k_gru_split): the state exchange [NCG][16][64] and, when a per-step Linear rides inside, its
+// partial sums [NCG][out_dim][32]; the kernel applies while this fits 64 KB
+inline size_t gru_split_lds_bytes(int ncg, int fc_out_dim) { return ((size_t)ncg * 1024 + (size_t)ncg * fc_out_dim * 32) * sizeof(float); }
+constexpr size_t GRU_SPLIT_LDS_MAX = 64 * 1024;
+// operand build of the hidden-tile-split / tile-major kernel (GruArgs::bf16, ::x3; the x3 tile-major kernels are instantiated in two
+// translation units: NCG 5 .. 8 and 1 .. 4)
+enum GruBuild : int { GRU_F32 = 0, GRU_BF16 = 1, GRU_X3_HI = 2, GRU_X3_LO = 3 };
+int launch_gru_split(const GruArgs& a, int ncg, int xmode, bool fc, hipStream_t s);      // hidden-tile split, fp32 / bf16 packs (xmode 3: pre-projected input)
+int launch_gru_split_x3(const GruArgs& a, int ncg, int xmode, bool fc, hipStream_t s);   // hidden-tile split on split operands
+int launch_gru_tile(const GruArgs& a, int ncg, int xmode, bool fc, GruBuild build, bool two, hipStream_t s);   // tile-major k_gru, `two` groups per wave
 bool gru_cm_supported(int ncg, int xmode, bool fc, int out_dim);
 int launch_gru_cm(const GruArgs& a, int ncg, int xmode, bool fc, hipStream_t s);
-int launch_gru_split_x3(const GruArgs& a, int ncg, int xmode, bool fc, hipStream_t s);
 int launch_reorder_xq(const float* src, float* dst, int ncg, int Qd, hipStream_t s);
-long gru_split_max_windows();
 int launch_gru_bwd(const GruBwdArgs& a, hipStream_t s);
 int launch_fingerprint(const FingerprintArgs& a, int n_tensors, unsigned long long* out, hipStream_t s);
 int launch_split3(const float* src, float* dst, long n_outer, int Qs, int Qd, int G, const float* scale, hipStream_t s);

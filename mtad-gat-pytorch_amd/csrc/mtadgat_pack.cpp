@@ -478,6 +478,124 @@ std::string validate_and_plan(Model& m) {
     return "";
 }
 
+// ---- recurrence routes (mtadgat_host.h) -----------------------------------------------------------------------------------------
+namespace {
+
+// The split-operand kernels read 16-feature input chunks on two fp16 pieces.  Layer 0 of the GRU stack reads the convolution's
+// (unbounded) output in its first qb3 chunks: those may go onto fp16 pieces only when the convolution recorded its output range --
+// both kernels are launched then and the device picks (GruRoute::fallback); every other layer reads states and sigmoids, |x| <= 1.
+bool gru_range_guarded(const GruPlan& g, const GruCall& c) { return c.range && g.wx2_off && g.qb3 > 0; }
+bool gru_pieces_apply(const GruPlan& g, const GruCall& c) {
+    if (g.xmode == 1) return g.Qxp16 == 1;                    // the decoder's folded input: one chunk per step
+    return gru_range_guarded(g, c) || g.qb3 == 0;
+}
+// whole turns of the weight ring: of two stages (inference builds) or of the six that keep the gates (training)
+bool gru_ring_turns(const GruPlan& g, int stages) { return g.Qxp16 == 1 || g.Qxp16 % stages == 0; }
+
+// Can k_gru_cm / the split-operand build of k_gru_split serve this layer in this call?  (hidden sizes above 160, windows of more than
+// 512 steps, a per-step Linear of more than 4 outputs, layer-0 packs that need the range guard without a recorded range cannot)
+bool gru_split_operands_fit(const Model& m, const GruPlan& g, const GruCall& c) {
+    return gru_cm_supported(g.NCG, g.xmode, c.fc, c.fc ? c.fc_out_dim : 0) && gru_ring_turns(g, 2) &&
+           (g.xmode == 1 || (g.wxq_off != 0 && g.Qx >= 3)) && gru_pieces_apply(g, c) && c.hend_fits && m.W <= 512;
+}
+
+}  // namespace
+
+// The small-batch fp32 recurrences (k_gru1 up to G1_MAX_WINDOWS, then k_gru16; mtadgat_gru16.hip) apply to a single-layer stack whose
+// weights fit a wave's registers, up to G16_MAX_WINDOWS.  Inference in the bf16 mode uses them up to 1024 windows -- faster there
+// than the bf16 build of the throughput kernels, and exact; inference in the split-operand arithmetic leaves them from
+// SPLIT3_MIN_WINDOWS on where the hidden-tile-split kernel's split-operand build applies (it is the faster one there; gru_kernel = 3
+// forces it at any size).  Layers the split-operand kernels cannot serve keep k_gru16 up to G16_MAX_WINDOWS.  The question is asked
+// before the call's buffers are known: the range counts as recorded when the front end is fused (the convolution records it only
+// there), the last-state rows as wide enough.
+bool gru_stack_small(const Model& m, const std::vector<GruPlan>& stack, int64_t n, bool training) {
+    if (stack.size() != 1 || !stack[0].has16) return false;
+    if (m.precision == 1) return !training && n <= 1024;
+    GruCall c;
+    c.range = m.temp.fused && m.feat.fused;
+    if (m.precision == 2 && !training && stack[0].NCG >= 2 && gru_split_operands_fit(m, stack[0], c) &&
+        (m.gru_kernel == 3 || (m.gru_kernel == 0 && n >= SPLIT3_MIN_WINDOWS))) return false;
+    return n <= G16_MAX_WINDOWS;
+}
+
+GruRoute gru_route(const Model& m, const std::vector<GruPlan>& stack, int layer, int64_t n, int cu, const GruCall& c) {
+    const GruPlan& g = stack[layer];
+    GruRoute r;
+    if (layer == 0 && c.xp && gru_stack_small(m, stack, n, c.training)) {
+        // input products of all steps ahead of the recurrence, register-resident weights; a per-step Linear is the caller's row GEMM
+        r.first = n <= G1_MAX_WINDOWS ? GRU_WINDOW : GRU_GROUP16;
+        r.hoist = true;
+        return r;
+    }
+    r.fc_rides = c.fc;
+    const bool p2 = m.precision == 2;
+    const bool lds_fits = gru_split_lds_bytes(g.NCG, c.fc ? c.fc_out_dim : 0) <= GRU_SPLIT_LDS_MAX;
+    const GruBuild plain = m.precision == 1 ? GRU_BF16 : GRU_F32;
+    if (c.training) {
+        // The hidden-tile-split kernel at every size (it is the one that keeps the gates): from SPLIT3_MIN_WINDOWS on its
+        // split-operand build -- the input part in the kernel (no pre-projection GEMM on the fp32 pipe), any per-step Linear --
+        // with the fp32 build behind it where layer 0's range guard may refuse; below, on fp32 packs behind the hoisted projection.
+        const bool sp = p2 && g.NCG >= 2 && m.gru_kernel != 1 && n >= SPLIT3_MIN_WINDOWS && gru_ring_turns(g, 6) &&
+                        gru_pieces_apply(g, c) && c.hend_fits && lds_fits;
+        r.first = sp ? GRU_SPLIT_X3 : GRU_SPLIT;
+        r.guarded = sp && g.xmode == 0 && g.qb3 > 0;
+        r.fallback = r.guarded ? GRU_SPLIT : GRU_NONE;
+        r.build = plain;
+        r.split_packs = sp;
+        r.hoist = !sp && c.xp && g.has_xproj && g.xmode == 0;
+        return r;
+    }
+    // Chunk-major recurrence (k_gru_cm): 32 windows per wave, the weight stream shared by a workgroup's waves through LDS, from
+    // CM_MIN_WINDOWS on.  Measured against the kernels it replaces (MSL shape, GRU layer + decoder): 12 288 windows 5.9 -> 4.0 ms,
+    // 32 768: 7.3 -> 4.4, 65 536: 12.0 -> 9.1.  Between SPLIT3_MIN_WINDOWS and SPLIT3_MAX_WINDOWS the split-operand build of the
+    // hidden-tile-split kernel instead (same packs, same range guard): there a 32-window wave per SIMD is a latency chain, five waves
+    // per 32 windows are not.
+    const bool fit = p2 && gru_split_operands_fit(m, g, c);
+    const bool sp = fit && g.NCG >= 2 && (m.gru_kernel == 3 || (m.gru_kernel == 0 && n >= SPLIT3_MIN_WINDOWS && n <= SPLIT3_MAX_WINDOWS));
+    const bool cm = fit && !sp && (m.gru_kernel == 2 || (m.gru_kernel == 0 && n >= CM_MIN_WINDOWS));
+    // Split-bf16 operands (fp32-class results from the bf16 matrix pipe) for the tile-major kernel from 1.25 32-window groups per CU
+    // on (measured: 12 320 windows 10.5 ms against 13.1 ms for the hidden-tile-split kernel at 12 288; 8 192 windows 7.4 ms there),
+    // and wherever a split-operand kernel runs in front of it.
+    const long groups = (long)((n + 31) / 32);
+    const bool x3 = p2 && gru_ring_turns(g, 2) && (groups > 5L * cu / 4 || cm || sp);
+    r.split_packs = x3;
+    r.guarded = x3 && gru_range_guarded(g, c);
+    // small batch: all steps' input products as one throughput GEMM, the recurrence keeps only its h part
+    r.hoist = !x3 && c.xp && g.has_xproj && g.xmode == 0 && gru_xp_serves(n, cu);
+    // The kernel on un-split (or three-piece) operands.  Up to two groups per CU the 32-window groups are spread over NCG waves each
+    // (k_gru_split) -- k_gru needs ~2 groups per SIMD to fill the machine and leaves it mostly idle below that.  Measured on MI355X
+    // (W=100, F=55, H=150, GRU + decoder): 256 windows 12.0 -> 4.9 ms, 16 k windows 12.2 -> 9.9 ms, 32 k windows 12.2 vs 19.6 (the 5
+    // waves of a group land 2/1/1/1 on the SIMDs, so the split form loses once the machine is full).  Pre-projected input: only the
+    // split kernel takes it.  k_gru takes two groups per wave once that still gives every SIMD a wave.
+    GruKernel tail = GRU_TILE;
+    if (r.hoist || (!x3 && g.NCG >= 2 && groups <= 2L * cu && lds_fits)) tail = GRU_SPLIT;
+    if (tail == GRU_TILE) r.two = groups >= 8L * cu;
+    r.build = x3 ? (g.NCG >= 5 ? GRU_X3_HI : GRU_X3_LO) : plain;
+    if ((sp && lds_fits) || cm) {
+        r.first = sp ? GRU_SPLIT_X3 : GRU_CM;
+        r.fallback = r.guarded ? tail : GRU_NONE;
+        if (r.fallback == GRU_NONE) { r.build = GRU_F32; r.two = false; }
+    } else {
+        r.first = tail;
+    }
+    return r;
+}
+
+GruCall gru_call_facts(const Model& m, bool decoder, int layer, int64_t n, bool training) {
+    GruCall c;
+    c.training = training;
+    if (!decoder) {
+        c.range = layer == 0 && (training || (m.temp.fused && m.feat.fused));
+        c.xp = layer == 0 && (training || (m.gru[0].has_xproj && gru_xp_serves(n, XP_PLAN_CUS)));
+        return c;
+    }
+    const bool last = layer == (int)m.rec.size() - 1;
+    c.fc = last && (training ? rec_fc_rides_train(m) : m.cfg.out_dim <= 4);
+    c.fc_out_dim = m.rec_fc.out_dim;
+    c.xp = layer == 0 && m.rec.size() == 1 && m.rec[0].has16 && n <= G16_MAX_WINDOWS;
+    return c;
+}
+
 void plan_workspace(const Model& m, int64_t n, Workspace& ws) {
     size_t off = 0;
     auto take = [&](size_t cnt) {
@@ -523,7 +641,7 @@ void plan_workspace(const Model& m, int64_t n, Workspace& ws) {
     const bool rseq = m.rec.size() > 1 || m.cfg.out_dim > 4 || rec16;
     ws.rseq0 = take(rseq ? N * m.W * m.rec[0].Hp : 0);
     ws.rseq1 = take((m.rec.size() > 2 || (m.rec.size() > 1 && m.cfg.out_dim > 4)) ? N * m.W * m.rec[0].Hp : 0);
-    ws.has_xp = m.gru[0].has_xproj && n <= 16384;          // 64 windows per CU x 256 CUs: above that k_gru streams x itself
+    ws.has_xp = m.gru[0].has_xproj && gru_xp_serves(n, XP_PLAN_CUS);
     ws.xp = take((ws.has_xp || rec16) ? N * m.W * 3 * std::max(m.gru[0].Hp, m.rec[0].Hp) : 0);
     ws.vmax = take(64);
     ws.winflag = take(both_fused ? (N + 3) / 4 + 16 : 0);
