@@ -407,6 +407,31 @@ int mtadgat_eval_epsilon_table(const float* e_dev, int64_t n, const double* eps_
                                double* out_host, void* stream);
 int mtadgat_eval_point_adjust(const float* score_dev, const unsigned char* label_dev, int64_t n, const double* thr_host,
                               int n_thr, int compare_f32, int max_seg, double* scratch_dev, double* out_host, void* stream);
+/* The two find_epsilon passes for every column of an (n, d) array with row stride ld >= d (floats) in one launch each.
+ * moments: scratch >= 2*d doubles, out_host d x [sum, sumsq].  epsilon table: eps_host d x nz thresholds, scratch >= 5*d*nz
+ * doubles, out_host d x nz x [pruned sum, pruned sumsq, pruned count, dilated count].  d <= 2048, nz <= 64. */
+int mtadgat_eval_moments_columns(const float* e_dev, int64_t n, int d, int64_t ld, double* scratch_dev, double* out_host,
+                                 void* stream);
+int mtadgat_eval_epsilon_table_columns(const float* e_dev, int64_t n, int d, int64_t ld, const double* eps_host, int nz,
+                                       int halo, double* scratch_dev, double* out_host, void* stream);
+/* Quantiles of every column of a (n, d, ld) float32 array (prediction.py:84-88, --scale_scores): out_dev (nq, d) float32 in
+ * np.percentile's "linear" definition -- pos = q (n - 1) in float64, lo = floor(pos), hi = min(lo + 1, n - 1),
+ * s[lo] + (s[hi] - s[lo]) (pos - lo) evaluated in float64 from the two EXACT order statistics (radix select, no sort) and
+ * rounded once.  A column holding a NaN gives NaN for every q.  Bitwise reproducible; asynchronous on `stream` (q_host is
+ * read before the call returns).  n <= 2^31 - 1, d <= 2048, nq <= 4096, every q in [0, 1]; scratch_dev: 16-byte aligned,
+ * at least mtadgat_eval_column_quantiles_scratch(n, d, nq) bytes (0 for invalid sizes), need not be initialised.
+ * Status 0 / -1 (bad argument) / -3 (HIP) / -5 (scratch too small or misaligned); nothing is launched on an error. */
+size_t mtadgat_eval_column_quantiles_scratch(int64_t n, int d, int nq);
+int mtadgat_eval_column_quantiles(const float* a_dev, int64_t n, int d, int64_t ld, const double* q_host, int nq,
+                                  void* scratch_dev, size_t scratch_bytes, float* out_dev, void* stream);
+/* Exponentially weighted mean of a 1-D float32 array (pandas ewm(span).mean(), adjust=True; prediction.py:99-103,
+ * --use_mov_av): alpha = 2 / (span + 1) in (0, 1], y[t] = N_t / D_t with N_t = x_t + (1 - alpha) N_{t-1} and
+ * D_t = (1 - (1 - alpha)^(t + 1)) / alpha, a blocked scan in float64 with a fixed order of operations (bitwise
+ * reproducible), stored as float32.  out_dev may be x_dev.  Asynchronous on `stream`.  scratch_dev: 8-byte aligned, at least
+ * mtadgat_eval_ewm_scratch(n) bytes, need not be initialised.  Status as above. */
+size_t mtadgat_eval_ewm_scratch(int64_t n);
+int mtadgat_eval_ewm(const float* x_dev, int64_t n, double alpha, void* scratch_dev, size_t scratch_bytes, float* out_dev,
+                     void* stream);
 
 /* Per-kernel launch timing for bench.py's roofline leg: when enabled, forward()
  * brackets each kernel family with hipEvents on `stream`; mtadgat_profile_read

@@ -626,6 +626,8 @@ int check_common(mtadgat_handle h, int64_t batch, void* ws, size_t ws_bytes, boo
 
 }  // namespace
 
+int mtadgat::record_error(int code, const char* msg) { return fail(code, msg); }
+
 extern "C" {
 
 int mtadgat_abi_version(void) { return MTADGAT_ABI_VERSION; }

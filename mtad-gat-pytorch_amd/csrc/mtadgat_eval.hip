@@ -36,40 +36,63 @@ __device__ __forceinline__ double block_sum(double v, double* sm) {
     return r;
 }
 
-// out[0] += sum e, out[1] += sum e^2  (double)
-__global__ void k_eval_moments(const float* __restrict__ e, long n, double* __restrict__ out) {
+// column blockIdx.y of an (n, d) array with row stride ld (a 1-D array: d = ld = 1): out[2 col] += sum e, out[2 col + 1] += sum e^2  (double)
+__global__ void k_eval_moments(const float* __restrict__ e, long n, long ld, double* __restrict__ out) {
     __shared__ double sm[256];
+    e += blockIdx.y;
     double s = 0.0, s2 = 0.0;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const double v = e[i];
+        const double v = e[i * ld];
         s += v;
         s2 += v * v;
     }
     s = block_sum(s, sm);
     s2 = block_sum(s2, sm);
     if (threadIdx.x == 0) {
-        atomicAdd(&out[0], s);
-        atomicAdd(&out[1], s2);
+        atomicAdd(&out[2 * blockIdx.y], s);
+        atomicAdd(&out[2 * blockIdx.y + 1], s2);
     }
 }
 
-// find_epsilon, one z per blockIdx.y: epsilon = mean + sd * z;
-//   out[z] = { sum of e < eps, sum of squares, count of e < eps, |{ i : some |k| <= 49 has e[i + k] >= eps }| }
-__global__ void k_eval_epsilon(const float* __restrict__ e, long n, const double* __restrict__ eps, int halo, double* __restrict__ out) {
+// find_epsilon, one z per blockIdx.y and one column per blockIdx.z: epsilon = mean + sd * z, eps[col * nz + z];
+//   out[col * nz + z] = { sum of e < eps, sum of squares, count of e < eps, |{ i : some |k| <= 49 has e[i + k] >= eps }| }
+// Each step of the grid-stride loop stages its 256 rows and their halo once in LDS as the flags e >= eps, so the dilation reads
+// LDS and the array is read once per z instead of 2 halo + 1 times (halo <= EPS_HALO_MAX; wider halos read memory directly).
+constexpr int EPS_HALO_MAX = 128;
+__global__ void k_eval_epsilon(const float* __restrict__ e, long n, long ld, const double* __restrict__ eps, int halo, double* __restrict__ out) {
     __shared__ double sm[256];
-    const double ez = eps[blockIdx.y];
+    __shared__ unsigned char hot[256 + 2 * EPS_HALO_MAX];
+    e += blockIdx.z;
+    const long cell = (long)blockIdx.z * gridDim.y + blockIdx.y;
+    const double ez = eps[cell];
+    const bool tiled = halo <= EPS_HALO_MAX;
     double s = 0.0, s2 = 0.0, cnt = 0.0, dil = 0.0;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const double v = e[i];
-        if (v < ez) { s += v; s2 += v * v; cnt += 1.0; }
-        const long lo = i - halo < 0 ? 0 : i - halo, hi = i + halo >= n ? n - 1 : i + halo;
-        bool any = false;
-        for (long k = lo; k <= hi; ++k) any = any || ((double)e[k] >= ez);
-        dil += any ? 1.0 : 0.0;
+    for (long base = (long)blockIdx.x * blockDim.x; base < n; base += (long)gridDim.x * blockDim.x) {   // block-uniform trip count
+        const long i = base + threadIdx.x;
+        if (tiled) {
+            __syncthreads();                              // the previous step's reads of `hot` are done
+            for (int t = threadIdx.x; t < 256 + 2 * halo; t += 256) {
+                const long k = base - halo + t;
+                hot[t] = (k >= 0 && k < n) ? ((double)e[k * ld] >= ez) : 0;
+            }
+            __syncthreads();
+        }
+        if (i < n) {
+            const double v = e[i * ld];
+            if (v < ez) { s += v; s2 += v * v; cnt += 1.0; }
+            bool any = false;
+            if (tiled) {
+                for (int t = 0; t <= 2 * halo; ++t) any = any || hot[threadIdx.x + t];
+            } else {
+                const long lo = i - halo < 0 ? 0 : i - halo, hi = i + halo >= n ? n - 1 : i + halo;
+                for (long k = lo; k <= hi; ++k) any = any || ((double)e[k * ld] >= ez);
+            }
+            dil += any ? 1.0 : 0.0;
+        }
     }
     s = block_sum(s, sm); s2 = block_sum(s2, sm); cnt = block_sum(cnt, sm); dil = block_sum(dil, sm);
     if (threadIdx.x == 0) {
-        double* o = out + 4 * blockIdx.y;
+        double* o = out + 4 * cell;
         atomicAdd(&o[0], s); atomicAdd(&o[1], s2); atomicAdd(&o[2], cnt); atomicAdd(&o[3], dil);
     }
 }
@@ -144,7 +167,7 @@ int mtadgat_eval_moments(const float* e_dev, int64_t n, double* scratch_dev, dou
     if (!e_dev || !scratch_dev || !out_host || n <= 0) return -1;
     hipStream_t s = (hipStream_t)stream;
     if (hipMemsetAsync(scratch_dev, 0, 2 * sizeof(double), s) != hipSuccess) return -3;
-    hipLaunchKernelGGL(k_eval_moments, dim3(256), dim3(256), 0, s, e_dev, (long)n, scratch_dev);
+    hipLaunchKernelGGL(k_eval_moments, dim3(256), dim3(256), 0, s, e_dev, (long)n, 1L, scratch_dev);
     if (hipMemcpyAsync(out_host, scratch_dev, 2 * sizeof(double), hipMemcpyDeviceToHost, s) != hipSuccess) return -3;
     return hipStreamSynchronize(s) == hipSuccess ? 0 : -3;
 }
@@ -157,9 +180,43 @@ int mtadgat_eval_epsilon_table(const float* e_dev, int64_t n, const double* eps_
     double* tab = scratch_dev + 64;              // 4 * nz
     if (hipMemcpyAsync(eps_dev, eps_host, nz * sizeof(double), hipMemcpyHostToDevice, s) != hipSuccess) return -3;
     if (hipMemsetAsync(tab, 0, 4 * nz * sizeof(double), s) != hipSuccess) return -3;
-    hipLaunchKernelGGL(k_eval_epsilon, dim3(128, nz), dim3(256), 0, s, e_dev, (long)n, eps_dev, halo, tab);
+    hipLaunchKernelGGL(k_eval_epsilon, dim3(128, nz), dim3(256), 0, s, e_dev, (long)n, 1L, eps_dev, halo, tab);
     if (hipMemcpyAsync(out_host, tab, 4 * nz * sizeof(double), hipMemcpyDeviceToHost, s) != hipSuccess) return -3;
     return hipStreamSynchronize(s) == hipSuccess ? 0 : -3;
+}
+
+// The two calls above for every column of an (n, d) array with row stride ld in one launch each.
+// scratch_dev: >= 2*d doubles.  out_host: d x [sum, sumsq].
+int mtadgat_eval_moments_columns(const float* e_dev, int64_t n, int d, int64_t ld, double* scratch_dev, double* out_host, void* stream) {
+    if (!e_dev || !scratch_dev || !out_host) return record_error(-1, "moments_columns: null pointer");
+    if (n < 1 || d < 1 || d > 2048 || ld < d) return record_error(-1, "moments_columns: needs n >= 1, 1 <= d <= 2048, ld >= d");
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(scratch_dev, 0, 2 * (size_t)d * sizeof(double), s) != hipSuccess) return record_error(-3, "moments_columns: memset failed");
+    const long bx = (n + 255) / 256;
+    hipLaunchKernelGGL(k_eval_moments, dim3((unsigned)(bx < 256 ? bx : 256), d), dim3(256), 0, s, e_dev, (long)n, (long)ld, scratch_dev);
+    if (hipMemcpyAsync(out_host, scratch_dev, 2 * (size_t)d * sizeof(double), hipMemcpyDeviceToHost, s) != hipSuccess)
+        return record_error(-3, "moments_columns: copy failed");
+    return hipStreamSynchronize(s) == hipSuccess ? 0 : record_error(-3, "moments_columns: stream failed");
+}
+
+// eps_host: d x nz thresholds.  scratch_dev: >= 5*d*nz doubles.  out_host: d x nz x [pruned sum, pruned sumsq, pruned count, dilated count].
+int mtadgat_eval_epsilon_table_columns(const float* e_dev, int64_t n, int d, int64_t ld, const double* eps_host, int nz, int halo,
+                                       double* scratch_dev, double* out_host, void* stream) {
+    if (!e_dev || !eps_host || !scratch_dev || !out_host) return record_error(-1, "epsilon_table_columns: null pointer");
+    if (n < 1 || d < 1 || d > 2048 || ld < d || nz < 1 || nz > 64 || halo < 0)
+        return record_error(-1, "epsilon_table_columns: needs n >= 1, 1 <= d <= 2048, ld >= d, 1 <= nz <= 64, halo >= 0");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t cells = (size_t)d * nz;
+    double* eps_dev = scratch_dev;               // d * nz
+    double* tab = scratch_dev + cells;           // 4 * d * nz
+    if (hipMemcpyAsync(eps_dev, eps_host, cells * sizeof(double), hipMemcpyHostToDevice, s) != hipSuccess)
+        return record_error(-3, "epsilon_table_columns: copy failed");
+    if (hipMemsetAsync(tab, 0, 4 * cells * sizeof(double), s) != hipSuccess) return record_error(-3, "epsilon_table_columns: memset failed");
+    const long bx = (n + 255) / 256;
+    hipLaunchKernelGGL(k_eval_epsilon, dim3((unsigned)(bx < 128 ? bx : 128), nz, d), dim3(256), 0, s, e_dev, (long)n, (long)ld, eps_dev, halo, tab);
+    if (hipMemcpyAsync(out_host, tab, 4 * cells * sizeof(double), hipMemcpyDeviceToHost, s) != hipSuccess)
+        return record_error(-3, "epsilon_table_columns: copy failed");
+    return hipStreamSynchronize(s) == hipSuccess ? 0 : record_error(-3, "epsilon_table_columns: stream failed");
 }
 
 // scratch_dev: >= 7*n_thr doubles followed by (2*max_seg + 2) ints;  out_host: n_thr x [TP, TN, FP, FN, latency sum, detected]

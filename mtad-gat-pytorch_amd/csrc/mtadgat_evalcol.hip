@@ -1,0 +1,320 @@
+// Per-column order statistics and the exponentially weighted mean of the anomaly scores (reference prediction.py:65-165:
+// --scale_scores, --use_mov_av), so that the Predictor's post-processing stays on the device with the scores.
+//
+//   k_eval_colq_*: np.percentile ("linear") of every column of an (n, d) array for nq probabilities at once.  The two order
+//       statistics each probability needs are EXACT: a most-significant-digit radix select (four 8-bit digits) on the
+//       order-preserving 32-bit key of the float, all columns and all 2 nq ranks per pass.  Histograms are built with integer
+//       atomics in LDS and merged with integer atomics in memory -- integer sums do not depend on their order, so two runs give
+//       the same bits -- and the digit of every (column, rank) is chosen on the device between the passes.  Nothing is sorted.
+//   k_eval_ewm_*: pandas' ewm(span).mean() (adjust=True) as a blocked scan in float64: chunk-local scans, one wave that
+//       composes the chunk carries in chunk order, and a pass that applies carry and closed-form denominator.  No atomics.
+#include "mtadgat_device.h"
+
+namespace mtadgat {
+
+// ---- column quantiles ------------------------------------------------------------------------------------------------------------
+constexpr int CQ_CT = 8;        // columns per workgroup: 8 neighbouring lanes read 8 neighbouring columns of a row
+constexpr int CQ_RT = 6;        // ranks per workgroup: CQ_RT * CQ_CT histograms of 256 bins = 48 KiB of LDS
+constexpr int CQ_ROWS = 256 / CQ_CT;
+
+// float -> unsigned with the same order (negative: all bits flipped; non-negative: sign bit set); -0.0 sorts just below +0.0
+__device__ __forceinline__ unsigned colq_key(float v) {
+    const unsigned u = __builtin_bit_cast(unsigned, v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float colq_value(unsigned k) {
+    return __builtin_bit_cast(float, (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+// position of probability q among n sorted values: lo = floor(q (n - 1)) in float64, the weight of s[lo + 1] returned in *frac
+__device__ __forceinline__ unsigned colq_rank(double q, long n, double* frac) {
+    const double pos = __dmul_rn(q, (double)(n - 1));     // rounded product: a fused pos - lo would use the unrounded one
+    const double lo = floor(pos);
+    if (frac) *frac = __dsub_rn(pos, lo);
+    return (unsigned)lo;
+}
+
+constexpr int CQ_INLINE = 8;    // up to this many probabilities travel in the kernel arguments: no host-to-device copy
+struct ColqProbs {
+    double v[CQ_INLINE];
+};
+
+// state[(col * R + r) * 2] = { key bits chosen so far, rank still to find among the keys that share them }
+// inl: the probabilities are in `pv` and are written to q for the interpolation; otherwise q already holds them
+__global__ void k_eval_colq_init(double* __restrict__ q, ColqProbs pv, int inl, int nq, long n, int d, unsigned* __restrict__ state,
+                                 unsigned* __restrict__ nanflag, unsigned* __restrict__ hist) {
+    const int R = 2 * nq;
+    if (inl && blockIdx.x == 0 && threadIdx.x < nq) q[threadIdx.x] = pv.v[threadIdx.x];
+    const long nstate = (long)d * R;
+    const long nhist = nstate * 256;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nhist; i += (long)gridDim.x * blockDim.x) {
+        hist[i] = 0u;
+        if (i < nstate) {
+            const int r = (int)(i % R);
+            const unsigned lo = colq_rank(inl ? pv.v[r >> 1] : q[r >> 1], n, nullptr);
+            const unsigned hi = (long)lo + 1 < n ? lo + 1 : (unsigned)(n - 1);
+            state[2 * i] = 0u;
+            state[2 * i + 1] = (r & 1) ? hi : lo;
+        }
+        if (i < d) nanflag[i] = 0u;
+    }
+}
+
+// One radix pass: for every (column, rank) the histogram of digit (key >> shift) & 255 over the keys whose higher digits equal
+// the rank's prefix.  grid = (column tiles, row slices, rank groups); the rows are walked grid-stride.
+__global__ void __launch_bounds__(256) k_eval_colq_hist(const float* __restrict__ a, long n, int d, long ld, int R, int shift,
+                                                         const unsigned* __restrict__ state, unsigned* __restrict__ hist,
+                                                         unsigned* __restrict__ nanflag) {
+    __shared__ unsigned h[CQ_RT * CQ_CT * 256];
+    const int tid = threadIdx.x;
+    const int c = tid & (CQ_CT - 1);
+    const int col = blockIdx.x * CQ_CT + c;
+    const int r0 = blockIdx.z * CQ_RT;
+    const int nr = R - r0 < CQ_RT ? R - r0 : CQ_RT;
+    for (int i = tid; i < CQ_RT * CQ_CT * 256; i += 256) h[i] = 0u;
+    const unsigned high = shift == 24 ? 0u : (0xffffffffu << (shift + 8));
+    unsigned pfx[CQ_RT];
+#pragma unroll
+    for (int r = 0; r < CQ_RT; ++r) pfx[r] = (col < d && r < nr) ? state[2 * ((long)col * R + r0 + r)] : 0u;
+    __syncthreads();
+    if (col < d) {
+        bool seen_nan = false;
+        for (long row = (long)blockIdx.y * CQ_ROWS + (tid >> 3); row < n; row += (long)gridDim.y * CQ_ROWS) {
+            const float v = a[row * ld + col];
+            seen_nan = seen_nan || (v != v);
+            const unsigned key = colq_key(v);
+            const unsigned bin = (key >> shift) & 255u;
+#pragma unroll
+            for (int r = 0; r < CQ_RT; ++r)
+                if (r < nr && ((key ^ pfx[r]) & high) == 0u) atomicAdd(&h[(r * CQ_CT + c) * 256 + bin], 1u);
+        }
+        if (seen_nan && shift == 24 && blockIdx.z == 0) atomicOr(&nanflag[col], 1u);
+    }
+    __syncthreads();
+    for (int i = tid; i < nr * CQ_CT * 256; i += 256) {
+        const unsigned v = h[i];
+        const int cc = blockIdx.x * CQ_CT + ((i >> 8) & (CQ_CT - 1));
+        if (v && cc < d) atomicAdd(&hist[((long)cc * R + r0 + (i >> 8) / CQ_CT) * 256 + (i & 255)], v);
+    }
+}
+
+// One wave per (column, rank): the digit whose bin holds the rank, appended to the prefix; the bins are cleared for the next pass.
+// After the last digit the prefix is the key of the order statistic.
+__global__ void __launch_bounds__(64) k_eval_colq_pick(unsigned* __restrict__ state, unsigned* __restrict__ hist, int shift,
+                                                        float* __restrict__ ord) {
+    const long idx = blockIdx.x;
+    const int lane = threadIdx.x;
+    uint4* bins = reinterpret_cast<uint4*>(hist + idx * 256) + lane;
+    const uint4 b = *bins;
+    *bins = make_uint4(0u, 0u, 0u, 0u);
+    const unsigned mine = b.x + b.y + b.z + b.w;
+    unsigned incl = mine;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned t = __shfl_up(incl, off);
+        if (lane >= off) incl += t;
+    }
+    const unsigned k = state[2 * idx + 1];
+    unsigned below = incl - mine;
+    if (below <= k && k < incl) {                       // exactly one lane: the bins hold more than k keys in all
+        unsigned digit = 4u * lane;
+        if (k >= below + b.x) { below += b.x; ++digit;
+            if (k >= below + b.y) { below += b.y; ++digit;
+                if (k >= below + b.z) { below += b.z; ++digit; } } }
+        const unsigned key = state[2 * idx] | (digit << shift);
+        state[2 * idx] = key;
+        state[2 * idx + 1] = k - below;
+        if (shift == 0) ord[idx] = colq_value(key);
+    }
+}
+
+// out[qi][col] = s[lo] + (s[hi] - s[lo]) (pos - lo) in float64, rounded once; NaN for a column that holds a NaN
+__global__ void k_eval_colq_interp(const float* __restrict__ ord, const double* __restrict__ q, const unsigned* __restrict__ nanflag,
+                                   long n, int d, int nq, float* __restrict__ out) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)nq * d) return;
+    const int qi = (int)(i / d), col = (int)(i % d);
+    double frac;
+    colq_rank(q[qi], n, &frac);
+    const double lo = ord[((long)col * nq + qi) * 2], hi = ord[((long)col * nq + qi) * 2 + 1];
+    const double v = lo + (hi - lo) * frac;
+    out[i] = nanflag[col] ? __builtin_nanf("") : (float)v;
+}
+
+// ---- exponentially weighted mean -------------------------------------------------------------------------------------------------
+constexpr int EWM_L = 1024;      // elements per chunk: 256 threads x 4
+
+// N just before this thread's four elements, for the recurrence N_t = x_t + b N_{t-1} started from `carry` before the chunk.
+// Wave scan by shuffles (factor b^(4 off) at distance off), then the four wave totals composed in order.
+__device__ __forceinline__ double ewm_thread_prefix(const double (&x)[4], double b, double carry, double* sm) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double s = ((x[0] * b + x[1]) * b + x[2]) * b + x[3];
+    double f = (b * b) * (b * b);
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const double t = __shfl_up(s, off);
+        if (lane >= off) s = t * f + s;
+        f *= f;
+    }                                                   // f = b^256
+    if (lane == 63) sm[wave] = s;
+    double ex = __shfl_up(s, 1);
+    if (lane == 0) ex = 0.0;
+    __syncthreads();
+    double in = carry;
+    for (int w = 0; w < wave; ++w) in = in * f + sm[w];
+    return ex + in * pow(b, (double)(4 * lane));
+}
+
+__device__ __forceinline__ void ewm_load(const float* __restrict__ x, long n, long base, double (&v)[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = base + j < n ? (double)x[base + j] : 0.0;
+}
+
+// S[c] = N at the end of chunk c when nothing precedes it
+__global__ void __launch_bounds__(256) k_eval_ewm_chunk(const float* __restrict__ x, long n, double b, double* __restrict__ S) {
+    __shared__ double sm[4];
+    double v[4];
+    ewm_load(x, n, (long)blockIdx.x * EWM_L + 4 * threadIdx.x, v);
+    double s = ewm_thread_prefix(v, b, 0.0, sm);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s = s * b + v[j];
+    if (threadIdx.x == 255) S[blockIdx.x] = s;
+}
+
+// carry[c] = N just before chunk c: carry[c] = carry[c-1] b^L + S[c-1], 64 chunks per step of one wave, in chunk order
+__global__ void __launch_bounds__(64) k_eval_ewm_carry(const double* __restrict__ S, long nchunks, double fL, double* __restrict__ carry) {
+    const int lane = threadIdx.x;
+    const double fl = pow(fL, (double)lane);
+    double run = 0.0;
+    for (long base = 0; base < nchunks; base += 64) {
+        const long i = base + lane;
+        double s = i < nchunks ? S[i] : 0.0;
+        double f = fL;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const double t = __shfl_up(s, off);
+            if (lane >= off) s = t * f + s;
+            f *= f;
+        }                                               // f = fL^64
+        double ex = __shfl_up(s, 1);
+        if (lane == 0) ex = 0.0;
+        if (i < nchunks) carry[i] = run * fl + ex;
+        run = run * f + __shfl(s, 63);
+    }
+}
+
+// y[t] = N_t / D_t, D_t = (1 - b^(t+1)) / alpha
+__global__ void __launch_bounds__(256) k_eval_ewm_apply(const float* __restrict__ x, long n, double b, double alpha,
+                                                         const double* __restrict__ carry, float* __restrict__ y) {
+    __shared__ double sm[4];
+    double v[4];
+    const long base = (long)blockIdx.x * EWM_L + 4 * threadIdx.x;
+    ewm_load(x, n, base, v);
+    double s = ewm_thread_prefix(v, b, carry[blockIdx.x], sm);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        s = s * b + v[j];
+        if (base + j < n) y[base + j] = (float)(s / ((1.0 - pow(b, (double)(base + j + 1))) / alpha));
+    }
+}
+
+}  // namespace mtadgat
+
+using namespace mtadgat;
+
+namespace {
+
+struct ColqLayout {
+    size_t q, hist, state, nan, ord, bytes;     // byte offsets
+};
+ColqLayout colq_layout(int64_t d, int64_t nq) {
+    const size_t cells = (size_t)d * 2 * (size_t)nq;
+    ColqLayout l;
+    l.q = 0;
+    l.hist = 8 * (size_t)nq;
+    l.hist = (l.hist + 15) / 16 * 16;           // the pick kernel reads the bins as 16-byte words
+    l.state = l.hist + cells * 256 * 4;
+    l.nan = l.state + cells * 2 * 4;
+    l.ord = l.nan + (size_t)d * 4;
+    l.bytes = l.ord + cells * 4;
+    return l;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t mtadgat_eval_column_quantiles_scratch(int64_t n, int d, int nq) {
+    if (n < 1 || d < 1 || nq < 1) return 0;
+    return colq_layout(d, nq).bytes;
+}
+
+int mtadgat_eval_column_quantiles(const float* a_dev, int64_t n, int d, int64_t ld, const double* q_host, int nq, void* scratch_dev,
+                                  size_t scratch_bytes, float* out_dev, void* stream) {
+    if (!a_dev || !q_host || !scratch_dev || !out_dev) return record_error(-1, "column_quantiles: null pointer");
+    if (n < 1 || n > 2147483647LL) return record_error(-1, "column_quantiles: n must lie in [1, 2^31 - 1]");
+    if (d < 1 || d > 2048) return record_error(-1, "column_quantiles: d must lie in [1, 2048]");
+    if (ld < d) return record_error(-1, "column_quantiles: ld < d");
+    if (nq < 1 || nq > 4096) return record_error(-1, "column_quantiles: nq must lie in [1, 4096]");
+    for (int i = 0; i < nq; ++i)
+        if (!(q_host[i] >= 0.0 && q_host[i] <= 1.0)) return record_error(-1, "column_quantiles: q outside [0, 1]");
+    const ColqLayout l = colq_layout(d, nq);
+    if (scratch_bytes < l.bytes) return record_error(-5, "column_quantiles: scratch too small (see mtadgat_eval_column_quantiles_scratch)");
+    if ((uintptr_t)scratch_dev & 15) return record_error(-5, "column_quantiles: scratch must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    char* base = static_cast<char*>(scratch_dev);
+    double* q = reinterpret_cast<double*>(base + l.q);
+    unsigned* hist = reinterpret_cast<unsigned*>(base + l.hist);
+    unsigned* state = reinterpret_cast<unsigned*>(base + l.state);
+    unsigned* nanflag = reinterpret_cast<unsigned*>(base + l.nan);
+    float* ord = reinterpret_cast<float*>(base + l.ord);
+    const int R = 2 * nq;
+    const long cells = (long)d * R;
+    // q_host is not touched after this call returns: few probabilities ride in the kernel arguments, more are copied and waited for
+    ColqProbs pv = {};
+    const int inl = nq <= CQ_INLINE;
+    if (inl) {
+        for (int i = 0; i < nq; ++i) pv.v[i] = q_host[i];
+    } else if (hipMemcpyAsync(q, q_host, nq * sizeof(double), hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+        return record_error(-3, "column_quantiles: copy of q failed");
+    }
+    const long init_blocks = (cells * 256 + 255) / 256;
+    hipLaunchKernelGGL(k_eval_colq_init, dim3((unsigned)(init_blocks < 2048 ? init_blocks : 2048)), dim3(256), 0, s, q, pv, inl, nq, (long)n, d,
+                       state, nanflag, hist);
+    // bounded grid: about 1024 workgroups in all, each walking at least four row groups
+    const int tiles = (d + CQ_CT - 1) / CQ_CT, groups = (R + CQ_RT - 1) / CQ_RT;
+    long slices = (n + 4 * CQ_ROWS - 1) / (4 * CQ_ROWS);
+    const long cap = 1024 / ((long)tiles * groups) > 0 ? 1024 / ((long)tiles * groups) : 1;
+    if (slices > cap) slices = cap;
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        hipLaunchKernelGGL(k_eval_colq_hist, dim3(tiles, (unsigned)slices, groups), dim3(256), 0, s, a_dev, (long)n, d, (long)ld, R, shift,
+                           state, hist, nanflag);
+        hipLaunchKernelGGL(k_eval_colq_pick, dim3((unsigned)cells), dim3(64), 0, s, state, hist, shift, ord);
+    }
+    const long outs = (long)nq * d;
+    hipLaunchKernelGGL(k_eval_colq_interp, dim3((unsigned)((outs + 255) / 256)), dim3(256), 0, s, ord, q, nanflag, (long)n, d, nq, out_dev);
+    return hipGetLastError() == hipSuccess ? 0 : record_error(-3, "column_quantiles: kernel launch failed");
+}
+
+size_t mtadgat_eval_ewm_scratch(int64_t n) {
+    if (n < 1) return 0;
+    return 16 * (size_t)((n + EWM_L - 1) / EWM_L);
+}
+
+int mtadgat_eval_ewm(const float* x_dev, int64_t n, double alpha, void* scratch_dev, size_t scratch_bytes, float* out_dev, void* stream) {
+    if (!x_dev || !scratch_dev || !out_dev) return record_error(-1, "ewm: null pointer");
+    if (n < 1 || n > 2147483647LL) return record_error(-1, "ewm: n must lie in [1, 2^31 - 1]");
+    if (!(alpha > 0.0 && alpha <= 1.0)) return record_error(-1, "ewm: alpha outside (0, 1]");
+    if (scratch_bytes < mtadgat_eval_ewm_scratch(n)) return record_error(-5, "ewm: scratch too small (see mtadgat_eval_ewm_scratch)");
+    if ((uintptr_t)scratch_dev & 7) return record_error(-5, "ewm: scratch must be 8-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const long nchunks = (long)((n + EWM_L - 1) / EWM_L);
+    double* S = static_cast<double*>(scratch_dev);
+    double* carry = S + nchunks;
+    const double b = 1.0 - alpha;
+    hipLaunchKernelGGL(k_eval_ewm_chunk, dim3((unsigned)nchunks), dim3(256), 0, s, x_dev, (long)n, b, S);
+    hipLaunchKernelGGL(k_eval_ewm_carry, dim3(1), dim3(64), 0, s, S, nchunks, pow(b, (double)EWM_L), carry);
+    hipLaunchKernelGGL(k_eval_ewm_apply, dim3((unsigned)nchunks), dim3(256), 0, s, x_dev, (long)n, b, alpha, carry, out_dev);
+    return hipGetLastError() == hipSuccess ? 0 : record_error(-3, "ewm: kernel launch failed");
+}
+
+}  // extern "C"

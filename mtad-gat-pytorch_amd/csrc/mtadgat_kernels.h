@@ -493,5 +493,7 @@ int launch_transpose_win(const float* src, long lds, float* dst, long ldd, long 
 int att_mean_slabs(long n, int K);
 int launch_att_mean_part(const float* A, long n, int K, int nslab, int first, float* PS, float* PC, hipStream_t s);
 int launch_att_mean_final(const float* PS, const float* PC, int K, int nslab, long n_total, float* out, hipStream_t s);
+// records `msg` for mtadgat_last_error() and returns `code` (mtadgat_capi.cpp): for the entry points defined beside their kernels
+int record_error(int code, const char* msg);
 
 }  // namespace mtadgat

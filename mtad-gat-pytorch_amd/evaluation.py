@@ -8,6 +8,15 @@ epsilon_eval :164-186, bf_search :117-158) and the score arithmetic of `Predicto
 threshold wins, precision / recall / F1 from the counts) is done here in float64 exactly as the reference writes
 it.  Results equal the reference's dictionaries (tests/test_gpu_eval.py: the shipped MSL run's summary.txt).
 
+The Predictor's options on top of the raw score (prediction.py:65-165) stay on the device too
+(csrc/mtadgat_evalcol.hip, tests/test_gpu_score_pipeline.py):
+  column_quantiles / scale_scores   --scale_scores: (a - median) / (1 + IQR) per output dimension; np.percentile's linear
+                                    quantiles of all columns from one exact radix select (no sort, any n < 2^31)
+  moving_average                    --use_mov_av: pandas' ewm(span).mean() as a float64 blocked scan
+  find_epsilon_columns /            the per-feature thresholds and predictions (prediction.py:140-154): both find_epsilon
+  feature_predictions               passes over all columns in one launch each
+  predict_anomalies                 what Predictor.predict_anomalies computes from a train and a test series, in one call
+
 POT (`pot_eval`: SPOT's Grimshaw fit, spot.py) is not ported: it is a sequential scalar algorithm over the
 peaks only; the reference's implementation runs unchanged on `scores.cpu().numpy()`.
 """
@@ -30,6 +39,16 @@ def _lib():
         lib.mtadgat_eval_moments.argtypes = [vp, i64, vp, _c_double_p, vp]
         lib.mtadgat_eval_epsilon_table.argtypes = [vp, i64, _c_double_p, ci, ci, vp, _c_double_p, vp]
         lib.mtadgat_eval_point_adjust.argtypes = [vp, vp, i64, _c_double_p, ci, ci, ci, vp, _c_double_p, vp]
+        sz, f64 = ctypes.c_size_t, ctypes.c_double
+        lib.mtadgat_eval_moments_columns.argtypes = [vp, i64, ci, i64, vp, _c_double_p, vp]
+        lib.mtadgat_eval_epsilon_table_columns.argtypes = [vp, i64, ci, i64, _c_double_p, ci, ci, vp, _c_double_p, vp]
+        lib.mtadgat_eval_column_quantiles_scratch.argtypes = [i64, ci, ci]
+        lib.mtadgat_eval_column_quantiles_scratch.restype = sz
+        lib.mtadgat_eval_column_quantiles.argtypes = [vp, i64, ci, i64, _c_double_p, ci, vp, sz, vp, vp]
+        lib.mtadgat_eval_ewm_scratch.argtypes = [i64]
+        lib.mtadgat_eval_ewm_scratch.restype = sz
+        lib.mtadgat_eval_ewm.argtypes = [vp, i64, f64, vp, sz, vp, vp]
+        lib.mtadgat_last_error.restype = ctypes.c_char_p
         lib._eval_bound = True
     return lib
 
@@ -50,6 +69,24 @@ def _stream(t):
 def _check(rc, what):
     if rc != 0:
         raise RuntimeError(f"mtadgat {what} failed (status {rc})")
+
+
+def _dev2d(t, name):
+    """A float32 (n, d) GPU tensor whose rows are contiguous (a column slice keeps its row stride: no copy)."""
+    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+        raise RuntimeError(f"{name} must be a tensor on the GPU (the evaluation kernels are HIP only)")
+    t = t.detach()
+    if t.ndim == 1:
+        t = t.reshape(-1, 1)
+    if t.ndim != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError(f"{name} must have shape (n, d) with n, d >= 1, got {tuple(t.shape)}")
+    if t.dtype != torch.float32:
+        t = t.float()
+    if t.shape[0] == 1:
+        t = t.reshape(1, -1).clone()       # a single row: any row stride is legal in torch, the kernels want ld >= d
+    if t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+        t = t.contiguous()
+    return t
 
 
 def anomaly_scores(preds, recons, values, window_size, target_dims=None, gamma=1.0):
@@ -83,26 +120,13 @@ def anomaly_scores(preds, recons, values, window_size, target_dims=None, gamma=1
     return glob, per_dim
 
 
-def find_epsilon(errors, reg_level=1):
-    """Threshold of Hundman et al. as the reference computes it (eval_methods.py:189-236)."""
-    lib = _lib()
-    e = _dev1d(errors, torch.float32, "errors")
-    n = e.numel()
-    scratch = torch.empty(64 + 4 * 64, dtype=torch.float64, device=e.device)
-    mom = (ctypes.c_double * 2)()
-    with torch.cuda.device(e.device):
-        _check(lib.mtadgat_eval_moments(e.data_ptr(), n, scratch.data_ptr(), mom, _stream(e)), "eval_moments")
-    mean = mom[0] / n
-    sd = math.sqrt(max(mom[1] / n - mean * mean, 0.0))
-    zs = np.arange(2.5, 12, 0.5)
-    eps = mean + sd * zs
-    tab = (ctypes.c_double * (4 * len(zs)))()
-    with torch.cuda.device(e.device):
-        _check(lib.mtadgat_eval_epsilon_table(e.data_ptr(), n, eps.ctypes.data_as(_c_double_p), len(zs), 49, scratch.data_ptr(), tab,
-                                              _stream(e)), "eval_epsilon_table")
+def _choose_epsilon(n, mean, sd, eps, tab, reg_level):
+    """The host half of find_epsilon (eval_methods.py:205-236): the z whose threshold scores best, from the table the
+    device pass returns for one array -- tab[4 k : 4 k + 4] = pruned sum, pruned sum of squares, pruned count, dilated count
+    for threshold eps[k].  None when no z qualifies."""
     best, max_score = None, -10000000
     mean64, sd64 = np.float64(mean), np.float64(sd)
-    for k in range(len(zs)):
+    for k in range(len(eps)):
         ps, ps2, pc, dil = tab[4 * k], tab[4 * k + 1], tab[4 * k + 2], tab[4 * k + 3]
         if dil > 0:
             if pc > 0:
@@ -123,9 +147,128 @@ def find_epsilon(errors, reg_level=1):
             at_least = score >= max_score or (math.isfinite(max_score) and score >= max_score - 1e-9 * abs(max_score))
             if at_least and dil < n * 0.5:
                 max_score, best = max(score, max_score), float(eps[k])
+    return best
+
+
+_EPSILON_ZS = np.arange(2.5, 12, 0.5)
+_EPSILON_HALO = 49
+
+
+def find_epsilon(errors, reg_level=1):
+    """Threshold of Hundman et al. as the reference computes it (eval_methods.py:189-236)."""
+    lib = _lib()
+    e = _dev1d(errors, torch.float32, "errors")
+    n = e.numel()
+    scratch = torch.empty(64 + 4 * 64, dtype=torch.float64, device=e.device)
+    mom = (ctypes.c_double * 2)()
+    with torch.cuda.device(e.device):
+        _check(lib.mtadgat_eval_moments(e.data_ptr(), n, scratch.data_ptr(), mom, _stream(e)), "eval_moments")
+    mean = mom[0] / n
+    sd = math.sqrt(max(mom[1] / n - mean * mean, 0.0))
+    zs = _EPSILON_ZS
+    eps = mean + sd * zs
+    tab = (ctypes.c_double * (4 * len(zs)))()
+    with torch.cuda.device(e.device):
+        _check(lib.mtadgat_eval_epsilon_table(e.data_ptr(), n, eps.ctypes.data_as(_c_double_p), len(zs), _EPSILON_HALO,
+                                              scratch.data_ptr(), tab, _stream(e)), "eval_epsilon_table")
+    best = _choose_epsilon(n, mean, sd, eps, tab, reg_level)
     if best is None:
         best = float(e.max().item())
     return best
+
+
+def find_epsilon_columns(errors, reg_level=1):
+    """find_epsilon of every column of an (n, d) array (the per-feature thresholds of prediction.py:140-147): the moments
+    and the z table of all columns in one launch each.  Returns a list of d floats; a column where no z qualifies gets its
+    maximum, as in find_epsilon."""
+    lib = _lib()
+    e = _dev2d(errors, "errors")
+    n, d = e.shape
+    ld = e.stride(0)
+    zs = _EPSILON_ZS
+    nz = len(zs)
+    scratch = _native._empty(max(2 * d, 5 * d * nz), dtype=torch.float64, device=e.device)
+    mom = (ctypes.c_double * (2 * d))()
+    with torch.cuda.device(e.device):
+        _check(lib.mtadgat_eval_moments_columns(e.data_ptr(), n, d, ld, scratch.data_ptr(), mom, _stream(e)), "eval_moments_columns")
+    means = [mom[2 * c] / n for c in range(d)]
+    sds = [math.sqrt(max(mom[2 * c + 1] / n - means[c] * means[c], 0.0)) for c in range(d)]
+    eps = np.ascontiguousarray(np.stack([means[c] + sds[c] * zs for c in range(d)]))
+    tab = (ctypes.c_double * (4 * nz * d))()
+    with torch.cuda.device(e.device):
+        _check(lib.mtadgat_eval_epsilon_table_columns(e.data_ptr(), n, d, ld, eps.ctypes.data_as(_c_double_p), nz, _EPSILON_HALO,
+                                                      scratch.data_ptr(), tab, _stream(e)), "eval_epsilon_table_columns")
+    out, col_max = [], None
+    for c in range(d):
+        best = _choose_epsilon(n, means[c], sds[c], eps[c], tab[4 * nz * c:4 * nz * (c + 1)], reg_level)
+        if best is None:
+            if col_max is None:
+                col_max = e.max(dim=0).values.cpu()
+            best = float(col_max[c])
+        out.append(best)
+    return out
+
+
+def column_quantiles(a, qs):
+    """np.percentile(a, 100 * qs, axis=0) for an (n, d) float32 GPU tensor, (len(qs), d) float32 on the device: the "linear"
+    definition, interpolated in float64 between the two exact order statistics and rounded once.  A column that holds a NaN
+    gives NaN, as in numpy.  A column slice of a wider tensor is read in place.  Bitwise reproducible."""
+    lib = _lib()
+    a = _dev2d(a, "a")
+    n, d = a.shape
+    q = np.ascontiguousarray(np.asarray(qs, dtype=np.float64).reshape(-1))
+    if q.size < 1 or not np.all((q >= 0.0) & (q <= 1.0)):
+        raise ValueError(f"quantile probabilities must lie in [0, 1], got {qs!r}")
+    nbytes = lib.mtadgat_eval_column_quantiles_scratch(n, d, q.size)
+    scratch = _native._empty((nbytes + 7) // 8, dtype=torch.float64, device=a.device)
+    out = _native._empty((q.size, d), dtype=torch.float32, device=a.device)
+    with torch.cuda.device(a.device):
+        rc = lib.mtadgat_eval_column_quantiles(a.data_ptr(), n, d, a.stride(0), q.ctypes.data_as(_c_double_p), q.size,
+                                               scratch.data_ptr(), scratch.numel() * 8, out.data_ptr(), _stream(a))
+    if rc != 0:
+        raise RuntimeError(f"mtadgat eval_column_quantiles failed (status {rc}): {lib.mtadgat_last_error().decode()}")
+    return out
+
+
+def scale_scores(per_dim):
+    """(a - median) / (1 + IQR) per column (prediction.py:84-88), quantiles from column_quantiles."""
+    q = column_quantiles(per_dim, [0.25, 0.5, 0.75])
+    return (per_dim - q[1]) / (1.0 + (q[2] - q[0]))
+
+
+def moving_average(scores, span):
+    """pandas.DataFrame(scores).ewm(span=span).mean() (prediction.py:99-103) of a 1-D GPU tensor: (n,) float32.
+    Accumulated in float64 on the device, stored as float32; bitwise reproducible."""
+    if not span >= 1:
+        raise ValueError(f"span must be >= 1, got {span!r}")
+    lib = _lib()
+    x = _dev1d(scores, torch.float32, "scores")
+    n = x.numel()
+    if n < 1:
+        raise ValueError("scores is empty")
+    nbytes = lib.mtadgat_eval_ewm_scratch(n)
+    scratch = _native._empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device)
+    out = _native._empty((n,), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = lib.mtadgat_eval_ewm(x.data_ptr(), n, 2.0 / (float(span) + 1.0), scratch.data_ptr(), scratch.numel() * 8, out.data_ptr(),
+                                  _stream(x))
+    if rc != 0:
+        raise RuntimeError(f"mtadgat eval_ewm failed (status {rc}): {lib.mtadgat_last_error().decode()}")
+    return out
+
+
+def feature_predictions(train_per_dim, test_per_dim, reg_level=1):
+    """Per-feature thresholds and predictions (prediction.py:140-154): eps_i = find_epsilon(train_per_dim[:, i]) and
+    preds[:, i] = test_per_dim[:, i] >= eps_i.  The comparison is `>=`: the reference tree was not at hand to pin the
+    operator, so this package fixes it -- a score equal to its threshold counts as anomalous.
+    Returns (thresholds (d,) float64 on the host, preds (n_test, d) uint8 on the device)."""
+    test = _dev2d(test_per_dim, "test_per_dim")
+    thr = find_epsilon_columns(train_per_dim, reg_level)
+    if test.shape[1] != len(thr):
+        raise ValueError(f"train has {len(thr)} columns, test has {test.shape[1]}")
+    # compared in float64 like a float32 array against Python floats in numpy
+    thr_d = torch.tensor(thr, dtype=torch.float64, device=test.device)
+    return np.asarray(thr, dtype=np.float64), (test.double() >= thr_d).to(torch.uint8)
 
 
 def point_adjust_counts(score, label, thresholds, compare_f32=False, max_segments=65536):
@@ -192,3 +335,36 @@ def bf_search(score, label, start, end=None, step_num=1, display_freq=1, verbose
     if best_row is None:
         return {"f1": -1.0, "precision": -1.0, "recall": -1.0, "TP": -1.0, "TN": -1.0, "FP": -1.0, "FN": -1.0, "threshold": 0.0, "latency": 0}
     return _result(best_row, best_thr)
+
+
+_sweep = bf_search       # predict_anomalies has a keyword of that name
+
+
+def predict_anomalies(model, train, test, labels=None, target_dims=None, gamma=1.0, scale_scores=False, use_mov_av=False, reg_level=1,
+                      bf_search=None):
+    """What Predictor.predict_anomalies (prediction.py:106-165) derives from a train and a test series, with every score array
+    staying on the device.  train, test: device-resident (N, F) series; labels: the test labels for rows window_size.. (one
+    per score) or None; bf_search: (start, end, step_num) for the best-F1 sweep, run when labels are given too.
+    Returns a dict:
+      train_scores, test_scores   (N - W,) global scores from model.anomaly_scores with the options given
+      test_per_dim                (N_test - W, out_dim) per-dimension scores (scaled if asked, never smoothed)
+      feature_thresholds,         feature_predictions(train per-dimension scores, test_per_dim, reg_level)
+      feature_preds
+      epsilon_result              epsilon_eval(train_scores, test_scores, labels, reg_level), or None without labels
+      bf_result                   bf_search(test_scores, labels, *bf_search), or None without labels or bf_search
+    Not included: POT (`pot_eval`), a sequential scalar fit that runs unchanged on `test_scores.cpu().numpy()` (see the module
+    docstring); and `adjust_anomaly_scores` for MSL / SMAP, which needs the datasets' channel metadata files and the reference
+    source to pin its behaviour, neither of which this package ships."""
+    train_scores, train_per_dim = model.anomaly_scores(train, target_dims=target_dims, gamma=gamma, scale_scores=scale_scores,
+                                                       use_mov_av=use_mov_av)
+    test_scores, test_per_dim = model.anomaly_scores(test, target_dims=target_dims, gamma=gamma, scale_scores=scale_scores,
+                                                     use_mov_av=use_mov_av)
+    eps_result = bf_result = None
+    if labels is not None:
+        eps_result = epsilon_eval(train_scores, test_scores, labels, reg_level)
+        if bf_search is not None:
+            start, end, step_num = bf_search
+            bf_result = _sweep(test_scores, labels, start, end, step_num)
+    thr, preds = feature_predictions(train_per_dim, test_per_dim, reg_level)
+    return {"epsilon_result": eps_result, "bf_result": bf_result, "feature_thresholds": thr, "train_scores": train_scores,
+            "test_scores": test_scores, "test_per_dim": test_per_dim, "feature_preds": preds}

@@ -522,14 +522,23 @@ class MTAD_GAT(nn.Module):
                                        lambda eng: eng.forward_series(vf, None, 0, 1, n + 1, want_recons=False, want_last=True))
         return p[:n], last[1:n + 1]
 
-    def anomaly_scores(self, values, target_dims=None, gamma=1.0, scale_scores=False):
-        """The per-timestamp anomaly score of `Predictor.get_score` (reference prediction.py:65-91) for a
+    def anomaly_scores(self, values, target_dims=None, gamma=1.0, scale_scores=False, use_mov_av=False, smoothing_span=None):
+        """The per-timestamp anomaly score of `Predictor.get_score` (reference prediction.py:65-103) for a
         whole series (N, F), computed on the device from `score_series`:
             a_i[d] = |y_hat_i[d] - x_{i+W}[d]| + gamma * |recon_i[d] - x_{i+W}[d]|
         (the reference writes sqrt((.)**2)), optionally (a - median) / (1 + IQR) per dimension
-        (`scale_scores`), then the mean over the target dimensions.  target_dims as in the reference
+        (`scale_scores`; quantiles from evaluation.column_quantiles), then the mean over the target dimensions,
+        optionally smoothed (`use_mov_av`: pandas' ewm(span).mean() of the global score, evaluation.moving_average;
+        the span is `smoothing_span`, or the reference's int(256 * window_size * 0.05) -- its Predictor's
+        hard-coded batch size of 256 -- and a span below 1 raises ValueError).  target_dims as in the reference
         (`utils.get_target_dims`): None = all features, an int or a list of column indices.
-        Returns (scores (N-W,), per-dimension scores (N-W, out_dim)), both on the device."""
+        Returns (scores (N-W,), per-dimension scores (N-W, out_dim)), both on the device; the per-dimension
+        scores are never smoothed, as in the reference."""
+        span = None
+        if use_mov_av:
+            span = int(256 * self.window_size * 0.05) if smoothing_span is None else smoothing_span
+            if not span >= 1:
+                raise ValueError(f"the smoothing span must be >= 1, got {span!r}")
         preds, recons = self.score_series(values)
         actual = values[self.window_size:].float()
         if target_dims is not None:
@@ -539,12 +548,13 @@ class MTAD_GAT(nn.Module):
             raise RuntimeError(f"target_dims select {actual.shape[1]} columns but the model has out_dim={preds.shape[1]}")
         a = (preds - actual).abs() + gamma * (recons - actual).abs()
         if scale_scores:
-            # np.percentile's default (linear) interpolation per column; torch.quantile refuses inputs of more
-            # than 16 M elements, so the columns go through it one at a time
-            qs = torch.tensor([0.25, 0.5, 0.75], device=a.device, dtype=a.dtype)
-            q = torch.stack([_column_quantiles(a[:, d], qs) for d in range(a.shape[1])], dim=1)
+            q = _column_quantiles(a, [0.25, 0.5, 0.75])
             a = (a - q[1]) / (1.0 + (q[2] - q[0]))
-        return a.mean(dim=1), a
+        scores = a.mean(dim=1)
+        if use_mov_av:
+            import evaluation
+            scores = evaluation.moving_average(scores, span)
+        return scores, a
 
     # -- which inputs pushed a score up: gradient attribution of anomaly_scores ---------------------------------------------------
     def score_attribution(self, values, indices, target_dims=None, gamma=1.0, scale_scores=False, method="gradient", steps=32,
@@ -605,8 +615,7 @@ class MTAD_GAT(nn.Module):
             else:
                 import _torchpath
                 per_dim = _torchpath.per_dim_scores(self, vf, dims, gamma)
-            qs = torch.tensor([0.25, 0.75], device=per_dim.device, dtype=per_dim.dtype)
-            q = torch.stack([_column_quantiles(per_dim[:, d], qs) for d in range(per_dim.shape[1])], dim=1)
+            q = _column_quantiles(per_dim, [0.25, 0.75])
             dim_w = dim_w / (1.0 + (q[1] - q[0]).double().cpu())
         if not gpu:
             import _torchpath
@@ -618,14 +627,15 @@ class MTAD_GAT(nn.Module):
             return self._checked(dev, False, lambda eng: eng.score_attribution(vf, idx_d, dims_d, w_d, gamma, m, baseline))
 
 
-def _column_quantiles(col, qs):
-    """Linear-interpolation quantiles of a 1-D tensor of any length (sort based: no 16 M element limit)."""
-    n = col.numel()
-    if n <= (1 << 24):
-        return torch.quantile(col, qs)
-    s, _ = torch.sort(col)
-    pos = qs.double() * (n - 1)
-    lo = pos.floor().long()
-    hi = torch.clamp(lo + 1, max=n - 1)
-    frac = (pos - lo.double()).to(col.dtype)
-    return s[lo] + (s[hi] - s[lo]) * frac
+def _column_quantiles(a, qs):
+    """np.percentile's linear quantiles of a column (n,) -> (len(qs),), or of every column of (n, d) -> (len(qs), d).
+    GPU tensors of any length go through evaluation.column_quantiles (one radix select over all columns);
+    CPU tensors keep torch.quantile, a column at a time (it refuses more than 16 M elements per call)."""
+    if a.device.type == "cuda":
+        import evaluation
+        q = evaluation.column_quantiles(a, qs.tolist() if isinstance(qs, torch.Tensor) else qs).to(a.dtype)
+        return q[:, 0] if a.dim() == 1 else q
+    qs = torch.as_tensor(qs, dtype=a.dtype)
+    if a.dim() == 1:
+        return torch.quantile(a, qs)
+    return torch.stack([torch.quantile(a[:, d], qs) for d in range(a.shape[1])], dim=1)
