@@ -432,6 +432,51 @@ int mtadgat_eval_column_quantiles(const float* a_dev, int64_t n, int d, int64_t 
 size_t mtadgat_eval_ewm_scratch(int64_t n);
 int mtadgat_eval_ewm(const float* x_dev, int64_t n, double alpha, void* scratch_dev, size_t scratch_bytes, float* out_dev,
                      void* stream);
+/* ---- from thresholded scores to events (csrc/mtadgat_events.hip; evaluation.anomaly_events) ----------------------------
+ * Conventions of the two calls above: no float atomics, no library kernels, nothing sorted, bitwise reproducible; scratch
+ * is 8-byte aligned, at least what the _scratch function returns (0 for invalid sizes), and need not be initialised;
+ * status 0 / -1 (bad argument) / -3 (HIP) / -5 (scratch too small or misaligned; more runs than max_runs), with a
+ * mtadgat_last_error() message; nothing is launched when validation fails.  n <= 2^31 - 1, d <= 2048, indices are int64.
+ *
+ * The flag of sample i comes from exactly one source (the other pointer is NULL): score_dev -- flag = score_i > threshold,
+ * compared in float64, or in float32 with compare_f32 (mtadgat_eval_point_adjust's convention); NaN and equality are not
+ * flagged -- or label_dev (uint8): flag = label_i != 0, threshold and compare_f32 ignored.
+ *
+ * mtadgat_eval_runs: the maximal runs of flagged samples as [start, end), in ascending order.  Consecutive runs whose
+ * separation start_{k+1} - end_k is at most merge_gap >= 0 are merged (this chains; the gap samples belong to the event),
+ * then events with end - start < min_length (>= 1) are dropped.  start_dev / end_dev hold max_runs >= 1 entries; the true
+ * count is written to *count_host and the call synchronises the stream.  A count above max_runs returns -5 with
+ * *count_host set and the first max_runs events written: call again with that capacity.  mtadgat_eval_runs_chunk() is the
+ * chunk length of the blocked scans behind it (for tests that want sizes around it). */
+int mtadgat_eval_runs_chunk(void);
+size_t mtadgat_eval_runs_scratch(int64_t n);
+int mtadgat_eval_runs(const float* score_dev, const unsigned char* label_dev, int64_t n, double threshold, int compare_f32,
+                      int64_t merge_gap, int64_t min_length, int64_t max_runs, void* scratch_dev, size_t scratch_bytes,
+                      int64_t* start_dev, int64_t* end_dev, int64_t* count_host, void* stream);
+/* mtadgat_eval_run_stats: reductions over `count` given runs [start_k, end_k) of score_dev (n) -- disjoint and ascending,
+ * as mtadgat_eval_runs returns them; bounds are cut to [0, n].  Asynchronous on `stream`.
+ *   peak_dev[k]        the smallest index attaining the maximum of the run's scores with NaN read as -inf (-1: empty run)
+ *   peak_score_dev[k]  that maximum
+ *   mean_score_dev[k]  the float64 sum over the run divided by end - start, stored as float32 (a NaN inside gives NaN)
+ * With per_dim_dev, an (n, d) float32 array with row stride ld >= d (NULL: d, ld, top_k are ignored and the four outputs
+ * below may be NULL):
+ *   feature_means_dev  (count, d) the same mean per column
+ *   top_idx_dev, top_val_dev  (count, top_k) the top_k columns by the stored float32 mean, descending, ties to the lower
+ *                      column, NaN last; 1 <= top_k <= min(d, 64)
+ * With thr_dev as well, (d) float64 on the device:
+ *   feature_hits_dev   (count, d) int32: the run's rows with per_dim >= thr_j, compared in float64
+ * The sums are float64 partials of fixed row blocks added in block order: the bits do not depend on the launch shape.
+ * scratch: mtadgat_eval_run_stats_scratch(n, count, d) bytes, d = 0 without per_dim. */
+size_t mtadgat_eval_run_stats_scratch(int64_t n, int64_t count, int d);
+int mtadgat_eval_run_stats(const float* score_dev, int64_t n, const int64_t* start_dev, const int64_t* end_dev, int64_t count,
+                           const float* per_dim_dev, int d, int64_t ld, const double* thr_dev, int top_k, void* scratch_dev,
+                           size_t scratch_bytes, int64_t* peak_dev, float* peak_score_dev, float* mean_score_dev,
+                           float* feature_means_dev, int* top_idx_dev, float* top_val_dev, int* feature_hits_dev, void* stream);
+/* mtadgat_eval_first_hit: first_dev[k] = the smallest index in [start_k, end_k) whose flag is set, or -1; one wave per run,
+ * so long runs are fine.  Scores as the source and labelled segments as the runs: detection and latency per segment;
+ * labels as the source and events as the runs: whether an event overlaps a label.  Asynchronous on `stream`. */
+int mtadgat_eval_first_hit(const float* score_dev, const unsigned char* label_dev, int64_t n, double threshold, int compare_f32,
+                           const int64_t* start_dev, const int64_t* end_dev, int64_t count, int64_t* first_dev, void* stream);
 
 /* Per-kernel launch timing for bench.py's roofline leg: when enabled, forward()
  * brackets each kernel family with hipEvents on `stream`; mtadgat_profile_read

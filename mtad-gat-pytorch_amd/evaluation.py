@@ -17,6 +17,14 @@ The Predictor's options on top of the raw score (prediction.py:65-165) stay on t
   feature_predictions               passes over all columns in one launch each
   predict_anomalies                 what Predictor.predict_anomalies computes from a train and a test series, in one call
 
+From the thresholded scores to alarms (csrc/mtadgat_events.hip, tests/test_gpu_events.py), beyond what the reference offers:
+  flag_runs                         ordered [start, end) runs of scores > threshold or of labels, near-by runs merged and short
+                                    ones dropped: three stream compactions as blocked scans, nothing sorted, no atomics
+  run_statistics                    per run: peak, mean, per-feature means and hit counts, top-k features (segmented reductions)
+  first_hits                        the first flagged sample per run: detection latency per labelled segment, true / false events
+  anomaly_events                    the three together: the event table of a score array, in score-index space
+  explain_events                    model.score_attribution at the events' peaks, with per-feature and per-lag marginals
+
 POT (`pot_eval`: SPOT's Grimshaw fit, spot.py) is not ported: it is a sequential scalar algorithm over the
 peaks only; the reference's implementation runs unchanged on `scores.cpu().numpy()`.
 """
@@ -48,6 +56,15 @@ def _lib():
         lib.mtadgat_eval_ewm_scratch.argtypes = [i64]
         lib.mtadgat_eval_ewm_scratch.restype = sz
         lib.mtadgat_eval_ewm.argtypes = [vp, i64, f64, vp, sz, vp, vp]
+        lib.mtadgat_eval_runs_chunk.argtypes = []
+        lib.mtadgat_eval_runs_chunk.restype = ci
+        lib.mtadgat_eval_runs_scratch.argtypes = [i64]
+        lib.mtadgat_eval_runs_scratch.restype = sz
+        lib.mtadgat_eval_runs.argtypes = [vp, vp, i64, f64, ci, i64, i64, i64, vp, sz, vp, vp, ctypes.POINTER(ctypes.c_int64), vp]
+        lib.mtadgat_eval_run_stats_scratch.argtypes = [i64, i64, ci]
+        lib.mtadgat_eval_run_stats_scratch.restype = sz
+        lib.mtadgat_eval_run_stats.argtypes = [vp, i64, vp, vp, i64, vp, ci, i64, vp, ci, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.mtadgat_eval_first_hit.argtypes = [vp, vp, i64, f64, ci, vp, vp, i64, vp, vp]
         lib.mtadgat_last_error.restype = ctypes.c_char_p
         lib._eval_bound = True
     return lib
@@ -341,7 +358,7 @@ _sweep = bf_search       # predict_anomalies has a keyword of that name
 
 
 def predict_anomalies(model, train, test, labels=None, target_dims=None, gamma=1.0, scale_scores=False, use_mov_av=False, reg_level=1,
-                      bf_search=None):
+                      bf_search=None, events=None):
     """What Predictor.predict_anomalies (prediction.py:106-165) derives from a train and a test series, with every score array
     staying on the device.  train, test: device-resident (N, F) series; labels: the test labels for rows window_size.. (one
     per score) or None; bf_search: (start, end, step_num) for the best-F1 sweep, run when labels are given too.
@@ -352,6 +369,8 @@ def predict_anomalies(model, train, test, labels=None, target_dims=None, gamma=1
       feature_preds
       epsilon_result              epsilon_eval(train_scores, test_scores, labels, reg_level), or None without labels
       bf_result                   bf_search(test_scores, labels, *bf_search), or None without labels or bf_search
+      events                      only with events=dict(merge_gap=, min_length=, top_k=) (any subset): anomaly_events of test_scores
+                                  against find_epsilon(train_scores, reg_level), with test_per_dim, the feature thresholds and the labels
     Not included: POT (`pot_eval`), a sequential scalar fit that runs unchanged on `test_scores.cpu().numpy()` (see the module
     docstring); and `adjust_anomaly_scores` for MSL / SMAP, which needs the datasets' channel metadata files and the reference
     source to pin its behaviour, neither of which this package ships."""
@@ -366,5 +385,205 @@ def predict_anomalies(model, train, test, labels=None, target_dims=None, gamma=1
             start, end, step_num = bf_search
             bf_result = _sweep(test_scores, labels, start, end, step_num)
     thr, preds = feature_predictions(train_per_dim, test_per_dim, reg_level)
-    return {"epsilon_result": eps_result, "bf_result": bf_result, "feature_thresholds": thr, "train_scores": train_scores,
-            "test_scores": test_scores, "test_per_dim": test_per_dim, "feature_preds": preds}
+    out = {"epsilon_result": eps_result, "bf_result": bf_result, "feature_thresholds": thr, "train_scores": train_scores,
+           "test_scores": test_scores, "test_per_dim": test_per_dim, "feature_preds": preds}
+    if events is not None:
+        unknown = set(events) - {"merge_gap", "min_length", "top_k"}
+        if unknown:
+            raise ValueError(f"events takes merge_gap, min_length and top_k, got {sorted(unknown)}")
+        eps = eps_result["threshold"] if eps_result is not None else find_epsilon(train_scores, reg_level)
+        out["events"] = anomaly_events(test_scores, eps, per_dim=test_per_dim, feature_thresholds=thr, labels=labels, **events)
+    return out
+
+
+# ---- events ----------------------------------------------------------------------------------------------------------------------
+RUNS_CHUNK = 1024        # chunk length of the run-extraction scans (mtadgat_eval_runs_chunk(); tests pick sizes around it)
+
+_c_int64_p = ctypes.POINTER(ctypes.c_int64)
+
+
+def _fail(lib, rc, what):
+    raise RuntimeError(f"mtadgat {what} failed (status {rc}): {lib.mtadgat_last_error().decode()}")
+
+
+def _labels_u8(label, name="labels"):
+    """Labels as point_adjust_counts reads them: bool as it is, numbers as label > 0.1."""
+    if not isinstance(label, torch.Tensor) or label.device.type != "cuda":
+        raise RuntimeError(f"{name} must be a tensor on the GPU (the evaluation kernels are HIP only)")
+    return _dev1d(label if label.dtype == torch.bool else (label > 0.1), torch.uint8, name)
+
+
+def _flag_source(scores, labels):
+    if (scores is None) == (labels is None):
+        raise ValueError("give scores or labels, not both")
+    if scores is not None:
+        return _dev1d(scores, torch.float32, "scores"), None
+    return None, _labels_u8(labels)
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def flag_runs(scores=None, labels=None, threshold=0.0, merge_gap=0, min_length=1, compare_f32=False, max_runs=65536):
+    """The maximal runs of flagged samples as (count, start, end): `count` a Python int, start / end (count,) int64 on the device,
+    ascending, end exclusive.  flag_i = scores_i > threshold (compared in float64 like a float32 array against a Python float, or
+    in float32 with compare_f32; NaN and equality are not flagged), or labels_i set.  Runs separated by at most merge_gap samples
+    are merged (chains; the gap belongs to the event), then events shorter than min_length are dropped.  max_runs sizes the
+    first attempt only: when there are more, the call is repeated once with the count the library reported."""
+    lib = _lib()
+    s, lab = _flag_source(scores, labels)
+    src = s if s is not None else lab
+    n = src.numel()
+    if n < 1:
+        raise ValueError("the flag source is empty")
+    if merge_gap < 0 or min_length < 1 or max_runs < 1:
+        raise ValueError(f"needs merge_gap >= 0, min_length >= 1, max_runs >= 1, got {merge_gap}, {min_length}, {max_runs}")
+    nbytes = lib.mtadgat_eval_runs_scratch(n)
+    scratch = _native._empty((nbytes + 7) // 8, dtype=torch.float64, device=src.device)
+    count = ctypes.c_int64(0)
+    cap = int(max_runs)
+    for attempt in range(2):
+        start = torch.empty(cap, dtype=torch.int64, device=src.device)
+        end = torch.empty(cap, dtype=torch.int64, device=src.device)
+        with torch.cuda.device(src.device):
+            rc = lib.mtadgat_eval_runs(_ptr(s), _ptr(lab), n, float(threshold), 1 if compare_f32 else 0, int(merge_gap), int(min_length), cap,
+                                       scratch.data_ptr(), scratch.numel() * 8, start.data_ptr(), end.data_ptr(), ctypes.byref(count),
+                                       _stream(src))
+        if rc == -5 and attempt == 0 and count.value > cap:
+            cap = count.value
+            continue
+        if rc != 0:
+            _fail(lib, rc, "eval_runs")
+        break
+    return count.value, start[:count.value], end[:count.value]
+
+
+def _runs(start, end, device):
+    st, en = _dev1d(start, torch.int64, "start"), _dev1d(end, torch.int64, "end")
+    if st.numel() != en.numel() or st.device != device or en.device != device:
+        raise ValueError("start and end must have the same length and live on the device of the scores")
+    return st, en
+
+
+def run_statistics(scores, start, end, per_dim=None, feature_thresholds=None, top_k=5):
+    """Per-run reductions over the runs [start_k, end_k) of flag_runs: a dict of device tensors
+      peak (int64), peak_score   the first index attaining the run's maximum score (NaN read as -inf), and that score
+      mean_score                 float64 sum / length, stored as float32
+      feature_means (E, d), top_features (E, k) int32, top_values (E, k)      with per_dim (n, d): the column means of the run and
+                                 its k = min(top_k, d, 64) largest (descending, ties to the lower column, NaN last)
+      feature_hits (E, d) int32  with feature_thresholds (d,): the run's rows with per_dim >= threshold, compared in float64
+    Bitwise reproducible; nothing is copied to the host."""
+    lib = _lib()
+    s = _dev1d(scores, torch.float32, "scores")
+    n, dev = s.numel(), s.device
+    st, en = _runs(start, end, dev)
+    count = st.numel()
+    pd, thr, d, ld, k = None, None, 0, 0, 0
+    if per_dim is not None:
+        pd = _dev2d(per_dim, "per_dim")
+        if pd.device != dev or pd.shape[0] != n:
+            raise ValueError(f"per_dim must hold one row per score on the same device, got {tuple(pd.shape)} for {n} scores")
+        d, ld = pd.shape[1], pd.stride(0)
+        if top_k < 1:
+            raise ValueError(f"top_k must be >= 1, got {top_k}")
+        k = min(int(top_k), d, 64)
+        if feature_thresholds is not None:
+            thr = torch.as_tensor(feature_thresholds, dtype=torch.float64).reshape(-1).to(dev).contiguous()
+            if thr.numel() != d:
+                raise ValueError(f"{thr.numel()} feature thresholds for {d} columns")
+    elif feature_thresholds is not None:
+        raise ValueError("feature_thresholds need per_dim")
+    out = {"peak": torch.empty(count, dtype=torch.int64, device=dev), "peak_score": _native._empty(count, dtype=torch.float32, device=dev),
+           "mean_score": _native._empty(count, dtype=torch.float32, device=dev)}
+    if pd is not None:
+        out["feature_means"] = _native._empty((count, d), dtype=torch.float32, device=dev)
+        out["top_features"] = torch.empty((count, k), dtype=torch.int32, device=dev)
+        out["top_values"] = _native._empty((count, k), dtype=torch.float32, device=dev)
+    if thr is not None:
+        out["feature_hits"] = torch.empty((count, d), dtype=torch.int32, device=dev)
+    if count == 0:
+        return out
+    nbytes = lib.mtadgat_eval_run_stats_scratch(n, count, d)
+    scratch = _native._empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.mtadgat_eval_run_stats(s.data_ptr(), n, st.data_ptr(), en.data_ptr(), count, _ptr(pd), d, ld, _ptr(thr), k, scratch.data_ptr(),
+                                        scratch.numel() * 8, out["peak"].data_ptr(), out["peak_score"].data_ptr(), out["mean_score"].data_ptr(),
+                                        _ptr(out.get("feature_means")), _ptr(out.get("top_features")), _ptr(out.get("top_values")),
+                                        _ptr(out.get("feature_hits")), _stream(s))
+    if rc != 0:
+        _fail(lib, rc, "eval_run_stats")
+    return out
+
+
+def first_hits(start, end, scores=None, labels=None, threshold=0.0, compare_f32=False):
+    """The first flagged index inside every run [start_k, end_k), or -1: (E,) int64 on the device.  The flag source is read as in
+    flag_runs.  Scores against labelled segments: where each segment was detected; labels against events: which events are true."""
+    lib = _lib()
+    s, lab = _flag_source(scores, labels)
+    src = s if s is not None else lab
+    st, en = _runs(start, end, src.device)
+    first = torch.empty(st.numel(), dtype=torch.int64, device=src.device)
+    if st.numel() == 0:
+        return first
+    if src.numel() < 1:
+        raise ValueError("the flag source is empty")
+    with torch.cuda.device(src.device):
+        rc = lib.mtadgat_eval_first_hit(_ptr(s), _ptr(lab), src.numel(), float(threshold), 1 if compare_f32 else 0, st.data_ptr(), en.data_ptr(),
+                                        st.numel(), first.data_ptr(), _stream(src))
+    if rc != 0:
+        _fail(lib, rc, "eval_first_hit")
+    return first
+
+
+def anomaly_events(scores, threshold, per_dim=None, feature_thresholds=None, labels=None, merge_gap=0, min_length=1, top_k=5,
+                   compare_f32=False, max_events=65536):
+    """The alarms behind a thresholded score array: the contiguous stretches with scores > threshold, merged across gaps of at
+    most merge_gap samples and kept from min_length samples on, each with its peak, its means and the features that carry it.
+    Everything is computed on the device (csrc/mtadgat_events.hip); only the number of events comes to the host.
+
+    Indices are in score-index space: event [start, end) covers scores[start:end], and score i belongs to row i + W of the series
+    the windows were cut from (W = window_size).  `peak` is therefore what `model.score_attribution(values, indices)` takes.
+
+    Returns a dict:
+      count                                  Python int; threshold: the float compared against
+      start, end, peak                       (E,) int64; peak_score, mean_score (E,) float32    (flag_runs, run_statistics)
+      feature_means, top_features, top_values   with per_dim (n, d): (E, d), (E, k) int32, (E, k), k = min(top_k, d, 64)
+      feature_hits                           with feature_thresholds (d,) too: (E, d) int32 rows with per_dim >= threshold
+      event_is_true                          with labels (n,): (E,) bool, the event overlaps a labelled sample
+      segments                               with labels: dict of start, end (the labelled runs), first_hit (the first sample of the
+                                             segment with scores > threshold, -1 if none) and latency = first_hit - start (-1 if
+                                             undetected), all (S,) int64 -- the per-segment view of point_adjust_counts
+    No events gives empty tensors of these shapes.  max_events sizes the first attempt; more events cost one repeat."""
+    s = _dev1d(scores, torch.float32, "scores")
+    count, start, end = flag_runs(scores=s, threshold=threshold, merge_gap=merge_gap, min_length=min_length, compare_f32=compare_f32,
+                                  max_runs=max_events)
+    out = {"count": count, "threshold": float(threshold), "start": start, "end": end}
+    out.update(run_statistics(s, start, end, per_dim=per_dim, feature_thresholds=feature_thresholds if per_dim is not None else None,
+                              top_k=top_k))
+    if labels is not None:
+        lab = _labels_u8(labels)
+        if lab.numel() != s.numel():
+            raise ValueError("scores and labels must have the same length")
+        out["event_is_true"] = first_hits(start, end, labels=lab) >= 0
+        _, seg_start, seg_end = flag_runs(labels=lab, max_runs=max_events)
+        hit = first_hits(seg_start, seg_end, scores=s, threshold=threshold, compare_f32=compare_f32)
+        out["segments"] = {"start": seg_start, "end": seg_end, "first_hit": hit, "latency": torch.where(hit >= 0, hit - seg_start, hit)}
+    return out
+
+
+def explain_events(model, values, events, which=None, max_events=64, **attribution_kwargs):
+    """Attribution of the events' peak scores to the input: model.score_attribution(values, events["peak"][which], ...) and its two
+    marginals.  `which` selects events (None: all; an index, slice, list or tensor); every selected peak costs two training
+    forwards, so more than max_events of them is an error rather than a long wait.
+    Returns a dict: peaks (E',) int64, attributions (E', W+1, F), per_feature (E', F) = |attributions| summed over the W+1 rows,
+    per_lag (E', W+1) = summed over the features."""
+    peaks = events["peak"]
+    if which is not None:
+        peaks = peaks[which]
+    peaks = peaks.reshape(-1)
+    if peaks.numel() > max_events:
+        raise ValueError(f"{peaks.numel()} events selected, max_events is {max_events}: pick some with `which` or raise max_events")
+    attr = model.score_attribution(values, peaks, **attribution_kwargs)
+    mag = attr.abs()
+    return {"peaks": peaks, "attributions": attr, "per_feature": mag.sum(1), "per_lag": mag.sum(2)}
