@@ -478,6 +478,72 @@ int mtadgat_eval_run_stats(const float* score_dev, int64_t n, const int64_t* sta
 int mtadgat_eval_first_hit(const float* score_dev, const unsigned char* label_dev, int64_t n, double threshold, int compare_f32,
                            const int64_t* start_dev, const int64_t* end_dev, int64_t count, int64_t* first_dev, void* stream);
 
+/* ---- scoring live streams row by row (csrc/mtadgat_stream.hip; streaming.StreamScorer) ---------------------------------
+ * A deployment's loop: rows of n_streams independent series arrive a few at a time, and each needs its anomaly score, an alarm
+ * flag and -- when an alarm ends -- the finished event.  Everything that carries over from one push to the next lives in ONE
+ * device allocation of mtadgat_stream_state_bytes() bytes (16-byte aligned) that the host never reads: per stream its row
+ * counter, the last W + max_block - 1 rows (a ring stored twice, so that every window is contiguous; the rings of all streams
+ * form one flat series for mtadgat_forward_series), the forecast pending for its next row, the moving-average state and the
+ * open event.  Scores, indices and events are in the score-index space of Predictor.get_score (prediction.py:65-91): score
+ * i of a stream belongs to its row i + W, the first row with both a full window behind it and a forecast from the row before;
+ * rows 0 .. W - 1 give NaN scores and no flag.
+ *   per_dim[d] = |forecast[d] - x[d]| + gamma |recon_last[d] - x[d]| in float64, optionally (. - center[d]) / (1 + spread[d])
+ *   score      = the float64 mean over d, rounded once to float32; with alpha in (0, 1] the moving average of those float32
+ *                scores (pandas ewm(span).mean(), alpha = 2 / (span + 1), adjust=True: N_t = x_t + (1 - alpha) N_{t-1},
+ *                D_t = 1 + (1 - alpha) D_{t-1} in float64, N_t / D_t stored as float32); alpha = 0: no smoothing
+ *   flag       = (double)score > threshold (NaN and equality are not flagged): `threshold`, or thresholds_dev[stream] when
+ *                thresholds_dev, (n_streams) float64 on the device, is given
+ *   events     = mtadgat_eval_runs' semantics, incrementally: flagged runs at most merge_gap apart merge, events shorter than
+ *                min_length are dropped.  An event whose last flagged sample is e - 1 becomes final at sample e + merge_gap
+ *                if nothing from e on was flagged, and is reported AT that sample: at most one per stream and sample.
+ * Outputs of a push of T rows for n streams, each (n, T) in (stream, t) order and each optional (NULL): scores float32,
+ * flags uint8, per_dim (n, T, d) float32, and the event that closed at the sample -- closed_start (-1: none), closed_end
+ * (exclusive), closed_peak (the first index of the largest score) int64, closed_peak_score, closed_mean (float64 sum / length)
+ * float32.  No atomics: the bits depend on the data and on the order of pushes per stream, not on how rows are cut into pushes.
+ *
+ * streams_dev: (n) distinct int64 stream indices on the device, or NULL for streams 0 .. n - 1; an index outside
+ * [0, n_streams) gets "nothing" outputs and touches no state.  rows_dev (n, T, F) float32, T <= max_block.  n_streams and
+ * max_block must be those of mtadgat_stream_init (the kernels refuse a state initialised for another geometry).  Nothing
+ * synchronises except mtadgat_stream_init (it copies the three host vectors).  Status as everywhere. */
+typedef struct mtadgat_stream_outputs {
+    float*   scores;
+    uint8_t* flags;
+    float*   per_dim;
+    int64_t* closed_start;
+    int64_t* closed_end;
+    int64_t* closed_peak;
+    float*   closed_peak_score;
+    float*   closed_mean;
+} mtadgat_stream_outputs;
+size_t mtadgat_stream_state_bytes(mtadgat_handle h, int64_t n_streams, int64_t max_block);
+/* Zeroes the state.  dims_host (out_dim) int32: the series column of each output dimension, or NULL for 0 .. out_dim - 1
+ * (needs out_dim == n_features); center_host / spread_host (out_dim) float32, both or neither. */
+int mtadgat_stream_init(mtadgat_handle h, void* state_dev, int64_t n_streams, int64_t max_block, double gamma, double alpha,
+                        int64_t merge_gap, int64_t min_length, const int32_t* dims_host, const float* center_host,
+                        const float* spread_host, void* stream);
+/* Workspace of mtadgat_stream_push for n * T = windows: the forward's, the window starts and the two model outputs --
+ * preds (windows, out_dim) at its beginning, recons_last (windows, out_dim) right behind. */
+size_t mtadgat_stream_workspace_bytes(mtadgat_handle h, int64_t windows);
+/* The stage kernel, ONE mtadgat_forward_series over the flat history (preds and recons_last only) and the score kernel.
+ * out == NULL stops after the forward: the rows are in the history and the model outputs in the workspace, but no counter
+ * has moved, so the call can be repeated (re-packed weights) -- mtadgat_stream_update with staged = 1 then commits it. */
+int mtadgat_stream_push(mtadgat_handle h, void* state_dev, int64_t n_streams, int64_t max_block, const float* rows_dev,
+                        const int64_t* streams_dev, int64_t n, int64_t T, double threshold, const double* thresholds_dev,
+                        const mtadgat_stream_outputs* out, void* workspace_dev, size_t workspace_bytes, void* stream);
+/* The stage and score kernels with the model outputs of the windows ending at the new rows supplied by the caller, (n, T,
+ * out_dim) each: the state machine without a model in the way.  staged != 0: the rows are in the history already. */
+int mtadgat_stream_update(mtadgat_handle h, void* state_dev, int64_t n_streams, int64_t max_block, const float* preds_dev,
+                          const float* recons_last_dev, const float* rows_dev, const int64_t* streams_dev, int64_t n, int64_t T,
+                          int staged, double threshold, const double* thresholds_dev, const mtadgat_stream_outputs* out, void* stream);
+/* The still-open event of each selected stream, its end at the last flagged sample + 1, in the closed_* fields of `out` ((n)
+ * each; may be NULL with reset); the state is left as it is unless reset != 0, which returns those streams to their state
+ * after mtadgat_stream_init (history zeroed). */
+int mtadgat_stream_flush(mtadgat_handle h, void* state_dev, int64_t n_streams, int64_t max_block, const int64_t* streams_dev,
+                         int64_t n, int reset, const mtadgat_stream_outputs* out, void* stream);
+/* Host only: the first slot, within a stream's 2R ring slots, of the window ending at the stream's row count + t -- the
+ * function the stage kernel calls.  R = W + max_block - 1; -1 for count < 0, t < 0, W < 1 or R < W. */
+int64_t mtadgat_stream_window_start(int64_t count, int64_t t, int64_t W, int64_t R);
+
 /* Per-kernel launch timing for bench.py's roofline leg: when enabled, forward()
  * brackets each kernel family with hipEvents on `stream`; mtadgat_profile_read
  * synchronises those events and returns accumulated milliseconds + launch counts

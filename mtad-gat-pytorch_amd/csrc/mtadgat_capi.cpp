@@ -2280,3 +2280,141 @@ int mtadgat_dropout_masks(mtadgat_handle h, int64_t batch, int64_t window0, floa
 }
 
 }  // extern "C"
+
+// ---- scoring live streams row by row (kernels: mtadgat_stream.hip) -----------------------------------------------------------
+namespace {
+
+constexpr int64_t STREAM_MAX_BLOCK = 65536;
+
+bool stream_sizes_ok(int64_t n_streams, int64_t max_block) {
+    return n_streams >= 1 && n_streams <= 2147483647LL && max_block >= 1 && max_block <= STREAM_MAX_BLOCK;
+}
+StreamGeom stream_geom(const Model& m, int64_t n_streams, int64_t max_block) {
+    return StreamGeom{(long)n_streams, (long)(m.W + max_block - 1), (long)m.W, (long)m.F, (long)m.cfg.out_dim};
+}
+// what every call on an initialised state checks on the host
+int stream_check(mtadgat_handle h, const void* state, int64_t n_streams, int64_t max_block, int64_t n, int64_t T, const char* who) {
+    if (!h) return fail(MTADGAT_ERR_INVALID, std::string(who) + ": null handle");
+    if (!state) return fail(MTADGAT_ERR_INVALID, std::string(who) + ": state is NULL");
+    if (!aligned16(state)) return fail(MTADGAT_ERR_INVALID, std::string(who) + ": state must be 16-byte aligned");
+    if (!stream_sizes_ok(n_streams, max_block))
+        return fail(MTADGAT_ERR_INVALID, std::string(who) + ": needs 1 <= n_streams < 2^31 and 1 <= max_block <= 65536");
+    if (n < 1 || n > n_streams) return fail(MTADGAT_ERR_INVALID, std::string(who) + ": n must lie in [1, n_streams]");
+    if (T < 1 || T > max_block) return fail(MTADGAT_ERR_INVALID, std::string(who) + ": T must lie in [1, max_block]");
+    return 0;
+}
+StreamOut stream_out(const mtadgat_stream_outputs* o) {
+    StreamOut r{};
+    if (!o) return r;
+    r.scores = o->scores; r.flags = o->flags; r.per_dim = o->per_dim;
+    r.closed_start = reinterpret_cast<long*>(o->closed_start); r.closed_end = reinterpret_cast<long*>(o->closed_end);
+    r.closed_peak = reinterpret_cast<long*>(o->closed_peak); r.closed_peak_score = o->closed_peak_score; r.closed_mean = o->closed_mean;
+    return r;
+}
+struct StreamWs {                // float offsets into the push workspace
+    size_t preds, last, starts, fwd, total;
+};
+StreamWs stream_ws(const Model& m, int64_t windows) {
+    const size_t od = ((size_t)windows * m.cfg.out_dim + 3) / 4 * 4;
+    StreamWs w;
+    w.preds = 0;
+    w.last = od;
+    w.starts = 2 * od;
+    w.fwd = w.starts + ((size_t)windows * 2 + 3) / 4 * 4;          // (an int64 per window)
+    w.total = w.fwd + workspace_floats(m, windows);
+    return w;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t mtadgat_stream_state_bytes(mtadgat_handle h, int64_t n_streams, int64_t max_block) {
+    if (!h || !stream_sizes_ok(n_streams, max_block)) return 0;
+    return stream_layout((long)n_streams, (long)max_block, h->m.W, h->m.F, h->m.cfg.out_dim).bytes;
+}
+
+int mtadgat_stream_init(mtadgat_handle h, void* state, int64_t n_streams, int64_t max_block, double gamma, double alpha, int64_t merge_gap,
+                        int64_t min_length, const int32_t* dims_host, const float* center_host, const float* spread_host, void* stream) {
+    int rc = stream_check(h, state, n_streams, max_block, 1, 1, "stream_init");
+    if (rc) return rc;
+    const Model& m = h->m;
+    const int d = m.cfg.out_dim;
+    if (!(alpha >= 0.0 && alpha <= 1.0)) return fail(MTADGAT_ERR_INVALID, "stream_init: alpha outside [0, 1]");
+    if (!(gamma == gamma)) return fail(MTADGAT_ERR_INVALID, "stream_init: gamma is NaN");
+    if (merge_gap < 0) return fail(MTADGAT_ERR_INVALID, "stream_init: merge_gap must be >= 0");
+    if (min_length < 1) return fail(MTADGAT_ERR_INVALID, "stream_init: min_length must be >= 1");
+    if ((center_host == nullptr) != (spread_host == nullptr)) return fail(MTADGAT_ERR_INVALID, "stream_init: give center and spread, or neither");
+    std::vector<int> dims(d);
+    for (int c = 0; c < d; ++c) {
+        dims[c] = dims_host ? dims_host[c] : c;
+        if (dims[c] < 0 || dims[c] >= m.F) return fail(MTADGAT_ERR_INVALID, "stream_init: a target dimension lies outside [0, n_features)");
+    }
+    StreamHeader hd{};
+    hd.S = n_streams; hd.R = m.W + max_block - 1; hd.W = m.W; hd.F = m.F; hd.d = d; hd.max_block = max_block;
+    hd.merge_gap = merge_gap; hd.min_length = min_length; hd.gamma = gamma; hd.decay = 1.0 - alpha;
+    hd.smooth = alpha > 0.0 ? 1 : 0; hd.scaled = center_host ? 1 : 0;
+    HIP_TRY((hipError_t)launch_stream_init(state, hd, dims.data(), center_host, spread_host, (hipStream_t)stream));
+    return 0;
+}
+
+size_t mtadgat_stream_workspace_bytes(mtadgat_handle h, int64_t windows) {
+    if (!h || windows < 1 || windows > 2147483647LL) return 0;
+    return stream_ws(h->m, windows).total * sizeof(float);
+}
+
+int mtadgat_stream_update(mtadgat_handle h, void* state, int64_t n_streams, int64_t max_block, const float* preds, const float* recons_last,
+                          const float* rows, const int64_t* streams, int64_t n, int64_t T, int staged, double threshold,
+                          const double* thresholds, const mtadgat_stream_outputs* out, void* stream) {
+    int rc = stream_check(h, state, n_streams, max_block, n, T, "stream_update");
+    if (rc) return rc;
+    if (!preds || !recons_last || !rows) return fail(MTADGAT_ERR_INVALID, "stream_update: null tensor");
+    const StreamGeom g = stream_geom(h->m, n_streams, max_block);
+    const long* st = reinterpret_cast<const long*>(streams);
+    hipStream_t s = (hipStream_t)stream;
+    if (!staged) K_TRY(launch_stream_stage(state, g, rows, st, n, T, nullptr, s), "stream stage");
+    K_TRY(launch_stream_score(state, g, rows, st, n, T, preds, recons_last, threshold, thresholds, stream_out(out), s), "stream score");
+    return 0;
+}
+
+int mtadgat_stream_push(mtadgat_handle h, void* state, int64_t n_streams, int64_t max_block, const float* rows, const int64_t* streams,
+                        int64_t n, int64_t T, double threshold, const double* thresholds, const mtadgat_stream_outputs* out, void* ws_,
+                        size_t ws_bytes, void* stream) {
+    int rc = stream_check(h, state, n_streams, max_block, n, T, "stream_push");
+    if (rc) return rc;
+    if (!rows) return fail(MTADGAT_ERR_INVALID, "stream_push: null tensor");
+    const Model& m = h->m;
+    const int64_t windows = n * T;
+    if (windows > 2147483647LL) return fail(MTADGAT_ERR_INVALID, "stream_push: n * T must stay below 2^31");
+    const StreamWs w = stream_ws(m, windows);
+    if (!ws_) return fail(MTADGAT_ERR_WORKSPACE, "stream_push: workspace is NULL");
+    if (!aligned16(ws_)) return fail(MTADGAT_ERR_WORKSPACE, "stream_push: workspace must be 16-byte aligned");
+    if (ws_bytes < w.total * sizeof(float)) return fail(MTADGAT_ERR_WORKSPACE, "stream_push: workspace too small (see mtadgat_stream_workspace_bytes)");
+    if ((rc = check_common(h, windows, nullptr, 0, false))) return rc;
+    const StreamGeom g = stream_geom(m, n_streams, max_block);
+    const StreamLayout l = stream_layout(g.S, (long)max_block, g.W, g.F, g.d);
+    float* ws = static_cast<float*>(ws_);
+    int64_t* starts = reinterpret_cast<int64_t*>(ws + w.starts);
+    const long* st = reinterpret_cast<const long*>(streams);
+    hipStream_t s = (hipStream_t)stream;
+    K_TRY(launch_stream_stage(state, g, rows, st, n, T, reinterpret_cast<long*>(starts), s), "stream stage");
+    const float* history = reinterpret_cast<const float*>(static_cast<const char*>(state) + l.ring);
+    if ((rc = mtadgat_forward_series(h, history, g.S * 2 * g.R, starts, 0, 1, windows, ws + w.preds, nullptr, ws + w.last, ws + w.fwd,
+                                     (w.total - w.fwd) * sizeof(float), stream)))
+        return rc;
+    if (!out) return 0;
+    K_TRY(launch_stream_score(state, g, rows, st, n, T, ws + w.preds, ws + w.last, threshold, thresholds, stream_out(out), s), "stream score");
+    return 0;
+}
+
+int mtadgat_stream_flush(mtadgat_handle h, void* state, int64_t n_streams, int64_t max_block, const int64_t* streams, int64_t n, int reset,
+                         const mtadgat_stream_outputs* out, void* stream) {
+    int rc = stream_check(h, state, n_streams, max_block, n, 1, "stream_flush");
+    if (rc) return rc;
+    if (!out && !reset) return fail(MTADGAT_ERR_INVALID, "stream_flush: neither outputs nor reset asked for");
+    K_TRY(launch_stream_flush(state, stream_geom(h->m, n_streams, max_block), reinterpret_cast<const long*>(streams), n, out ? 1 : 0,
+                              reset ? 1 : 0, stream_out(out), (hipStream_t)stream), "stream flush");
+    return 0;
+}
+
+}  // extern "C"

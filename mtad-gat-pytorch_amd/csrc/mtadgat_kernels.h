@@ -496,4 +496,52 @@ int launch_att_mean_final(const float* PS, const float* PC, int K, int nslab, lo
 // records `msg` for mtadgat_last_error() and returns `code` (mtadgat_capi.cpp): for the entry points defined beside their kernels
 int record_error(int code, const char* msg);
 
+// ---- row-by-row scoring of live streams (mtadgat_stream.hip; entry points in mtadgat_capi.cpp) ----
+// Every stream keeps its last rows in a ring of R = W + max_block - 1 rows stored twice: row number k goes to slots k % R and
+// k % R + R of the stream's 2R slots.  The window ending at row k = count + t (count rows seen before the push, t-th row of the
+// push) then lies in slots [start, start + W) with start = k % R + R - W + 1: its last row is read from the upper copy, the
+// rows before it from whichever copy is contiguous with it.  start lies in [R - W + 1, 2R - W]; rows count + t + 1 .. of the
+// same push land in slots (k + i) % R (+ R), 1 <= i < max_block, and i + j < R for every row k - j of the window, so none of
+// them overwrites a slot the window reads.  The one place this arithmetic lives: host (mtadgat_stream_window_start) and kernel.
+__host__ __device__ inline long stream_row_slot(long k, long R) { return k % R; }
+__host__ __device__ inline long stream_window_start(long count, long t, long W, long R) { return stream_row_slot(count + t, R) + R - W + 1; }
+
+struct StreamSlot {          // per-stream state, advanced by k_stream_score only
+    long count;              // rows seen
+    double num, den;         // N_t, D_t of the moving average over the scored rows
+    long ev_start, ev_last, ev_peak;     // the open event, in score-index space (row number - W)
+    double ev_sum, ev_tail;  // sum of the scores in [ev_start, ev_last], and of the unflagged ones after ev_last
+    float ev_peak_score;
+    int ev_open;
+};
+struct StreamHeader {        // written by mtadgat_stream_init; geometry is checked by every kernel against its arguments
+    long S, R, W, F, d, max_block, merge_gap, min_length;
+    double gamma, decay;     // decay = 1 - alpha of the moving average
+    int smooth, scaled;
+    long pad[3];
+};
+struct StreamLayout {        // byte offsets into the state allocation
+    size_t dims, center, spread, slots, pending, ring, bytes;
+    long R;
+};
+StreamLayout stream_layout(long S, long max_block, long W, long F, long d);
+struct StreamGeom { long S, R, W, F, d; };
+struct StreamOut {           // (n, T) each, per_dim (n, T, d); any may be null
+    float* scores;
+    unsigned char* flags;
+    float* per_dim;
+    long* closed_start;
+    long* closed_end;
+    long* closed_peak;
+    float* closed_peak_score;
+    float* closed_mean;
+};
+int launch_stream_init(void* state, const StreamHeader& hd, const int* dims_host, const float* center_host, const float* spread_host,
+                       hipStream_t s);
+int launch_stream_stage(void* state, const StreamGeom& g, const float* rows, const long* streams, long n, long T, long* starts, hipStream_t s);
+int launch_stream_score(void* state, const StreamGeom& g, const float* rows, const long* streams, long n, long T, const float* preds,
+                        const float* recons_last, double threshold, const double* thresholds, const StreamOut& out, hipStream_t s);
+int launch_stream_flush(void* state, const StreamGeom& g, const long* streams, long n, int report, int reset, const StreamOut& out,
+                        hipStream_t s);
+
 }  // namespace mtadgat
