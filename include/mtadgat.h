@@ -544,6 +544,61 @@ int mtadgat_stream_flush(mtadgat_handle h, void* state_dev, int64_t n_streams, i
  * function the stage kernel calls.  R = W + max_block - 1; -1 for count < 0, t < 0, W < 1 or R < W. */
 int64_t mtadgat_stream_window_start(int64_t count, int64_t t, int64_t W, int64_t R);
 
+/* ---- adaptive peaks-over-threshold thresholds (csrc/mtadgat_spot.hip, csrc/mtadgat_spot.h; evaluation.spot_*) ------------
+ * SPOT (Siffer et al., KDD 2017) per column of a score matrix: each column keeps an initial threshold t, its excesses x - t over
+ * it, and the alarm threshold z at the q-quantile of a generalized Pareto tail fitted to those excesses.  The definition of the
+ * fit (candidates, root search, choice, threshold) is spelled out in csrc/mtadgat_spot.h; it follows the paper, not the
+ * reference's spot.py, and tests/spot_refs.py is its specification.  One state allocation of mtadgat_spot_state_bytes() bytes
+ * (16-byte aligned) holds, per column, (t, z, n, Nt, gamma, sigma) and a ring of the most recent max_peaks excesses.  The ring
+ * is this library's own bound: Nt counts every excess, the fit sees only the stored ones -- until a ring wraps this is the
+ * paper's Algorithm 1.  All arithmetic is float64; one wave fits one column; no atomics; bitwise reproducible.
+ *
+ * The step for one score x: the threshold reported for the row is z before the step; a NaN changes nothing and is not
+ * flagged; x > z is flagged (and, when the state is dynamic, leaves it alone: alarms are not absorbed); otherwise a dynamic
+ * state with x > t pushes x - t into the ring (dropping the oldest when full), increments Nt and n, refits and takes the new z,
+ * and any other x increments n.  A static state (dynamic = 0) never changes.
+ *
+ * Refused with a message before anything is launched: q or level outside (0, 1), max_peaks outside [8, 4096], n_init < 16. */
+size_t mtadgat_spot_state_bytes(int64_t n_columns, int64_t max_peaks);          /* 0 for sizes that are refused */
+size_t mtadgat_spot_calibrate_scratch(int64_t n_init, int64_t n_columns);
+/* Calibrates every column of init_dev (n_init, n_columns) float32, row stride ld: t = sorted[int(level * n_init)] (exact radix
+ * select), the excesses in row order (the last max_peaks of them are kept), the first fit.  At most 65536 columns per call.
+ * Synchronises the stream: a column with fewer than 8 excesses, a NaN or a non-positive mean excess fails the call with -1 and
+ * a message naming the column. */
+int mtadgat_spot_calibrate(const float* init_dev, int64_t n_init, int64_t n_columns, int64_t ld, double q, double level,
+                           int64_t max_peaks, int dynamic, void* state_dev, void* scratch_dev, size_t scratch_bytes, void* stream);
+/* The step over the rows of scores_dev (n, n_columns) float32, row stride ld, in order: thresholds_dev (n, n_columns) float64
+ * and flags_dev (n, n_columns) uint8, either may be NULL.  The state is left advanced, so a second call continues where the
+ * first stopped.  Asynchronous.  A state calibrated for other sizes gives NaN thresholds, no flags, and is not touched. */
+int mtadgat_spot_run(void* state_dev, int64_t n_columns, int64_t max_peaks, const float* scores_dev, int64_t n, int64_t ld,
+                     double* thresholds_dev, uint8_t* flags_dev, void* stream);
+/* out_host (n_columns, 6) float64: t, z, n, Nt, gamma, sigma per column.  Synchronises the stream. */
+int mtadgat_spot_read(const void* state_dev, int64_t n_columns, int64_t max_peaks, double* out_host, void* stream);
+/* Columns columns_dev[0 .. n) (NULL: 0 .. n - 1) of dst <- the same columns of src, or src's only column when src_columns is 1.
+ * init != 0: dst is a fresh allocation that also takes src's header; then all its columns are copied (n = dst_columns, no
+ * selection).  Asynchronous. */
+int mtadgat_spot_copy(void* dst_dev, int64_t dst_columns, const void* src_dev, int64_t src_columns, int64_t max_peaks,
+                      const int64_t* columns_dev, int64_t n, int init, void* stream);
+/* Host only, no GPU needed: the fit over m >= 1 positive excesses (oldest first) for n observations, Nt excesses, initial
+ * threshold t and risk q, with the sums taken in the order a wave takes them.  out[3] = gamma, sigma, z. */
+int mtadgat_spot_fit_host(const double* peaks, int64_t m, int64_t n, int64_t Nt, double t, double q, double* out);
+/* mtadgat_stream_push / _update with each stream compared against ITS column of a SPOT state of n_streams columns (a second
+ * device allocation beside the stream state), after the smoothing; the column advances with the stream.  thresholds_out_dev:
+ * (n, T) float64, what each row was compared against (NaN for a stream's first W rows), or NULL. */
+int mtadgat_stream_push_spot(mtadgat_handle h, void* state_dev, int64_t n_streams, int64_t max_block, const float* rows_dev,
+                             const int64_t* streams_dev, int64_t n, int64_t T, void* spot_dev, int64_t max_peaks,
+                             double* thresholds_out_dev, const mtadgat_stream_outputs* out, void* workspace_dev, size_t workspace_bytes,
+                             void* stream);
+int mtadgat_stream_update_spot(mtadgat_handle h, void* state_dev, int64_t n_streams, int64_t max_block, const float* preds_dev,
+                               const float* recons_last_dev, const float* rows_dev, const int64_t* streams_dev, int64_t n, int64_t T,
+                               int staged, void* spot_dev, int64_t max_peaks, double* thresholds_out_dev,
+                               const mtadgat_stream_outputs* out, void* stream);
+/* mtadgat_stream_flush with reset for the selected streams, and their SPOT columns restored from a calibrated state of one
+ * column or n_streams columns. */
+int mtadgat_stream_reset_spot(mtadgat_handle h, void* state_dev, int64_t n_streams, int64_t max_block, void* spot_dev,
+                              const void* spot_calibrated_dev, int64_t calibrated_columns, int64_t max_peaks,
+                              const int64_t* streams_dev, int64_t n, void* stream);
+
 /* Per-kernel launch timing for bench.py's roofline leg: when enabled, forward()
  * brackets each kernel family with hipEvents on `stream`; mtadgat_profile_read
  * synchronises those events and returns accumulated milliseconds + launch counts

@@ -2363,33 +2363,105 @@ size_t mtadgat_stream_workspace_bytes(mtadgat_handle h, int64_t windows) {
     return stream_ws(h->m, windows).total * sizeof(float);
 }
 
-int mtadgat_stream_update(mtadgat_handle h, void* state, int64_t n_streams, int64_t max_block, const float* preds, const float* recons_last,
-                          const float* rows, const int64_t* streams, int64_t n, int64_t T, int staged, double threshold,
-                          const double* thresholds, const mtadgat_stream_outputs* out, void* stream) {
-    int rc = stream_check(h, state, n_streams, max_block, n, T, "stream_update");
+}  // extern "C"
+
+namespace {
+
+// the SPOT state of the *_spot entry points, checked on the host like the stream state
+int stream_spot_check(const void* spot, int64_t max_peaks, const char* who) {
+    if (max_peaks < 8 || max_peaks > 4096) return fail(MTADGAT_ERR_INVALID, std::string(who) + ": max_peaks must lie in [8, 4096]");
+    if (!spot) return fail(MTADGAT_ERR_INVALID, std::string(who) + ": the SPOT state is NULL");
+    if (!aligned16(spot)) return fail(MTADGAT_ERR_INVALID, std::string(who) + ": the SPOT state must be 16-byte aligned");
+    return 0;
+}
+
+// mtadgat_stream_update and mtadgat_stream_update_spot (spot non-null)
+int stream_update(mtadgat_handle h, void* state, int64_t n_streams, int64_t max_block, const float* preds, const float* recons_last,
+                  const float* rows, const int64_t* streams, int64_t n, int64_t T, int staged, double threshold, const double* thresholds,
+                  const StreamSpot* spot, const mtadgat_stream_outputs* out, void* stream, const char* who) {
+    int rc = stream_check(h, state, n_streams, max_block, n, T, who);
     if (rc) return rc;
-    if (!preds || !recons_last || !rows) return fail(MTADGAT_ERR_INVALID, "stream_update: null tensor");
+    if (spot && (rc = stream_spot_check(spot->state, spot->max_peaks, who))) return rc;
+    if (!preds || !recons_last || !rows) return fail(MTADGAT_ERR_INVALID, std::string(who) + ": null tensor");
     const StreamGeom g = stream_geom(h->m, n_streams, max_block);
     const long* st = reinterpret_cast<const long*>(streams);
     hipStream_t s = (hipStream_t)stream;
     if (!staged) K_TRY(launch_stream_stage(state, g, rows, st, n, T, nullptr, s), "stream stage");
-    K_TRY(launch_stream_score(state, g, rows, st, n, T, preds, recons_last, threshold, thresholds, stream_out(out), s), "stream score");
+    K_TRY(launch_stream_score(state, g, rows, st, n, T, preds, recons_last, threshold, thresholds, stream_out(out), s, spot), "stream score");
     return 0;
+}
+
+int stream_push(mtadgat_handle h, void* state, int64_t n_streams, int64_t max_block, const float* rows, const int64_t* streams, int64_t n,
+                int64_t T, double threshold, const double* thresholds, const StreamSpot* spot, const mtadgat_stream_outputs* out, void* ws_,
+                size_t ws_bytes, void* stream, const char* who);
+
+}  // namespace
+
+extern "C" {
+
+int mtadgat_stream_update(mtadgat_handle h, void* state, int64_t n_streams, int64_t max_block, const float* preds, const float* recons_last,
+                          const float* rows, const int64_t* streams, int64_t n, int64_t T, int staged, double threshold,
+                          const double* thresholds, const mtadgat_stream_outputs* out, void* stream) {
+    return stream_update(h, state, n_streams, max_block, preds, recons_last, rows, streams, n, T, staged, threshold, thresholds, nullptr, out,
+                         stream, "stream_update");
+}
+
+int mtadgat_stream_update_spot(mtadgat_handle h, void* state, int64_t n_streams, int64_t max_block, const float* preds,
+                               const float* recons_last, const float* rows, const int64_t* streams, int64_t n, int64_t T, int staged,
+                               void* spot, int64_t max_peaks, double* thresholds_out, const mtadgat_stream_outputs* out, void* stream) {
+    const StreamSpot sp{spot, (long)max_peaks, thresholds_out};
+    return stream_update(h, state, n_streams, max_block, preds, recons_last, rows, streams, n, T, staged, 0.0, nullptr, &sp, out, stream,
+                         "stream_update_spot");
 }
 
 int mtadgat_stream_push(mtadgat_handle h, void* state, int64_t n_streams, int64_t max_block, const float* rows, const int64_t* streams,
                         int64_t n, int64_t T, double threshold, const double* thresholds, const mtadgat_stream_outputs* out, void* ws_,
                         size_t ws_bytes, void* stream) {
-    int rc = stream_check(h, state, n_streams, max_block, n, T, "stream_push");
+    return stream_push(h, state, n_streams, max_block, rows, streams, n, T, threshold, thresholds, nullptr, out, ws_, ws_bytes, stream,
+                       "stream_push");
+}
+
+int mtadgat_stream_push_spot(mtadgat_handle h, void* state, int64_t n_streams, int64_t max_block, const float* rows, const int64_t* streams,
+                             int64_t n, int64_t T, void* spot, int64_t max_peaks, double* thresholds_out, const mtadgat_stream_outputs* out,
+                             void* ws_, size_t ws_bytes, void* stream) {
+    const StreamSpot sp{spot, (long)max_peaks, thresholds_out};
+    return stream_push(h, state, n_streams, max_block, rows, streams, n, T, 0.0, nullptr, &sp, out, ws_, ws_bytes, stream, "stream_push_spot");
+}
+
+int mtadgat_stream_reset_spot(mtadgat_handle h, void* state, int64_t n_streams, int64_t max_block, void* spot, const void* spot_calibrated,
+                              int64_t calibrated_columns, int64_t max_peaks, const int64_t* streams, int64_t n, void* stream) {
+    int rc = stream_check(h, state, n_streams, max_block, n, 1, "stream_reset_spot");
     if (rc) return rc;
-    if (!rows) return fail(MTADGAT_ERR_INVALID, "stream_push: null tensor");
+    if ((rc = stream_spot_check(spot, max_peaks, "stream_reset_spot")) || (rc = stream_spot_check(spot_calibrated, max_peaks, "stream_reset_spot")))
+        return rc;
+    if (calibrated_columns != 1 && calibrated_columns != n_streams)
+        return fail(MTADGAT_ERR_INVALID, "stream_reset_spot: the calibrated state needs one column or n_streams columns");
+    const long* st = reinterpret_cast<const long*>(streams);
+    K_TRY(launch_stream_flush(state, stream_geom(h->m, n_streams, max_block), st, n, 0, 1, StreamOut{}, (hipStream_t)stream), "stream flush");
+    K_TRY(launch_spot_copy(spot, (long)n_streams, spot_calibrated, (long)calibrated_columns, (long)max_peaks, st, (long)n, (hipStream_t)stream),
+          "spot copy");
+    return 0;
+}
+
+}  // extern "C"
+
+namespace {
+
+int stream_push(mtadgat_handle h, void* state, int64_t n_streams, int64_t max_block, const float* rows, const int64_t* streams, int64_t n,
+                int64_t T, double threshold, const double* thresholds, const StreamSpot* spot, const mtadgat_stream_outputs* out, void* ws_,
+                size_t ws_bytes, void* stream, const char* who_) {
+    const std::string who(who_);
+    int rc = stream_check(h, state, n_streams, max_block, n, T, who_);
+    if (rc) return rc;
+    if (spot && (rc = stream_spot_check(spot->state, spot->max_peaks, who_))) return rc;
+    if (!rows) return fail(MTADGAT_ERR_INVALID, who + ": null tensor");
     const Model& m = h->m;
     const int64_t windows = n * T;
-    if (windows > 2147483647LL) return fail(MTADGAT_ERR_INVALID, "stream_push: n * T must stay below 2^31");
+    if (windows > 2147483647LL) return fail(MTADGAT_ERR_INVALID, who + ": n * T must stay below 2^31");
     const StreamWs w = stream_ws(m, windows);
-    if (!ws_) return fail(MTADGAT_ERR_WORKSPACE, "stream_push: workspace is NULL");
-    if (!aligned16(ws_)) return fail(MTADGAT_ERR_WORKSPACE, "stream_push: workspace must be 16-byte aligned");
-    if (ws_bytes < w.total * sizeof(float)) return fail(MTADGAT_ERR_WORKSPACE, "stream_push: workspace too small (see mtadgat_stream_workspace_bytes)");
+    if (!ws_) return fail(MTADGAT_ERR_WORKSPACE, who + ": workspace is NULL");
+    if (!aligned16(ws_)) return fail(MTADGAT_ERR_WORKSPACE, who + ": workspace must be 16-byte aligned");
+    if (ws_bytes < w.total * sizeof(float)) return fail(MTADGAT_ERR_WORKSPACE, who + ": workspace too small (see mtadgat_stream_workspace_bytes)");
     if ((rc = check_common(h, windows, nullptr, 0, false))) return rc;
     const StreamGeom g = stream_geom(m, n_streams, max_block);
     const StreamLayout l = stream_layout(g.S, (long)max_block, g.W, g.F, g.d);
@@ -2403,9 +2475,13 @@ int mtadgat_stream_push(mtadgat_handle h, void* state, int64_t n_streams, int64_
                                      (w.total - w.fwd) * sizeof(float), stream)))
         return rc;
     if (!out) return 0;
-    K_TRY(launch_stream_score(state, g, rows, st, n, T, ws + w.preds, ws + w.last, threshold, thresholds, stream_out(out), s), "stream score");
+    K_TRY(launch_stream_score(state, g, rows, st, n, T, ws + w.preds, ws + w.last, threshold, thresholds, stream_out(out), s, spot), "stream score");
     return 0;
 }
+
+}  // namespace
+
+extern "C" {
 
 int mtadgat_stream_flush(mtadgat_handle h, void* state, int64_t n_streams, int64_t max_block, const int64_t* streams, int64_t n, int reset,
                          const mtadgat_stream_outputs* out, void* stream) {

@@ -59,6 +59,20 @@ __global__ void k_eval_colq_init(double* __restrict__ q, ColqProbs pv, int inl, 
     }
 }
 
+// the same select for ONE given rank per column (R = 1): sorted[rank] of every column, for launch_column_rank
+__global__ void k_eval_colq_init_rank(unsigned rank, int d, unsigned* __restrict__ state, unsigned* __restrict__ nanflag,
+                                      unsigned* __restrict__ hist) {
+    const long nhist = (long)d * 256;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nhist; i += (long)gridDim.x * blockDim.x) {
+        hist[i] = 0u;
+        if (i < d) {
+            state[2 * i] = 0u;
+            state[2 * i + 1] = rank;
+            nanflag[i] = 0u;
+        }
+    }
+}
+
 // One radix pass: for every (column, rank) the histogram of digit (key >> shift) & 255 over the keys whose higher digits equal
 // the rank's prefix.  grid = (column tiles, row slices, rank groups); the rows are walked grid-stride.
 __global__ void __launch_bounds__(256) k_eval_colq_hist(const float* __restrict__ a, long n, int d, long ld, int R, int shift,
@@ -239,7 +253,44 @@ ColqLayout colq_layout(int64_t d, int64_t nq) {
     return l;
 }
 
+// the four digit passes of the select for R ranks per column, on an initialised state
+void colq_passes(const float* a_dev, long n, int d, long ld, int R, unsigned* state, unsigned* hist, unsigned* nanflag, float* ord,
+                 hipStream_t s) {
+    // bounded grid: about 1024 workgroups in all, each walking at least four row groups
+    const long cells = (long)d * R;
+    const int tiles = (d + CQ_CT - 1) / CQ_CT, groups = (R + CQ_RT - 1) / CQ_RT;
+    long slices = (n + 4 * CQ_ROWS - 1) / (4 * CQ_ROWS);
+    const long cap = 1024 / ((long)tiles * groups) > 0 ? 1024 / ((long)tiles * groups) : 1;
+    if (slices > cap) slices = cap;
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        hipLaunchKernelGGL(k_eval_colq_hist, dim3(tiles, (unsigned)slices, groups), dim3(256), 0, s, a_dev, (long)n, d, (long)ld, R, shift,
+                           state, hist, nanflag);
+        hipLaunchKernelGGL(k_eval_colq_pick, dim3((unsigned)cells), dim3(64), 0, s, state, hist, shift, ord);
+    }
+}
+
 }  // namespace
+
+namespace mtadgat {
+
+size_t column_rank_scratch(int d) { return colq_layout(d, 1).bytes; }
+
+int launch_column_rank(const float* a_dev, long n, int d, long ld, long rank, void* scratch_dev, const float** ord_dev, hipStream_t s) {
+    const ColqLayout l = colq_layout(d, 1);
+    char* base = static_cast<char*>(scratch_dev);
+    unsigned* hist = reinterpret_cast<unsigned*>(base + l.hist);
+    unsigned* state = reinterpret_cast<unsigned*>(base + l.state);
+    unsigned* nanflag = reinterpret_cast<unsigned*>(base + l.nan);
+    float* ord = reinterpret_cast<float*>(base + l.ord);
+    const long init_blocks = ((long)d * 256 + 255) / 256;
+    hipLaunchKernelGGL(k_eval_colq_init_rank, dim3((unsigned)(init_blocks < 2048 ? init_blocks : 2048)), dim3(256), 0, s, (unsigned)rank, d, state,
+                       nanflag, hist);
+    colq_passes(a_dev, n, d, ld, 1, state, hist, nanflag, ord, s);
+    *ord_dev = ord;
+    return (int)hipGetLastError();
+}
+
+}  // namespace mtadgat
 
 extern "C" {
 
@@ -280,16 +331,7 @@ int mtadgat_eval_column_quantiles(const float* a_dev, int64_t n, int d, int64_t 
     const long init_blocks = (cells * 256 + 255) / 256;
     hipLaunchKernelGGL(k_eval_colq_init, dim3((unsigned)(init_blocks < 2048 ? init_blocks : 2048)), dim3(256), 0, s, q, pv, inl, nq, (long)n, d,
                        state, nanflag, hist);
-    // bounded grid: about 1024 workgroups in all, each walking at least four row groups
-    const int tiles = (d + CQ_CT - 1) / CQ_CT, groups = (R + CQ_RT - 1) / CQ_RT;
-    long slices = (n + 4 * CQ_ROWS - 1) / (4 * CQ_ROWS);
-    const long cap = 1024 / ((long)tiles * groups) > 0 ? 1024 / ((long)tiles * groups) : 1;
-    if (slices > cap) slices = cap;
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        hipLaunchKernelGGL(k_eval_colq_hist, dim3(tiles, (unsigned)slices, groups), dim3(256), 0, s, a_dev, (long)n, d, (long)ld, R, shift,
-                           state, hist, nanflag);
-        hipLaunchKernelGGL(k_eval_colq_pick, dim3((unsigned)cells), dim3(64), 0, s, state, hist, shift, ord);
-    }
+    colq_passes(a_dev, (long)n, d, (long)ld, R, state, hist, nanflag, ord, s);
     const long outs = (long)nq * d;
     hipLaunchKernelGGL(k_eval_colq_interp, dim3((unsigned)((outs + 255) / 256)), dim3(256), 0, s, ord, q, nanflag, (long)n, d, nq, out_dev);
     return hipGetLastError() == hipSuccess ? 0 : record_error(-3, "column_quantiles: kernel launch failed");

@@ -539,9 +539,27 @@ struct StreamOut {           // (n, T) each, per_dim (n, T, d); any may be null
 int launch_stream_init(void* state, const StreamHeader& hd, const int* dims_host, const float* center_host, const float* spread_host,
                        hipStream_t s);
 int launch_stream_stage(void* state, const StreamGeom& g, const float* rows, const long* streams, long n, long T, long* starts, hipStream_t s);
+// peaks-over-threshold thresholds per stream: the state of mtadgat_spot_calibrate with g.S columns and rings of max_peaks excesses,
+// and where the threshold each row was compared with goes ((n, T) float64, may be null)
+struct StreamSpot {
+    void* state;
+    long max_peaks;
+    double* thresholds_out;
+};
+// spot null: the fixed-threshold kernel; otherwise its variant that takes each row's threshold from the SPOT state and advances it
 int launch_stream_score(void* state, const StreamGeom& g, const float* rows, const long* streams, long n, long T, const float* preds,
-                        const float* recons_last, double threshold, const double* thresholds, const StreamOut& out, hipStream_t s);
+                        const float* recons_last, double threshold, const double* thresholds, const StreamOut& out, hipStream_t s,
+                        const StreamSpot* spot = nullptr);
 int launch_stream_flush(void* state, const StreamGeom& g, const long* streams, long n, int report, int reset, const StreamOut& out,
                         hipStream_t s);
+
+// ---- peaks-over-threshold (SPOT) thresholds (mtadgat_spot.hip; the fit and the step are in mtadgat_spot.h) ----
+// sorted[rank] of every column of an (n, d) array by the exact radix select of mtadgat_evalcol.hip: *ord_dev points at (d) floats
+// inside the scratch (column_rank_scratch(d) bytes, 16-byte aligned)
+size_t column_rank_scratch(int d);
+int launch_column_rank(const float* a_dev, long n, int d, long ld, long rank, void* scratch_dev, const float** ord_dev, hipStream_t s);
+// columns[j] (or j when null) of dst <- the same column of src, or src's only column when it has one; both with rings of P
+// write_header: dst is new and takes src's header (with its own column count) before all its columns
+int launch_spot_copy(void* dst, long dstS, const void* src, long srcS, long P, const long* columns, long n, hipStream_t s, int write_header = 0);
 
 }  // namespace mtadgat

@@ -11,10 +11,13 @@
 //       columns in ascending order, then a butterfly over the lanes -- and round the mean once to float32.  The moving average, the
 //       threshold compare and the event state machine then advance by one sample, wave-uniform; lane 0 stores.  Rows are walked in
 //       order, so the bits depend on the data and on the order of pushes per stream only, not on how rows are cut into pushes.
-//       The kernel is the only writer of the slots: it advances the row counter last.
+//       The kernel is the only writer of the slots: it advances the row counter last.  Its second instance, k_stream_score<true>,
+//       takes each row's threshold from the stream's column of a SPOT state (mtadgat_spot.h: spot_step, after the smoothing) and
+//       advances that column too; the fixed-threshold instance compiles to the code it had before the variant existed.
 //   k_stream_flush: the still-open event of each selected stream, and / or the stream's reset to its initial state (ring zeroed).
 // No atomics.  A stream index outside [0, S) writes "nothing here" (NaN / -1 / 0) and touches no state.
 #include "mtadgat_device.h"
+#include "mtadgat_spot.h"
 
 namespace mtadgat {
 
@@ -123,19 +126,23 @@ __device__ __forceinline__ void put_closed(const StreamOut& o, long at, const Cl
 }  // namespace
 
 // grid (ceil(n / 4)) x 256 threads: one wave per selected stream
+template <bool SPOT>
 __global__ void __launch_bounds__(256) k_stream_score(StreamPtrs p, StreamGeom g, const float* __restrict__ rows,
                                                        const long* __restrict__ streams, long n, long T, const float* __restrict__ preds,
                                                        const float* __restrict__ recons_last, double threshold,
-                                                       const double* __restrict__ thresholds, StreamOut o) {
+                                                       const double* __restrict__ thresholds, StreamOut o, StreamSpot sp) {
     const long j = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (j >= n) return;
     const long s = stream_of(streams, j);
     const int d = (int)g.d;
     const float nanf32 = __builtin_nanf("");
-    if (!geom_matches(p.hd, g) || s < 0 || s >= g.S || T > p.hd->max_block) {
+    if (!geom_matches(p.hd, g) || s < 0 || s >= g.S || T > p.hd->max_block ||
+        (SPOT && !spot_header_matches(static_cast<const SpotHeader*>(sp.state), g.S, sp.max_peaks))) {
         for (long t = 0; t < T; ++t) {
             const long at = j * T + t;
+            if constexpr (SPOT)
+                if (lane == 0 && sp.thresholds_out) sp.thresholds_out[at] = __builtin_nan("");
             if (o.per_dim)
                 for (int col = lane; col < d; col += 64) o.per_dim[at * d + col] = nanf32;
             if (lane == 0) {
@@ -149,6 +156,21 @@ __global__ void __launch_bounds__(256) k_stream_score(StreamPtrs p, StreamGeom g
     const StreamHeader hd = *p.hd;
     StreamSlot sl = p.slots[s];                                 // wave-uniform copy; lane 0 stores it back
     const double thr = thresholds ? thresholds[s] : threshold;
+    // the stream's SPOT column: a wave-uniform copy like the slot; lane 0 stores it back
+    SpotCol sc{};
+    SpotCol* spot_cols = nullptr;
+    double* spot_ring = nullptr;
+    double spot_q = 0.0;
+    bool spot_adaptive = false;
+    if constexpr (SPOT) {
+        char* sb = static_cast<char*>(sp.state);
+        const SpotHeader* sh = reinterpret_cast<const SpotHeader*>(sb);
+        spot_cols = reinterpret_cast<SpotCol*>(sb + spot_cols_offset());
+        spot_ring = reinterpret_cast<double*>(sb + spot_ring_offset(g.S)) + s * sp.max_peaks;
+        spot_q = sh->q;
+        spot_adaptive = sh->dynamic != 0;
+        sc = spot_cols[s];
+    }
     for (long t = 0; t < T; ++t) {
         const long at = j * T + t;
         const long k = sl.count + t;                            // this row's number in its stream
@@ -165,6 +187,7 @@ __global__ void __launch_bounds__(256) k_stream_score(StreamPtrs p, StreamGeom g
         float score = (float)(wave_sum(acc) / (double)d);
         Closed closed = no_event();
         bool flag = false;
+        double compared = __builtin_nan("");                    // SPOT: the threshold this row met
         if (scored) {
             const long i = k - g.W;                             // score index, as in anomaly_scores / anomaly_events
             if (hd.smooth) {
@@ -172,7 +195,12 @@ __global__ void __launch_bounds__(256) k_stream_score(StreamPtrs p, StreamGeom g
                 sl.den = 1.0 + hd.decay * sl.den;
                 score = (float)(sl.num / sl.den);
             }
-            flag = (double)score > thr;                         // NaN and equality are not flagged
+            if constexpr (SPOT) {
+                compared = sc.z;
+                flag = spot_step(sc, spot_ring, sp.max_peaks, spot_q, spot_adaptive, (double)score, lane);
+            } else {
+                flag = (double)score > thr;                     // NaN and equality are not flagged
+            }
             if (flag) {
                 if (!sl.ev_open) {
                     sl.ev_open = 1;
@@ -201,12 +229,16 @@ __global__ void __launch_bounds__(256) k_stream_score(StreamPtrs p, StreamGeom g
             if (o.scores) o.scores[at] = score;
             if (o.flags) o.flags[at] = flag ? 1 : 0;
             put_closed(o, at, closed);
+            if constexpr (SPOT)
+                if (sp.thresholds_out) sp.thresholds_out[at] = compared;
         }
     }
     // the forecast of the row after this push's last one (a wave runs in lockstep: every read of the old values is done)
     for (int col = lane; col < d; col += 64) p.pending[s * d + col] = preds[(j * T + T - 1) * d + col];
     sl.count += T;
     if (lane == 0) p.slots[s] = sl;
+    if constexpr (SPOT)
+        if (lane == 0) spot_cols[s] = sc;
 }
 
 // grid (ceil(n / 4)) x 256 threads: one wave per selected stream; out arrays are (n)
@@ -249,9 +281,15 @@ int launch_stream_stage(void* state, const StreamGeom& g, const float* rows, con
 }
 
 int launch_stream_score(void* state, const StreamGeom& g, const float* rows, const long* streams, long n, long T, const float* preds,
-                        const float* recons_last, double threshold, const double* thresholds, const StreamOut& out, hipStream_t s) {
-    hipLaunchKernelGGL(k_stream_score, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, stream_ptrs(state, g), g, rows, streams, n, T, preds,
-                       recons_last, threshold, thresholds, out);
+                        const float* recons_last, double threshold, const double* thresholds, const StreamOut& out, hipStream_t s,
+                        const StreamSpot* spot) {
+    const dim3 grid((unsigned)((n + 3) / 4));
+    if (spot)
+        hipLaunchKernelGGL(k_stream_score<true>, grid, dim3(256), 0, s, stream_ptrs(state, g), g, rows, streams, n, T, preds, recons_last,
+                           threshold, thresholds, out, *spot);
+    else
+        hipLaunchKernelGGL(k_stream_score<false>, grid, dim3(256), 0, s, stream_ptrs(state, g), g, rows, streams, n, T, preds, recons_last,
+                           threshold, thresholds, out, StreamSpot{});
     return (int)hipGetLastError();
 }
 

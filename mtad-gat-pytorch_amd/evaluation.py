@@ -25,8 +25,14 @@ From the thresholded scores to alarms (csrc/mtadgat_events.hip, tests/test_gpu_e
   anomaly_events                    the three together: the event table of a score array, in score-index space
   explain_events                    model.score_attribution at the events' peaks, with per-feature and per-lag marginals
 
-POT (`pot_eval`: SPOT's Grimshaw fit, spot.py) is not ported: it is a sequential scalar algorithm over the
-peaks only; the reference's implementation runs unchanged on `scores.cpu().numpy()`.
+Peaks-over-threshold thresholds, static and adaptive (csrc/mtadgat_spot.hip and mtadgat_spot.h, tests/test_gpu_spot.py):
+  spot_calibrate / spot_run         SPOT (Siffer et al., KDD 2017) for every column of a score matrix at once: one wave per column
+                                    fits the generalized Pareto tail of the column's excesses in float64; the state stays on the
+                                    device and also serves streaming.StreamScorer as a per-stream adaptive threshold
+  pot_eval                          the reference's third threshold method beside epsilon_eval and bf_search (`--dynamic_pot` with
+                                    dynamic=True)
+The fit follows the paper, not the reference's vendored spot.py (its optimiser-based root search cannot be reproduced bit for
+bit): tests/spot_refs.py is the specification, csrc/mtadgat_spot.h spells it out.
 """
 import ctypes
 import math
@@ -65,6 +71,16 @@ def _lib():
         lib.mtadgat_eval_run_stats_scratch.restype = sz
         lib.mtadgat_eval_run_stats.argtypes = [vp, i64, vp, vp, i64, vp, ci, i64, vp, ci, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.mtadgat_eval_first_hit.argtypes = [vp, vp, i64, f64, ci, vp, vp, i64, vp, vp]
+        u64p = ctypes.POINTER(ctypes.c_double)
+        lib.mtadgat_spot_state_bytes.argtypes = [i64, i64]
+        lib.mtadgat_spot_state_bytes.restype = sz
+        lib.mtadgat_spot_calibrate_scratch.argtypes = [i64, i64]
+        lib.mtadgat_spot_calibrate_scratch.restype = sz
+        lib.mtadgat_spot_calibrate.argtypes = [vp, i64, i64, i64, f64, f64, i64, ci, vp, vp, sz, vp]
+        lib.mtadgat_spot_run.argtypes = [vp, i64, i64, vp, i64, i64, vp, vp, vp]
+        lib.mtadgat_spot_read.argtypes = [vp, i64, i64, u64p, vp]
+        lib.mtadgat_spot_copy.argtypes = [vp, i64, vp, i64, i64, vp, i64, ci, vp]
+        lib.mtadgat_spot_fit_host.argtypes = [u64p, i64, i64, i64, f64, f64, u64p]
         lib.mtadgat_last_error.restype = ctypes.c_char_p
         lib._eval_bound = True
     return lib
@@ -357,8 +373,138 @@ def bf_search(score, label, start, end=None, step_num=1, display_freq=1, verbose
 _sweep = bf_search       # predict_anomalies has a keyword of that name
 
 
+# ---- peaks over threshold ----------------------------------------------------------------------------------------------------------
+class SpotState:
+    """The device-resident SPOT state of `n_columns` score series (made by spot_calibrate): per column the initial threshold t, the
+    alarm threshold z, the counts n and Nt, the fitted tail (gamma, sigma) and a ring of its most recent `max_peaks` excesses.
+    The ring is this package's own bound -- Nt counts every excess, the fit sees only the stored ones; until the ring wraps this
+    is SPOT's Algorithm 1.  spot_run and a StreamScorer advance the state in place."""
+
+    def __init__(self, buf, n_columns, max_peaks, q, level, dynamic):
+        self.buf, self.n_columns, self.max_peaks = buf, int(n_columns), int(max_peaks)
+        self.q, self.level, self.dynamic = float(q), float(level), bool(dynamic)
+
+    @property
+    def device(self):
+        return self.buf.device
+
+    def data_ptr(self):
+        return self.buf.data_ptr()
+
+    def read(self):
+        """The per-column values as float64 numpy arrays: a dict of t, z, n, Nt, gamma, sigma.  Synchronises."""
+        lib = _lib()
+        out = np.empty((self.n_columns, 6), dtype=np.float64)
+        with torch.cuda.device(self.device):
+            rc = lib.mtadgat_spot_read(self.data_ptr(), self.n_columns, self.max_peaks, out.ctypes.data_as(_c_double_p), _stream(self.buf))
+        if rc != 0:
+            _fail(lib, rc, "spot_read")
+        return {name: out[:, k].copy() for k, name in enumerate(("t", "z", "n", "Nt", "gamma", "sigma"))}
+
+    def thresholds(self):
+        """The current alarm threshold z of every column: (n_columns,) float64 on the state's device."""
+        return torch.from_numpy(self.read()["z"]).to(self.device)
+
+    def clone(self):
+        """An independent copy of the state as it stands."""
+        return SpotState(self.buf.clone(), self.n_columns, self.max_peaks, self.q, self.level, self.dynamic)
+
+    def expand(self, n_columns):
+        """A new state of `n_columns` columns that each start as this state's ONE column: one training series serving many streams."""
+        if self.n_columns != 1:
+            raise ValueError(f"expand needs a state of one column, this one has {self.n_columns}")
+        if int(n_columns) != n_columns or n_columns < 1:
+            raise ValueError(f"n_columns must be a positive integer, got {n_columns!r}")
+        lib = _lib()
+        nbytes = lib.mtadgat_spot_state_bytes(int(n_columns), self.max_peaks)
+        if nbytes == 0:
+            raise ValueError(f"{n_columns} columns are refused")
+        buf = torch.zeros((nbytes + 7) // 8, dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = lib.mtadgat_spot_copy(buf.data_ptr(), int(n_columns), self.data_ptr(), 1, self.max_peaks, None, int(n_columns), 1,
+                                       _stream(self.buf))
+        if rc != 0:
+            _fail(lib, rc, "spot_copy")
+        return SpotState(buf, n_columns, self.max_peaks, self.q, self.level, self.dynamic)
+
+
+def spot_calibrate(init_scores, q=1e-3, level=0.98, max_peaks=1024, dynamic=True):
+    """Calibrate SPOT on `init_scores`, an (n_init,) or (n_init, S) GPU tensor (read as float32 like every score array here), one
+    independent problem per column: the initial threshold t = sorted[int(level * n_init)], the excesses over it in row order (the last
+    `max_peaks` of them are kept), and the first generalized Pareto fit, whose q-quantile is the alarm threshold z.  dynamic=False
+    makes a state that spot_run and StreamScorer never change (the reference's static POT).  Returns a SpotState.
+    The fit is the package's own definition from the paper (tests/spot_refs.py is its specification), not the reference's spot.py.
+    Raises ValueError for q or level outside (0, 1), max_peaks outside [8, 4096] or n_init < 16, and RuntimeError naming the
+    column when a column has fewer than 8 excesses, holds a NaN or has a non-positive mean excess."""
+    lib = _lib()
+    if not (0.0 < q < 1.0) or not (0.0 < level < 1.0):
+        raise ValueError(f"q and level must lie in (0, 1), got {q!r}, {level!r}")
+    if int(max_peaks) != max_peaks or not 8 <= max_peaks <= 4096:
+        raise ValueError(f"max_peaks must be an integer in [8, 4096], got {max_peaks!r}")
+    e = _dev2d(init_scores, "init_scores")
+    n, S = e.shape
+    if n < 16:
+        raise ValueError(f"calibration needs at least 16 scores, got {n}")
+    nbytes = lib.mtadgat_spot_state_bytes(S, int(max_peaks))
+    sbytes = lib.mtadgat_spot_calibrate_scratch(n, S)
+    if nbytes == 0 or sbytes == 0:
+        raise ValueError(f"{S} columns are refused (at most 65536 per call)")
+    buf = torch.zeros((nbytes + 7) // 8, dtype=torch.float64, device=e.device)
+    scratch = _native._empty((sbytes + 7) // 8, dtype=torch.float64, device=e.device)
+    with torch.cuda.device(e.device):
+        rc = lib.mtadgat_spot_calibrate(e.data_ptr(), n, S, e.stride(0), float(q), float(level), int(max_peaks), 1 if dynamic else 0,
+                                        buf.data_ptr(), scratch.data_ptr(), scratch.numel() * 8, _stream(e))
+    if rc != 0:
+        _fail(lib, rc, "spot_calibrate")
+    return SpotState(buf, S, max_peaks, q, level, dynamic)
+
+
+def spot_run(state, scores):
+    """The SPOT step over the rows of `scores`, (n,) or (n, S) on the GPU with S = state.n_columns, in order.  Returns (thresholds,
+    flags): (n, S) float64 -- what each score was compared against, the column's z BEFORE the step -- and (n, S) uint8
+    (score > threshold; NaN is not flagged and changes nothing); 1-D for 1-D scores.  The state is advanced in place, so a second call
+    continues where the first stopped; a state calibrated with dynamic=False never changes."""
+    lib = _lib()
+    if not isinstance(state, SpotState):
+        raise TypeError("state must be a SpotState (spot_calibrate)")
+    one_d = isinstance(scores, torch.Tensor) and scores.ndim == 1
+    x = _dev2d(scores, "scores")
+    n, S = x.shape
+    if S != state.n_columns or x.device != state.device:
+        raise ValueError(f"scores have {S} columns on '{x.device}', the state {state.n_columns} on '{state.device}'")
+    thr = _native._empty((n, S), dtype=torch.float64, device=x.device)
+    flags = torch.empty((n, S), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = lib.mtadgat_spot_run(state.data_ptr(), S, state.max_peaks, x.data_ptr(), n, x.stride(0), thr.data_ptr(), flags.data_ptr(), _stream(x))
+    if rc != 0:
+        _fail(lib, rc, "spot_run")
+    return (thr.reshape(-1), flags.reshape(-1)) if one_d else (thr, flags)
+
+
+def pot_eval(init_scores, scores, labels, q=1e-3, level=0.98, dynamic=False, max_peaks=1024):
+    """The reference's pot_eval on the device, in epsilon_eval's shape: SPOT calibrated on the 1-D `init_scores` (the training
+    scores), applied to `scores`, point-adjusted metrics against `labels` (None: the threshold only).
+    Static: the one threshold z of the calibration, through point_adjust_counts.  dynamic (`--dynamic_pot`): the adaptive run's
+    flags through the same point-adjust pass, `threshold` being the mean of the per-row thresholds.
+    The fit is the package's own definition (see spot_calibrate), so thresholds differ from spot.py's in the last digits."""
+    init = _dev1d(init_scores, torch.float32, "init_scores")
+    s = _dev1d(scores, torch.float32, "scores")
+    state = spot_calibrate(init, q=q, level=level, max_peaks=max_peaks, dynamic=dynamic)
+    extra = {"q": q, "level": level, "dynamic": bool(dynamic)}
+    if not dynamic:
+        z = float(state.read()["z"][0])
+        if labels is None:
+            return dict(threshold=z, **extra)
+        return _result(point_adjust_counts(s, labels, [z])[0], z, **extra)
+    thr, flags = spot_run(state, s)
+    z = float(thr.mean().item())
+    if labels is None:
+        return dict(threshold=z, **extra)
+    return _result(point_adjust_counts(flags.float(), labels, [0.5])[0], z, **extra)
+
+
 def predict_anomalies(model, train, test, labels=None, target_dims=None, gamma=1.0, scale_scores=False, use_mov_av=False, reg_level=1,
-                      bf_search=None, events=None):
+                      bf_search=None, events=None, pot=None):
     """What Predictor.predict_anomalies (prediction.py:106-165) derives from a train and a test series, with every score array
     staying on the device.  train, test: device-resident (N, F) series; labels: the test labels for rows window_size.. (one
     per score) or None; bf_search: (start, end, step_num) for the best-F1 sweep, run when labels are given too.
@@ -371,8 +517,9 @@ def predict_anomalies(model, train, test, labels=None, target_dims=None, gamma=1
       bf_result                   bf_search(test_scores, labels, *bf_search), or None without labels or bf_search
       events                      only with events=dict(merge_gap=, min_length=, top_k=) (any subset): anomaly_events of test_scores
                                   against find_epsilon(train_scores, reg_level), with test_per_dim, the feature thresholds and the labels
-    Not included: POT (`pot_eval`), a sequential scalar fit that runs unchanged on `test_scores.cpu().numpy()` (see the module
-    docstring); and `adjust_anomaly_scores` for MSL / SMAP, which needs the datasets' channel metadata files and the reference
+      pot_result                  only with pot=dict(q=, level=, dynamic=) (any subset): pot_eval(train_scores, test_scores, labels, ...),
+                                  SPOT calibrated on the training scores; without labels its threshold only
+    Not included: `adjust_anomaly_scores` for MSL / SMAP, which needs the datasets' channel metadata files and the reference
     source to pin its behaviour, neither of which this package ships."""
     train_scores, train_per_dim = model.anomaly_scores(train, target_dims=target_dims, gamma=gamma, scale_scores=scale_scores,
                                                        use_mov_av=use_mov_av)
@@ -387,6 +534,11 @@ def predict_anomalies(model, train, test, labels=None, target_dims=None, gamma=1
     thr, preds = feature_predictions(train_per_dim, test_per_dim, reg_level)
     out = {"epsilon_result": eps_result, "bf_result": bf_result, "feature_thresholds": thr, "train_scores": train_scores,
            "test_scores": test_scores, "test_per_dim": test_per_dim, "feature_preds": preds}
+    if pot is not None:
+        unknown = set(pot) - {"q", "level", "dynamic"}
+        if unknown:
+            raise ValueError(f"pot takes q, level and dynamic, got {sorted(unknown)}")
+        out["pot_result"] = pot_eval(train_scores, test_scores, labels, **pot)
     if events is not None:
         unknown = set(events) - {"merge_gap", "min_length", "top_k"}
         if unknown:

@@ -16,12 +16,17 @@ the histories, run the model on the windows that end at the new rows (forecast a
 state machines.  The only host read of a push is the 8-byte weight fingerprint every `MTAD_GAT` entry point waits for
 (`model._checked`); it sits between the forward and the state update, so a repeated forward (weights edited in place) never
 advances a stream twice.
+
+The threshold may adapt per stream: pass an `evaluation.SpotState` (spot_calibrate on training scores) as `threshold` and every
+stream runs SPOT's step on its own (smoothed) score inside the same kernel -- its excesses, its generalized Pareto fit and its alarm
+threshold live in a second device allocation, and `out["thresholds"]` reports what each row was compared against.
 """
 import ctypes
 
 import torch
 
 import _native
+from evaluation import SpotState
 
 
 class _Outputs(ctypes.Structure):
@@ -48,6 +53,9 @@ def _lib():
         lib.mtadgat_stream_flush.argtypes = [vp, vp, i64, i64, vp, i64, ci, out_p, vp]
         lib.mtadgat_stream_window_start.argtypes = [i64, i64, i64, i64]
         lib.mtadgat_stream_window_start.restype = i64
+        lib.mtadgat_stream_update_spot.argtypes = [vp, vp, i64, i64, vp, vp, vp, vp, i64, i64, ci, vp, i64, vp, out_p, vp]
+        lib.mtadgat_stream_push_spot.argtypes = [vp, vp, i64, i64, vp, vp, i64, i64, vp, i64, vp, out_p, vp, sz, vp]
+        lib.mtadgat_stream_reset_spot.argtypes = [vp, vp, i64, i64, vp, vp, i64, i64, vp, i64, vp]
         lib._stream_bound = True
     return lib
 
@@ -62,7 +70,10 @@ class StreamScorer:
     """Row-by-row anomaly scoring of `n_streams` independent series with one trained `model` (on the GPU, in eval()).
 
     threshold       a float, or an (n_streams,) tensor of per-stream thresholds: flag = float64(score) > threshold (NaN and
-                    equality are not flagged, as evaluation.flag_runs)
+                    equality are not flagged, as evaluation.flag_runs); or an evaluation.SpotState of one column (every stream
+                    starts from it) or n_streams columns: the scorer clones it, each stream then runs SPOT's step on its score
+                    (after the smoothing) -- push / update also return "thresholds", (n, T) float64, what each row was compared
+                    against (NaN for the warm-up rows) --, reset() restores the calibrated state, spot_state() is the live one
     target_dims     as MTAD_GAT.anomaly_scores: None (all features), an int or a list of series columns, one per out_dim
     gamma           weight of the reconstruction error in the score
     smoothing_span  None, or the span (>= 1) of the moving average of the score (evaluation.moving_average, per stream)
@@ -97,7 +108,12 @@ class StreamScorer:
             if center.numel() != d or spread.numel() != d:
                 raise ValueError(f"scale must be a (center, spread) pair of ({d},) values")
         thr = None
-        if isinstance(threshold, torch.Tensor) and threshold.dim() > 0:
+        spot = threshold if isinstance(threshold, SpotState) else None
+        if spot is not None:
+            if spot.n_columns not in (1, n_streams):
+                raise ValueError(f"a SpotState of {spot.n_columns} columns for {n_streams} streams: it needs one column or one per stream")
+            threshold = 0.0
+        elif isinstance(threshold, torch.Tensor) and threshold.dim() > 0:
             if threshold.numel() != n_streams:
                 raise ValueError(f"{threshold.numel()} thresholds for {n_streams} streams")
             thr = threshold
@@ -113,6 +129,12 @@ class StreamScorer:
                            int(min_length), torch.tensor(dims, dtype=torch.int32), center, spread)
         self._state = None
         self._ws = None
+        self._spot = self._spot_calibrated = None
+        if spot is not None:
+            if spot.device != self.device:
+                raise ValueError(f"the SpotState is on '{spot.device}', the model on '{self.device}'")
+            self._spot_calibrated = spot.clone()
+            self._spot = spot.expand(self.n_streams) if spot.n_columns == 1 and self.n_streams != 1 else spot.clone()
 
     # -- plumbing ------------------------------------------------------------------------------------------------------------
     def _stream(self):
@@ -183,15 +205,27 @@ class StreamScorer:
             out[name] = torch.empty((n, T), dtype=dtype, device=dev)
         return out, _Outputs(**{k: v.data_ptr() for k, v in out.items()})
 
+    def spot_state(self):
+        """The live SpotState the streams advance (None for a scorer with fixed thresholds)."""
+        return self._spot
+
     def _thr_ptr(self):
         return self._thresholds.data_ptr() if self._thresholds is not None else None
 
     def _commit(self, eng, preds, last, rows, st, n, T, staged):
         out, c_out = self._outputs(n, T)
         with torch.cuda.device(self.device):
-            rc = _lib().mtadgat_stream_update(eng.handle, self._state.data_ptr(), self.n_streams, self.max_block, preds, last, rows.data_ptr(),
-                                              st.data_ptr() if st is not None else None, n, T, 1 if staged else 0, self.threshold,
-                                              self._thr_ptr(), ctypes.byref(c_out), self._stream())
+            if self._spot is not None:
+                thr = _native._empty((n, T), dtype=torch.float64, device=self.device)
+                rc = _lib().mtadgat_stream_update_spot(eng.handle, self._state.data_ptr(), self.n_streams, self.max_block, preds, last,
+                                                       rows.data_ptr(), st.data_ptr() if st is not None else None, n, T, 1 if staged else 0,
+                                                       self._spot.data_ptr(), self._spot.max_peaks, thr.data_ptr(), ctypes.byref(c_out),
+                                                       self._stream())
+                out["thresholds"] = thr
+            else:
+                rc = _lib().mtadgat_stream_update(eng.handle, self._state.data_ptr(), self.n_streams, self.max_block, preds, last,
+                                                  rows.data_ptr(), st.data_ptr() if st is not None else None, n, T, 1 if staged else 0,
+                                                  self.threshold, self._thr_ptr(), ctypes.byref(c_out), self._stream())
         if rc != 0:
             self._fail(rc, "stream_update")
         return out
@@ -253,17 +287,26 @@ class StreamScorer:
         c_out = _Outputs(**{k: v.data_ptr() for k, v in out.items()})
         with torch.cuda.device(self.device):
             rc = _lib().mtadgat_stream_flush(eng.handle, self._state.data_ptr(), self.n_streams, self.max_block,
-                                             st.data_ptr() if st is not None else None, n, 1 if reset else 0, ctypes.byref(c_out), self._stream())
+                                             st.data_ptr() if st is not None else None, n, 1 if reset and self._spot is None else 0,
+                                             ctypes.byref(c_out), self._stream())
         if rc != 0:
             self._fail(rc, "stream_flush")
+        if reset and self._spot is not None:
+            self.reset(streams)
         return out
 
     def reset(self, streams=None):
-        """Return the selected streams (None: all) to their initial state: no rows seen, no open event."""
+        """Return the selected streams (None: all) to their initial state: no rows seen, no open event, and -- with a SpotState --
+        the calibrated thresholds, counts and excesses."""
         st, n = self._select(streams)
         eng = self._engine()
+        sp = st.data_ptr() if st is not None else None
         with torch.cuda.device(self.device):
-            rc = _lib().mtadgat_stream_flush(eng.handle, self._state.data_ptr(), self.n_streams, self.max_block,
-                                             st.data_ptr() if st is not None else None, n, 1, None, self._stream())
+            if self._spot is not None:
+                cal = self._spot_calibrated
+                rc = _lib().mtadgat_stream_reset_spot(eng.handle, self._state.data_ptr(), self.n_streams, self.max_block, self._spot.data_ptr(),
+                                                      cal.data_ptr(), cal.n_columns, cal.max_peaks, sp, n, self._stream())
+            else:
+                rc = _lib().mtadgat_stream_flush(eng.handle, self._state.data_ptr(), self.n_streams, self.max_block, sp, n, 1, None, self._stream())
         if rc != 0:
             self._fail(rc, "stream_flush")
