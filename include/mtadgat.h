@@ -163,6 +163,36 @@ int mtadgat_read_packed(mtadgat_handle h, float* dst_host, int64_t n_floats, voi
  *   out[7]  the stack takes the small-batch kernels (what the heads and the backward ask; equals out[0] in {1, 2} for layer 0)
  * Returns 0, or MTADGAT_ERR_INVALID. */
 int mtadgat_gru_route(mtadgat_handle h, int stack, int layer, int64_t n, int training, int compute_units, int* out);
+/* Test hook (host only: needs neither a GPU nor loaded weights): which kernels run the front end -- window convolution, temporal
+ * and feature attention layer -- of one call on n windows (one piece of a forward()).  The answer is the one the library's own
+ * dispatch uses under the handle's current mtadgat_set_precision mode and "conv_kernel" / "gat_kernel" / "conv_fused" /
+ * "conv_shared" / "rowgemm_kernel" options.
+ *   kind    0 a whole inference forward (h_cat only, output range recorded; a model with an un-fused layer gets kind 1),
+ *           1 the un-fused inference forward and mtadgat_gat (xc, xc^T, h_cat), 2 the training forward, 3 attention maps (fp32
+ *           arithmetic whatever the mode), 4 mtadgat_conv (y only, no layers)
+ *   source  0 float32 windows, 1 bfloat16 windows, 2 a series with stride 1 and no `starts`, 3 any other series
+ *   facts   bit 0: the node rows the fused layers read are 16-byte aligned; bit 1: their row stride is a multiple of 4 floats and
+ *           at least the node columns rounded up to 4; bit 2: h_cat is 16-byte aligned (all set in the library's own calls)
+ * Writes 14 ints:
+ *   out[0]  convolution: 0 none (inside the temporal layer's k_gath), 1 k_conv_win on fp16 pieces, 2 shared rows of a series
+ *           (three launch_conv calls and the row placement), 3 launch_conv
+ *   out[1]  operands of that launch_conv: 0 fp32, 1 the bf16 pack, 2 three bf16 pieces (rows too long for LDS staging)
+ *   out[2]  the convolution's split packs are needed (derived on first use after an upload)
+ *   out[3]  the convolution's output range is recorded for the kernels behind it
+ *   out[4 .. 9) the temporal layer, out[9 .. 14) the feature layer:
+ *     [0]  0 none, 1 fused k_gat alone, 2 k_gath with k_gat behind it as the device-side fallback, 3 row GEMM projection +
+ *          k_gat_wide, 4 row GEMM projection + k_attend
+ *     [1]  operands of the projection: 0 fp32, 1 bf16, 2 three bf16 pieces
+ *     [2]  k_gat is handed the two-fp16-piece pack beside its bf16 pieces (never for a GATv2 layer without k_gath: its fp16
+ *          pack is in k_gath's column order)
+ *     [3]  the un-fused projection is the split row GEMM
+ *     [4]  the layer's split packs are needed
+ * Returns 0, or MTADGAT_ERR_INVALID. */
+int mtadgat_front_route(mtadgat_handle h, int kind, int source, int64_t n, int facts, int* out);
+/* Test hook (host only): does a row GEMM over `rows` rows take split-bf16 operands (k_rowgemm_x3) under the handle's precision mode
+ * and "rowgemm_kernel" option?  has_pack: a split pack was planned for its weights; backward: a site of mtadgat_backward (there
+ * "rowgemm_kernel" = 2 forces the split pack in every mode, in the forward only in the "fp32" mode).  Returns 1 / 0, negative: error. */
+int mtadgat_rowgemm_split(mtadgat_handle h, int has_pack, int64_t rows, int backward);
 
 /* Arithmetic of the inference entry points (forward / forward_series / stage calls):
  *   0 (default of a new handle)  fp32 operands on the exact fp32 MFMA: <= 1e-5 of the reference's float32 forward

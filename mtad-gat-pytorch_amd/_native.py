@@ -37,6 +37,15 @@ PROFILE_SLOTS = 6
 GRU_ROUTE_FIELDS = ("first", "fallback", "build", "two", "hoist", "split_packs", "fc_rides", "small_stack")
 GRU_KERNELS = ("none", "k_gru1", "k_gru16", "k_gru_split", "k_gru_split_x3", "k_gru_cm", "k_gru")
 GRU_BUILDS = ("fp32", "bf16", "x3_hi", "x3_lo")
+# mtadgat_front_route: the integers it writes (include/mtadgat.h) and the codes of csrc/mtadgat_host.h
+FRONT_ROUTE_FIELDS = ("conv", "conv_build", "conv_split_pack", "range",
+                      "temp_kernel", "temp_build", "temp_fp16", "temp_split_gemm", "temp_split_pack",
+                      "feat_kernel", "feat_build", "feat_fp16", "feat_split_gemm", "feat_split_pack")
+FRONT_KINDS = ("forward", "forward_unfused", "train", "attention", "conv")
+FRONT_SOURCES = ("windows", "windows_bf16", "series_unit", "series")
+FRONT_CONVS = ("in_gath", "k_conv_win", "shared_rows", "launch_conv")
+FRONT_LAYERS = ("none", "k_gat", "k_gath+k_gat", "rowgemm+k_gat_wide", "rowgemm+k_attend")
+FRONT_BUILDS = ("fp32", "bf16", "x3")
 
 _c_float_p = ctypes.POINTER(ctypes.c_float)
 
@@ -90,6 +99,8 @@ def load_library():
     lib.mtadgat_read_packed.argtypes = [vp, vp, i64, vp]
     lib.mtadgat_derived_regions.argtypes = [vp, ctypes.POINTER(i64), ctypes.c_int]
     lib.mtadgat_gru_route.argtypes = [vp, ctypes.c_int, ctypes.c_int, i64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+    lib.mtadgat_front_route.argtypes = [vp, ctypes.c_int, ctypes.c_int, i64, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+    lib.mtadgat_rowgemm_split.argtypes = [vp, ctypes.c_int, i64, ctypes.c_int]
     lib.mtadgat_workspace_bytes.argtypes = [vp, i64]
     lib.mtadgat_workspace_bytes.restype = sz
     lib.mtadgat_set_precision.argtypes = [vp, ctypes.c_int]
@@ -452,6 +463,14 @@ class Engine:
         buf = (ctypes.c_int * 8)()
         _check(self.lib.mtadgat_gru_route(self.handle, stack, layer, n, int(training), compute_units, buf), "mtadgat_gru_route")
         return dict(zip(GRU_ROUTE_FIELDS, (int(v) for v in buf)))
+
+    def front_route(self, kind, source, n, facts=7):
+        """Which kernels run the convolution and the two attention layers of a call of FRONT_KINDS[kind] on n windows from
+        FRONT_SOURCES[source], under the current precision and options (host only): dict of the 14 integers of
+        mtadgat_front_route (include/mtadgat.h)."""
+        buf = (ctypes.c_int * 14)()
+        _check(self.lib.mtadgat_front_route(self.handle, kind, source, n, facts, buf), "mtadgat_front_route")
+        return dict(zip(FRONT_ROUTE_FIELDS, (int(v) for v in buf)))
 
     def load_weights(self, sd, device, allow_device_pack=True):
         """sd: reference-format state_dict (any device).  The first load packs on the host and uploads on the current

@@ -73,12 +73,14 @@ struct XSource {
     int64_t start0 = 0, stride = 1;
 };
 
-// the batch sizes / options at which the fused front end's convolution is the window-per-workgroup kernel on fp16 pieces
-// (precision mode 1 -- bf16 operands -- takes the same front end from 4096 windows: its fp16-piece kernels are faster than the bf16
-// builds of k_conv_lds / k_gat, 10.5 against 12.3 ms per 65 536 windows, and closer to the fp32 results; the recurrences stay bf16)
-static bool split_front(const Model& m, int64_t n) { return m.precision == 1 && n >= 4096 && m.conv_kernel == 0 && m.gat_kernel == 0; }
-static bool conv_win_selected(const Model& m, int64_t n) {
-    return (m.precision == 2 || split_front(m, n)) && m.conv_kernel != 1 && (n >= 4096 || m.conv_kernel == 2);
+// the facts of a call whose fused layers read node rows v (row stride ldv, `cols` node columns); hcat: where the convolution writes
+FrontCall front_call(FrontKind kind, const XSource& src, const float* v, int ldv, int cols, const float* hcat) {
+    FrontCall c;
+    c.kind = kind;
+    if (src.gather) c.source = (!src.starts && src.stride == 1) ? SRC_SERIES_UNIT : SRC_SERIES;
+    else c.source = src.x_bf16 ? SRC_WINDOWS_BF16 : SRC_WINDOWS;
+    c.rows_aligned = aligned16(v); c.ldv_fits = (ldv & 3) == 0 && round_up(cols, 4) <= ldv; c.hcat_aligned = aligned16(hcat);
+    return c;
 }
 
 // Round 6: the split packs are derived LAZILY, by the first launch that reads them after an upload.  Rounds 2-5 re-derived all of
@@ -120,12 +122,8 @@ int ensure_all_split(Model& m, hipStream_t s) {
         if (int rc = ensure(m, i, s)) return rc;
     return 0;
 }
-// geo (optional): the rows are cut into `geo_W`-row windows instead of the model's W-row ones (run_conv_shared)
-int run_conv(Model& m, const XSource& src, int64_t c0, int64_t n, float* xc, float* xct, float* hcat, float* y, hipStream_t s,
-             unsigned* vmax = nullptr, int64_t geo_W = 0, bool keep_vmax = false) {
-    Scope sc(m, S_CONV, s);
-    ConvArgs a{};
-    const int64_t Wk = geo_W ? geo_W : m.W;
+// where window c0 of the source starts, for the kernels that read the input themselves
+template <class A> void fill_source(const Model& m, const XSource& src, int64_t c0, A& a) {
     if (src.gather) {
         a.X = src.x; a.gather = 1;
         a.starts = src.starts ? reinterpret_cast<const long*>(src.starts + c0) : nullptr;
@@ -136,40 +134,42 @@ int run_conv(Model& m, const XSource& src, int64_t c0, int64_t n, float* xc, flo
         a.X = src.x + c0 * (int64_t)m.W * m.F;
     }
     a.x_bf16 = src.x_bf16;
+}
+// launch_conv's fp32 arguments for n windows of Wk rows from window c0 on; the caller sets the outputs
+ConvArgs conv_args(const Model& m, const XSource& src, int64_t c0, int64_t n, int64_t Wk) {
+    ConvArgs a{};
+    fill_source(m, src, c0, a);
     a.B = n; a.W = (int)Wk; a.F = m.F; a.Fp = m.Fp; a.taps = m.taps; a.pad = m.pad;
     a.Fq = m.Fp;
     a.Wp = reinterpret_cast<const f32x4*>(m.packed_dev + m.conv_w_off);
-    // bf16 operand build: inference forward only (hcat / y outputs), when the LDS-staged kernel applies
-    if (m.precision == 1 && !xc && !xct && (size_t)(32 + m.taps - 1) * (m.Fp16 + 4) * sizeof(float) <= 20 * 1024 &&
-        !(conv_win_selected(m, n) && !geo_W && hcat && !y)) {
-        a.bf16 = 1; a.Fq = m.Fp16;
-        a.Wp = reinterpret_cast<const f32x4*>(m.packed_dev + m.conv_w16_off);
-    }
-    // (split-bf16 operands were tried for the convolution as well: 3.36 vs 3.37 ms at the flagship shape -- it is bound by its
-    // staging and stores, not by the matrix pipe; the fp32 MFMA build stays)
     a.bias = m.packed_dev + m.conv_b_off;
-    a.NT = m.convNT;
-    a.XC = xc; a.XCT = xct; a.Wpad = m.Wp; a.HCAT = hcat; a.Dp = m.Dp; a.Y = y;
-    if (vmax) {
-        if (!keep_vmax) HIP_TRY(hipMemsetAsync(vmax, 0, sizeof(unsigned), s));
+    a.NT = m.convNT; a.Wpad = m.Wp; a.Dp = m.Dp;
+    return a;
+}
+// the convolution launch the route names (CONV_WIN, CONV_LAUNCH); vmax: where the range is recorded when the route says so
+int run_conv(Model& m, const FrontRoute& r, const XSource& src, int64_t c0, int64_t n, float* xc, float* xct, float* hcat, float* y,
+             hipStream_t s, unsigned* vmax = nullptr) {
+    Scope sc(m, S_CONV, s);
+    ConvArgs a = conv_args(m, src, c0, n, m.W);
+    a.XC = xc; a.XCT = xct; a.HCAT = hcat; a.Y = y;
+    if (r.range) {
+        HIP_TRY(hipMemsetAsync(vmax, 0, sizeof(unsigned), s));
         a.vmax = vmax;
     }
-    // mode 2, the fused front end's call (h_cat only) on whole windows: the window-per-workgroup kernel on fp16 pieces
-    if (conv_win_selected(m, n) && !geo_W && hcat && !xc && !xct && !y) {
-        ConvArgs b = a;
-        b.Fq = m.Fp16;
+    if (r.conv_split_pack)
         if (int rc_ = ensure(m, m.conv_split, s)) return rc_;
-        b.Wp = reinterpret_cast<const f32x4*>(m.packed_dev + m.conv_w2h_off);
-        b.wscale = m.packed_dev + m.conv_scale_off + 1;
-        if (conv_win_applies(b)) {
-            K_TRY(launch_conv_win(b, s), "conv (window per workgroup)");
-            return 0;
-        }
+    if (r.conv == CONV_WIN) {
+        a.Fq = m.Fp16;
+        a.Wp = reinterpret_cast<const f32x4*>(m.packed_dev + m.conv_w2h_off);
+        a.wscale = m.packed_dev + m.conv_scale_off + 1;
+        K_TRY(launch_conv_win(a, s), "conv (window per workgroup)");
+        return 0;
     }
-    // wide models (rows too long for the LDS-staged kernels): the straight-from-memory kernel on three bf16 pieces per operand
-    if (m.precision == 2 && !a.bf16 && !src.x_bf16 && m.conv_kernel != 1 && (n * Wk >= 65536 || m.conv_kernel == 2) &&
-        (size_t)(32 + m.taps - 1) * (m.Fp + 4) * sizeof(float) > 20 * 1024) {
-        if (int rc_ = ensure(m, m.conv_split, s)) return rc_;
+    if (r.conv != CONV_LAUNCH) return fail(MTADGAT_ERR_INVALID, "internal: front route names no convolution launch");
+    if (r.conv_build == FRONT_BF16) {
+        a.bf16 = 1; a.Fq = m.Fp16;
+        a.Wp = reinterpret_cast<const f32x4*>(m.packed_dev + m.conv_w16_off);
+    } else if (r.conv_build == FRONT_X3) {
         a.Wp3 = reinterpret_cast<const f32x4*>(m.packed_dev + m.conv_w3_off);
         a.Fq = m.Fp16;
     }
@@ -177,34 +177,29 @@ int run_conv(Model& m, const XSource& src, int64_t c0, int64_t n, float* xc, flo
     return 0;
 }
 
-// The convolution of n stride-1 windows of a series without computing a shared row more than once (SURVEY section 8f row 3:
-// interior rows are shared by up to W windows; the per-window zero padding, modules.py:14,20, makes the first / last `pad`
-// rows of every window its own).  Three launches of the SAME kernel -- so every value equals the per-window launch's, bit
+// CONV_SHARED: the convolution of n stride-1 windows of a series without computing a shared row more than once (SURVEY section
+// 8f row 3: interior rows are shared by up to W windows; the per-window zero padding, modules.py:14,20, makes the first / last
+// `pad` rows of every window its own).  Three launches of the SAME kernel -- so every value equals the per-window launch's, bit
 // for bit: the segment as one (n + W - 1)-row window, the windows' first and last 2 pad rows as 2 pad-row windows -- and a
-// copy that places the rows into h_cat.  Applies when the LDS-staged kernel does (it records the output range).
-bool conv_shared_applies(const Model& m, const XSource& src, int64_t n) {
-    if (!src.gather || src.starts || src.stride != 1 || n < 1024 || m.precision == 1 || src.x_bf16) return false;   // (the bf16 build writes h_cat only)
-    // the window-per-workgroup kernel reads its window out of the series itself (the rows it re-reads are L2 hits) and is the
-    // faster of the two where it runs; taking it here also keeps forward_series == forward on the stacked windows bit for bit
-    if (conv_win_selected(m, n) && m.conv_shared != 1) {
-        ConvArgs b{};
-        b.F = m.F; b.Fp = m.Fp; b.Fq = m.Fp16; b.taps = m.taps; b.pad = m.pad; b.W = m.W; b.Dp = m.Dp; b.NT = m.convNT;
-        b.HCAT = m.packed_dev; b.wscale = m.packed_dev;      // (only looked at for presence)
-        if (conv_win_applies(b)) return false;
-    }
-    if (m.taps != 2 * m.pad + 1 || m.pad < 1 || m.W < 4 * m.pad) return false;
-    return (size_t)(32 + m.taps - 1) * (m.Fp + 4) * sizeof(float) <= 20 * 1024;
-}
+// copy that places the rows into h_cat.
 int run_conv_shared(Model& m, const XSource& src, int64_t c0, int64_t n, float* hcat, float* cf, float* el, float* er, hipStream_t s,
                     unsigned* vmax) {
-    int rc;
     XSource seg = src;
     seg.start0 = src.start0 + c0; seg.stride = 1;
     const int64_t L = n + m.W - 1, EW = 2 * m.pad;
-    if ((rc = run_conv(m, seg, 0, 1, cf, nullptr, nullptr, nullptr, s, vmax, L))) return rc;
-    if ((rc = run_conv(m, seg, 0, n, el, nullptr, nullptr, nullptr, s, vmax, EW, true))) return rc;
+    HIP_TRY(hipMemsetAsync(vmax, 0, sizeof(unsigned), s));
+    auto rows = [&](int64_t nwin, int64_t Wk, float* out) {
+        Scope sc(m, S_CONV, s);
+        ConvArgs a = conv_args(m, seg, 0, nwin, Wk);
+        a.XC = out; a.vmax = vmax;
+        K_TRY(launch_conv(a, s), "conv");
+        return 0;
+    };
+    int rc;
+    if ((rc = rows(1, L, cf))) return rc;
+    if ((rc = rows(n, EW, el))) return rc;
     seg.start0 += m.W - EW;
-    if ((rc = run_conv(m, seg, 0, n, er, nullptr, nullptr, nullptr, s, vmax, EW, true))) return rc;
+    if ((rc = rows(n, EW, er))) return rc;
     Scope sc(m, S_CONV, s);
     K_TRY(launch_conv_scatter(cf, el, er, hcat, n, m.W, m.F, m.Fp, m.Dp, m.pad, s), "conv row placement");
     return 0;
@@ -217,7 +212,8 @@ int run_conv_shared(Model& m, const XSource& src, int64_t c0, int64_t n, float* 
 static int pt_by_value(const Model& m, const GatPlan& g) { return m.cfg.use_gatv2 ? -1 : g.PT; }
 static int p8_by_value(const Model& m, const GatPlan& g) { return m.cfg.use_gatv2 ? -1 : g.P8; }
 
-int run_proj(Model& m, const GatPlan& g, const float* rows, long ld, int64_t nrows, float* lc, float* rt, hipStream_t s) {
+int run_proj(Model& m, const GatPlan& g, const FrontLayerRoute& lr, const float* rows, long ld, int64_t nrows, float* lc, float* rt,
+             hipStream_t s) {
     Scope sc(m, S_PROJ, s);
     RowGemmArgs a{};
     a.X = rows; a.ldx = ld; a.Kvalid = g.D; a.Q = g.Q;
@@ -226,8 +222,9 @@ int run_proj(Model& m, const GatPlan& g, const float* rows, long ld, int64_t nro
     a.Y = lc; a.ldy = g.ldl; a.Nvalid = g.ldl; a.vec_store = 1;
     a.R = nrows; a.NT = g.NT; a.relu = 0;
     a.NT_rm = g.NT_L; a.YT = rt; a.group = g.K; a.YT_rows = g.rt_rows; a.YT_ld = g.Kp;
-    if (m.precision == 2 && g.uw3_off && g.uQ16 > 0 && m.rowgemm_kernel != 1 && (nrows >= 65536 || m.rowgemm_kernel == 2)) {       // wide layers: three bf16 pieces per operand
+    if (lr.split_pack)
         if (int rc_ = ensure(m, g.split, s)) return rc_;
+    if (lr.build == FRONT_X3) {       // the split row GEMM
         a.x3 = 1; a.Q16 = g.uQ16;
         a.Wp3 = reinterpret_cast<const f32x4*>(m.packed_dev + g.uw3_off);
     }
@@ -235,11 +232,11 @@ int run_proj(Model& m, const GatPlan& g, const float* rows, long ld, int64_t nro
     return 0;
 }
 
-int run_attend(Model& m, const GatPlan& g, const float* lc, const float* rt, const float* v, int ldv, int64_t n, float* out,
-               long so_w, long so_i, long so_d, float* sc, hipStream_t s, float* att = nullptr, const DropArgs* drop = nullptr,
-               unsigned drop_stream = 0) {
+int run_attend(Model& m, const GatPlan& g, const FrontLayerRoute& lr, const float* lc, const float* rt, const float* v, int ldv,
+               int64_t n, float* out, long so_w, long so_i, long so_d, float* sc, hipStream_t s, float* att = nullptr,
+               const DropArgs* drop = nullptr, unsigned drop_stream = 0) {
     Scope sc_(m, S_ATTEND, s);
-    if (g.K <= 512 && g.D <= 512) {
+    if (lr.kernel == LAYER_WIDE) {
         // LDS-tiled pair grid of the fused kernel over the HBM-resident projections (BASELINE config 4 shapes)
         K_TRY(launch_gat_wide(lc, rt, g.ldl, g.rt_rows, g.Kp, pt_by_value(m, g), p8_by_value(m, g), m.packed_dev + g.bias_off, v, ldv, g.D, g.K, out, so_w,
                               so_i, so_d, n, m.cfg.use_gatv2 ? 0 : 1, m.cfg.alpha, s, att, drop, drop_stream,
@@ -264,32 +261,30 @@ int run_attend(Model& m, const GatPlan& g, const float* lc, const float* rt, con
     return 0;
 }
 
-bool use_fused(const GatPlan& g) { return g.fused; }
-
 // fused layer: V rows (n*K, ldv) -> out, nothing but V read from / out written to HBM
-// cv (temporal layer, inference): the window convolution runs inside k_gath's workgroup (fused_conv_args below said it can)
-int run_gat_fused(Model& m, const GatPlan& g, const float* v, int ldv, int vt, int64_t n, float* out, long so_w, long so_i,
-                  long so_d, hipStream_t s, float* att = nullptr, const DropArgs* drop = nullptr, unsigned drop_stream = 0,
-                  const unsigned* vmax = nullptr, const GatConvIn* cv = nullptr) {
+// vmax: the convolution's recorded range (the route's `range`); cv (temporal layer behind CONV_IN_GATH): the window convolution
+// runs inside k_gath's workgroup
+int run_gat_fused(Model& m, const GatPlan& g, const FrontLayerRoute& lr, const float* v, int ldv, int vt, int64_t n, float* out,
+                  long so_w, long so_i, long so_d, hipStream_t s, float* att = nullptr, const DropArgs* drop = nullptr,
+                  unsigned drop_stream = 0, const unsigned* vmax = nullptr, const GatConvIn* cv = nullptr) {
     Scope sc(m, S_ATTEND, s);
+    if (cv && lr.kernel != LAYER_GATH) return fail(MTADGAT_ERR_INVALID, "internal: fused convolution without k_gath");
     GatArgs a{};
     a.V = v; a.ldv = ldv; a.vt = vt; a.D = g.D; a.K = g.K; a.vld = g.f_vld; a.lr_floats = g.f_lr;
     a.Wp = reinterpret_cast<const f32x4*>(m.packed_dev + g.w_off);
     a.pbias = m.packed_dev + g.b_off;
     a.NT_L = g.NT_L; a.Q = g.Q; a.PT = pt_by_value(m, g); a.P8 = p8_by_value(m, g);
     a.ord = m.cfg.use_gatv2 ? reinterpret_cast<const int*>(m.packed_dev + g.ord_off) : nullptr;
-    if (m.precision == 1 && !att && !(split_front(m, n) && vmax)) {       // bf16 operand build of the projection (inference)
+    if (lr.split_pack)
+        if (int rc_ = ensure(m, g.split, s)) return rc_;
+    if (lr.build == FRONT_BF16) {
         a.bf16 = 1; a.Q = g.Q16;
         a.Wp = reinterpret_cast<const f32x4*>(m.packed_dev + g.w16_off);
-    } else if ((m.precision == 2 || (split_front(m, n) && !att)) && (n >= 4096 || (m.gat_kernel == 3 && !att))) {
-        // large batches: split-bf16 operands for the projection -- fp32-class L' / R' on the bf16 matrix pipe, which runs
-        // beside the pair grid of the other waves (the fp32 MFMA does not: profiles/r02_mfma_valu_overlap.txt).  Measured at
-        // (W=100, F=55): feature layer 5.90 -> 5.09 ms, temporal layer 7.40 -> 6.94 ms (two weight chunks in registers; with
-        // four the temporal layer's larger pair-grid block spilled and lost)
-        if (int rc_ = ensure(m, g.split, s)) return rc_;
+    } else if (lr.build == FRONT_X3) {
         a.bf16 = 2; a.Q = g.Q16;
         a.Wp = reinterpret_cast<const f32x4*>(m.packed_dev + g.w3_off);
-        // two fp16 pieces instead when the convolution that produced the node values recorded a maximum below 2^15
+    }
+    if (lr.fp16) {       // two fp16 pieces instead when the convolution that produced the node values recorded a maximum below 2^15
         a.vmax = vmax;
         a.Wp2 = reinterpret_cast<const f32x4*>(m.packed_dev + g.w2h_off);
         a.scale2 = m.packed_dev + g.gscale_off + 1;
@@ -302,13 +297,7 @@ int run_gat_fused(Model& m, const GatPlan& g, const float* v, int ldv, int vt, i
     a.ATT = att;
     if (drop) a.drop = *drop;
     a.drop_stream = drop_stream;
-    // the fp16-piece build of the row-split kernel (node vectors split once per window) serves the two-fp16-piece arithmetic
-    // (inference, node values below 2^15 -- decided on the device from the convolution's recorded maximum: of the two launches
-    // exactly one does the work)
-    const int scols = vt ? g.K : g.D;
-    // (training forward -- att set -- from 4096 windows as well: k_gath keeps the softmax rows and applies the dropout)
-    if (a.bf16 == 2 && vmax && (!att || n >= 4096) && (m.gat_kernel == 0 || m.gat_kernel == 3) && g.fh_lds_bytes <= 160 * 1024 && aligned16(v) &&
-        (ldv & 3) == 0 && ((scols + 3) & ~3) <= ldv) {
+    if (lr.kernel == LAYER_GATH) {
         GatArgs b = a;
         b.vld = g.fh_vld; b.lr_floats = g.fh_lr; b.n_full = g.fh_full; b.n_short = g.fh_short;
         b.lr_buf = g.fh_lr_buf;
@@ -318,53 +307,47 @@ int run_gat_fused(Model& m, const GatPlan& g, const float* v, int ldv, int vt, i
         K_TRY(launch_gath(b, g.fh_IBL, g.fh_JPL, g.fh_RJ, g.f_nw, g.fh_lds_bytes, cv != nullptr, s), cv ? "fused convolution + gat (fp16 pieces)" : "fused gat (fp16 pieces)");
         a.skip_h = 1;
         if (cv) a.winflag = cv->flag;    // per-window range guard: k_gat serves exactly the windows k_gath flagged
-    } else if (cv) {
-        return fail(MTADGAT_ERR_INVALID, "internal: fused convolution without k_gath");
-    } else if (m.cfg.use_gatv2) {
-        // without k_gath in front, k_gat would take the fp16 pieces itself -- but a GATv2 layer's fp16-piece pack is in k_gath's
-        // compact column order (launch_split2h_gath), not the 8-padded one k_gat's tiles walk: k_gat keeps the bf16 pieces
-        a.vmax = nullptr; a.Wp2 = nullptr; a.scale2 = nullptr;
     }
     K_TRY(launch_gat(a, g.f_IBL, g.f_JPL, g.f_RJ, g.f_nw, g.f_lds_bytes, s), "fused gat");
     return 0;
 }
 
-// Can the temporal layer's k_gath workgroup compute the convolution of its window itself (mtadgat_gath.hip, CONV build)?  The
-// conditions of k_conv_win and of k_gath's launch in run_gat_fused, and the staged input must fit the L' / R' region.  Fills `cv`.
-bool fused_conv_args(const Model& m, const XSource& src, int64_t c0, int64_t n, float* hcat, unsigned* vmax, unsigned char* flag, GatConvIn& cv) {
-    const GatPlan& g = m.temp;
-    if (m.conv_fused == 1 || !(m.precision == 2 || split_front(m, n)) || !conv_win_selected(m, n) || !g.fused || !m.feat.fused) return false;
-    if (!(n >= 4096 || m.gat_kernel == 3) || !(m.gat_kernel == 0 || m.gat_kernel == 3) || g.fh_lds_bytes > 160 * 1024) return false;
-    if (g.K != m.W || g.D != m.F || !aligned16(hcat) || (m.Dp & 3) != 0 || ((g.D + 3) & ~3) > m.Dp) return false;
-    cv = GatConvIn{};
-    if (src.gather) {
-        cv.X = src.x; cv.gather = 1;
-        cv.starts = src.starts ? reinterpret_cast<const long*>(src.starts + c0) : nullptr;
-        cv.start0 = src.start0 + c0 * src.stride; cv.stride = src.stride;
-    } else if (src.x_bf16) {
-        cv.X = reinterpret_cast<const float*>(reinterpret_cast<const uint16_t*>(src.x) + c0 * (int64_t)m.W * m.F);
-    } else {
-        cv.X = src.x + c0 * (int64_t)m.W * m.F;
-    }
-    cv.x_bf16 = src.x_bf16;
+// k_gath's convolution input (CONV_IN_GATH) for the windows from c0 on
+GatConvIn fused_conv_args(const Model& m, const XSource& src, int64_t c0, float* hcat, unsigned* vmax, unsigned char* flag) {
+    GatConvIn cv{};
+    fill_source(m, src, c0, cv);
     cv.taps = m.taps; cv.pad = m.pad; cv.Fq = m.Fp16; cv.NT = m.convNT; cv.Dp = m.Dp;
     cv.pvx = conv_win_pitch(m.F, m.Fp16);
     cv.Wp = reinterpret_cast<const f32x4*>(m.packed_dev + m.conv_w2h_off);
     cv.bias = m.packed_dev + m.conv_b_off;
     cv.wscale = m.packed_dev + m.conv_scale_off + 1;
     cv.HCAT = hcat; cv.vmax = vmax; cv.flag = flag;
-    GatArgs probe{};
-    probe.vt = 0; probe.K = g.K; probe.D = g.D; probe.lr_floats = g.fh_lr; probe.cv = cv;
-    return gath_conv_applies(probe, g.f_nw, m.F, m.W);
+    return cv;
 }
 
-// one graph-attention layer from its node rows, fused when the plan allows
-int run_gat_layer(Model& m, const GatPlan& g, const float* v, int ldv, int64_t n, float* lc, float* rt, float* out, long so_w,
-                  long so_i, long so_d, float* sc, hipStream_t s) {
-    if (use_fused(g)) return run_gat_fused(m, g, v, ldv, 0, n, out, so_w, so_i, so_d, s);
-    int rc = run_proj(m, g, v, ldv, n * g.K, lc, rt, s);
-    if (rc) return rc;
-    return run_attend(m, g, lc, rt, v, ldv, n, out, so_w, so_i, so_d, sc, s);
+// One graph-attention layer as its route says.  Fused: from the node rows v (vt = 1: their columns are the nodes); un-fused: the
+// projection through lc / rt, then the attention (sc: score scratch of k_attend).  att / drop: training forward and attention maps.
+struct LayerIo {
+    const float* v = nullptr; int ldv = 0, vt = 0;
+    float* lc = nullptr; float* rt = nullptr; float* sc = nullptr;
+    float* out = nullptr; long so_w = 0, so_i = 0, so_d = 0;
+    float* att = nullptr; const DropArgs* drop = nullptr; unsigned drop_stream = 0;
+    const unsigned* vmax = nullptr; const GatConvIn* cv = nullptr;
+};
+// a layer that writes its third of h_cat (forward, training forward, attention maps); node rows: those of h_cat[:, :F] -- a fused
+// feature layer reads its nodes from their columns -- or, un-fused feature layer, of xc^T
+LayerIo hcat_layer(const Model& m, bool temporal, bool fused, float* hcat, const float* xct, float* lc, float* rt) {
+    LayerIo io;
+    io.v = (temporal || fused) ? hcat : xct; io.ldv = (temporal || fused) ? m.Dp : m.Wp; io.vt = !temporal && fused;
+    io.lc = lc; io.rt = rt; io.out = hcat + (temporal ? 2 : 1) * m.F;
+    io.so_w = (long)m.W * m.Dp; io.so_i = temporal ? m.Dp : 1; io.so_d = temporal ? 1 : m.Dp;
+    return io;
+}
+int run_gat_layer(Model& m, const GatPlan& g, const FrontLayerRoute& lr, const LayerIo& io, int64_t n, hipStream_t s) {
+    if (lr.fused())
+        return run_gat_fused(m, g, lr, io.v, io.ldv, io.vt, n, io.out, io.so_w, io.so_i, io.so_d, s, io.att, io.drop, io.drop_stream, io.vmax, io.cv);
+    if (int rc = run_proj(m, g, lr, io.v, io.ldv, n * g.K, io.lc, io.rt, s)) return rc;
+    return run_attend(m, g, lr, io.lc, io.rt, io.v, io.ldv, n, io.out, io.so_w, io.so_i, io.so_d, io.sc, s, io.att, io.drop, io.drop_stream);
 }
 
 // A Linear over (window, step) rows in the default fp32 arithmetic: from 65 536 rows on the products come from three bf16 pieces per
@@ -373,7 +356,7 @@ int run_gat_layer(Model& m, const GatPlan& g, const float* v, int ldv, int64_t n
 // do.  Round 6: the GRU's hoisted input projection and recon_model.fc ran on the fp32 MFMA whatever the size (config 4: two 2.3 ms
 // launches per 896-window chunk, 42 of its 268 ms per 8 192 windows).
 int lin_split_operands(Model& m, const LinPlan& p, long rows, RowGemmArgs& a, hipStream_t s) {
-    if (!p.w3_off || p.Q16 <= 0 || m.precision != 2 || m.rowgemm_kernel == 1 || !(rows >= 65536 || m.rowgemm_kernel == 2)) return 0;
+    if (!rowgemm_split(m, p.w3_off && p.Q16 > 0, rows, false)) return 0;
     if (int rc_ = ensure(m, p.split, s)) return rc_;
     a.x3 = 1; a.Q16 = p.Q16;
     a.Wp3 = reinterpret_cast<const f32x4*>(m.packed_dev + p.w3_off);
@@ -910,6 +893,28 @@ int mtadgat_gru_route(mtadgat_handle h, int stack, int layer, int64_t n, int tra
     return 0;
 }
 
+/* Read-only test hook (no GPU, no weights): front_route of a call; include/mtadgat.h defines the arguments and the 14 ints */
+int mtadgat_front_route(mtadgat_handle h, int kind, int source, int64_t n, int facts, int* out) {
+    if (!h || !out) return fail(MTADGAT_ERR_INVALID, "null argument");
+    if (kind < 0 || kind > FRONT_CONV || source < 0 || source > SRC_SERIES || n < 1 || facts < 0 || facts > 7)
+        return fail(MTADGAT_ERR_INVALID, "call kind, source, window count or facts out of range");
+    FrontCall c;
+    c.kind = (FrontKind)kind; c.source = (FrontSource)source;
+    c.rows_aligned = facts & 1; c.ldv_fits = facts & 2; c.hcat_aligned = facts & 4;
+    const FrontRoute r = front_route(h->m, n, c);
+    auto split_gemm = [](const FrontLayerRoute& l) { return !l.fused() && l.build == FRONT_X3; };
+    const int v[14] = {r.conv, r.conv_build, r.conv_split_pack, r.range,
+                       r.temp.kernel, r.temp.build, r.temp.fp16, split_gemm(r.temp), r.temp.split_pack,
+                       r.feat.kernel, r.feat.build, r.feat.fp16, split_gemm(r.feat), r.feat.split_pack};
+    std::copy(v, v + 14, out);
+    return 0;
+}
+
+/* Read-only test hook: rowgemm_split under the handle's precision and "rowgemm_kernel" option (1 / 0, negative: error) */
+int mtadgat_rowgemm_split(mtadgat_handle h, int has_pack, int64_t rows, int backward) {
+    return h ? (int)rowgemm_split(h->m, has_pack != 0, rows, backward != 0) : fail(MTADGAT_ERR_INVALID, "null handle");
+}
+
 /* Host-only self check of the device-side re-pack's gather table (no GPU needed): packs `p` with the host packer, builds
  * the table and counts the image positions whose table entry does not reproduce the packed value from the flat
  * parameter buffer.  *n_gathered receives the number of positions the table covers.  Returns the mismatch count (0 =
@@ -1139,7 +1144,8 @@ static int forward_impl(mtadgat_handle h, const XSource& src, int64_t batch, flo
     // mtad_gat.py:76-77).  Same kernels, same results; the second stream joins before the call returns.
     // (large calls gain nothing from it: with the convolution as its own launch and both attention layers side by side, 65 536
     // windows take 21.0-21.2 ms against 21.1-21.3 one after the other -- the layers compete for the same vector ALUs)
-    const bool fork = !second && sched.size() == 1 && m.lanes == 0 && sched[0].n <= FORK_MAX_WINDOWS && use_fused(m.temp) && use_fused(m.feat);
+    const bool both_fused = m.temp.fused && m.feat.fused;
+    const bool fork = !second && sched.size() == 1 && m.lanes == 0 && sched[0].n <= FORK_MAX_WINDOWS && both_fused;
     if (second || fork) {
         int dev = 0;
         HIP_TRY(hipGetDevice(&dev));
@@ -1171,41 +1177,45 @@ static int forward_impl(mtadgat_handle h, const XSource& src, int64_t batch, flo
         float* xc = ws + o.xc;
         float* xct = ws + o.xct;
         float* hcat = ws + o.hcat;
-        if (use_fused(m.temp) && use_fused(m.feat)) {
+        LayerIo temp = hcat_layer(m, true, true, hcat, nullptr, ws + o.lct, ws + o.rtt), feat = hcat_layer(m, false, true, hcat, nullptr, ws + o.lcf, ws + o.rtf);
+        temp.sc = feat.sc = ws + o.sc;
+        if (both_fused) {
             // fused front: conv writes only h_cat[:, :F]; each layer's workgroup stages its window from
             // there (the feature layer transposes on the way into LDS) -- no xc / xc^T / L' / R' in HBM
+            const FrontRoute r = front_route(m, n, front_call(FRONT_FORWARD, src, hcat, m.Dp, F, hcat));
             unsigned* vmax = reinterpret_cast<unsigned*>(ws + o.vmax);
+            temp.vmax = feat.vmax = vmax;
             GatConvIn cv{};
-            bool conv_in_gat = false;
-            if (conv_shared_applies(m, src, n)) {
+            const bool conv_in_gat = r.conv == CONV_IN_GATH;
+            if (r.conv == CONV_SHARED) {
                 if ((rc = run_conv_shared(m, src, c0, n, hcat, ws + o.cf, ws + o.el, ws + o.er, s, vmax))) return rc;
-            } else if (fused_conv_args(m, src, c0, n, hcat, vmax, reinterpret_cast<unsigned char*>(ws + o.winflag), cv)) {
-                // the temporal layer's workgroups compute the convolution of their windows themselves: no convolution launch,
-                // h_cat[:, :F] is written once and not read back by that layer
-                conv_in_gat = true;
+            } else if (conv_in_gat) {
+                if ((rc = ensure(m, m.conv_split, s))) return rc;
+                cv = fused_conv_args(m, src, c0, hcat, vmax, reinterpret_cast<unsigned char*>(ws + o.winflag));
+                temp.cv = &cv;
                 HIP_TRY(hipMemsetAsync(vmax, 0, sizeof(unsigned), s));
-            } else if ((rc = run_conv(m, src, c0, n, nullptr, nullptr, hcat, nullptr, s, vmax))) return rc;
+            } else if ((rc = run_conv(m, r, src, c0, n, nullptr, nullptr, hcat, nullptr, s, vmax))) return rc;
             if (fork && !conv_in_gat) {                       // the feature layer on the second lane, beside the temporal one
                 HIP_TRY(hipEventRecord(m.fork_ev[0], s));
                 HIP_TRY(hipStreamWaitEvent(m.lane_stream, m.fork_ev[0], 0));
-                if ((rc = run_gat_fused(m, m.feat, hcat, m.Dp, 1, n, hcat + F, (long)W * m.Dp, 1, m.Dp, m.lane_stream, nullptr, nullptr, 0, vmax))) return rc;
+                if ((rc = run_gat_layer(m, m.feat, r.feat, feat, n, m.lane_stream))) return rc;
                 HIP_TRY(hipEventRecord(m.fork_ev[1], m.lane_stream));
             }
-            if ((rc = run_gat_fused(m, m.temp, hcat, m.Dp, 0, n, hcat + 2 * F, (long)W * m.Dp, m.Dp, 1, s, nullptr, nullptr, 0, vmax,
-                                           conv_in_gat ? &cv : nullptr))) return rc;
+            if ((rc = run_gat_layer(m, m.temp, r.temp, temp, n, s))) return rc;
             if (fork && !conv_in_gat) HIP_TRY(hipStreamWaitEvent(s, m.fork_ev[1], 0));
-            else if ((rc = run_gat_fused(m, m.feat, hcat, m.Dp, 1, n, hcat + F, (long)W * m.Dp, 1, m.Dp, s, nullptr, nullptr, 0, vmax))) return rc;
+            else if ((rc = run_gat_layer(m, m.feat, r.feat, feat, n, s))) return rc;
         } else {
-            if ((rc = run_conv(m, src, c0, n, xc, xct, hcat, nullptr, s))) return rc;
-            // temporal layer: nodes = time steps, rows of xc
-            if ((rc = run_gat_layer(m, m.temp, xc, m.Fp, n, ws + o.lct, ws + o.rtt, hcat + 2 * F, (long)W * m.Dp, m.Dp, 1, ws + o.sc, s))) return rc;
-            // feature layer: nodes = features, rows of xc^T
-            if ((rc = run_gat_layer(m, m.feat, xct, m.Wp, n, ws + o.lcf, ws + o.rtf, hcat + F, (long)W * m.Dp, 1, m.Dp, ws + o.sc, s))) return rc;
+            const FrontRoute r = front_route(m, n, front_call(FRONT_FORWARD_UNFUSED, src, xc, m.Fp, F, hcat));
+            if ((rc = run_conv(m, r, src, c0, n, xc, xct, hcat, nullptr, s))) return rc;
+            temp.v = xc; temp.ldv = m.Fp;        // temporal layer: nodes = time steps, rows of xc
+            feat.v = xct; feat.ldv = m.Wp; feat.vt = 0;      // feature layer: nodes = features, rows of xc^T
+            if ((rc = run_gat_layer(m, m.temp, r.temp, temp, n, s))) return rc;
+            if ((rc = run_gat_layer(m, m.feat, r.feat, feat, n, s))) return rc;
         }
         float* hend = ws + o.hend;
         const long ldh = m.gru.back().Hp;
         if ((rc = run_gru_stack(m, hcat, m.Dp, n, hend, ldh, ws, o, s,
-                                (use_fused(m.temp) && use_fused(m.feat)) ? reinterpret_cast<const unsigned*>(ws + o.vmax) : nullptr))) return rc;
+                                both_fused ? reinterpret_cast<const unsigned*>(ws + o.vmax) : nullptr))) return rc;
         if (hend_out)
             K_TRY(launch_copy2d(hend, ldh, hend_out + c0 * m.cfg.gru_hid_dim, m.cfg.gru_hid_dim, n, m.cfg.gru_hid_dim, s),
                   "h_end copy");
@@ -1236,7 +1246,7 @@ int mtadgat_forward(mtadgat_handle h, const float* x, int64_t batch, float* pred
 
 int mtadgat_forward_xbf16(mtadgat_handle h, const void* x_bf16, int64_t batch, float* preds, float* recons, float* hend_out,
                           void* ws_, size_t ws_bytes, void* stream) {
-    if (h && (size_t)(32 + h->m.taps - 1) * (std::max(h->m.Fp, h->m.Fp16) + 4) * sizeof(float) > 20 * 1024)
+    if (h && !conv_lds_staged(h->m.taps, std::max(h->m.Fp, h->m.Fp16)))
         return fail(MTADGAT_ERR_UNSUPPORTED, "bfloat16 input is read by the LDS-staged convolution only (n_features too large): pass float32");
     XSource src;
     src.x = static_cast<const float*>(x_bf16);
@@ -1265,7 +1275,8 @@ int mtadgat_conv(mtadgat_handle h, const float* x, int64_t batch, float* y, void
     if (!x || !y) return fail(MTADGAT_ERR_INVALID, "null tensor");
     XSource src;
     src.x = x;
-    return run_conv(h->m, src, 0, batch, nullptr, nullptr, nullptr, y, (hipStream_t)stream);
+    const FrontRoute r = front_route(h->m, batch, front_call(FRONT_CONV, src, nullptr, 0, 0, nullptr));
+    return run_conv(h->m, r, src, 0, batch, nullptr, nullptr, nullptr, y, (hipStream_t)stream);
 }
 
 int mtadgat_gat(mtadgat_handle h, int which, const float* xc_in, int64_t batch, float* out, void* ws_, size_t ws_bytes,
@@ -1285,13 +1296,17 @@ int mtadgat_gat(mtadgat_handle h, int which, const float* xc_in, int64_t batch, 
         plan_workspace(m, std::min<int64_t>(batch, m.chunk), o);
         const float* xin = xc_in + c0 * (int64_t)W * F;
         float* o_c = out + c0 * (int64_t)W * F;
+        LayerIo io;
+        io.out = o_c; io.so_w = (long)W * F; io.sc = ws + o.sc;
         if (which == 1) {
             K_TRY(launch_copy2d(xin, F, ws + o.xc, m.Fp, n * W, F, s), "pad copy");
-            if ((rc = run_gat_layer(m, m.temp, ws + o.xc, m.Fp, n, ws + o.lct, ws + o.rtt, o_c, (long)W * F, F, 1, ws + o.sc, s))) return rc;
+            io.v = ws + o.xc; io.ldv = m.Fp; io.lc = ws + o.lct; io.rt = ws + o.rtt; io.so_i = F; io.so_d = 1;
         } else {
             K_TRY(launch_transpose_win(xin, F, ws + o.xct, m.Wp, n, W, F, s), "transpose");
-            if ((rc = run_gat_layer(m, m.feat, ws + o.xct, m.Wp, n, ws + o.lcf, ws + o.rtf, o_c, (long)W * F, 1, F, ws + o.sc, s))) return rc;
+            io.v = ws + o.xct; io.ldv = m.Wp; io.lc = ws + o.lcf; io.rt = ws + o.rtf; io.so_i = 1; io.so_d = F;
         }
+        const FrontRoute r = front_route(m, n, front_call(FRONT_FORWARD_UNFUSED, XSource{}, io.v, io.ldv, which ? F : W, nullptr));
+        if ((rc = run_gat_layer(m, which ? m.temp : m.feat, which ? r.temp : r.feat, io, n, s))) return rc;
     }
     return 0;
 }
@@ -1380,8 +1395,7 @@ static void plan_attention(const Model& m, int64_t batch, bool reduce, AttPlan& 
 }
 
 // The maps come from the fp32 builds the training forward keeps its softmax rows with (k_gat / k_gat_wide / k_attend, no
-// dropout), whatever precision mode the handle is in: the mode is set to 0 for the call and restored, and so is profiling --
-// the call leaves the handle as it found it.
+// dropout), whatever precision mode the handle is in (front_route, FRONT_ATTENTION); profiling is off for the call and restored.
 static int attention_impl(mtadgat_handle h, const XSource& src, int64_t batch, bool reduce, float* att_f, float* att_t, void* ws_,
                           size_t ws_bytes, void* stream) {
     if (!h) return fail(MTADGAT_ERR_INVALID, "null handle");
@@ -1396,10 +1410,9 @@ static int attention_impl(mtadgat_handle h, const XSource& src, int64_t batch, b
     plan_attention(m, batch, reduce, p);
     if (ws_bytes < p.total * sizeof(float)) return fail(MTADGAT_ERR_WORKSPACE, "workspace too small");
     struct Restore {
-        Model& m; int precision; bool profile;
-        ~Restore() { m.precision = precision; m.profile = profile; }
-    } restore{m, m.precision, m.profile};
-    m.precision = 0;
+        Model& m; bool profile;
+        ~Restore() { m.profile = profile; }
+    } restore{m, m.profile};
     m.profile = false;
     hipStream_t s = (hipStream_t)stream;
     float* ws = static_cast<float*>(ws_);
@@ -1408,29 +1421,21 @@ static int attention_impl(mtadgat_handle h, const XSource& src, int64_t batch, b
     int rc;
     for (int64_t c0 = 0; c0 < batch; c0 += p.chunk) {
         const int64_t n = std::min<int64_t>(p.chunk, batch - c0);
-        if ((rc = run_conv(m, src, c0, n, nullptr, (att_f && !m.feat.fused) ? ws + p.xct : nullptr, hcat, nullptr, s))) return rc;
+        const FrontRoute r = front_route(m, n, front_call(FRONT_ATTENTION, src, hcat, m.Dp, F, hcat));
+        if ((rc = run_conv(m, r, src, c0, n, nullptr, (att_f && !r.feat.fused()) ? ws + p.xct : nullptr, hcat, nullptr, s))) return rc;
         // temporal layer: nodes = time steps, rows of h_cat[:, :F]
         if (att_t) {
-            float* dst = reduce ? ws + p.maps : att_t + c0 * (int64_t)W * W;
-            if (use_fused(m.temp)) {
-                if ((rc = run_gat_fused(m, m.temp, hcat, m.Dp, 0, n, hcat + 2 * F, (long)W * m.Dp, m.Dp, 1, s, dst))) return rc;
-            } else {
-                if ((rc = run_proj(m, m.temp, hcat, m.Dp, n * W, ws + p.lct, ws + p.rtt, s))) return rc;
-                if ((rc = run_attend(m, m.temp, ws + p.lct, ws + p.rtt, hcat, m.Dp, n, hcat + 2 * F, (long)W * m.Dp, m.Dp, 1, nullptr, s, dst))) return rc;
-            }
-            if (reduce) K_TRY(launch_att_mean_part(dst, n, W, p.slabs_t, c0 == 0, ws + p.ps_t, ws + p.pc_t, s), "attention mean (temporal)");
+            LayerIo io = hcat_layer(m, true, true, hcat, nullptr, ws + p.lct, ws + p.rtt);
+            io.att = reduce ? ws + p.maps : att_t + c0 * (int64_t)W * W;
+            if ((rc = run_gat_layer(m, m.temp, r.temp, io, n, s))) return rc;
+            if (reduce) K_TRY(launch_att_mean_part(io.att, n, W, p.slabs_t, c0 == 0, ws + p.ps_t, ws + p.pc_t, s), "attention mean (temporal)");
         }
         // feature layer: nodes = features, columns of h_cat[:, :F] (fused) or rows of x_c^T
         if (att_f) {
-            float* dst = reduce ? ws + p.maps : att_f + c0 * (int64_t)F * F;
-            if (use_fused(m.feat)) {
-                if ((rc = run_gat_fused(m, m.feat, hcat, m.Dp, 1, n, hcat + F, (long)W * m.Dp, 1, m.Dp, s, dst))) return rc;
-            } else {
-                const float* xct = ws + p.xct;
-                if ((rc = run_proj(m, m.feat, xct, m.Wp, n * F, ws + p.lcf, ws + p.rtf, s))) return rc;
-                if ((rc = run_attend(m, m.feat, ws + p.lcf, ws + p.rtf, xct, m.Wp, n, hcat + F, (long)W * m.Dp, 1, m.Dp, nullptr, s, dst))) return rc;
-            }
-            if (reduce) K_TRY(launch_att_mean_part(dst, n, F, p.slabs_f, c0 == 0, ws + p.ps_f, ws + p.pc_f, s), "attention mean (feature)");
+            LayerIo io = hcat_layer(m, false, r.feat.fused(), hcat, ws + p.xct, ws + p.lcf, ws + p.rtf);
+            io.att = reduce ? ws + p.maps : att_f + c0 * (int64_t)F * F;
+            if ((rc = run_gat_layer(m, m.feat, r.feat, io, n, s))) return rc;
+            if (reduce) K_TRY(launch_att_mean_part(io.att, n, F, p.slabs_f, c0 == 0, ws + p.ps_f, ws + p.pc_f, s), "attention mean (feature)");
         }
     }
     if (reduce && att_t) K_TRY(launch_att_mean_final(ws + p.ps_t, ws + p.pc_t, W, p.slabs_t, batch, att_t, s), "attention mean (temporal)");
@@ -1560,9 +1565,7 @@ int run_rowgemm_T(Model& m, const LinTPlan& p, const float* X, long ldx, long R,
     a.R = R; a.NT = p.NT; a.NT_rm = p.NT; a.group = 1; a.relu = 0;
     a.accumulate = accumulate ? 1 : 0;
     a.gate = gate; a.ldg = ldg; a.gate_scale = gate_scale;
-    // split-bf16 operands from 64 Ki rows on (batches of >= 656 windows at W = 100: below that the product is a few tens of
-    // microseconds either way and the pack would have to be re-split after every optimizer step for nothing)
-    if (p.w3_off && ((m.precision == 2 && m.rowgemm_kernel != 1 && R >= 65536) || m.rowgemm_kernel == 2)) {
+    if (rowgemm_split(m, p.w3_off != 0, R, true)) {
         if (int rc_ = ensure(m, p.split, s)) return rc_;
         a.x3 = 1; a.Q16 = p.Q16;
         a.Wp3 = reinterpret_cast<const f32x4*>(m.packed_dev + p.w3_off);
@@ -1580,7 +1583,7 @@ int run_bwd_projection(Model& m, const GatPlan& gp, const GatBwdPlan& gb, const 
     r.bias = m.packed_dev + gb.bu_off;
     r.Y = LR; r.ldy = 2L * gb.Ep; r.Nvalid = 2 * gb.Ep; r.vec_store = 1;
     r.R = rows; r.NT = 2 * gb.NTu; r.NT_rm = 2 * gb.NTu; r.group = 1; r.relu = 0;
-    if (gb.wu3_off && ((m.precision == 2 && m.rowgemm_kernel != 1 && rows >= 65536) || m.rowgemm_kernel == 2)) {
+    if (rowgemm_split(m, gb.wu3_off != 0, rows, true)) {
         if (int rc_ = ensure(m, gb.split, s)) return rc_;
         r.x3 = 1; r.Q16 = (gp.Q + 1) / 2;
         r.Wp3 = reinterpret_cast<const f32x4*>(m.packed_dev + gb.wu3_off);
@@ -1727,22 +1730,15 @@ int mtadgat_forward_train(mtadgat_handle h, const float* x, int64_t batch, int64
     XSource src;
     src.x = x;
     unsigned* vmax = reinterpret_cast<unsigned*>(T + t.vmax);
-    if ((rc = run_conv(m, src, 0, n, nullptr, T + t.xct, hcat, nullptr, s, vmax))) return rc;
+    const FrontRoute fr = front_route(m, n, front_call(FRONT_TRAIN, src, hcat, m.Dp, F, hcat));
+    if ((rc = run_conv(m, fr, src, 0, n, nullptr, T + t.xct, hcat, nullptr, s, vmax))) return rc;
     // the two attention layers: fused per-window kernels, or -- wide layers -- projection through memory + k_gat_wide; either way
     // the softmax rows are kept and the dropout of modules.py:90 / :189 is applied inside the kernel
-    if (use_fused(m.temp)) {
-        if ((rc = run_gat_fused(m, m.temp, hcat, m.Dp, 0, n, hcat + 2 * F, (long)W * m.Dp, m.Dp, 1, s, T + t.att_t, &drop, DROP_TEMP, vmax))) return rc;
-    } else {
-        if ((rc = run_proj(m, m.temp, hcat, m.Dp, n * W, T + t.lct, T + t.rtt, s))) return rc;
-        if ((rc = run_attend(m, m.temp, T + t.lct, T + t.rtt, hcat, m.Dp, n, hcat + 2 * F, (long)W * m.Dp, m.Dp, 1, nullptr, s, T + t.att_t, &drop, DROP_TEMP))) return rc;
-    }
-    if (use_fused(m.feat)) {
-        if ((rc = run_gat_fused(m, m.feat, hcat, m.Dp, 1, n, hcat + F, (long)W * m.Dp, 1, m.Dp, s, T + t.att_f, &drop, DROP_FEAT, vmax))) return rc;
-    } else {
-        const float* xct = T + t.xct;
-        if ((rc = run_proj(m, m.feat, xct, m.Wp, n * F, T + t.lcf, T + t.rtf, s))) return rc;
-        if ((rc = run_attend(m, m.feat, T + t.lcf, T + t.rtf, xct, m.Wp, n, hcat + F, (long)W * m.Dp, 1, m.Dp, nullptr, s, T + t.att_f, &drop, DROP_FEAT))) return rc;
-    }
+    LayerIo temp = hcat_layer(m, true, true, hcat, nullptr, T + t.lct, T + t.rtt), feat = hcat_layer(m, false, fr.feat.fused(), hcat, T + t.xct, T + t.lcf, T + t.rtf);
+    temp.att = T + t.att_t; temp.drop = &drop; temp.drop_stream = DROP_TEMP; temp.vmax = vmax;
+    feat.att = T + t.att_f; feat.drop = &drop; feat.drop_stream = DROP_FEAT; feat.vmax = vmax;
+    if ((rc = run_gat_layer(m, m.temp, fr.temp, temp, n, s))) return rc;
+    if ((rc = run_gat_layer(m, m.feat, fr.feat, feat, n, s))) return rc;
     // GRU stack (modules.py:235-238): every layer keeps its gates and states; between stacked layers nn.GRU's dropout
     // (training only; reference modules.py:232-233): the dropped sequence is what the next layer reads and is kept as well
     const int Lg = (int)m.gru.size(), Ld = (int)m.rec.size();

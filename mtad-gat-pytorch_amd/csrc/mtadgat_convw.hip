@@ -274,12 +274,15 @@ size_t conv_win_lds(int W, int F, int Fq, int taps) {
 }
 
 // window-per-workgroup convolution: fp32 or bfloat16 windows (materialised or gathered from a series), h_cat output only
+bool conv_win_fits(int W, int F, int Fq, int taps, int pad, int NT, int Dp) {
+    if (taps != 2 * pad + 1 || NT > 2 || W > 128 || W < 1) return false;
+    if ((long)W * F > 12L * 128 * 4 || (Fq & 15) != 0 || Fq < F) return false;
+    if ((Dp & 3) != 0) return false;
+    return conv_win_lds(W, F, Fq, taps) <= 64 * 1024;
+}
 bool conv_win_applies(const ConvArgs& a) {
     if (a.bf16 || !a.HCAT || a.XC || a.XCT || a.Y || !a.wscale) return false;
-    if (a.taps != 2 * a.pad + 1 || a.NT > 2 || a.W > 128 || a.W < 1) return false;
-    if ((long)a.W * a.F > 12L * 128 * 4 || (a.Fq & 15) != 0 || a.Fq < a.F) return false;
-    if ((a.Dp & 3) != 0) return false;
-    return conv_win_lds(a.W, a.F, a.Fq, a.taps) <= 64 * 1024;
+    return conv_win_fits(a.W, a.F, a.Fq, a.taps, a.pad, a.NT, a.Dp);
 }
 
 int launch_conv_win(const ConvArgs& a, hipStream_t s) {

@@ -908,13 +908,16 @@ extern "C" int mtadgat_debug_gath_stamps(unsigned long long* dst, size_t n) {
 
 // can the workgroup compute its window's convolution itself?  (temporal layer: nodes = time steps; what k_conv_win needs, the
 // staged input inside the L' / R' region, one 16-byte unit in three per thread of eight waves)
+bool gath_conv_fits(int W, int F, int Fq, int taps, int pad, int NT, int Dp, int nw, int K, int D, int lr_floats) {
+    if (K != W || D != F || nw != 8) return false;
+    if (taps != 2 * pad + 1 || NT > 2 || NT < 1 || W > 128 || W < 1 || (long)W * F > 6144) return false;
+    if ((Fq & 15) != 0 || Fq < F || (Dp & 3) != 0 || 32 * NT < F) return false;
+    return conv_win_lds(W, F, Fq, taps) + 24 * sizeof(float) <= (size_t)lr_floats * sizeof(float);
+}
 bool gath_conv_applies(const GatArgs& a, int nw, int F, int W) {
     const GatConvIn& c = a.cv;
-    if (a.vt != 0 || a.K != W || a.D != F || nw != 8 || !c.X || !c.HCAT || !c.Wp || !c.bias || !c.wscale) return false;
-    if (c.taps != 2 * c.pad + 1 || c.NT > 2 || c.NT < 1 || W > 128 || W < 1 || (long)W * F > 6144) return false;
-    if ((c.Fq & 15) != 0 || c.Fq < F || (c.Dp & 3) != 0 || 32 * c.NT < F) return false;
-    if (c.pvx != conv_win_pitch(F, c.Fq)) return false;
-    return conv_win_lds(W, F, c.Fq, c.taps) + 24 * sizeof(float) <= (size_t)a.lr_floats * sizeof(float);
+    if (a.vt != 0 || !c.X || !c.HCAT || !c.Wp || !c.bias || !c.wscale || c.pvx != conv_win_pitch(F, c.Fq)) return false;
+    return gath_conv_fits(W, F, c.Fq, c.taps, c.pad, c.NT, c.Dp, nw, a.K, a.D, a.lr_floats);
 }
 
 // the fp16-piece build of the fused layer (a.vld = piece pitch in halfs, a.lr_floats as for k_gat, a.Q = 16-feature chunks);

@@ -167,6 +167,59 @@ GruRoute gru_route(const Model& m, const std::vector<GruPlan>& stack, int layer,
 // wanted, n windows in one piece) or training forward: what mtadgat_gru_route reports
 GruCall gru_call_facts(const Model& m, bool decoder, int layer, int64_t n, bool training);
 
+// ---- front-end routes ----------------------------------------------------------------------------------------------------------
+// Which kernels run the window convolution and the two attention layers of one call.  front_route (mtadgat_pack.cpp) is the only
+// place that decides; run_conv / run_conv_shared / run_gat_layer (mtadgat_capi.cpp) launch what it names.  DESIGN.md section 4 has the
+// table of bands.
+enum FrontKind : int {
+    FRONT_FORWARD = 0,          // a whole inference forward: the convolution writes h_cat only and records its output range (a model
+                                // with an un-fused layer takes FRONT_FORWARD_UNFUSED instead, whichever of the two the caller names)
+    FRONT_FORWARD_UNFUSED = 1,  // the un-fused inference forward (and the stage entry point mtadgat_gat): xc, xc^T and h_cat, no range
+    FRONT_TRAIN = 2,            // the training forward: xc^T and h_cat, the range recorded, attention rows kept, dropout applied
+    FRONT_ATTENTION = 3,        // attention maps: fp32 arithmetic whatever the handle's mode, attention rows kept, no dropout, no range
+    FRONT_CONV = 4,             // the stage entry point mtadgat_conv: y only, no attention layer
+};
+enum FrontSource : int { SRC_WINDOWS = 0, SRC_WINDOWS_BF16 = 1, SRC_SERIES_UNIT = 2 /* stride 1, no `starts` */, SRC_SERIES = 3 };
+struct FrontCall {        // what the route depends on beside the model and the window count of the piece
+    FrontKind kind = FRONT_FORWARD;
+    FrontSource source = SRC_WINDOWS;
+    // of the node rows the fused layers read (h_cat rows in a forward / training forward); they decide whether k_gath may run
+    bool rows_aligned = true;     // 16-byte aligned
+    bool ldv_fits = true;         // row stride a multiple of 4 floats and at least the node columns rounded up to 4
+    bool hcat_aligned = true;     // h_cat 16-byte aligned (the convolution inside k_gath writes it with vector stores)
+};
+enum FrontConv : int {
+    CONV_IN_GATH = 0,     // no launch: the temporal layer's k_gath workgroup computes the convolution of its window
+    CONV_WIN = 1,         // k_conv_win: a window per workgroup on two fp16 pieces
+    CONV_SHARED = 2,      // stride-1 series: three launch_conv calls over the shared rows plus the row placement (run_conv_shared)
+    CONV_LAUNCH = 3,      // launch_conv on FrontRoute::conv_build operands
+};
+enum FrontBuild : int { FRONT_F32 = 0, FRONT_BF16 = 1, FRONT_X3 = 2 /* three bf16 pieces per operand */ };
+enum FrontLayerKernel : int {
+    LAYER_NONE = 0,       // FRONT_CONV
+    LAYER_GAT = 1,        // fused k_gat alone
+    LAYER_GATH = 2,       // k_gath (fp16 pieces), k_gat behind it for the ranges k_gath refuses (decided on the device)
+    LAYER_WIDE = 3,       // un-fused: row GEMM projection, then k_gat_wide (K, D <= 512)
+    LAYER_ATTEND = 4,     // un-fused: row GEMM projection, then k_attend through the score matrix
+};
+struct FrontLayerRoute {
+    FrontLayerKernel kernel = LAYER_NONE;
+    FrontBuild build = FRONT_F32;    // operands of the projection (fused: inside k_gat; un-fused: FRONT_X3 = the split row GEMM)
+    bool fp16 = false;               // k_gat is handed the two-fp16-piece pack and the recorded range beside its bf16 pieces
+    bool split_pack = false;         // the layer's split packs must be current (ensure)
+    bool fused() const { return kernel == LAYER_GAT || kernel == LAYER_GATH; }
+};
+struct FrontRoute {
+    FrontConv conv = CONV_LAUNCH;
+    FrontBuild conv_build = FRONT_F32;   // CONV_LAUNCH: fp32, the bf16 pack, or three bf16 pieces (rows too long for LDS staging)
+    bool conv_split_pack = false;        // the convolution's split packs must be current (ensure)
+    bool range = false;                  // the convolution records its output range (vmax) for the kernels behind it
+    FrontLayerRoute temp, feat;
+};
+FrontRoute front_route(const Model& m, int64_t n, const FrontCall& c);
+// Does a row GEMM over `rows` rows take split-bf16 operands (k_rowgemm_x3)?  has_pack: a split pack was planned for its weights.
+bool rowgemm_split(const Model& m, bool has_pack, int64_t rows, bool backward);
+
 // ---- backward (training) plans -------------------------------------------------------------------------
 // transposed Linear for the data gradient d X = d Y W through k_rowgemm: rows of the pack = input features
 struct LinTPlan {

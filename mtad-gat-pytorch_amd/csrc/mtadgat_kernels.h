@@ -360,7 +360,15 @@ int launch_rowgemm(const RowGemmArgs& a, hipStream_t s);
 // measurement / test hook (process-wide): 1 = the many-row launches of the split-bf16 row GEMM and wide convolution use the one-wave
 // kernels (k_rowgemm_x3 / k_conv_x3) instead of the workgroup kernels that share the weight words through LDS
 void set_gemm_lds_off(int off);
+// the LDS-staged convolution (k_conv_lds) keeps 32 + taps - 1 input rows of Fq + 4 floats per wave: >= 8 waves per CU up to 20 KB
+constexpr size_t CONV_LDS_STAGED_MAX = 20 * 1024;
+inline size_t conv_lds_bytes(int taps, int Fq) { return (size_t)(32 + taps - 1) * (Fq + 4) * sizeof(float); }
+inline bool conv_lds_staged(int taps, int Fq) { return conv_lds_bytes(taps, Fq) <= CONV_LDS_STAGED_MAX; }
 int launch_conv(const ConvArgs& a, hipStream_t s);
+// k_conv_win / the convolution inside k_gath: the shape fits (numbers only; front_route asks these), and -- *_applies, the
+// launchers' -2 validation -- the pointers the kernel needs are there as well
+bool conv_win_fits(int W, int F, int Fq, int taps, int pad, int NT, int Dp);
+bool gath_conv_fits(int W, int F, int Fq, int taps, int pad, int NT, int Dp, int nw, int K, int D, int lr_floats);
 bool conv_win_applies(const ConvArgs& a);
 int launch_conv_win(const ConvArgs& a, hipStream_t s);
 // training forward (drop set): S is the tape's attention matrix and keeps the softmax rows before dropout

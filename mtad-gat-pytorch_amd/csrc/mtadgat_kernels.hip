@@ -953,10 +953,10 @@ int launch_conv(const ConvArgs& a, hipStream_t s) {
     const long R = a.B * a.W;
     if (R <= 0) return 0;
     const unsigned grid = (unsigned)((R + 31) / 32);
-    const size_t lds = (size_t)(32 + a.taps - 1) * (a.Fq + 4) * sizeof(float);
-    if ((a.bf16 || a.x_bf16) && lds > 20 * 1024) return -2;
-    constexpr size_t lds_max = 20 * 1024;
-    if (lds <= lds_max || a.bf16 || a.x_bf16) {       // >= 8 waves per CU keep their tile in LDS
+    const size_t lds = conv_lds_bytes(a.taps, a.Fq);
+    const bool staged = conv_lds_staged(a.taps, a.Fq);
+    if ((a.bf16 || a.x_bf16) && !staged) return -2;
+    if (staged) {                                     // >= 8 waves per CU keep their tile in LDS
         if (lds > 64 * 1024) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_lds<2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_lds<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

@@ -596,6 +596,111 @@ GruCall gru_call_facts(const Model& m, bool decoder, int layer, int64_t n, bool 
     return c;
 }
 
+// The one rule "this row GEMM takes split-bf16 operands": the split-operand arithmetic (mode 2) from 65 536 rows on (below that the
+// product is a few tens of microseconds either way and the pack would be re-split after every optimizer step for nothing);
+// "rowgemm_kernel" = 1 keeps the fp32 MFMA, 2 takes the split pack at any size.  The forward and the backward sites differ and
+// always have: rowgemm_kernel = 2 forces the split pack in the backward (data gradients, the GATv2 score backward's projection)
+// whatever the precision mode, in the forward (attention projections, hoisted GRU input, recon_model.fc) only in mode 2.
+bool rowgemm_split(const Model& m, bool has_pack, int64_t rows, bool backward) {
+    if (!has_pack) return false;
+    if (backward) return (m.precision == 2 && m.rowgemm_kernel != 1 && rows >= 65536) || m.rowgemm_kernel == 2;
+    return m.precision == 2 && m.rowgemm_kernel != 1 && (rows >= 65536 || m.rowgemm_kernel == 2);
+}
+
+namespace {
+
+// One attention layer.  att: the softmax rows are kept (training forward, attention maps); range: the convolution recorded its
+// output range for this call; scols: the node columns of the rows the fused kernel stages.
+FrontLayerRoute front_layer(const Model& m, const GatPlan& g, int64_t n, const FrontCall& c, int prec, bool split_front, bool att,
+                            bool range) {
+    FrontLayerRoute r;
+    if (!g.fused) {
+        r.kernel = (g.K <= 512 && g.D <= 512) ? LAYER_WIDE : LAYER_ATTEND;
+        // wide layers: three bf16 pieces per operand for the projection's row GEMM
+        if (prec == 2 && rowgemm_split(m, g.uw3_off && g.uQ16 > 0, n * g.K, false)) { r.build = FRONT_X3; r.split_pack = true; }
+        return r;
+    }
+    r.kernel = LAYER_GAT;
+    if (prec == 1 && !att && !(split_front && range)) {
+        r.build = FRONT_BF16;            // bf16 operand build of the projection (inference)
+    } else if ((prec == 2 || (split_front && !att)) && (n >= 4096 || (m.gat_kernel == 3 && !att))) {
+        // large batches: split-bf16 operands for the projection -- fp32-class L' / R' on the bf16 matrix pipe, which runs beside the
+        // pair grid of the other waves (the fp32 MFMA does not: profiles/r02_mfma_valu_overlap.txt).  Measured at (W=100, F=55):
+        // feature layer 5.90 -> 5.09 ms, temporal layer 7.40 -> 6.94 ms (two weight chunks in registers; with four the temporal
+        // layer's larger pair-grid block spilled and lost)
+        r.build = FRONT_X3;
+        r.split_pack = true;
+        // k_gath, the fp16-piece build of the row-split kernel (node vectors split once per window), serves the two-fp16-piece
+        // arithmetic: node values below 2^15, decided on the device from the recorded range -- of its launch and k_gat's behind it
+        // exactly one does the work.  The training forward takes it from 4096 windows as well: it keeps the softmax rows and
+        // applies the dropout.
+        if (range && (!att || n >= 4096) && (m.gat_kernel == 0 || m.gat_kernel == 3) && g.fh_lds_bytes <= 160 * 1024 &&
+            c.rows_aligned && c.ldv_fits)
+            r.kernel = LAYER_GATH;
+        // Without k_gath in front k_gat would take the fp16 pieces itself -- but a GATv2 layer's fp16-piece pack is in k_gath's
+        // compact column order (launch_split2h_gath), not the 8-padded one k_gat's tiles walk: there k_gat keeps the bf16 pieces.
+        r.fp16 = r.kernel == LAYER_GATH || !m.cfg.use_gatv2;
+    }
+    return r;
+}
+
+}  // namespace
+
+// The front end of one call: window convolution, temporal layer, feature layer.
+FrontRoute front_route(const Model& m, int64_t n, const FrontCall& c) {
+    FrontRoute r;
+    const bool both_fused = m.temp.fused && m.feat.fused;
+    const FrontKind kind = (c.kind == FRONT_FORWARD && !both_fused) ? FRONT_FORWARD_UNFUSED : c.kind;
+    const int prec = kind == FRONT_ATTENTION ? 0 : m.precision;      // the maps come from the fp32 builds that keep the softmax rows
+    const bool att = kind == FRONT_TRAIN || kind == FRONT_ATTENTION;
+    const bool x_bf16 = c.source == SRC_WINDOWS_BF16;
+    r.range = kind == FRONT_FORWARD || kind == FRONT_TRAIN;
+    // The batch sizes / options at which the fused front end's convolution is the window-per-workgroup kernel on fp16 pieces.  The
+    // bf16 operand mode takes the same front end from 4096 windows: its fp16-piece kernels are faster than the bf16 builds of
+    // k_conv_lds / k_gat, 10.5 against 12.3 ms per 65 536 windows, and closer to the fp32 results; the recurrences stay bf16.
+    const bool split_front = prec == 1 && n >= 4096 && m.conv_kernel == 0 && m.gat_kernel == 0;
+    const bool win_selected = (prec == 2 || split_front) && m.conv_kernel != 1 && (n >= 4096 || m.conv_kernel == 2);
+    const bool win = kind == FRONT_FORWARD && win_selected && conv_win_fits(m.W, m.F, m.Fp16, m.taps, m.pad, m.convNT, m.Dp);
+    if (kind != FRONT_CONV) {
+        r.temp = front_layer(m, m.temp, n, c, prec, split_front, att, r.range);
+        r.feat = front_layer(m, m.feat, n, c, prec, split_front, att, r.range);
+    }
+    // Shared rows, for stride-1 windows of a series (run_conv_shared) where the LDS-staged kernel applies (it records the range;
+    // its bf16 build writes h_cat only).  Not where the window-per-workgroup kernel runs: that reads its window out of the series
+    // itself (the rows it re-reads are L2 hits) and is the faster of the two; taking it also keeps forward_series == forward on
+    // the stacked windows bit for bit.  "conv_shared" = 1 keeps the shared rows there.
+    if (kind == FRONT_FORWARD && c.source == SRC_SERIES_UNIT && n >= 1024 && prec != 1 && !(win && m.conv_shared != 1) &&
+        m.taps == 2 * m.pad + 1 && m.pad >= 1 && m.W >= 4 * m.pad && conv_lds_staged(m.taps, m.Fp)) {
+        r.conv = CONV_SHARED;
+        return r;
+    }
+    // Inside the temporal layer's k_gath workgroup: wherever k_conv_win is selected, k_gath runs and the staged input fits its
+    // L' / R' region -- no convolution launch, h_cat[:, :F] is written once and not read back by that layer.
+    if (kind == FRONT_FORWARD && m.conv_fused != 1 && win_selected && r.temp.kernel == LAYER_GATH && c.hcat_aligned &&
+        gath_conv_fits(m.W, m.F, m.Fp16, m.taps, m.pad, m.convNT, m.Dp, m.temp.f_nw, m.temp.K, m.temp.D, m.temp.fh_lr)) {
+        r.conv = CONV_IN_GATH;
+        r.conv_split_pack = true;
+        return r;
+    }
+    if (win) {
+        r.conv = CONV_WIN;
+        r.conv_split_pack = true;
+        return r;
+    }
+    r.conv = CONV_LAUNCH;
+    const bool h_cat_only = kind == FRONT_FORWARD || kind == FRONT_CONV;      // (mtadgat_conv's y counts: one plain output)
+    if (prec == 1 && h_cat_only && conv_lds_staged(m.taps, m.Fp16) && !(kind == FRONT_FORWARD && win_selected)) {
+        r.conv_build = FRONT_BF16;       // bf16 operand build: where the LDS-staged kernel applies
+    } else if (prec == 2 && !x_bf16 && m.conv_kernel != 1 && (n * m.W >= 65536 || m.conv_kernel == 2) && !conv_lds_staged(m.taps, m.Fp)) {
+        // wide models (rows too long for the LDS-staged kernels): the straight-from-memory kernel on three bf16 pieces per operand.
+        // (Split operands were tried for the LDS-staged convolution as well: 3.36 vs 3.37 ms at the flagship shape -- it is bound
+        // by its staging and stores, not by the matrix pipe; the fp32 MFMA build stays.)
+        r.conv_build = FRONT_X3;
+        r.conv_split_pack = true;
+    }
+    return r;
+}
+
 void plan_workspace(const Model& m, int64_t n, Workspace& ws) {
     size_t off = 0;
     auto take = [&](size_t cnt) {
