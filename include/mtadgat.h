@@ -508,6 +508,48 @@ int mtadgat_eval_run_stats(const float* score_dev, int64_t n, const int64_t* sta
 int mtadgat_eval_first_hit(const float* score_dev, const unsigned char* label_dev, int64_t n, double threshold, int compare_f32,
                            const int64_t* start_dev, const int64_t* end_dev, int64_t count, int64_t* first_dev, void* stream);
 
+/* ---- ranking curves (csrc/mtadgat_curves.hip; evaluation.score_order, ranking_curve, ranking_metrics) -------------------
+ * Conventions of the event calls above: no atomics, no library kernels, bitwise reproducible; scratch is 8-byte aligned, at
+ * least what the _scratch function returns (0 for invalid sizes) and need not be initialised; status 0 / -1 / -3 / -5 with a
+ * mtadgat_last_error() message; nothing is launched when validation fails.  1 <= n <= 2^31 - 1.
+ *
+ * mtadgat_eval_order_key (host): the 32-bit key whose unsigned order is the rank order of float32 values: -0.0 is read as
+ * +0.0, the sign bit is flipped for non-negative values and all bits for negative ones, the result is inverted when
+ * `descending`; every NaN gives 0xffffffff, the largest key, in both directions.
+ * mtadgat_eval_sort_tile(): the items per tile of the radix sort behind the calls below; mtadgat_eval_sort_scan_tiles(): the number
+ * of tiles above which the sort's (digit, tile) scan takes a second level (for tests that want sizes around both). */
+uint32_t mtadgat_eval_order_key(float value, int descending);
+int mtadgat_eval_sort_tile(void);
+int mtadgat_eval_sort_scan_tiles(void);
+/* mtadgat_eval_score_order: order_dev[r] = the index of the score of rank r, by ascending order key (see above) for the given
+ * direction; equal keys keep ascending index (a stable least-significant-digit radix sort, 8 bits per pass, 4 passes).
+ * Asynchronous on `stream`. */
+size_t mtadgat_eval_score_order_scratch(int64_t n);
+int mtadgat_eval_score_order(const float* score_dev, int64_t n, int descending, void* scratch_dev, size_t scratch_bytes,
+                             int64_t* order_dev, void* stream);
+/* mtadgat_eval_curve: every operating point of score_dev (n float32) against label_dev (n uint8, != 0 is positive).
+ * adjust 0: the scores as they are; 1: point adjust -- every sample of a labelled segment takes the segment's largest non-NaN
+ * score, except that sample 0 keeps its own (mtadgat_eval_point_adjust's back-fill never reaches index 0); 2: PA%K with
+ * 0 <= k_percent <= 100 -- a sample of a segment of length L takes max(own, the m-th largest non-NaN score of the segment),
+ * m = k_percent * L / 100 + 1 (integer division), and keeps its own when the segment has fewer than m non-NaN scores.
+ * thresholds_dev / tp_dev / fp_dev hold n entries each; the first G are written: the distinct non-NaN adjusted values in
+ * descending order (never -0.0) and the numbers of positives / negatives with adjusted score >= that value.  A NaN is below
+ * every threshold.  summary_host receives 12 int64 and the call synchronises the stream:
+ *   [0] G  [1] positives  [2] negatives  [3] positives with a NaN adjusted score  [4] negatives with one
+ *   [5] the doubled AUROC numerator: sum over the tie groups, the NaN samples being one last group, of
+ *       (positives of the group) x (2 x negatives below the group + negatives of the group)
+ *   [6] the bits of the float64 sum over the numeric groups of (positives of the group) x tp / (tp + fp), added in a fixed
+ *       order whose longest chain of additions has at most 4096 terms
+ *   [7] the group of largest F1 = 2 p r / (p + r + 1e-5), p = tp / (tp + fp + 1e-5), r = tp / (tp + fn + 1e-5), evaluated
+ *       in float64 without contraction, the lowest group among equals, -1 when G = 0; [8], [9] its tp and fp; [10] the bits
+ *       of its float32 threshold; [11] 0.
+ * With adjust != 0 the number of labelled segments is read back as well (mtadgat_eval_runs), with adjust = 2 also the number
+ * of labelled samples.  scratch: mtadgat_eval_curve_scratch(n, adjust) bytes. */
+size_t mtadgat_eval_curve_scratch(int64_t n, int adjust);
+int mtadgat_eval_curve(const float* score_dev, const unsigned char* label_dev, int64_t n, int adjust, int k_percent,
+                       void* scratch_dev, size_t scratch_bytes, float* thresholds_dev, int64_t* tp_dev, int64_t* fp_dev,
+                       int64_t* summary_host, void* stream);
+
 /* ---- scoring live streams row by row (csrc/mtadgat_stream.hip; streaming.StreamScorer) ---------------------------------
  * A deployment's loop: rows of n_streams independent series arrive a few at a time, and each needs its anomaly score, an alarm
  * flag and -- when an alarm ends -- the finished event.  Everything that carries over from one push to the next lives in ONE

@@ -31,6 +31,11 @@ Peaks-over-threshold thresholds, static and adaptive (csrc/mtadgat_spot.hip and 
                                     device and also serves streaming.StreamScorer as a per-stream adaptive threshold
   pot_eval                          the reference's third threshold method beside epsilon_eval and bf_search (`--dynamic_pot` with
                                     dynamic=True)
+Threshold-free quality of a score array (csrc/mtadgat_curves.hip, tests/test_gpu_curves.py; tests/curve_refs.py is the specification):
+  score_order                       the indices of a score array in rank order: a deterministic, stable key / payload radix sort
+  ranking_curve                     every distinct threshold with its cumulative TP / FP, for the raw scores, the reference's point
+                                    adjust or PA%K (Kim et al., AAAI 2022), adjusted and ranked without the scores leaving the device
+  ranking_metrics                   exact AUROC, average precision and the best-F1 point of that curve, from one small copy
 The fit follows the paper, not the reference's vendored spot.py (its optimiser-based root search cannot be reproduced bit for
 bit): tests/spot_refs.py is the specification, csrc/mtadgat_spot.h spells it out.
 """
@@ -81,6 +86,18 @@ def _lib():
         lib.mtadgat_spot_read.argtypes = [vp, i64, i64, u64p, vp]
         lib.mtadgat_spot_copy.argtypes = [vp, i64, vp, i64, i64, vp, i64, ci, vp]
         lib.mtadgat_spot_fit_host.argtypes = [u64p, i64, i64, i64, f64, f64, u64p]
+        lib.mtadgat_eval_order_key.argtypes = [f32, ci]
+        lib.mtadgat_eval_order_key.restype = ctypes.c_uint32
+        lib.mtadgat_eval_sort_tile.argtypes = []
+        lib.mtadgat_eval_sort_tile.restype = ci
+        lib.mtadgat_eval_sort_scan_tiles.argtypes = []
+        lib.mtadgat_eval_sort_scan_tiles.restype = ci
+        lib.mtadgat_eval_score_order_scratch.argtypes = [i64]
+        lib.mtadgat_eval_score_order_scratch.restype = sz
+        lib.mtadgat_eval_score_order.argtypes = [vp, i64, ci, vp, sz, vp, vp]
+        lib.mtadgat_eval_curve_scratch.argtypes = [i64, ci]
+        lib.mtadgat_eval_curve_scratch.restype = sz
+        lib.mtadgat_eval_curve.argtypes = [vp, vp, i64, ci, ci, vp, sz, vp, vp, vp, ctypes.POINTER(ctypes.c_int64), vp]
         lib.mtadgat_last_error.restype = ctypes.c_char_p
         lib._eval_bound = True
     return lib
@@ -504,7 +521,7 @@ def pot_eval(init_scores, scores, labels, q=1e-3, level=0.98, dynamic=False, max
 
 
 def predict_anomalies(model, train, test, labels=None, target_dims=None, gamma=1.0, scale_scores=False, use_mov_av=False, reg_level=1,
-                      bf_search=None, events=None, pot=None):
+                      bf_search=None, events=None, pot=None, curves=None):
     """What Predictor.predict_anomalies (prediction.py:106-165) derives from a train and a test series, with every score array
     staying on the device.  train, test: device-resident (N, F) series; labels: the test labels for rows window_size.. (one
     per score) or None; bf_search: (start, end, step_num) for the best-F1 sweep, run when labels are given too.
@@ -519,6 +536,8 @@ def predict_anomalies(model, train, test, labels=None, target_dims=None, gamma=1
                                   against find_epsilon(train_scores, reg_level), with test_per_dim, the feature thresholds and the labels
       pot_result                  only with pot=dict(q=, level=, dynamic=) (any subset): pot_eval(train_scores, test_scores, labels, ...),
                                   SPOT calibrated on the training scores; without labels its threshold only
+      curve_result                only with curves=dict(adjust=) (or an empty dict): ranking_metrics(test_scores, labels, adjust), or None
+                                  without labels
     Not included: `adjust_anomaly_scores` for MSL / SMAP, which needs the datasets' channel metadata files and the reference
     source to pin its behaviour, neither of which this package ships."""
     train_scores, train_per_dim = model.anomaly_scores(train, target_dims=target_dims, gamma=gamma, scale_scores=scale_scores,
@@ -539,6 +558,11 @@ def predict_anomalies(model, train, test, labels=None, target_dims=None, gamma=1
         if unknown:
             raise ValueError(f"pot takes q, level and dynamic, got {sorted(unknown)}")
         out["pot_result"] = pot_eval(train_scores, test_scores, labels, **pot)
+    if curves is not None:
+        unknown = set(curves) - {"adjust"}
+        if unknown:
+            raise ValueError(f"curves takes adjust, got {sorted(unknown)}")
+        out["curve_result"] = ranking_metrics(test_scores, labels, **curves) if labels is not None else None
     if events is not None:
         unknown = set(events) - {"merge_gap", "min_length", "top_k"}
         if unknown:
@@ -739,3 +763,124 @@ def explain_events(model, values, events, which=None, max_events=64, **attributi
     attr = model.score_attribution(values, peaks, **attribution_kwargs)
     mag = attr.abs()
     return {"peaks": peaks, "attributions": attr, "per_feature": mag.sum(1), "per_lag": mag.sum(2)}
+
+
+# ---- ranking curves ----------------------------------------------------------------------------------------------------------------
+def score_order(scores, descending=True):
+    """The indices of a 1-D float32 GPU tensor in rank order, (n,) int64 on the device: largest first (or smallest first), ties in
+    ascending index, -0.0 and +0.0 one value, +-inf ordinary values, NaNs last in both directions in index order.  A stable
+    radix sort without atomics: bitwise reproducible, any 1 <= n < 2**31."""
+    lib = _lib()
+    s = _dev1d(scores, torch.float32, "scores")
+    n = s.numel()
+    if n < 1:
+        raise ValueError("scores is empty")
+    nbytes = lib.mtadgat_eval_score_order_scratch(n)
+    if nbytes == 0:
+        raise ValueError(f"{n} scores are refused (fewer than 2**31)")
+    scratch = _native._empty((nbytes + 7) // 8, dtype=torch.float64, device=s.device)
+    order = torch.empty(n, dtype=torch.int64, device=s.device)
+    with torch.cuda.device(s.device):
+        rc = lib.mtadgat_eval_score_order(s.data_ptr(), n, 1 if descending else 0, scratch.data_ptr(), scratch.numel() * 8, order.data_ptr(),
+                                          _stream(s))
+    if rc != 0:
+        _fail(lib, rc, "eval_score_order")
+    return order
+
+
+def _adjust_code(adjust):
+    """(mode, K) of the library for adjust = None | "point" | ("k", K)."""
+    if adjust is None:
+        return 0, 0
+    if isinstance(adjust, str):
+        if adjust == "point":
+            return 1, 0
+    elif isinstance(adjust, (tuple, list)) and len(adjust) == 2 and adjust[0] == "k":
+        k = adjust[1]
+        if isinstance(k, (int, np.integer)) and not isinstance(k, bool) and 0 <= k <= 100:
+            return 2, int(k)
+        raise ValueError(f"K of ('k', K) must be an integer in [0, 100], got {k!r}")
+    raise ValueError(f"adjust must be None, 'point' or ('k', K), got {adjust!r}")
+
+
+_CURVE_SUMMARY = 12      # int64 the library copies back: G, n_pos, n_neg, nan_pos, nan_neg, 2 x AUROC numerator, AP sum, best ...
+
+
+def _curve(scores, labels, adjust):
+    lib = _lib()
+    s = _dev1d(scores, torch.float32, "scores")
+    lab = _labels_u8(labels)
+    mode, k = _adjust_code(adjust)
+    n = s.numel()
+    if n < 1:
+        raise ValueError("scores is empty")
+    if lab.numel() != n or lab.device != s.device:
+        raise ValueError("scores and labels must have the same length and live on the same device")
+    nbytes = lib.mtadgat_eval_curve_scratch(n, mode)
+    if nbytes == 0:
+        raise ValueError(f"{n} scores are refused (fewer than 2**31)")
+    scratch = _native._empty((nbytes + 7) // 8, dtype=torch.float64, device=s.device)
+    thr = _native._empty(n, dtype=torch.float32, device=s.device)
+    tp = _native._empty(n, dtype=torch.int64, device=s.device)
+    fp = _native._empty(n, dtype=torch.int64, device=s.device)
+    summary = (ctypes.c_int64 * _CURVE_SUMMARY)()
+    with torch.cuda.device(s.device):
+        rc = lib.mtadgat_eval_curve(s.data_ptr(), lab.data_ptr(), n, mode, k, scratch.data_ptr(), scratch.numel() * 8, thr.data_ptr(),
+                                    tp.data_ptr(), fp.data_ptr(), summary, _stream(s))
+    if rc != 0:
+        _fail(lib, rc, "eval_curve")
+    g = summary[0]
+    thr, tp, fp = thr[:g], tp[:g], fp[:g]
+    if 2 * g <= n:          # few distinct values: do not keep the n-entry buffers alive behind the views
+        thr, tp, fp = thr.clone(), tp.clone(), fp.clone()
+    return s, lab, thr, tp, fp, list(summary)
+
+
+def ranking_curve(scores, labels, adjust=None):
+    """Every operating point of a score array against labels (read as point_adjust_counts reads them): a dict of
+      thresholds        (G,) float32 on the device: the distinct non-NaN values of the adjusted scores, descending
+      tp, fp            (G,) int64: the positives / negatives with adjusted score >= thresholds[g]
+      n_pos, n_neg, nan_pos, nan_neg     Python ints; a NaN score is never flagged: a false or true negative at every threshold
+    adjust=None ranks the scores as they are (-0.0 read as +0.0); "point" gives every sample of a labelled segment the segment's
+    largest non-NaN score (sample 0 of a segment that starts at index 0 keeps its own: adjust_predicts' back-fill never reaches
+    index 0), so that point g equals point_adjust_counts at the float32 just below thresholds[g]; ("k", K) is PA%K: a sample of a
+    segment of length L takes max(own, the m-th largest non-NaN score of the segment), m = K * L // 100 + 1, and keeps its own when
+    the segment has fewer than m non-NaN scores.  The scores are adjusted, sorted and scanned on the device; the counts are the only
+    values read back.  Bitwise reproducible."""
+    _, _, thr, tp, fp, summary = _curve(scores, labels, adjust)
+    return {"thresholds": thr, "tp": tp, "fp": fp, "n_pos": summary[1], "n_neg": summary[2], "nan_pos": summary[3], "nan_neg": summary[4]}
+
+
+def ranking_metrics(scores, labels, adjust=None):
+    """Threshold-free quality of a score array under ranking_curve's `adjust`: a dict of Python numbers
+      auroc               area under the ROC curve, ties joined by straight lines, the NaN samples one last tie group; an exact
+                          integer numerator from the device over 2 n_pos n_neg; NaN when a class is empty
+      average_precision   sum over the tie groups of (positives of the group) x precision at the group / n_pos (scikit-learn's)
+      best                the curve point of largest F1 (the reference's 1e-5 guards; the highest threshold among equals), chosen on
+                          the device, in epsilon_eval's shape: f1, precision, recall, TP, TN, FP, FN, threshold -- flagged means
+                          adjusted score >= threshold -- and with adjust="point" the latency of point_adjust_counts just below that
+                          threshold (None at threshold -inf, below which no float32 lies); None when every score is NaN
+      best_index          its position in ranking_curve's arrays (None with best)
+      n_thresholds, n_pos, n_neg, adjust"""
+    s, lab, _, _, _, summary = _curve(scores, labels, adjust)
+    g, n_pos, n_neg, nan_pos, nan_neg, auc2, ap_bits, best, best_tp, best_fp, thr_bits = summary[:11]
+    auroc = auc2 / (2 * n_pos * n_neg) if n_pos and n_neg else float("nan")
+    ap_sum = float(np.array([ap_bits], dtype=np.int64).view(np.float64)[0])
+    out = {"auroc": auroc, "average_precision": ap_sum / n_pos if n_pos else float("nan"), "best": None, "best_index": None, "n_thresholds": g,
+           "n_pos": n_pos, "n_neg": n_neg, "adjust": adjust}
+    if best >= 0:
+        v = float(np.array([thr_bits], dtype=np.uint32).view(np.float32)[0])
+        counts = [float(best_tp), float(n_neg - best_fp), float(best_fp), float(n_pos - best_tp)]
+        f1, prec, rec = _scores_from_counts(*counts)
+        res = {"f1": f1, "precision": prec, "recall": rec, "TP": counts[0], "TN": counts[1], "FP": counts[2], "FN": counts[3], "threshold": v}
+        if adjust == "point":
+            below = float(np.nextafter(np.float32(v), np.float32(-np.inf)))
+            row = None
+            if v > -math.inf:           # no float32 lies below -inf: `> below` cannot flag what `>= v` flags
+                row = point_adjust_counts(s, lab.bool(), [below], compare_f32=True, max_segments=max(65536, (s.numel() + 1) // 2))[0]
+            if row is not None and (row[0] != counts[0] or row[2] != counts[2]):
+                raise RuntimeError(f"the curve's best point (TP {counts[0]}, FP {counts[2]}) differs from point_adjust_counts' "
+                                   f"(TP {row[0]}, FP {row[2]}) at threshold {below!r}")
+            res["latency"] = row[4] / (row[5] + 1e-4) if row is not None else None
+        out["best"], out["best_index"] = res, best
+    return out
