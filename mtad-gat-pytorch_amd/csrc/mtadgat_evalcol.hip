@@ -1,6 +1,7 @@
 // Per-column order statistics and the exponentially weighted mean of the anomaly scores (reference prediction.py:65-165:
 // --scale_scores, --use_mov_av), so that the Predictor's post-processing stays on the device with the scores.
 //
+//   Shared primitives (the wave sum, the order bits of a float, the scratch carver) come from mtadgat_scan.h.
 //   k_eval_colq_*: np.percentile ("linear") of every column of an (n, d) array for nq probabilities at once.  The two order
 //       statistics each probability needs are EXACT: a most-significant-digit radix select (four 8-bit digits) on the
 //       order-preserving 32-bit key of the float, all columns and all 2 nq ranks per pass.  Histograms are built with integer
@@ -8,7 +9,7 @@
 //       the same bits -- and the digit of every (column, rank) is chosen on the device between the passes.  Nothing is sorted.
 //   k_eval_ewm_*: pandas' ewm(span).mean() (adjust=True) as a blocked scan in float64: chunk-local scans, one wave that
 //       composes the chunk carries in chunk order, and a pass that applies carry and closed-form denominator.  No atomics.
-#include "mtadgat_device.h"
+#include "mtadgat_scan.h"
 
 namespace mtadgat {
 
@@ -17,14 +18,9 @@ constexpr int CQ_CT = 8;        // columns per workgroup: 8 neighbouring lanes r
 constexpr int CQ_RT = 6;        // ranks per workgroup: CQ_RT * CQ_CT histograms of 256 bins = 48 KiB of LDS
 constexpr int CQ_ROWS = 256 / CQ_CT;
 
-// float -> unsigned with the same order (negative: all bits flipped; non-negative: sign bit set); -0.0 sorts just below +0.0
-__device__ __forceinline__ unsigned colq_key(float v) {
-    const unsigned u = __builtin_bit_cast(unsigned, v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float colq_value(unsigned k) {
-    return __builtin_bit_cast(float, (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
+// the select's key: the order bits as they stand, so -0.0 sorts just below +0.0 (both are 0 in the interpolation)
+__device__ __forceinline__ unsigned colq_key(float v) { return float_order_bits(v); }
+__device__ __forceinline__ float colq_value(unsigned k) { return float_from_order_bits(k); }
 // position of probability q among n sorted values: lo = floor(q (n - 1)) in float64, the weight of s[lo + 1] returned in *frac
 __device__ __forceinline__ unsigned colq_rank(double q, long n, double* frac) {
     const double pos = __dmul_rn(q, (double)(n - 1));     // rounded product: a fused pos - lo would use the unrounded one
@@ -121,12 +117,7 @@ __global__ void __launch_bounds__(64) k_eval_colq_pick(unsigned* __restrict__ st
     const uint4 b = *bins;
     *bins = make_uint4(0u, 0u, 0u, 0u);
     const unsigned mine = b.x + b.y + b.z + b.w;
-    unsigned incl = mine;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned t = __shfl_up(incl, off);
-        if (lane >= off) incl += t;
-    }
+    const unsigned incl = wave_inclusive_sum(mine);
     const unsigned k = state[2 * idx + 1];
     unsigned below = incl - mine;
     if (below <= k && k < incl) {                       // exactly one lane: the bins hold more than k keys in all
@@ -237,19 +228,19 @@ using namespace mtadgat;
 
 namespace {
 
-struct ColqLayout {
-    size_t q, hist, state, nan, ord, bytes;     // byte offsets
+struct ColqScratch {
+    double* q;
+    unsigned *hist, *state, *nanflag;
+    float* ord;
 };
-ColqLayout colq_layout(int64_t d, int64_t nq) {
+ColqScratch colq_scratch(ScratchCarver& c, int64_t d, int64_t nq) {
     const size_t cells = (size_t)d * 2 * (size_t)nq;
-    ColqLayout l;
-    l.q = 0;
-    l.hist = 8 * (size_t)nq;
-    l.hist = (l.hist + 15) / 16 * 16;           // the pick kernel reads the bins as 16-byte words
-    l.state = l.hist + cells * 256 * 4;
-    l.nan = l.state + cells * 2 * 4;
-    l.ord = l.nan + (size_t)d * 4;
-    l.bytes = l.ord + cells * 4;
+    ColqScratch l;
+    l.q = c.take<double>(nq);
+    l.hist = c.take<unsigned>(cells * 256, 16);         // the pick kernel reads the bins as 16-byte words
+    l.state = c.take<unsigned>(cells * 2, 4);           // 4-byte regions back to back
+    l.nanflag = c.take<unsigned>(d, 4);
+    l.ord = c.take<float>(cells, 4);
     return l;
 }
 
@@ -273,20 +264,16 @@ void colq_passes(const float* a_dev, long n, int d, long ld, int R, unsigned* st
 
 namespace mtadgat {
 
-size_t column_rank_scratch(int d) { return colq_layout(d, 1).bytes; }
+size_t column_rank_scratch(int d) { return scratch_bytes_of([&](ScratchCarver& c) { colq_scratch(c, d, 1); }); }
 
 int launch_column_rank(const float* a_dev, long n, int d, long ld, long rank, void* scratch_dev, const float** ord_dev, hipStream_t s) {
-    const ColqLayout l = colq_layout(d, 1);
-    char* base = static_cast<char*>(scratch_dev);
-    unsigned* hist = reinterpret_cast<unsigned*>(base + l.hist);
-    unsigned* state = reinterpret_cast<unsigned*>(base + l.state);
-    unsigned* nanflag = reinterpret_cast<unsigned*>(base + l.nan);
-    float* ord = reinterpret_cast<float*>(base + l.ord);
+    ScratchCarver carver(scratch_dev);
+    const ColqScratch l = colq_scratch(carver, d, 1);
     const long init_blocks = ((long)d * 256 + 255) / 256;
-    hipLaunchKernelGGL(k_eval_colq_init_rank, dim3((unsigned)(init_blocks < 2048 ? init_blocks : 2048)), dim3(256), 0, s, (unsigned)rank, d, state,
-                       nanflag, hist);
-    colq_passes(a_dev, n, d, ld, 1, state, hist, nanflag, ord, s);
-    *ord_dev = ord;
+    hipLaunchKernelGGL(k_eval_colq_init_rank, dim3((unsigned)(init_blocks < 2048 ? init_blocks : 2048)), dim3(256), 0, s, (unsigned)rank, d, l.state,
+                       l.nanflag, l.hist);
+    colq_passes(a_dev, n, d, ld, 1, l.state, l.hist, l.nanflag, l.ord, s);
+    *ord_dev = l.ord;
     return (int)hipGetLastError();
 }
 
@@ -296,7 +283,7 @@ extern "C" {
 
 size_t mtadgat_eval_column_quantiles_scratch(int64_t n, int d, int nq) {
     if (n < 1 || d < 1 || nq < 1) return 0;
-    return colq_layout(d, nq).bytes;
+    return scratch_bytes_of([&](ScratchCarver& c) { colq_scratch(c, d, nq); });
 }
 
 int mtadgat_eval_column_quantiles(const float* a_dev, int64_t n, int d, int64_t ld, const double* q_host, int nq, void* scratch_dev,
@@ -308,16 +295,11 @@ int mtadgat_eval_column_quantiles(const float* a_dev, int64_t n, int d, int64_t 
     if (nq < 1 || nq > 4096) return record_error(-1, "column_quantiles: nq must lie in [1, 4096]");
     for (int i = 0; i < nq; ++i)
         if (!(q_host[i] >= 0.0 && q_host[i] <= 1.0)) return record_error(-1, "column_quantiles: q outside [0, 1]");
-    const ColqLayout l = colq_layout(d, nq);
-    if (scratch_bytes < l.bytes) return record_error(-5, "column_quantiles: scratch too small (see mtadgat_eval_column_quantiles_scratch)");
+    ScratchCarver carver(scratch_dev);
+    const ColqScratch l = colq_scratch(carver, d, nq);
+    if (scratch_bytes < carver.bytes()) return record_error(-5, "column_quantiles: scratch too small (see mtadgat_eval_column_quantiles_scratch)");
     if ((uintptr_t)scratch_dev & 15) return record_error(-5, "column_quantiles: scratch must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    char* base = static_cast<char*>(scratch_dev);
-    double* q = reinterpret_cast<double*>(base + l.q);
-    unsigned* hist = reinterpret_cast<unsigned*>(base + l.hist);
-    unsigned* state = reinterpret_cast<unsigned*>(base + l.state);
-    unsigned* nanflag = reinterpret_cast<unsigned*>(base + l.nan);
-    float* ord = reinterpret_cast<float*>(base + l.ord);
     const int R = 2 * nq;
     const long cells = (long)d * R;
     // q_host is not touched after this call returns: few probabilities ride in the kernel arguments, more are copied and waited for
@@ -325,15 +307,16 @@ int mtadgat_eval_column_quantiles(const float* a_dev, int64_t n, int d, int64_t 
     const int inl = nq <= CQ_INLINE;
     if (inl) {
         for (int i = 0; i < nq; ++i) pv.v[i] = q_host[i];
-    } else if (hipMemcpyAsync(q, q_host, nq * sizeof(double), hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+    } else if (hipMemcpyAsync(l.q, q_host, nq * sizeof(double), hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
         return record_error(-3, "column_quantiles: copy of q failed");
     }
     const long init_blocks = (cells * 256 + 255) / 256;
-    hipLaunchKernelGGL(k_eval_colq_init, dim3((unsigned)(init_blocks < 2048 ? init_blocks : 2048)), dim3(256), 0, s, q, pv, inl, nq, (long)n, d,
-                       state, nanflag, hist);
-    colq_passes(a_dev, (long)n, d, (long)ld, R, state, hist, nanflag, ord, s);
+    hipLaunchKernelGGL(k_eval_colq_init, dim3((unsigned)(init_blocks < 2048 ? init_blocks : 2048)), dim3(256), 0, s, l.q, pv, inl, nq, (long)n, d,
+                       l.state, l.nanflag, l.hist);
+    colq_passes(a_dev, (long)n, d, (long)ld, R, l.state, l.hist, l.nanflag, l.ord, s);
     const long outs = (long)nq * d;
-    hipLaunchKernelGGL(k_eval_colq_interp, dim3((unsigned)((outs + 255) / 256)), dim3(256), 0, s, ord, q, nanflag, (long)n, d, nq, out_dev);
+    hipLaunchKernelGGL(k_eval_colq_interp, dim3((unsigned)((outs + 255) / 256)), dim3(256), 0, s, (const float*)l.ord, (const double*)l.q,
+                       (const unsigned*)l.nanflag, (long)n, d, nq, out_dev);
     return hipGetLastError() == hipSuccess ? 0 : record_error(-3, "column_quantiles: kernel launch failed");
 }
 

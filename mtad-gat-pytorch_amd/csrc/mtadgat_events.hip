@@ -3,21 +3,17 @@
 //   k_eval_runs_*: the maximal runs of flagged samples as ordered [start, end) pairs, near-by runs merged, short events dropped.
 //       Three stream compactions of the same shape -- samples -> raw runs, raw runs -> merged runs (a run opens an event when the
 //       gap before it is wider than merge_gap and closes one when the gap after it is), merged runs -> events of at least
-//       min_length -- each a blocked scan like k_eval_ewm_*: per-chunk counts, one wave that composes the chunk carries in chunk
-//       order, and a pass that recomputes the predicate and writes every item at its rank.  Within a wave the rank is the
-//       population count of the __ballot mask below the lane.  The k-th "closes" item pairs with the k-th "opens" item, so one
-//       scan (over the opens) ranks both.  No atomics, nothing sorted: the output order is the input order.
+//       min_length -- each the blocked scan of counts of mtadgat_scan.h over the "opens" predicate.  The k-th "closes" item pairs
+//       with the k-th "opens" item, so that one scan ranks both.  No atomics, nothing sorted: the output order is the input order.
 //   k_eval_run_part / _final: per-run peak, mean, per-column means, hit counts and the top columns.  Rows are cut into blocks of
-//       RS_RB rows per run; a workgroup reduces a block with lanes on columns (coalesced rows) in a fixed tree and stores the
+//       SPAN_RB rows per run; a workgroup reduces a block with lanes on columns (coalesced rows) in a fixed tree and stores the
 //       partial in the block's own slot; one wave per run then adds the slots in block order, so the bits depend on the data and
-//       on RS_RB only, not on the grid.  The top columns are top_k rounds of a wave-wide arg-max over an ordered integer key.
+//       on SPAN_RB only, not on the grid.  The top columns are top_k rounds of a wave-wide arg-max over an ordered integer key.
 //   k_eval_first_hit: the first flagged sample of every run, one wave per run, 64 samples per step, ballot + count-trailing-zeros.
-#include "mtadgat_device.h"
+#include "mtadgat_scan.h"
 
 namespace mtadgat {
 
-constexpr int RUN_L = 1024;      // items per chunk of the compaction scans: 4 waves x 4 rounds x 64 lanes
-constexpr int RS_RB = 1024;      // rows per block of the segmented reductions
 constexpr long NO_INDEX = 0x7fffffffffffffffL;
 
 // flag_i = score_i > threshold (float64, or float32 with cmp_f32: k_eval_adjust's convention; NaN and equality are not flagged),
@@ -77,40 +73,10 @@ template <class Op>
 __global__ void __launch_bounds__(256) k_eval_runs_count(Op op, const long* __restrict__ n_dev, long n_host, unsigned* __restrict__ T) {
     __shared__ unsigned sm[4];
     const long n = item_count(n_dev, n_host);
-    const long base = (long)blockIdx.x * RUN_L;
+    const long base = (long)blockIdx.x * CHUNK_L;
     if (base >= n) return;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned c = 0;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const long i = base + wave * 256 + r * 64 + lane;
-        c += (unsigned)__popcll(__ballot(i < n && op.opens(i, n)));
-    }
-    if (lane == 0) sm[wave] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) T[blockIdx.x] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
-}
-
-// C[c] = number of opening items before chunk c, 64 chunks per step of one wave in chunk order; *total = all of them
-__global__ void __launch_bounds__(64) k_eval_runs_carry(const unsigned* __restrict__ T, const long* __restrict__ n_dev, long n_host,
-                                                         unsigned* __restrict__ C, long* __restrict__ total) {
-    const long n = item_count(n_dev, n_host);
-    const long nchunks = (n + RUN_L - 1) / RUN_L;
-    const int lane = threadIdx.x;
-    unsigned run = 0;
-    for (long base = 0; base < nchunks; base += 64) {
-        const long i = base + lane;
-        const unsigned mine = i < nchunks ? T[i] : 0u;
-        unsigned s = mine;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const unsigned t = __shfl_up(s, off);
-            if (lane >= off) s += t;
-        }
-        if (i < nchunks) C[i] = run + s - mine;
-        run += __shfl(s, 63);
-    }
-    if (lane == 0) *total = (long)run;
+    const ChunkRank open = chunk_rank(base, [&](long i) { return i < n && op.opens(i, n); }, sm);
+    if (threadIdx.x == 0) T[blockIdx.x] = open.total;
 }
 
 // every opening item to rank (openings before it), every closing item to rank (openings up to and including it) - 1
@@ -118,48 +84,28 @@ template <class Op>
 __global__ void __launch_bounds__(256) k_eval_runs_emit(Op op, const long* __restrict__ n_dev, long n_host, const unsigned* __restrict__ C) {
     __shared__ unsigned sm[4];
     const long n = item_count(n_dev, n_host);
-    const long base = (long)blockIdx.x * RUN_L;
+    const long base = (long)blockIdx.x * CHUNK_L;
     if (base >= n) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    bool p[4], q[4];
-    unsigned long long m[4];
-    unsigned c = 0;
+    bool q[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const long i = base + wave * 256 + r * 64 + lane;
-        p[r] = i < n && op.opens(i, n);
         q[r] = i < n && op.closes(i, n);
-        m[r] = __ballot(p[r]);
-        c += (unsigned)__popcll(m[r]);
     }
-    if (lane == 0) sm[wave] = c;
-    __syncthreads();
-    long rank = C[blockIdx.x];
-    for (int w = 0; w < wave; ++w) rank += sm[w];
-    const unsigned long long below = (1ull << lane) - 1ull;
+    const ChunkRank open = chunk_rank(base, [&](long i) { return i < n && op.opens(i, n); }, sm);
+    const long rank0 = C[blockIdx.x];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const long i = base + wave * 256 + r * 64 + lane;
-        const long ex = rank + __popcll(m[r] & below);
-        if (p[r]) op.put_open(ex, i);
-        if (q[r]) op.put_close(ex + (p[r] ? 1 : 0) - 1, i);       // a closing item lies in a run that opened at or before it
-        rank += __popcll(m[r]);
+        const bool p = open.set[r];
+        const long ex = rank0 + rank_before(open, r);
+        if (p) op.put_open(ex, i);
+        if (q[r]) op.put_close(ex + (p ? 1 : 0) - 1, i);           // a closing item lies in a run that opened at or before it
     }
 }
 
 // ---- per-run statistics ----------------------------------------------------------------------------------------------------------
-// the run's bounds cut to [0, n]; an empty or inverted run has length 0
-__device__ __forceinline__ void run_bounds(const long* __restrict__ start, const long* __restrict__ end, long k, long n, long& s, long& e) {
-    s = start[k];
-    e = end[k];
-    if (s < 0) s = 0;
-    if (e > n) e = n;
-    if (e < s) e = s;
-}
-// slot of row block b of run k: runs are disjoint and ascending, so floor(s / RS_RB) + k + b is different for every (k, b) and
-// stays below n / RS_RB + count + 1
-__device__ __forceinline__ long run_slot0(long s, long k) { return s / RS_RB + k; }
-
 // (value, index) of the larger value, the smaller index among equals
 __device__ __forceinline__ void peak_merge(float& best, long& arg, float v, long i) {
     if (v > best || (v == best && i < arg)) { best = v; arg = i; }
@@ -178,13 +124,13 @@ __global__ void __launch_bounds__(256) k_eval_run_part(const float* __restrict__
     const int tid = threadIdx.x;
     const long k = blockIdx.x;
     long s, e;
-    run_bounds(start, end, k, n, s, e);
-    const long nb = (e - s + RS_RB - 1) / RS_RB;
-    const long slot0 = run_slot0(s, k);
+    span_bounds(start, end, k, n, s, e);
+    const long nb = (e - s + SPAN_RB - 1) / SPAN_RB;
+    const long slot0 = span_slot0(s, k);
     const int c = tid & (ct - 1), rsub = tid / ct, rp = 256 / ct;
     for (long b = blockIdx.y; b < nb; b += gridDim.y) {
-        const long r0 = s + b * RS_RB;
-        const int rows = e - r0 < RS_RB ? (int)(e - r0) : RS_RB;
+        const long r0 = s + b * SPAN_RB;
+        const int rows = e - r0 < SPAN_RB ? (int)(e - r0) : SPAN_RB;
         const long slot = slot0 + b;
         double sum = 0.0;
         float best = -INFINITY;
@@ -237,9 +183,7 @@ __global__ void __launch_bounds__(256) k_eval_run_part(const float* __restrict__
 __device__ __forceinline__ unsigned long long rank_key(float m, int col) {
     unsigned ord = 1u;
     if (m == m) {
-        if (m == 0.f) m = 0.f;
-        const unsigned u = __builtin_bit_cast(unsigned, m);
-        ord = (u & 0x80000000u) ? ~u : (u | 0x80000000u);          // order-preserving; -inf maps to 0x007fffff
+        ord = float_order_bits(m == 0.f ? 0.f : m);                 // -inf maps to 0x007fffff
     }
     return ((unsigned long long)ord << 32) | (unsigned long long)(0xffffffffu - (unsigned)col);
 }
@@ -257,10 +201,10 @@ __global__ void __launch_bounds__(64) k_eval_run_final(long n, const long* __res
     const long k = blockIdx.x;
     const int lane = threadIdx.x;
     long s, e;
-    run_bounds(start, end, k, n, s, e);
+    span_bounds(start, end, k, n, s, e);
     const long len = e - s;
-    const long nb = (len + RS_RB - 1) / RS_RB;
-    const long slot0 = run_slot0(s, k);
+    const long nb = (len + SPAN_RB - 1) / SPAN_RB;
+    const long slot0 = span_slot0(s, k);
     if (lane == 0) {
         double sum = 0.0;
         float best = -INFINITY;
@@ -314,7 +258,7 @@ __global__ void __launch_bounds__(256) k_eval_first_hit(FlagSrc f, long n, const
     const int lane = threadIdx.x & 63;
     if (k >= count) return;
     long s, e;
-    run_bounds(start, end, k, n, s, e);
+    span_bounds(start, end, k, n, s, e);
     long hit = -1;
     for (long base = s; base < e; base += 64) {
         const long i = base + lane;
@@ -330,46 +274,48 @@ using namespace mtadgat;
 
 namespace {
 
-size_t up8(size_t v) { return (v + 7) / 8 * 8; }
-
-struct RunsLayout {
-    size_t counts, T, C, rs, re, ms, me, bytes;     // byte offsets
+struct RunsScratch {
+    long* counts;                // raw, merged and kept counts
+    unsigned *T, *C;
+    int *rs, *re, *ms, *me;
     long nchunks, max_raw;
 };
-RunsLayout runs_layout(int64_t n) {
-    RunsLayout l;
-    l.nchunks = (long)((n + RUN_L - 1) / RUN_L);
+RunsScratch runs_scratch(ScratchCarver& c, int64_t n) {
+    RunsScratch l;
+    l.nchunks = (long)((n + CHUNK_L - 1) / CHUNK_L);
     l.max_raw = (long)((n + 1) / 2);                // flagged and unflagged samples alternate
-    l.counts = 0;                                   // raw, merged and kept counts (int64), padded to 32 bytes
-    l.T = 32;
-    l.C = l.T + up8(4 * (size_t)l.nchunks);
-    l.rs = l.C + up8(4 * (size_t)l.nchunks);
-    l.re = l.rs + up8(4 * (size_t)l.max_raw);
-    l.ms = l.re + up8(4 * (size_t)l.max_raw);
-    l.me = l.ms + up8(4 * (size_t)l.max_raw);
-    l.bytes = l.me + up8(4 * (size_t)l.max_raw);
+    l.counts = c.take<long>(4);
+    l.T = c.take<unsigned>(l.nchunks);
+    l.C = c.take<unsigned>(l.nchunks);
+    l.rs = c.take<int>(l.max_raw);
+    l.re = c.take<int>(l.max_raw);
+    l.ms = c.take<int>(l.max_raw);
+    l.me = c.take<int>(l.max_raw);
     return l;
 }
 
-struct StatsLayout {
-    size_t ssum, sarg, smax, psum, phit, bytes;     // byte offsets
+struct StatsScratch {
+    double* ssum;
+    long* sarg;
+    float* smax;
+    double* psum;
+    int* phit;
 };
-StatsLayout stats_layout(int64_t n, int64_t count, int d) {
-    const size_t slots = (size_t)(n / RS_RB) + (size_t)count + 2;
-    StatsLayout l;
-    l.ssum = 0;
-    l.sarg = l.ssum + 8 * slots;
-    l.smax = l.sarg + 8 * slots;
-    l.psum = l.smax + up8(4 * slots);
-    l.phit = l.psum + 8 * slots * (size_t)d;
-    l.bytes = l.phit + up8(4 * slots * (size_t)d);
+StatsScratch stats_scratch(ScratchCarver& c, int64_t n, int64_t count, int d) {
+    const size_t slots = span_slots(n, count);
+    StatsScratch l;
+    l.ssum = c.take<double>(slots);
+    l.sarg = c.take<long>(slots);
+    l.smax = c.take<float>(slots);
+    l.psum = c.take<double>(slots * (size_t)d);
+    l.phit = c.take<int>(slots * (size_t)d);
     return l;
 }
 
 template <class Op>
 void compact(const Op& op, long grid, const long* n_dev, long n_host, unsigned* T, unsigned* C, long* total, hipStream_t s) {
     hipLaunchKernelGGL(k_eval_runs_count<Op>, dim3((unsigned)grid), dim3(256), 0, s, op, n_dev, n_host, T);
-    hipLaunchKernelGGL(k_eval_runs_carry, dim3(1), dim3(64), 0, s, T, n_dev, n_host, C, total);
+    hipLaunchKernelGGL(k_scan_carry, dim3(1), dim3(64), 0, s, (const unsigned*)T, n_dev, grid, C, total);
     hipLaunchKernelGGL(k_eval_runs_emit<Op>, dim3((unsigned)grid), dim3(256), 0, s, op, n_dev, n_host, C);
 }
 
@@ -387,11 +333,11 @@ FlagSrc flag_source(const float* score, const unsigned char* label, double thres
 
 extern "C" {
 
-int mtadgat_eval_runs_chunk(void) { return RUN_L; }
+int mtadgat_eval_runs_chunk(void) { return CHUNK_L; }
 
 size_t mtadgat_eval_runs_scratch(int64_t n) {
     if (n < 1 || n > 2147483647LL) return 0;
-    return runs_layout(n).bytes;
+    return scratch_bytes_of([&](ScratchCarver& c) { runs_scratch(c, n); });
 }
 
 int mtadgat_eval_runs(const float* score_dev, const unsigned char* label_dev, int64_t n, double threshold, int compare_f32,
@@ -403,26 +349,19 @@ int mtadgat_eval_runs(const float* score_dev, const unsigned char* label_dev, in
     if (merge_gap < 0) return record_error(-1, "runs: merge_gap must be >= 0");
     if (min_length < 1) return record_error(-1, "runs: min_length must be >= 1");
     if (max_runs < 1) return record_error(-1, "runs: max_runs must be >= 1");
-    const RunsLayout l = runs_layout(n);
-    if (scratch_bytes < l.bytes) return record_error(-5, "runs: scratch too small (see mtadgat_eval_runs_scratch)");
+    ScratchCarver carver(scratch_dev);
+    const RunsScratch l = runs_scratch(carver, n);
+    if (scratch_bytes < carver.bytes()) return record_error(-5, "runs: scratch too small (see mtadgat_eval_runs_scratch)");
     if ((uintptr_t)scratch_dev & 7) return record_error(-5, "runs: scratch must be 8-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    char* base = static_cast<char*>(scratch_dev);
-    long* counts = reinterpret_cast<long*>(base + l.counts);
-    unsigned* T = reinterpret_cast<unsigned*>(base + l.T);
-    unsigned* C = reinterpret_cast<unsigned*>(base + l.C);
-    int* rs = reinterpret_cast<int*>(base + l.rs);
-    int* re = reinterpret_cast<int*>(base + l.re);
-    int* ms = reinterpret_cast<int*>(base + l.ms);
-    int* me = reinterpret_cast<int*>(base + l.me);
     // the run counts stay on the device between the stages, so the later grids cover the most runs n samples can hold
-    const long run_grid = (l.max_raw + RUN_L - 1) / RUN_L;
-    compact(RawRuns{flag_source(score_dev, label_dev, threshold, compare_f32), rs, re}, l.nchunks, nullptr, (long)n, T, C, counts, s);
-    compact(MergeRuns{rs, re, (long)merge_gap, ms, me}, run_grid, counts, 0L, T, C, counts + 1, s);
-    compact(KeepRuns{ms, me, (long)min_length, (long)max_runs, reinterpret_cast<long*>(start_dev), reinterpret_cast<long*>(end_dev)}, run_grid,
-            counts + 1, 0L, T, C, counts + 2, s);
+    const long run_grid = (l.max_raw + CHUNK_L - 1) / CHUNK_L;
+    compact(RawRuns{flag_source(score_dev, label_dev, threshold, compare_f32), l.rs, l.re}, l.nchunks, nullptr, (long)n, l.T, l.C, l.counts, s);
+    compact(MergeRuns{l.rs, l.re, (long)merge_gap, l.ms, l.me}, run_grid, l.counts, 0L, l.T, l.C, l.counts + 1, s);
+    compact(KeepRuns{l.ms, l.me, (long)min_length, (long)max_runs, reinterpret_cast<long*>(start_dev), reinterpret_cast<long*>(end_dev)}, run_grid,
+            l.counts + 1, 0L, l.T, l.C, l.counts + 2, s);
     if (hipGetLastError() != hipSuccess) return record_error(-3, "runs: kernel launch failed");
-    if (hipMemcpyAsync(count_host, counts + 2, sizeof(int64_t), hipMemcpyDeviceToHost, s) != hipSuccess) return record_error(-3, "runs: copy failed");
+    if (hipMemcpyAsync(count_host, l.counts + 2, sizeof(int64_t), hipMemcpyDeviceToHost, s) != hipSuccess) return record_error(-3, "runs: copy failed");
     if (hipStreamSynchronize(s) != hipSuccess) return record_error(-3, "runs: stream failed");
     if (*count_host > max_runs) return record_error(-5, "runs: more runs than max_runs (the count is set: call again with that capacity)");
     return 0;
@@ -430,7 +369,7 @@ int mtadgat_eval_runs(const float* score_dev, const unsigned char* label_dev, in
 
 size_t mtadgat_eval_run_stats_scratch(int64_t n, int64_t count, int d) {
     if (n < 1 || n > 2147483647LL || count < 0 || count > 2147483647LL || d < 0 || d > 2048) return 0;
-    return stats_layout(n, count, d).bytes;
+    return scratch_bytes_of([&](ScratchCarver& c) { stats_scratch(c, n, count, d); });
 }
 
 int mtadgat_eval_run_stats(const float* score_dev, int64_t n, const int64_t* start_dev, const int64_t* end_dev, int64_t count,
@@ -450,30 +389,21 @@ int mtadgat_eval_run_stats(const float* score_dev, int64_t n, const int64_t* sta
     } else {
         d = 0;
     }
-    const StatsLayout l = stats_layout(n, count, d);
-    if (scratch_bytes < l.bytes) return record_error(-5, "run_stats: scratch too small (see mtadgat_eval_run_stats_scratch)");
+    ScratchCarver carver(scratch_dev);
+    const StatsScratch l = stats_scratch(carver, n, count, d);
+    if (scratch_bytes < carver.bytes()) return record_error(-5, "run_stats: scratch too small (see mtadgat_eval_run_stats_scratch)");
     if ((uintptr_t)scratch_dev & 7) return record_error(-5, "run_stats: scratch must be 8-byte aligned");
     if (count == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    char* base = static_cast<char*>(scratch_dev);
-    double* ssum = reinterpret_cast<double*>(base + l.ssum);
-    long* sarg = reinterpret_cast<long*>(base + l.sarg);
-    float* smax = reinterpret_cast<float*>(base + l.smax);
-    double* psum = reinterpret_cast<double*>(base + l.psum);
-    int* phit = reinterpret_cast<int*>(base + l.phit);
     int ct = 1;
     while (ct < d && ct < 64) ct <<= 1;
-    // slices per run: enough workgroups for a few long runs, few idle ones for many short runs; the results do not depend on it
-    const long blocks_max = (long)((n + RS_RB - 1) / RS_RB);
-    long slices = 8192 / count;
-    slices = slices < 4 ? 4 : (slices > 1024 ? 1024 : slices);
-    if (slices > blocks_max) slices = blocks_max;
+    const long slices = span_slices(n, count, SPAN_RB);
     const long* st = reinterpret_cast<const long*>(start_dev);
     const long* en = reinterpret_cast<const long*>(end_dev);
     hipLaunchKernelGGL(k_eval_run_part, dim3((unsigned)count, (unsigned)slices), dim3(256), 0, s, score_dev, (long)n, st, en, per_dim_dev, d,
-                       (long)ld, thr_dev, ct, ssum, smax, sarg, psum, phit);
-    hipLaunchKernelGGL(k_eval_run_final, dim3((unsigned)count), dim3(64), 0, s, (long)n, st, en, d, thr_dev ? 1 : 0, top_k, ssum, smax, sarg, psum,
-                       phit, reinterpret_cast<long*>(peak_dev), peak_score_dev, mean_score_dev, feature_means_dev, top_idx_dev, top_val_dev,
+                       (long)ld, thr_dev, ct, l.ssum, l.smax, l.sarg, l.psum, l.phit);
+    hipLaunchKernelGGL(k_eval_run_final, dim3((unsigned)count), dim3(64), 0, s, (long)n, st, en, d, thr_dev ? 1 : 0, top_k, l.ssum, l.smax, l.sarg, l.psum,
+                       l.phit, reinterpret_cast<long*>(peak_dev), peak_score_dev, mean_score_dev, feature_means_dev, top_idx_dev, top_val_dev,
                        feature_hits_dev);
     return hipGetLastError() == hipSuccess ? 0 : record_error(-3, "run_stats: kernel launch failed");
 }

@@ -121,6 +121,14 @@ def _check(rc, what):
         raise RuntimeError(f"mtadgat {what} failed (status {rc})")
 
 
+def _fail(lib, rc, what):
+    raise RuntimeError(f"mtadgat {what} failed (status {rc}): {lib.mtadgat_last_error().decode()}")
+
+
+def _scratch(nbytes, device):              # 8-byte words from _native._empty: poisoned under MTADGAT_POISON_SCRATCH
+    return _native._empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
+
+
 def _dev2d(t, name):
     """A float32 (n, d) GPU tensor whose rows are contiguous (a column slice keeps its row stride: no copy)."""
     if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
@@ -269,14 +277,13 @@ def column_quantiles(a, qs):
     q = np.ascontiguousarray(np.asarray(qs, dtype=np.float64).reshape(-1))
     if q.size < 1 or not np.all((q >= 0.0) & (q <= 1.0)):
         raise ValueError(f"quantile probabilities must lie in [0, 1], got {qs!r}")
-    nbytes = lib.mtadgat_eval_column_quantiles_scratch(n, d, q.size)
-    scratch = _native._empty((nbytes + 7) // 8, dtype=torch.float64, device=a.device)
+    scratch = _scratch(lib.mtadgat_eval_column_quantiles_scratch(n, d, q.size), a.device)
     out = _native._empty((q.size, d), dtype=torch.float32, device=a.device)
     with torch.cuda.device(a.device):
         rc = lib.mtadgat_eval_column_quantiles(a.data_ptr(), n, d, a.stride(0), q.ctypes.data_as(_c_double_p), q.size,
                                                scratch.data_ptr(), scratch.numel() * 8, out.data_ptr(), _stream(a))
     if rc != 0:
-        raise RuntimeError(f"mtadgat eval_column_quantiles failed (status {rc}): {lib.mtadgat_last_error().decode()}")
+        _fail(lib, rc, "eval_column_quantiles")
     return out
 
 
@@ -296,14 +303,13 @@ def moving_average(scores, span):
     n = x.numel()
     if n < 1:
         raise ValueError("scores is empty")
-    nbytes = lib.mtadgat_eval_ewm_scratch(n)
-    scratch = _native._empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device)
+    scratch = _scratch(lib.mtadgat_eval_ewm_scratch(n), x.device)
     out = _native._empty((n,), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
         rc = lib.mtadgat_eval_ewm(x.data_ptr(), n, 2.0 / (float(span) + 1.0), scratch.data_ptr(), scratch.numel() * 8, out.data_ptr(),
                                   _stream(x))
     if rc != 0:
-        raise RuntimeError(f"mtadgat eval_ewm failed (status {rc}): {lib.mtadgat_last_error().decode()}")
+        _fail(lib, rc, "eval_ewm")
     return out
 
 
@@ -467,7 +473,7 @@ def spot_calibrate(init_scores, q=1e-3, level=0.98, max_peaks=1024, dynamic=True
     if nbytes == 0 or sbytes == 0:
         raise ValueError(f"{S} columns are refused (at most 65536 per call)")
     buf = torch.zeros((nbytes + 7) // 8, dtype=torch.float64, device=e.device)
-    scratch = _native._empty((sbytes + 7) // 8, dtype=torch.float64, device=e.device)
+    scratch = _scratch(sbytes, e.device)
     with torch.cuda.device(e.device):
         rc = lib.mtadgat_spot_calibrate(e.data_ptr(), n, S, e.stride(0), float(q), float(level), int(max_peaks), 1 if dynamic else 0,
                                         buf.data_ptr(), scratch.data_ptr(), scratch.numel() * 8, _stream(e))
@@ -578,10 +584,6 @@ RUNS_CHUNK = 1024        # chunk length of the run-extraction scans (mtadgat_eva
 _c_int64_p = ctypes.POINTER(ctypes.c_int64)
 
 
-def _fail(lib, rc, what):
-    raise RuntimeError(f"mtadgat {what} failed (status {rc}): {lib.mtadgat_last_error().decode()}")
-
-
 def _labels_u8(label, name="labels"):
     """Labels as point_adjust_counts reads them: bool as it is, numbers as label > 0.1."""
     if not isinstance(label, torch.Tensor) or label.device.type != "cuda":
@@ -615,8 +617,7 @@ def flag_runs(scores=None, labels=None, threshold=0.0, merge_gap=0, min_length=1
         raise ValueError("the flag source is empty")
     if merge_gap < 0 or min_length < 1 or max_runs < 1:
         raise ValueError(f"needs merge_gap >= 0, min_length >= 1, max_runs >= 1, got {merge_gap}, {min_length}, {max_runs}")
-    nbytes = lib.mtadgat_eval_runs_scratch(n)
-    scratch = _native._empty((nbytes + 7) // 8, dtype=torch.float64, device=src.device)
+    scratch = _scratch(lib.mtadgat_eval_runs_scratch(n), src.device)
     count = ctypes.c_int64(0)
     cap = int(max_runs)
     for attempt in range(2):
@@ -680,8 +681,7 @@ def run_statistics(scores, start, end, per_dim=None, feature_thresholds=None, to
         out["feature_hits"] = torch.empty((count, d), dtype=torch.int32, device=dev)
     if count == 0:
         return out
-    nbytes = lib.mtadgat_eval_run_stats_scratch(n, count, d)
-    scratch = _native._empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+    scratch = _scratch(lib.mtadgat_eval_run_stats_scratch(n, count, d), dev)
     with torch.cuda.device(dev):
         rc = lib.mtadgat_eval_run_stats(s.data_ptr(), n, st.data_ptr(), en.data_ptr(), count, _ptr(pd), d, ld, _ptr(thr), k, scratch.data_ptr(),
                                         scratch.numel() * 8, out["peak"].data_ptr(), out["peak_score"].data_ptr(), out["mean_score"].data_ptr(),
@@ -778,7 +778,7 @@ def score_order(scores, descending=True):
     nbytes = lib.mtadgat_eval_score_order_scratch(n)
     if nbytes == 0:
         raise ValueError(f"{n} scores are refused (fewer than 2**31)")
-    scratch = _native._empty((nbytes + 7) // 8, dtype=torch.float64, device=s.device)
+    scratch = _scratch(nbytes, s.device)
     order = torch.empty(n, dtype=torch.int64, device=s.device)
     with torch.cuda.device(s.device):
         rc = lib.mtadgat_eval_score_order(s.data_ptr(), n, 1 if descending else 0, scratch.data_ptr(), scratch.numel() * 8, order.data_ptr(),
@@ -819,7 +819,7 @@ def _curve(scores, labels, adjust):
     nbytes = lib.mtadgat_eval_curve_scratch(n, mode)
     if nbytes == 0:
         raise ValueError(f"{n} scores are refused (fewer than 2**31)")
-    scratch = _native._empty((nbytes + 7) // 8, dtype=torch.float64, device=s.device)
+    scratch = _scratch(nbytes, s.device)
     thr = _native._empty(n, dtype=torch.float32, device=s.device)
     tp = _native._empty(n, dtype=torch.int64, device=s.device)
     fp = _native._empty(n, dtype=torch.int64, device=s.device)

@@ -129,6 +129,21 @@ def test_ranking_curve_and_metrics(n, gpu_device):
     _assert_curve(ev.ranking_curve(t, as_float), curve_refs.ranking_curve(s, layouts["mixed"]), (n, "float labels"))
 
 
+def test_pak_with_more_segments_than_one_scan_block(gpu_device):
+    """B + 3 labelled segments (length 3, gaps of 1; the first at index 0, the last at n - 1), B = the entries one scan block takes:
+    the span starts of PA%K come from the scan's multi-block route.  One segment has two NaN of three, one is all NaN."""
+    B = 256 * LEVEL2
+    n = 4 * (B + 2) + 1
+    lab = np.arange(n) % 4 != 3
+    s = (np.random.default_rng(7).integers(0, 41, n) / np.float32(40) - np.float32(0.25)).astype(np.float32)
+    s[0] = -0.25
+    s[[9, 10, 12, 13, 14, 30]] = np.nan
+    t, tl = torch.from_numpy(s).to(gpu_device), torch.from_numpy(lab).to(gpu_device)
+    for adjust in (None, "point", ("k", 0), ("k", 50), ("k", 100)):
+        _assert_curve(ev.ranking_curve(t, tl, adjust), curve_refs.ranking_curve(s, lab, adjust), ("segments", adjust))
+        _assert_metrics(ev.ranking_metrics(t, tl, adjust), curve_refs.ranking_metrics(s, lab, adjust), ("segments", adjust))
+
+
 def test_all_scores_nan(gpu_device):
     s = np.full(300, np.nan, np.float32)
     lab = np.arange(300) % 3 == 0
