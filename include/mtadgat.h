@@ -429,7 +429,9 @@ int mtadgat_train_layout(mtadgat_handle h, int64_t batch, int64_t* offsets_out, 
  * (eval_methods.py: find_epsilon :189-236, adjust_predicts :6-55 + calc_point2point :58-72 for one threshold --
  * epsilon_eval -- or a whole sweep -- bf_search :117-158).  Device arrays in, small host tables out (these calls
  * synchronise the stream); the scalar bookkeeping on top is mtad-gat-pytorch_amd/evaluation.py.  Status 0 / -1
- * (bad argument) / -3 (HIP) / -5 (more anomaly segments than max_seg). */
+ * (bad argument) / -3 (HIP) / -5 (more anomaly segments than max_seg).
+ * Scratch (device, need not be initialised): moments >= 2 doubles; epsilon_table >= 64 + 4*nz doubles (1 <= nz <= 64, halo >= 0:
+ * the table starts at scratch_dev + 64 whatever nz is); point_adjust >= 7*n_thr doubles followed by 2*max_seg + 2 ints. */
 int mtadgat_eval_scores(const float* preds_dev, const float* recons_dev, const float* actual_dev, int64_t n, int d,
                         int64_t ld_actual, const int* dims_dev, float gamma, float* per_dim_dev, float* global_dev, void* stream);
 int mtadgat_eval_moments(const float* e_dev, int64_t n, double* scratch_dev, double* out_host, void* stream);

@@ -161,7 +161,8 @@ int mtadgat_eval_scores(const float* preds_dev, const float* recons_dev, const f
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
-// scratch_dev: >= 2 + 4*nz doubles.  out_host: [sum, sumsq] then nz x [pruned sum, pruned sumsq, pruned count, dilated count].
+// moments: scratch_dev >= 2 doubles, out_host [sum, sumsq].  epsilon_table: scratch_dev >= 64 + 4*nz doubles (the thresholds sit in
+// the first 64, the table starts at scratch_dev + 64 whatever nz is), out_host nz x [pruned sum, pruned sumsq, pruned count, dilated count].
 // eps = f(mean, sd) is formed by the caller between the two phases: phase 0 computes the moments, phase 1 the z table.
 int mtadgat_eval_moments(const float* e_dev, int64_t n, double* scratch_dev, double* out_host, void* stream) {
     if (!e_dev || !scratch_dev || !out_host || n <= 0) return -1;
@@ -174,7 +175,7 @@ int mtadgat_eval_moments(const float* e_dev, int64_t n, double* scratch_dev, dou
 
 int mtadgat_eval_epsilon_table(const float* e_dev, int64_t n, const double* eps_host, int nz, int halo, double* scratch_dev,
                                double* out_host, void* stream) {
-    if (!e_dev || !eps_host || !scratch_dev || !out_host || n <= 0 || nz < 1 || nz > 64) return -1;
+    if (!e_dev || !eps_host || !scratch_dev || !out_host || n <= 0 || nz < 1 || nz > 64 || halo < 0) return -1;
     hipStream_t s = (hipStream_t)stream;
     double* eps_dev = scratch_dev;               // nz
     double* tab = scratch_dev + 64;              // 4 * nz
