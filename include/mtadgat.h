@@ -189,6 +189,17 @@ int mtadgat_gru_route(mtadgat_handle h, int stack, int layer, int64_t n, int tra
  *     [4]  the layer's split packs are needed
  * Returns 0, or MTADGAT_ERR_INVALID. */
 int mtadgat_front_route(mtadgat_handle h, int kind, int source, int64_t n, int facts, int* out);
+/* Test hook (host only: needs neither a GPU nor loaded weights): how a forward call of `batch` windows is cut up and where each part
+ * lives in the caller's workspace.  The answer is the one the library's own forward uses under the handle's current
+ * mtadgat_set_chunk_windows size, mtadgat_set_precision mode and "lanes" option.  Writes 5 + 3 * n_pieces values:
+ *   out[0]  n_pieces: pieces of the call, run in this order
+ *   out[1]  1 when the call is small enough to run its independent stages side by side on the handle's second stream
+ *   out[2]  floats of the workspace part of lane 0 (the caller's stream), which begins at the workspace's start
+ *   out[3]  floats of the part of lane 1 (the handle's second stream), which begins out[2] floats in; 0 when no piece runs there
+ *   out[4]  floats of the whole workspace: mtadgat_workspace_bytes / 4
+ *   out[5 + 3 i .. 8 + 3 i)  piece i: its first window, its window count, its lane
+ * Returns the count of values written, or MTADGAT_ERR_INVALID (a NULL argument, batch < 1, max_n too small: nothing is written). */
+int mtadgat_forward_plan(mtadgat_handle h, int64_t batch, int64_t* out, int max_n);
 /* Test hook (host only): does a row GEMM over `rows` rows take split-bf16 operands (k_rowgemm_x3) under the handle's precision mode
  * and "rowgemm_kernel" option?  has_pack: a split pack was planned for its weights; backward: a site of mtadgat_backward (there
  * "rowgemm_kernel" = 2 forces the split pack in every mode, in the forward only in the "fp32" mode).  Returns 1 / 0, negative: error. */

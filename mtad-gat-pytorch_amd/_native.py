@@ -100,6 +100,7 @@ def load_library():
     lib.mtadgat_derived_regions.argtypes = [vp, ctypes.POINTER(i64), ctypes.c_int]
     lib.mtadgat_gru_route.argtypes = [vp, ctypes.c_int, ctypes.c_int, i64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
     lib.mtadgat_front_route.argtypes = [vp, ctypes.c_int, ctypes.c_int, i64, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+    lib.mtadgat_forward_plan.argtypes = [vp, i64, ctypes.POINTER(i64), ctypes.c_int]
     lib.mtadgat_rowgemm_split.argtypes = [vp, ctypes.c_int, i64, ctypes.c_int]
     lib.mtadgat_workspace_bytes.argtypes = [vp, i64]
     lib.mtadgat_workspace_bytes.restype = sz
@@ -471,6 +472,21 @@ class Engine:
         buf = (ctypes.c_int * 14)()
         _check(self.lib.mtadgat_front_route(self.handle, kind, source, n, facts, buf), "mtadgat_front_route")
         return dict(zip(FRONT_ROUTE_FIELDS, (int(v) for v in buf)))
+
+    def forward_plan(self, batch):
+        """How forward() walks a call of `batch` windows under the current chunk size, precision and "lanes" option (host only):
+        dict of fork, lane_floats (2), total_floats and pieces [(first window, windows, lane)] -- mtadgat_forward_plan (include/mtadgat.h)."""
+        n = 5 + 3 * min(int(batch), 64)
+        while True:                                              # (no piece is empty: 5 + 3 * batch values always suffice)
+            buf = (ctypes.c_int64 * n)()
+            got = self.lib.mtadgat_forward_plan(self.handle, int(batch), buf, n)
+            if got > 0 or n >= 5 + 3 * batch:
+                break
+            n = min(8 * n, 5 + 3 * int(batch))
+        if got <= 0:
+            _check(got, "mtadgat_forward_plan")
+        v = [int(x) for x in buf[:got]]
+        return dict(fork=bool(v[1]), lane_floats=(v[2], v[3]), total_floats=v[4], pieces=[tuple(v[i:i + 3]) for i in range(5, got, 3)])
 
     def load_weights(self, sd, device, allow_device_pack=True):
         """sd: reference-format state_dict (any device).  The first load packs on the host and uploads on the current

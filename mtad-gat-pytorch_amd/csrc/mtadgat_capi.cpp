@@ -593,7 +593,8 @@ int run_heads(Model& m, const float* hend, long ldh, int64_t n, float* preds, fl
     return 0;
 }
 
-int check_common(mtadgat_handle h, int64_t batch, void* ws, size_t ws_bytes, bool need_ws) {
+// plan: the call's forward plan where the caller has made it (forward_impl)
+int check_common(mtadgat_handle h, int64_t batch, void* ws, size_t ws_bytes, bool need_ws, const ForwardPlan* plan = nullptr) {
     if (!h) return fail(MTADGAT_ERR_INVALID, "null handle");
     if (batch < 0) return fail(MTADGAT_ERR_INVALID, "negative batch");
     if (!h->m.have_weights) return fail(MTADGAT_ERR_NOWEIGHTS, "mtadgat_load_weights has not been called");
@@ -602,7 +603,8 @@ int check_common(mtadgat_handle h, int64_t batch, void* ws, size_t ws_bytes, boo
     if (need_ws && batch > 0) {
         if (!ws) return fail(MTADGAT_ERR_WORKSPACE, "workspace is NULL");
         if (!aligned16(ws)) return fail(MTADGAT_ERR_WORKSPACE, "workspace must be 16-byte aligned");
-        if (ws_bytes < mtadgat_workspace_bytes(h, batch)) return fail(MTADGAT_ERR_WORKSPACE, "workspace too small");
+        if (ws_bytes < (plan ? plan->total_floats : plan_forward(h->m, batch).total_floats) * sizeof(float))
+            return fail(MTADGAT_ERR_WORKSPACE, "workspace too small");
     }
     return 0;
 }
@@ -626,24 +628,8 @@ int mtadgat_create(const mtadgat_config* cfg, mtadgat_handle* out) {
         delete h;
         return fail(MTADGAT_ERR_UNSUPPORTED, err);
     }
-    // default chunk: up to 65 536 windows, fewer when a window needs a lot of scratch (wide models on the
-    // un-fused attention path: ~8 MB per window at F=512, W=256), so that the workspace stays within a
-    // quarter of the device memory (16 GB when no device can be queried)
-    {
-        Workspace o;
-        plan_workspace(h->m, 65536, o);       // large batches: without the small-batch extras (pre-projected inputs, decoder states)
-        const double per_window = (double)o.total * sizeof(float) / 65536.0;
-        size_t free_b = 0, total_b = 0;
-        double budget = (hipMemGetInfo(&free_b, &total_b) == hipSuccess && total_b > 0) ? (double)total_b / 4 : 16.0 * 1024 * 1024 * 1024;
-        const bool unfused = !(h->m.temp.fused && h->m.feat.fused);
-        if (unfused) budget = std::min(budget, 6.0 * 1024 * 1024 * 1024);   // projections through HBM: a few hundred windows fill the machine
-        int64_t c = (int64_t)(budget / per_window);
-        // (more than 512 features: score matrices of up to 16 MB and projections of up to 4 096 columns per window, ~70 MB of
-        // scratch per window at F = 2048, W = 512 -- fewer than 128 windows fit the budget)
-        const int64_t gran = unfused ? (h->m.F > 512 ? 8 : 128) : 2048;
-        c = c / gran * gran;
-        h->m.chunk = c < gran ? gran : (c > 65536 ? 65536 : c);
-    }
+    size_t free_b = 0, total_b = 0;
+    h->m.chunk = default_chunk(h->m, hipMemGetInfo(&free_b, &total_b) == hipSuccess ? (double)total_b : 0.0);
     *out = h;
     return 0;
 }
@@ -910,6 +896,19 @@ int mtadgat_front_route(mtadgat_handle h, int kind, int source, int64_t n, int f
     return 0;
 }
 
+/* Read-only test hook (no GPU, no weights): plan_forward of a call of `batch` windows under the handle's chunk size, precision and
+ * "lanes" option; include/mtadgat.h defines the values written.  Returns their count. */
+int mtadgat_forward_plan(mtadgat_handle h, int64_t batch, int64_t* out, int max_n) {
+    if (!h || !out) return fail(MTADGAT_ERR_INVALID, "null argument");
+    if (batch < 1) return fail(MTADGAT_ERR_INVALID, "the plan needs at least one window");
+    const ForwardPlan p = plan_forward(h->m, batch);
+    std::vector<int64_t> v = {(int64_t)p.pieces.size(), p.fork, (int64_t)p.lane_floats[0], (int64_t)p.lane_floats[1], (int64_t)p.total_floats};
+    for (const ForwardPiece& pc : p.pieces) v.insert(v.end(), {pc.c0, pc.n, pc.lane});
+    if ((int64_t)v.size() > max_n) return fail(MTADGAT_ERR_INVALID, "plan array too small");
+    std::copy(v.begin(), v.end(), out);
+    return (int)v.size();
+}
+
 /* Read-only test hook: rowgemm_split under the handle's precision and "rowgemm_kernel" option (1 / 0, negative: error) */
 int mtadgat_rowgemm_split(mtadgat_handle h, int has_pack, int64_t rows, int backward) {
     return h ? (int)rowgemm_split(h->m, has_pack != 0, rows, backward != 0) : fail(MTADGAT_ERR_INVALID, "null handle");
@@ -1008,98 +1007,17 @@ int mtadgat_set_option(mtadgat_handle h, const char* name, int value) {
     return fail(MTADGAT_ERR_INVALID, "unknown option or value");
 }
 
-// How forward() walks a call of `batch` windows: chunks of at most m.chunk windows one after the other (each planned for its own
-// size: a short last chunk gets the small-batch kernels and their buffers), and -- fused front end, split-operand arithmetic --
-// a chunk in PIECES that alternate between two lanes (the caller's stream and the handle's own), each lane with its own
-// workspace.  Why: the large-batch recurrence (k_gru_cm) is a 100-step latency chain on one 4-wave workgroup per 128 windows
-// and per CU, so its time is the same for any chunk up to 32 768 windows and doubles at 32 769; and while it runs it owns the
-// register file but not the vector ALU.  Two lanes let one piece's convolution / attention fill the other's recurrence:
-// measured (MSL shape, profiles/r04_overlap_experiment.txt) 10 240 windows 6.0 -> 5.4 ms, 12 288: 6.3 -> 5.7, 36 864:
-// 15.9 -> 12.4, 40 960: 16.7 -> 14.1, 49 152: 18.0 -> 16.4; no gain at 16 384 .. 32 768 (one piece) and at whole multiples of
-// 32 768.  The pieces' results are those of forward() called on each piece (the kernels are chosen by the piece's size).
-struct Piece { int64_t c0, n; int lane; };
-static void forward_schedule(const Model& m, int64_t batch, std::vector<Piece>& out) {
-    out.clear();
-    const bool two = m.lanes == 0 && m.precision == 2 && m.temp.fused && m.feat.fused;
-    // Round 6: models on the un-fused (wide) attention path walk a call of several chunks with the chunks ALTERNATING between the
-    // lanes.  Their chunks are a few hundred windows (projections through HBM: ~7 MB of scratch per window at F = 512, W = 256), so the
-    // recurrences of a chunk are small-batch latency chains on a quarter of the CUs (896 windows: ~56 workgroups; GRU layer + decoder
-    // 68.7 of config 4's 273 ms in round 5, strictly behind the chunk's front end) -- on the other lane the next chunk's convolution,
-    // projections and attention fill the rest of the machine meanwhile.  Each lane has its own workspace (lane_floats).
-    const bool alt = m.lanes == 0 && !(m.temp.fused && m.feat.fused) && batch > m.chunk && !getenv("MTADGAT_PIECES");
-    if (alt) {
-        // the first piece is HALF a chunk: with equal pieces the lanes run in lock step (both front ends side by side, then both
-        // recurrences on 2 x 56 CUs: 258 vs 268 ms for one lane); offset by half a chunk, one lane's recurrences sit under the other's
-        // front end
-        int64_t c0 = 0, ci = 0;
-        const int64_t half = std::max<int64_t>(32, m.chunk / 2 / 32 * 32);
-        while (c0 < batch) {
-            const int64_t n = std::min<int64_t>(ci == 0 ? half : m.chunk, batch - c0);
-            out.push_back({c0, n, (int)(ci & 1)});
-            c0 += n; ++ci;
-        }
-        return;
-    }
-    for (int64_t c0 = 0; c0 < batch; c0 += m.chunk) {
-        const int64_t n = std::min<int64_t>(m.chunk, batch - c0);
-        int64_t k = 1, base = n;
-        if (two && n > SPLIT3_MAX_WINDOWS && n <= 2 * SPLIT3_MAX_WINDOWS) {                // two halves for the hidden-tile-split kernel
-            k = 2;
-            base = n / 2 / 32 * 32;                                                        // (whole 32-window groups, the last piece takes the rest)
-            // a short tail rides beside a full piece instead (9 216 windows: 5.15 -> 4.77 ms; from 10 240 on the halves are as fast)
-            if (n - SPLIT3_MAX_WINDOWS <= 1536) base = SPLIT3_MAX_WINDOWS;
-        } else if (two && n > 32768 && n % 32768 != 0) {                                   // full k_gru_cm rounds (256 workgroups of 128 windows), then the rest
-            // (whole multiples of 32 768 gain nothing from the second lane -- every round is full -- and stay one piece on the caller's stream)
-            k = (n + 32767) / 32768;
-            base = 32768;
-        }
-        if (const char* e_ = getenv("MTADGAT_PIECES")) {                                   // measurement hook: "a,b,c": piece sizes, alternating lanes
-            int64_t at = 0;
-            int lane = 0;
-            for (const char* q = e_; *q && at < n;) {
-                int64_t len = std::min<int64_t>(n - at, strtoll(q, const_cast<char**>(&q), 10));
-                if (*q == ',') ++q;
-                if (len <= 0) break;
-                out.push_back({c0 + at, len, lane});
-                lane ^= 1; at += len;
-            }
-            if (at < n) out.push_back({c0 + at, n - at, lane});
-            continue;
-        }
-        for (int64_t i = 0, at = 0; i < k; ++i) {
-            const int64_t len = i + 1 < k ? base : n - at;
-            out.push_back({c0 + at, len, (int)(i & 1)});
-            at += len;
-        }
-    }
-}
-// workspace: per lane the largest plan of the pieces it runs; lane 1 starts behind lane 0
-static void lane_floats(const Model& m, int64_t batch, size_t (&need)[2]) {
-    std::vector<Piece> sched;
-    forward_schedule(m, batch, sched);
-    need[0] = need[1] = 0;
-    int64_t seen[2][2] = {{0, 0}, {0, 0}};                    // (plans repeat: sizes seen last per lane)
-    for (const Piece& pc : sched) {
-        if (pc.n == seen[pc.lane][0] || pc.n == seen[pc.lane][1]) continue;
-        seen[pc.lane][1] = seen[pc.lane][0]; seen[pc.lane][0] = pc.n;
-        Workspace o;
-        plan_workspace(m, pc.n, o);
-        need[pc.lane] = std::max(need[pc.lane], o.total);
-    }
-}
 /* Largest value the convolution wrote during the last forward() on this workspace (of its last chunk), read back after
  * the stream has drained: below 2^15 the large-batch kernels formed their products from two fp16 pieces per operand, above
  * from three bf16 pieces (the device-side range guard).  0 when the forward did not record it (un-fused attention path). */
 int mtadgat_last_conv_max(mtadgat_handle h, const void* ws, int64_t batch, float* out_host, void* stream) {
     if (!h || !ws || !out_host || batch <= 0) return fail(MTADGAT_ERR_INVALID, "null argument");
+    const ForwardPlan p = plan_forward(h->m, batch);          // the layout of the call's last piece (each piece has its own plan, each lane its own workspace)
+    const ForwardPiece& last = p.pieces.back();
     Workspace o;
-    std::vector<Piece> sched;                                 // the layout of the call's last piece (each piece has its own plan, each lane its own workspace)
-    forward_schedule(h->m, batch, sched);
-    size_t need[2];
-    lane_floats(h->m, batch, need);
-    plan_workspace(h->m, sched.back().n, o);
+    plan_workspace(h->m, last.n, o);
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    HIP_TRY(hipMemcpy(out_host, static_cast<const float*>(ws) + (sched.back().lane ? need[0] : 0) + o.vmax, sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_host, static_cast<const float*>(ws) + p.lane_offset(last.lane) + o.vmax, sizeof(float), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -1110,21 +1028,15 @@ int mtadgat_set_chunk_windows(mtadgat_handle h, int64_t w) {
     return 0;
 }
 
-static size_t workspace_floats(const Model& m, int64_t batch) {
-    size_t need[2];
-    lane_floats(m, batch, need);
-    Workspace o;                                              // (the stage entry points plan one chunk on one lane)
-    plan_workspace(m, std::min<int64_t>(batch, m.chunk), o);
-    return std::max(need[0] + need[1], o.total);
-}
 size_t mtadgat_workspace_bytes(mtadgat_handle h, int64_t batch) {
     if (!h || batch <= 0) return 0;
-    return workspace_floats(h->m, batch) * sizeof(float);
+    return plan_forward(h->m, batch).total_floats * sizeof(float);
 }
 
 static int forward_impl(mtadgat_handle h, const XSource& src, int64_t batch, float* preds, float* recons, float* recons_last,
                         float* hend_out, void* ws_, size_t ws_bytes, void* stream) {
-    int rc = check_common(h, batch, ws_, ws_bytes, true);
+    const ForwardPlan plan = h && batch > 0 ? plan_forward(h->m, batch) : ForwardPlan();
+    int rc = check_common(h, batch, ws_, ws_bytes, true, &plan);
     if (rc) return rc;
     if (batch == 0) return 0;
     if (!src.x) return fail(MTADGAT_ERR_INVALID, "input is NULL");
@@ -1132,20 +1044,8 @@ static int forward_impl(mtadgat_handle h, const XSource& src, int64_t batch, flo
     hipStream_t s0 = (hipStream_t)stream;
     const int F = m.F, W = m.W;
     if ((rc = ensure_all_split(m, s0))) return rc;        // (no-ops while the weights are unchanged; before any lane forks off)
-    std::vector<Piece> sched;
-    forward_schedule(m, batch, sched);
-    size_t lane_need[2];
-    lane_floats(m, batch, lane_need);
-    bool second = false;
-    for (const Piece& pc : sched) second = second || pc.lane == 1;
-    // Small calls (the reference Predictor's 256 windows, prediction.py:31): no launch fills the machine, the forward is a chain of
-    // latencies -- so the stages that do not depend on each other run side by side: the feature layer next to the temporal one
-    // (both read the convolution, mtad_gat.py:68-69), the forecasting head next to the reconstruction decoder (both read h_end,
-    // mtad_gat.py:76-77).  Same kernels, same results; the second stream joins before the call returns.
-    // (large calls gain nothing from it: with the convolution as its own launch and both attention layers side by side, 65 536
-    // windows take 21.0-21.2 ms against 21.1-21.3 one after the other -- the layers compete for the same vector ALUs)
+    const bool second = plan.second, fork = plan.fork;        // (a small call runs its independent stages side by side: plan_forward)
     const bool both_fused = m.temp.fused && m.feat.fused;
-    const bool fork = !second && sched.size() == 1 && m.lanes == 0 && sched[0].n <= FORK_MAX_WINDOWS && both_fused;
     if (second || fork) {
         int dev = 0;
         HIP_TRY(hipGetDevice(&dev));
@@ -1168,10 +1068,10 @@ static int forward_impl(mtadgat_handle h, const XSource& src, int64_t batch, flo
             if (on && hipEventRecord(m.lane_end, m.lane_stream) == hipSuccess) (void)hipStreamWaitEvent(s0, m.lane_end, 0);
         }
     } joiner{m, s0, second || fork};
-    for (const Piece& pc : sched) {
+    for (const ForwardPiece& pc : plan.pieces) {
         const int64_t c0 = pc.c0, n = pc.n;
         hipStream_t s = pc.lane ? m.lane_stream : s0;
-        float* ws = static_cast<float*>(ws_) + (pc.lane ? lane_need[0] : 0);
+        float* ws = static_cast<float*>(ws_) + plan.lane_offset(pc.lane);
         Workspace o;
         plan_workspace(m, n, o);
         float* xc = ws + o.xc;
@@ -1290,10 +1190,10 @@ int mtadgat_gat(mtadgat_handle h, int which, const float* xc_in, int64_t batch, 
     hipStream_t s = (hipStream_t)stream;
     float* ws = static_cast<float*>(ws_);
     const int F = m.F, W = m.W;
+    Workspace o;
+    plan_workspace(m, std::min<int64_t>(batch, m.chunk), o);
     for (int64_t c0 = 0; c0 < batch; c0 += m.chunk) {
         const int64_t n = std::min<int64_t>(m.chunk, batch - c0);
-        Workspace o;
-        plan_workspace(m, std::min<int64_t>(batch, m.chunk), o);
         const float* xin = xc_in + c0 * (int64_t)W * F;
         float* o_c = out + c0 * (int64_t)W * F;
         LayerIo io;
@@ -1319,10 +1219,10 @@ int mtadgat_gru(mtadgat_handle h, const float* hcat, int64_t batch, float* hend,
     Model& m = h->m;
     float* ws = static_cast<float*>(ws_);
     const int D = 3 * m.F, H = m.cfg.gru_hid_dim;
+    Workspace o;
+    plan_workspace(m, std::min<int64_t>(batch, m.chunk), o);
     for (int64_t c0 = 0; c0 < batch; c0 += m.chunk) {
         const int64_t n = std::min<int64_t>(m.chunk, batch - c0);
-        Workspace o;
-        plan_workspace(m, std::min<int64_t>(batch, m.chunk), o);
         // the kernel wants 16-byte aligned, zero padded rows: stage the caller's (b, W, 3F) tensor into the padded buffer
         hipStream_t s = (hipStream_t)stream;
         HIP_TRY(hipMemsetAsync(ws + o.hcat, 0, (size_t)n * m.W * m.Dp * sizeof(float), s));
@@ -1341,10 +1241,10 @@ int mtadgat_heads(mtadgat_handle h, const float* hend, int64_t batch, float* pre
     Model& m = h->m;
     float* ws = static_cast<float*>(ws_);
     const int H = m.cfg.gru_hid_dim;
+    Workspace o;
+    plan_workspace(m, std::min<int64_t>(batch, m.chunk), o);
     for (int64_t c0 = 0; c0 < batch; c0 += m.chunk) {
         const int64_t n = std::min<int64_t>(m.chunk, batch - c0);
-        Workspace o;
-        plan_workspace(m, std::min<int64_t>(batch, m.chunk), o);
         hipStream_t s = (hipStream_t)stream;
         const long ldh = m.gru.back().Hp;
         HIP_TRY(hipMemsetAsync(ws + o.hend, 0, (size_t)n * ldh * sizeof(float), s));
@@ -1356,44 +1256,7 @@ int mtadgat_heads(mtadgat_handle h, const float* hend, int64_t batch, float* pre
     return 0;
 }
 
-// ---- attention maps (the post-softmax `attention` of modules.py:85-89 / :184-188, eval mode) -------------------------------
-// Scratch of one chunk: h_cat (the convolution in [:, :F], the layers' outputs behind it), x_c^T and the projections of un-fused
-// layers -- as in the training forward's tape --, and in the mean mode the chunk's maps of one layer at a time plus the running
-// (sum, compensation) slabs of k_att_mean_part.
-struct AttPlan {
-    int64_t chunk;
-    size_t hcat, xct, lct, rtt, lcf, rtf, maps, ps_f, pc_f, ps_t, pc_t, total;
-    int slabs_f, slabs_t;
-};
-// mean mode: at most 2^26 floats (256 MB) of per-window maps per chunk (MSL's temporal layer: 6 710 windows of 100 x 100)
-static constexpr int64_t ATT_MAPS_FLOATS = int64_t(1) << 26;
-static void plan_attention(const Model& m, int64_t batch, bool reduce, AttPlan& p) {
-    size_t off = 0;
-    auto take = [&](size_t cnt) {
-        size_t o = off;
-        off = (off + cnt + 63) / 64 * 64;
-        return o;
-    };
-    const int64_t kk = std::max<int64_t>((int64_t)m.F * m.F, (int64_t)m.W * m.W);
-    p.chunk = reduce ? std::min<int64_t>(m.chunk, std::max<int64_t>(1, ATT_MAPS_FLOATS / kk)) : m.chunk;
-    const int64_t n = std::min<int64_t>(batch, p.chunk);
-    const size_t N = (size_t)n;
-    p.hcat = take(N * m.W * m.Dp);
-    p.xct = take(m.feat.fused ? 0 : N * m.F * m.Wp);
-    p.lct = take(m.temp.fused ? 0 : N * m.W * m.temp.ldl);
-    p.rtt = take(m.temp.fused ? 0 : N * m.temp.rt_rows * m.temp.Kp);
-    p.lcf = take(m.feat.fused ? 0 : N * m.F * m.feat.ldl);
-    p.rtf = take(m.feat.fused ? 0 : N * m.feat.rt_rows * m.feat.Kp);
-    p.slabs_f = reduce ? att_mean_slabs(n, m.F) : 0;
-    p.slabs_t = reduce ? att_mean_slabs(n, m.W) : 0;
-    p.maps = take(reduce ? N * (size_t)kk : 0);
-    p.ps_f = take((size_t)p.slabs_f * m.F * m.F);
-    p.pc_f = take((size_t)p.slabs_f * m.F * m.F);
-    p.ps_t = take((size_t)p.slabs_t * m.W * m.W);
-    p.pc_t = take((size_t)p.slabs_t * m.W * m.W);
-    p.total = off;
-}
-
+// ---- attention maps (the post-softmax `attention` of modules.py:85-89 / :184-188, eval mode; scratch: plan_attention) ------------
 // The maps come from the fp32 builds the training forward keeps its softmax rows with (k_gat / k_gat_wide / k_attend, no
 // dropout), whatever precision mode the handle is in (front_route, FRONT_ATTENTION); profiling is off for the call and restored.
 static int attention_impl(mtadgat_handle h, const XSource& src, int64_t batch, bool reduce, float* att_f, float* att_t, void* ws_,
@@ -2135,53 +1998,7 @@ int mtadgat_backward_input(mtadgat_handle h, int64_t batch, const void* ws_, siz
     return input_gradient(m, batch, static_cast<const float*>(ws_), w, dx, (hipStream_t)stream);
 }
 
-/* ---- score attribution --------------------------------------------------------------------------------------------------- */
-// Per chunk: the A / B windows of `units` (index, step) units -- A windows first --, the heads' outputs and their seeds, the
-// units' targets and d a / d y, d x of every window, and the training tape / backward workspace of 2 * units windows.
-struct AttrPlan {
-    int64_t units;
-    size_t x, y, preds, recons, dpreds, drecons, gy, dx, tape, bws, total;
-    size_t tape_floats, bws_floats;
-};
-// the chunk's scratch stays below 4 GiB (MSL shape: ~2 300 windows; BASELINE config 4: ~190), and below mtadgat_chunk_windows()
-static constexpr double ATTR_WS_BYTES = 4.0 * 1024 * 1024 * 1024;
-static void plan_attribution(const Model& m, int64_t count, int steps, AttrPlan& p) {
-    const int W = m.W, F = m.F, od = m.cfg.out_dim;
-    const int64_t U = count * std::max(steps, 1);
-    Tape t64;
-    plan_tape(m, 64, t64);
-    BwdWorkspace w64;
-    plan_bwd_workspace(m, 64, w64);
-    const double per_window = ((double)(t64.total + w64.total) / 64 + 2.0 * W * F + 2.0 * (W + 1) * od + 2.0 * od) * sizeof(float);
-    int64_t win = std::min<int64_t>(m.chunk, (int64_t)(ATTR_WS_BYTES / per_window));
-    win = std::max<int64_t>(2, win / 2 * 2);
-    p.units = std::max<int64_t>(1, std::min<int64_t>(U, win / 2));
-    const size_t n = (size_t)(2 * p.units), nu = (size_t)p.units;
-    size_t off = 0;
-    auto take = [&](size_t cnt) {
-        size_t o = off;
-        off = (off + cnt + 63) / 64 * 64;
-        return o;
-    };
-    p.x = take(n * W * F);
-    p.y = take(nu * od);
-    p.preds = take(n * od);
-    p.recons = take(n * W * od);
-    p.dpreds = take(n * od);
-    p.drecons = take(n * W * od);
-    p.gy = take(nu * od);
-    p.dx = take(n * W * F);
-    Tape t;
-    plan_tape(m, (int64_t)n, t);
-    BwdWorkspace w;
-    plan_bwd_workspace(m, (int64_t)n, w);
-    p.tape_floats = t.total;
-    p.bws_floats = w.total;
-    p.tape = take(t.total);
-    p.bws = take(w.total);
-    p.total = off;
-}
-
+/* ---- score attribution (scratch: plan_attribution) ------------------------------------------------------------------------- */
 size_t mtadgat_score_attribution_workspace_bytes(mtadgat_handle h, int64_t count, int steps) {
     if (!h || count < 1 || steps < 0 || !h->m.bw.supported) return 0;
     AttrPlan p;
@@ -2306,19 +2123,6 @@ StreamOut stream_out(const mtadgat_stream_outputs* o) {
     r.closed_start = reinterpret_cast<long*>(o->closed_start); r.closed_end = reinterpret_cast<long*>(o->closed_end);
     r.closed_peak = reinterpret_cast<long*>(o->closed_peak); r.closed_peak_score = o->closed_peak_score; r.closed_mean = o->closed_mean;
     return r;
-}
-struct StreamWs {                // float offsets into the push workspace
-    size_t preds, last, starts, fwd, total;
-};
-StreamWs stream_ws(const Model& m, int64_t windows) {
-    const size_t od = ((size_t)windows * m.cfg.out_dim + 3) / 4 * 4;
-    StreamWs w;
-    w.preds = 0;
-    w.last = od;
-    w.starts = 2 * od;
-    w.fwd = w.starts + ((size_t)windows * 2 + 3) / 4 * 4;          // (an int64 per window)
-    w.total = w.fwd + workspace_floats(m, windows);
-    return w;
 }
 
 }  // namespace

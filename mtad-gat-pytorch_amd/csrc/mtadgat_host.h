@@ -12,6 +12,12 @@
 namespace mtadgat {
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+inline size_t align64(size_t v) { return (v + 63) / 64 * 64; }
+// Regions of one buffer, handed out one behind the other, each starting on a multiple of 64 floats; `off`: the floats taken so far
+struct Carver {
+    size_t off = 0;
+    size_t take(size_t n) { size_t o = off; off = align64(off + n); return o; }
+};
 
 // ---- split packs ---------------------------------------------------------------------------------------------------------------
 // Copies of fp32 packs of the image as two fp16 or three bf16 pieces, and power-of-two scale slots [bits of max |W|, S, 1 / S, 0],
@@ -335,7 +341,7 @@ struct Model {
     float* staging_pinned = nullptr; // pinned host image of the last upload (source of the async copy)
     size_t staging_floats = 0;
     hipEvent_t upload_ev = nullptr;  // recorded after the last upload
-    // second lane of forward(): pieces of a call alternate between the caller's stream and this one (forward_schedule, mtadgat_capi.cpp)
+    // second lane of forward(): pieces of a call alternate between the caller's stream and this one (plan_forward, mtadgat_pack.cpp)
     hipStream_t lane_stream = nullptr;
     hipEvent_t lane_begin = nullptr, lane_end = nullptr;
     hipEvent_t fork_ev[3] = {nullptr, nullptr, nullptr};   // small calls: stage hand-offs between the caller's stream and the second lane
@@ -390,6 +396,35 @@ struct BwdWorkspace {
     size_t wds, wlr;         // wide attention layers (one layer at a time): d S (N K ldS), [L | R] (N K 2 Ep)
     size_t wpart_floats;
 };
+// How forward() walks a call: pieces in call order, each on lane 0 (the caller's stream) or 1 (the handle's own), every lane with its
+// own part of the workspace (plan_forward)
+struct ForwardPiece { int64_t c0, n; int lane; };
+struct ForwardPlan {
+    std::vector<ForwardPiece> pieces;
+    size_t lane_floats[2] = {0, 0};  // per lane the largest plan of the pieces it runs
+    size_t total_floats = 0;         // what mtadgat_workspace_bytes reports
+    bool second = false;             // some piece runs on the second lane
+    bool fork = false;               // small call: independent stages side by side on the two lanes
+    size_t lane_offset(int lane) const { return lane ? lane_floats[0] : 0; }   // lane 1 starts behind lane 0
+};
+// Scratch of one chunk of the attention maps: h_cat (the convolution in [:, :F], the layers' outputs behind it), x_c^T and the
+// projections of un-fused layers -- as in the training forward's tape --, and in the mean mode the chunk's maps of one layer at a time
+// plus the running (sum, compensation) slabs of k_att_mean_part.
+struct AttPlan {
+    int64_t chunk;
+    size_t hcat, xct, lct, rtt, lcf, rtf, maps, ps_f, pc_f, ps_t, pc_t, total;
+    int slabs_f, slabs_t;
+};
+// Score attribution, per chunk: the A / B windows of `units` (index, step) units -- A windows first --, the heads' outputs and their
+// seeds, the units' targets and d a / d y, d x of every window, and the training tape / backward workspace of 2 * units windows.
+struct AttrPlan {
+    int64_t units;
+    size_t x, y, preds, recons, dpreds, drecons, gy, dx, tape, bws, total;
+    size_t tape_floats, bws_floats;
+};
+struct StreamWs {                // float offsets into the push workspace
+    size_t preds, last, starts, fwd, total;
+};
 
 // the input gradient of a window of more than 64 KB (W F floats) is the k_conv convolution over conv_wT_off instead of k_conv_dx
 inline bool conv_dx_wide(const Model& m) { return (size_t)m.W * m.F * sizeof(float) > 64 * 1024; }
@@ -404,6 +439,11 @@ void gat_column_order(const float* a, int E, double alpha, std::vector<int>& col
 void plan_workspace(const Model& m, int64_t n, Workspace& ws); // sizes for n windows
 void plan_tape(const Model& m, int64_t n, Tape& t);
 void plan_bwd_workspace(const Model& m, int64_t n, BwdWorkspace& w);
+ForwardPlan plan_forward(const Model& m, int64_t batch);       // pieces, lanes, fork and workspace of one forward call
+void plan_attention(const Model& m, int64_t batch, bool reduce, AttPlan& p);
+void plan_attribution(const Model& m, int64_t count, int steps, AttrPlan& p);
+StreamWs stream_ws(const Model& m, int64_t windows);
+int64_t default_chunk(const Model& m, double device_bytes);    // windows per chunk of a new handle (device_bytes 0: assume 16 GB)
 int wgrad_slabs(long R, int Mp, int Np);                       // row slabs of one weight-gradient GEMM
 // packs params into host buffer `out` (size m.packed_floats); returns "" on success
 std::string pack_weights(Model& m, const mtadgat_params& p, std::vector<float>& out);

@@ -14,8 +14,6 @@ namespace mtadgat {
 
 namespace {
 
-size_t align64(size_t v) { return (v + 63) / 64 * 64; }
-
 // tile format: [NT][Q][64 lanes][4]; lane (j = lane&31, g = lane>>5), element s holds
 // M[32n + j][8q + 4g + s] (zero outside the matrix)
 template <class T, class Get>
@@ -99,32 +97,27 @@ std::string validate_and_plan(Model& m) {
     m.taps = c.kernel_size;
     m.pad = (c.kernel_size - 1) / 2;
 
-    size_t off = 0;
-    auto take = [&](size_t n) {
-        size_t o = off;
-        off = align64(off + n);
-        return o;
-    };
+    Carver img;          // the packed image
     // split packs (SplitTable): take_split reserves a region for one, split_group records the steps that derive a group of them
     using S = SplitStep;
     m.split = SplitTable();
-    auto take_split = [&](size_t n) { const size_t o = take(n); m.split.regions.emplace_back(o, n); return o; };
+    auto take_split = [&](size_t n) { const size_t o = img.take(n); m.split.regions.emplace_back(o, n); return o; };
     auto split_group = [&](std::vector<SplitStep> st) { m.split.groups.push_back(SplitGroup{std::move(st)}); return (int)m.split.groups.size() - 1; };
     auto lin_split = [&](auto& p) { p.split = split_group({{S::SPLIT3, 0, p.w_off, p.w3_off, p.NT, p.Q, p.Q16}}); };
     // conv
     m.convNT = (m.F + 31) / 32;
     {
         const int Q = m.taps * m.Fp / 8;
-        m.conv_w_off = take((size_t)m.convNT * Q * 256);
-        m.conv_b_off = take((size_t)m.convNT * 32);
-        m.conv_wraw_off = take((size_t)m.F * m.F * m.taps);
+        m.conv_w_off = img.take((size_t)m.convNT * Q * 256);
+        m.conv_b_off = img.take((size_t)m.convNT * 32);
+        m.conv_wraw_off = img.take((size_t)m.F * m.F * m.taps);
         m.Fp16 = round_up(m.F, 16);
-        m.conv_w16_off = take((size_t)m.convNT * (m.taps * m.Fp16 / 16) * 256);
-        m.conv_wf16_off = take((size_t)m.convNT * (m.taps * m.Fp16 / 8) * 256);
+        m.conv_w16_off = img.take((size_t)m.convNT * (m.taps * m.Fp16 / 16) * 256);
+        m.conv_wf16_off = img.take((size_t)m.convNT * (m.taps * m.Fp16 / 8) * 256);
         m.conv_w3_off = take_split((size_t)m.convNT * (m.taps * m.Fp16 / 16) * 3 * 256);
         m.conv_w2h_off = take_split((size_t)m.convNT * (m.taps * m.Fp16 / 16) * 2 * 256);
         m.conv_scale_off = take_split(4);
-        m.conv_wT_off = conv_dx_wide(m) ? take((size_t)m.convNT * Q * 256) : 0;
+        m.conv_wT_off = conv_dx_wide(m) ? img.take((size_t)m.convNT * Q * 256) : 0;
         // k_conv_win's two fp16 pieces of S * W in the 16-channel geometry; three bf16 pieces for the wide models' k_conv_x3
         const int q8 = m.taps * m.Fp16 / 8;
         const size_t sc = m.conv_scale_off;
@@ -167,10 +160,10 @@ std::string validate_and_plan(Model& m) {
                 g.Q = qf;
             }
         }
-        g.w_off = take((size_t)g.NT * g.Q * 256);
-        g.b_off = take((size_t)g.NT * 32);
-        g.bias_off = take((size_t)K * K);
-        g.ord_off = take(16);
+        g.w_off = img.take((size_t)g.NT * g.Q * 256);
+        g.b_off = img.take((size_t)g.NT * 32);
+        g.bias_off = img.take((size_t)K * K);
+        g.ord_off = img.take(16);
         g.PTcap = ptcap;
         g.Q16 = g.fused ? (D + 1 + 15) / 16 : 0;
         if (g.fused) {      // fp16-piece build: pitch 4 x odd halfs (conflict-free 8-byte operand reads of 32 consecutive nodes)
@@ -213,7 +206,7 @@ std::string validate_and_plan(Model& m) {
             // measurement hook (profiles/gath_timeline.py): more LDS per workgroup = fewer resident workgroups per CU
             if (const char* e_ = getenv("MTADGAT_GATH_PADLDS")) g.fh_lds_bytes = std::max<size_t>(g.fh_lds_bytes, (size_t)atoi(e_) * 1024);
         }
-        g.w16_off = take((size_t)g.NT * g.Q16 * 256);
+        g.w16_off = img.take((size_t)g.NT * g.Q16 * 256);
         g.w3_off = take_split((size_t)g.NT * g.Q16 * 3 * 256);
         g.w2h_off = take_split((size_t)g.NT * g.Q16 * 2 * 256);
         g.gscale_off = take_split(4);
@@ -252,11 +245,11 @@ std::string validate_and_plan(Model& m) {
         const int Hp16 = round_up(g.H, 16);
         if (Hp16 > 160 || (g.xmode == 1 && g.Qx != 1)) return;       // weights must fit the wave's registers; 8 folded columns
         g.has16 = true; g.KS16 = (g.H + 3) / 4; g.NT16 = Hp16 / 16;
-        g.g16_off = take((size_t)g.NT16 * 3 * g.KS16 * 64);
-        g.g16T_off = take((size_t)g.NT16 * 3 * g.KS16 * 64);
-        if (g.xmode == 1) g.fold_off = take((size_t)m.W * 3 * g.Hp * 8);
-        g.g1_off = take((size_t)g1_waves(g.H, g.Hp, false) * 16 * g1_ksm(g.H) * 64);
-        g.g1T_off = take((size_t)g1_waves(g.H, g.Hp, true) * 16 * g1_ksm(g.H) * 64);
+        g.g16_off = img.take((size_t)g.NT16 * 3 * g.KS16 * 64);
+        g.g16T_off = img.take((size_t)g.NT16 * 3 * g.KS16 * 64);
+        if (g.xmode == 1) g.fold_off = img.take((size_t)m.W * 3 * g.Hp * 8);
+        g.g1_off = img.take((size_t)g1_waves(g.H, g.Hp, false) * 16 * g1_ksm(g.H) * 64);
+        g.g1T_off = img.take((size_t)g1_waves(g.H, g.Hp, true) * 16 * g1_ksm(g.H) * 64);
     };
     // GRU stack
     m.gru.assign(c.gru_n_layers, GruPlan());
@@ -269,12 +262,12 @@ std::string validate_and_plan(Model& m) {
         g.Qx = (g.in_dim + 7) / 8;
         g.Qxp = round_up(g.Qx, 3);
         g.xmode = 0;
-        g.wx_off = take((size_t)g.NCG * g.Qxp * 3 * 256);
-        g.wh_off = take((size_t)g.NCG * (4 * g.NCG + 2) * 3 * 256);   // 2 zero chunks per tile: k_gru_split's ring padding
-        g.b_off = take((size_t)4 * g.Hp);
+        g.wx_off = img.take((size_t)g.NCG * g.Qxp * 3 * 256);
+        g.wh_off = img.take((size_t)g.NCG * (4 * g.NCG + 2) * 3 * 256);   // 2 zero chunks per tile: k_gru_split's ring padding
+        g.b_off = img.take((size_t)4 * g.Hp);
         g.Qxp16 = round_up((g.Qx + 1) / 2, 6);       // whole turns of the bf16 weight ring (6 stages; k_gru_split: 3)
-        g.wx16_off = take((size_t)g.NCG * g.Qxp16 * 3 * 256);
-        g.wh16_off = take((size_t)g.NCG * (2 * g.NCG + 2) * 3 * 256);
+        g.wx16_off = img.take((size_t)g.NCG * g.Qxp16 * 3 * 256);
+        g.wh16_off = img.take((size_t)g.NCG * (2 * g.NCG + 2) * 3 * 256);
         g.wx3_off = take_split((size_t)g.NCG * g.Qxp16 * 9 * 256);
         g.wh3_off = take_split((size_t)g.NCG * (2 * g.NCG + 2) * 6 * 256 + 3 * 256);
         g.scale_off = take_split(4);
@@ -288,8 +281,8 @@ std::string validate_and_plan(Model& m) {
             g.has_xproj = true;
             g.xproj.in_dim = g.in_dim; g.xproj.out_dim = 3 * g.Hp;
             g.xproj.NT = 3 * g.Hp / 32; g.xproj.Q = (g.in_dim + 7) / 8;
-            g.xproj.w_off = take((size_t)g.xproj.NT * g.xproj.Q * 256);
-            g.xproj.b_off = take((size_t)3 * g.Hp);
+            g.xproj.w_off = img.take((size_t)g.xproj.NT * g.xproj.Q * 256);
+            g.xproj.b_off = img.take((size_t)3 * g.Hp);
             g.xproj.Q16 = (g.in_dim + 15) / 16;
             g.xproj.w3_off = take_split((size_t)g.xproj.NT * g.xproj.Q16 * 3 * 256);
             lin_split(g.xproj);
@@ -304,8 +297,8 @@ std::string validate_and_plan(Model& m) {
         p.out_dim = (i == c.forecast_n_linear - 1) ? c.out_dim : c.forecast_hid_dim;
         p.NT = (p.out_dim + 31) / 32;
         p.Q = (p.in_dim + 7) / 8;
-        p.w_off = take((size_t)p.NT * p.Q * 256);
-        p.b_off = take((size_t)p.NT * 32);
+        p.w_off = img.take((size_t)p.NT * p.Q * 256);
+        p.b_off = img.take((size_t)p.NT * 32);
     }
     // reconstruction decoder
     m.rec.assign(c.recon_n_layers, GruPlan());
@@ -326,20 +319,20 @@ std::string validate_and_plan(Model& m) {
             g.xmode = 1;
             g.Qx = (nm + 7) / 8;
             g.Qxp = g.Qx == 1 ? 1 : round_up(g.Qx, 3);
-            g.wx_off = take((size_t)T * g.NCG * g.Qxp * 3 * 256);
-            g.m0_off = take((size_t)T);
+            g.wx_off = img.take((size_t)T * g.NCG * g.Qxp * 3 * 256);
+            g.m0_off = img.take((size_t)T);
         } else {
             g.in_dim = c.recon_hid_dim;
             g.xmode = 0;
             g.Qx = (g.in_dim + 7) / 8;
             g.Qxp = round_up(g.Qx, 3);
-            g.wx_off = take((size_t)g.NCG * g.Qxp * 3 * 256);
+            g.wx_off = img.take((size_t)g.NCG * g.Qxp * 3 * 256);
         }
-        g.wh_off = take((size_t)g.NCG * (4 * g.NCG + 2) * 3 * 256);   // 2 zero chunks per tile: k_gru_split's ring padding
-        g.b_off = take((size_t)4 * g.Hp);
+        g.wh_off = img.take((size_t)g.NCG * (4 * g.NCG + 2) * 3 * 256);   // 2 zero chunks per tile: k_gru_split's ring padding
+        g.b_off = img.take((size_t)4 * g.Hp);
         g.Qxp16 = g.xmode == 1 ? (g.Qx == 1 ? 1 : round_up((g.Qx + 1) / 2, 6)) : round_up((g.Qx + 1) / 2, 6);
-        g.wx16_off = take((size_t)(g.xmode == 1 ? m.W : 1) * g.NCG * g.Qxp16 * 3 * 256);
-        g.wh16_off = take((size_t)g.NCG * (2 * g.NCG + 2) * 3 * 256);
+        g.wx16_off = img.take((size_t)(g.xmode == 1 ? m.W : 1) * g.NCG * g.Qxp16 * 3 * 256);
+        g.wh16_off = img.take((size_t)g.NCG * (2 * g.NCG + 2) * 3 * 256);
         g.wx3_off = take_split((size_t)(g.xmode == 1 ? m.W : 1) * g.NCG * g.Qxp16 * 9 * 256);
         g.wh3_off = take_split((size_t)g.NCG * (2 * g.NCG + 2) * 6 * 256 + 3 * 256);
         g.scale_off = take_split(4);
@@ -353,8 +346,8 @@ std::string validate_and_plan(Model& m) {
         p.out_dim = c.out_dim;
         p.NT = (p.out_dim + 31) / 32;
         p.Q = m.rec.back().Hp / 8;
-        p.w_off = take((size_t)p.NT * p.Q * 256);
-        p.b_off = take((size_t)p.NT * 32);
+        p.w_off = img.take((size_t)p.NT * p.Q * 256);
+        p.b_off = img.take((size_t)p.NT * 32);
         p.Q16 = (p.Q + 1) / 2;
         p.w3_off = take_split((size_t)p.NT * p.Q16 * 3 * 256);
         lin_split(p);
@@ -368,7 +361,7 @@ std::string validate_and_plan(Model& m) {
         auto lint = [&](LinTPlan& p, int kdim, int outdim) {
             p.in_dim = kdim; p.out_dim = outdim;
             p.NT = (outdim + 31) / 32; p.Q = (kdim + 7) / 8;
-            p.w_off = take((size_t)p.NT * p.Q * 256);
+            p.w_off = img.take((size_t)p.NT * p.Q * 256);
             p.Q16 = (kdim + 15) / 16;
             p.w3_off = take_split((size_t)p.NT * p.Q16 * 3 * 256);
             lin_split(p);
@@ -376,9 +369,9 @@ std::string validate_and_plan(Model& m) {
         auto wg = [&](WgradPlan& p, int M, int N, bool bias) {
             p.M = M; p.N = N; p.has_bias = bias;
             p.Mp = round_up(M, 32); p.Np = round_up(N + 1, 32);
-            p.rowW_off = take((size_t)p.Mp);
-            p.col_off = take((size_t)p.Np);
-            p.rowB_off = take((size_t)p.Mp);
+            p.rowW_off = img.take((size_t)p.Mp);
+            p.col_off = img.take((size_t)p.Np);
+            p.rowB_off = img.take((size_t)p.Mp);
         };
         // flat gradient layout: the reference's parameters in the order of mtadgat_params
         GradLayout& gl = b.gl;
@@ -411,11 +404,11 @@ std::string validate_and_plan(Model& m) {
         // GATv2: the un-scaled projection pack (and its three bf16 pieces), its bias, `a`, the transposed pack of d V, the weight gradient
         // (round 6: the score backward's projections are a row GEMM for fused layers too)
         auto gat_wu = [&](GatBwdPlan& gb, const GatPlan& g) {
-            gb.wu_off = take((size_t)2 * gb.NTu * g.Q * 256);
+            gb.wu_off = img.take((size_t)2 * gb.NTu * g.Q * 256);
             gb.wu3_off = take_split((size_t)2 * gb.NTu * ((g.Q + 1) / 2) * 3 * 256);
             gb.split = split_group({{S::SPLIT3, 0, gb.wu_off, gb.wu3_off, 2 * gb.NTu, g.Q, (g.Q + 1) / 2}});
-            gb.bu_off = take((size_t)2 * gb.Ep);
-            gb.a_off = take((size_t)gb.Ep);
+            gb.bu_off = img.take((size_t)2 * gb.Ep);
+            gb.a_off = img.take((size_t)gb.Ep);
             lint(gb.lrT, 2 * gb.Ep, g.D);
             wg(gb.wg, 2 * gb.Ep, g.D, true);
         };
@@ -428,9 +421,9 @@ std::string validate_and_plan(Model& m) {
                 gb.Ep = round_up(g.E, 32); gb.NTu = gb.Ep / 32;
                 gb.wide = !g.fused;
                 if (gb.wide && !c.use_gatv2) {       // GAT (v1), wide: plain parameter copies for k_gat_v1_prep / k_bw_v1 / k_gat_v1_finish
-                    gb.w1_off = take((size_t)g.E * g.D);
-                    gb.b1_off = take((size_t)g.E);
-                    gb.a_off = take((size_t)2 * g.E);
+                    gb.w1_off = img.take((size_t)g.E * g.D);
+                    gb.b1_off = img.take((size_t)g.E);
+                    gb.a_off = img.take((size_t)2 * g.E);
                     continue;
                 }
                 if (gb.wide) {
@@ -440,9 +433,9 @@ std::string validate_and_plan(Model& m) {
                 gb.att_lds = gat_bwd_att_lds(g.K, g.D, g.f_vld, (g.K + 15) / 16);
                 if (!c.use_gatv2) {
                     // GAT (v1): the score backward is linear in the node vectors (mtadgat_bwd.hip): plain parameter copies
-                    gb.w1_off = take((size_t)g.E * g.D);
-                    gb.b1_off = take((size_t)g.E);
-                    gb.a_off = take((size_t)2 * g.E);
+                    gb.w1_off = img.take((size_t)g.E * g.D);
+                    gb.b1_off = img.take((size_t)g.E);
+                    gb.a_off = img.take((size_t)2 * g.E);
                     gb.pair_lds = gat_bwd_v1_lds(g.K, g.D);
                     if (gb.att_lds > 160 * 1024 || gb.pair_lds > 160 * 1024) { b.supported = false; b.why = "attention backward tiles exceed the LDS"; }
                     continue;
@@ -451,7 +444,7 @@ std::string validate_and_plan(Model& m) {
                 if (gb.att_lds > 160 * 1024) { b.supported = false; b.why = "attention backward tiles exceed the LDS"; }
             }
             auto gru_b = [&](GruBwdPlan& gb, const GruPlan& g) {
-                gb.whT_off = take((size_t)g.NCG * 12 * g.NCG * 256);
+                gb.whT_off = img.take((size_t)g.NCG * 12 * g.NCG * 256);
                 gb.whT3_off = take_split((size_t)g.NCG * 6 * g.NCG * 3 * 256);
                 gb.split = split_group({{S::SPLIT3, 0, gb.whT_off, gb.whT3_off, g.NCG, 12 * g.NCG, 6 * g.NCG}});
                 lint(gb.wihT, 3 * g.Hp, g.in_dim);
@@ -471,10 +464,10 @@ std::string validate_and_plan(Model& m) {
             lint(b.recfcT, c.out_dim, m.rec.back().Hp);
             wg(b.recfc_wg, c.out_dim, c.recon_hid_dim, true);
             wg(b.conv_wg, m.F, m.taps * m.F, true);
-            b.zero_off = take(1024);
+            b.zero_off = img.take(1024);
         }
     }
-    m.packed_floats = off;
+    m.packed_floats = img.off;
     return "";
 }
 
@@ -702,65 +695,163 @@ FrontRoute front_route(const Model& m, int64_t n, const FrontCall& c) {
 }
 
 void plan_workspace(const Model& m, int64_t n, Workspace& ws) {
-    size_t off = 0;
-    auto take = [&](size_t cnt) {
-        size_t o = off;
-        off = align64(off + cnt);
-        return o;
-    };
+    Carver cv;
     const size_t N = (size_t)n;
     // un-fused path intermediates (also used by the stage entry point mtadgat_gat, which copies its input
     // into xc / xcT): the projected L'/R'^T only exist when a layer's tiles do not fit in LDS
     const bool both_fused = m.temp.fused && m.feat.fused;
     const size_t xc_n = N * m.W * m.Fp, xct_n = N * m.F * m.Wp;
     if (!both_fused) {
-        ws.xc = take(xc_n);
-        ws.xct = take(xct_n);
+        ws.xc = cv.take(xc_n);
+        ws.xct = cv.take(xct_n);
     }
-    ws.lct = take(m.temp.fused ? 0 : N * m.W * m.temp.ldl);
-    ws.rtt = take(m.temp.fused ? 0 : N * m.temp.rt_rows * m.temp.Kp);
-    ws.lcf = take(m.feat.fused ? 0 : N * m.F * m.feat.ldl);
-    ws.rtf = take(m.feat.fused ? 0 : N * m.feat.rt_rows * m.feat.Kp);
+    ws.lct = cv.take(m.temp.fused ? 0 : N * m.W * m.temp.ldl);
+    ws.rtt = cv.take(m.temp.fused ? 0 : N * m.temp.rt_rows * m.temp.Kp);
+    ws.lcf = cv.take(m.feat.fused ? 0 : N * m.F * m.feat.ldl);
+    ws.rtf = cv.take(m.feat.fused ? 0 : N * m.feat.rt_rows * m.feat.Kp);
     if (both_fused) {
         // forward() never materialises xc / xc^T then; the stage entry point mtadgat_gat stages its input
         // there, and does not use h_cat: the two share the space
         const size_t hc = N * m.W * m.Dp;
-        ws.hcat = take(std::max(hc, align64(xc_n) + xct_n));
+        ws.hcat = cv.take(std::max(hc, align64(xc_n) + xct_n));
         ws.xc = ws.hcat;
         ws.xct = ws.hcat + align64(xc_n);
     } else {
-        ws.hcat = take(N * m.W * m.Dp);
+        ws.hcat = cv.take(N * m.W * m.Dp);
     }
-    ws.hend = take(N * m.gru.back().Hp);
+    ws.hend = cv.take(N * m.gru.back().Hp);
     const bool gseq = m.gru.size() > 1;
-    ws.seq0 = take(gseq ? N * m.W * m.gru[0].Hp : 0);
-    ws.seq1 = take(m.gru.size() > 2 ? N * m.W * m.gru[0].Hp : 0);
+    ws.seq0 = cv.take(gseq ? N * m.W * m.gru[0].Hp : 0);
+    ws.seq1 = cv.take(m.gru.size() > 2 ? N * m.W * m.gru[0].Hp : 0);
     size_t fcw = 0;
     for (const LinPlan& p : m.fc) fcw = std::max(fcw, (size_t)p.NT * 32);
-    ws.fc0 = take(N * fcw);
-    ws.fc1 = take(N * fcw);
+    ws.fc0 = cv.take(N * fcw);
+    ws.fc1 = cv.take(N * fcw);
     // decoder state sequences: between stacked decoder layers, and -- when the per-step Linear has more than a
     // few outputs -- of the last layer, so that recon_model.fc runs as one row GEMM after the recurrence
     const bool rec16 = m.rec.size() == 1 && m.rec[0].has16 && n <= G16_MAX_WINDOWS;
     ws.rec16 = rec16;
     const bool rseq = m.rec.size() > 1 || m.cfg.out_dim > 4 || rec16;
-    ws.rseq0 = take(rseq ? N * m.W * m.rec[0].Hp : 0);
-    ws.rseq1 = take((m.rec.size() > 2 || (m.rec.size() > 1 && m.cfg.out_dim > 4)) ? N * m.W * m.rec[0].Hp : 0);
+    ws.rseq0 = cv.take(rseq ? N * m.W * m.rec[0].Hp : 0);
+    ws.rseq1 = cv.take((m.rec.size() > 2 || (m.rec.size() > 1 && m.cfg.out_dim > 4)) ? N * m.W * m.rec[0].Hp : 0);
     ws.has_xp = m.gru[0].has_xproj && gru_xp_serves(n, XP_PLAN_CUS);
-    ws.xp = take((ws.has_xp || rec16) ? N * m.W * 3 * std::max(m.gru[0].Hp, m.rec[0].Hp) : 0);
-    ws.vmax = take(64);
-    ws.winflag = take(both_fused ? (N + 3) / 4 + 16 : 0);
+    ws.xp = cv.take((ws.has_xp || rec16) ? N * m.W * 3 * std::max(m.gru[0].Hp, m.rec[0].Hp) : 0);
+    ws.vmax = cv.take(64);
+    ws.winflag = cv.take(both_fused ? (N + 3) / 4 + 16 : 0);
     // series path with stride-1 windows: the convolution of the segment (n + W - 1 rows) and of the windows' edge rows
-    ws.cf = take(both_fused ? (N + m.W) * m.Fp : 0);
-    ws.el = take(both_fused ? N * 2 * m.pad * m.Fp : 0);
-    ws.er = take(both_fused ? N * 2 * m.pad * m.Fp : 0);
+    ws.cf = cv.take(both_fused ? (N + m.W) * m.Fp : 0);
+    ws.el = cv.take(both_fused ? N * 2 * m.pad * m.Fp : 0);
+    ws.er = cv.take(both_fused ? N * 2 * m.pad * m.Fp : 0);
     size_t kk = 0;       // layers beyond k_gat_wide (more than 512 nodes / node dimensions) run through a score matrix, one at a time
     for (const GatPlan* g : {&m.feat, &m.temp})
         if (!g->fused && (g->K > 512 || g->D > 512)) kk = std::max(kk, (size_t)g->K * g->K);
-    ws.sc = take(N * kk);
-    ws.total = off;
+    ws.sc = cv.take(N * kk);
+    ws.total = cv.off;
 }
 
+// How forward() walks a call of `batch` windows: chunks of at most m.chunk windows one after the other (each planned for its own
+// size: a short last chunk gets the small-batch kernels and their buffers), and -- fused front end, split-operand arithmetic --
+// a chunk in PIECES that alternate between two lanes (the caller's stream and the handle's own), each lane with its own
+// workspace.  Why: the large-batch recurrence (k_gru_cm) is a 100-step latency chain on one 4-wave workgroup per 128 windows
+// and per CU, so its time is the same for any chunk up to 32 768 windows and doubles at 32 769; and while it runs it owns the
+// register file but not the vector ALU.  Two lanes let one piece's convolution / attention fill the other's recurrence:
+// measured (MSL shape, profiles/r04_overlap_experiment.txt) 10 240 windows 6.0 -> 5.4 ms, 12 288: 6.3 -> 5.7, 36 864:
+// 15.9 -> 12.4, 40 960: 16.7 -> 14.1, 49 152: 18.0 -> 16.4; no gain at 16 384 .. 32 768 (one piece) and at whole multiples of
+// 32 768.  The pieces' results are those of forward() called on each piece (the kernels are chosen by the piece's size).
+ForwardPlan plan_forward(const Model& m, int64_t batch) {
+    ForwardPlan p;
+    const char* hook = getenv("MTADGAT_PIECES");                                           // measurement hook: "a,b,c": piece sizes, alternating lanes
+    const bool both_fused = m.temp.fused && m.feat.fused;
+    const bool two = m.lanes == 0 && m.precision == 2 && both_fused;
+    // Round 6: models on the un-fused (wide) attention path walk a call of several chunks with the chunks ALTERNATING between the
+    // lanes.  Their chunks are a few hundred windows (projections through HBM: ~7 MB of scratch per window at F = 512, W = 256), so the
+    // recurrences of a chunk are small-batch latency chains on a quarter of the CUs (896 windows: ~56 workgroups; GRU layer + decoder
+    // 68.7 of config 4's 273 ms in round 5, strictly behind the chunk's front end) -- on the other lane the next chunk's convolution,
+    // projections and attention fill the rest of the machine meanwhile.  Each lane has its own workspace (lane_floats).
+    const bool alt = m.lanes == 0 && !both_fused && batch > m.chunk && !hook;
+    if (alt) {
+        // the first piece is HALF a chunk: with equal pieces the lanes run in lock step (both front ends side by side, then both
+        // recurrences on 2 x 56 CUs: 258 vs 268 ms for one lane); offset by half a chunk, one lane's recurrences sit under the other's
+        // front end
+        int64_t c0 = 0, ci = 0;
+        const int64_t half = std::max<int64_t>(32, m.chunk / 2 / 32 * 32);
+        while (c0 < batch) {
+            const int64_t n = std::min<int64_t>(ci == 0 ? half : m.chunk, batch - c0);
+            p.pieces.push_back({c0, n, (int)(ci & 1)});
+            c0 += n; ++ci;
+        }
+    }
+    for (int64_t c0 = 0; !alt && c0 < batch; c0 += m.chunk) {
+        const int64_t n = std::min<int64_t>(m.chunk, batch - c0);
+        int64_t k = 1, base = n;
+        if (two && n > SPLIT3_MAX_WINDOWS && n <= 2 * SPLIT3_MAX_WINDOWS) {                // two halves for the hidden-tile-split kernel
+            k = 2;
+            base = n / 2 / 32 * 32;                                                        // (whole 32-window groups, the last piece takes the rest)
+            // a short tail rides beside a full piece instead (9 216 windows: 5.15 -> 4.77 ms; from 10 240 on the halves are as fast)
+            if (n - SPLIT3_MAX_WINDOWS <= 1536) base = SPLIT3_MAX_WINDOWS;
+        } else if (two && n > 32768 && n % 32768 != 0) {                                   // full k_gru_cm rounds (256 workgroups of 128 windows), then the rest
+            // (whole multiples of 32 768 gain nothing from the second lane -- every round is full -- and stay one piece on the caller's stream)
+            k = (n + 32767) / 32768;
+            base = 32768;
+        }
+        if (hook) {
+            int64_t at = 0;
+            int lane = 0;
+            for (const char* q = hook; *q && at < n;) {
+                int64_t len = std::min<int64_t>(n - at, strtoll(q, const_cast<char**>(&q), 10));
+                if (*q == ',') ++q;
+                if (len <= 0) break;
+                p.pieces.push_back({c0 + at, len, lane});
+                lane ^= 1; at += len;
+            }
+            if (at < n) p.pieces.push_back({c0 + at, n - at, lane});
+            continue;
+        }
+        for (int64_t i = 0, at = 0; i < k; ++i) {
+            const int64_t len = i + 1 < k ? base : n - at;
+            p.pieces.push_back({c0 + at, len, (int)(i & 1)});
+            at += len;
+        }
+    }
+    // workspace: per lane the largest plan of the pieces it runs; lane 1 starts behind lane 0 (ForwardPlan::lane_offset)
+    Workspace o;
+    int64_t seen[2][2] = {{0, 0}, {0, 0}};                    // (plans repeat: sizes seen last per lane)
+    for (const ForwardPiece& pc : p.pieces) {
+        p.second = p.second || pc.lane == 1;
+        if (pc.n == seen[pc.lane][0] || pc.n == seen[pc.lane][1]) continue;
+        seen[pc.lane][1] = seen[pc.lane][0]; seen[pc.lane][0] = pc.n;
+        plan_workspace(m, pc.n, o);
+        p.lane_floats[pc.lane] = std::max(p.lane_floats[pc.lane], o.total);
+    }
+    plan_workspace(m, std::min<int64_t>(batch, m.chunk), o);  // (the stage entry points plan one chunk on one lane)
+    p.total_floats = std::max(p.lane_floats[0] + p.lane_floats[1], o.total);
+    // Small calls (the reference Predictor's 256 windows, prediction.py:31): no launch fills the machine, the forward is a chain of
+    // latencies -- so the stages that do not depend on each other run side by side: the feature layer next to the temporal one
+    // (both read the convolution, mtad_gat.py:68-69), the forecasting head next to the reconstruction decoder (both read h_end,
+    // mtad_gat.py:76-77).  Same kernels, same results; the second stream joins before the call returns.
+    // (large calls gain nothing from it: with the convolution as its own launch and both attention layers side by side, 65 536
+    // windows take 21.0-21.2 ms against 21.1-21.3 one after the other -- the layers compete for the same vector ALUs)
+    p.fork = !p.second && p.pieces.size() == 1 && m.lanes == 0 && p.pieces[0].n <= FORK_MAX_WINDOWS && both_fused;
+    return p;
+}
+
+// Default chunk of a new handle: up to 65 536 windows, fewer when a window needs a lot of scratch (wide models on the
+// un-fused attention path: ~8 MB per window at F=512, W=256), so that the workspace stays within a
+// quarter of the device memory (device_bytes; 0 = no device can be queried: within 16 GB)
+int64_t default_chunk(const Model& m, double device_bytes) {
+    Workspace o;
+    plan_workspace(m, 65536, o);       // large batches: without the small-batch extras (pre-projected inputs, decoder states)
+    const double per_window = (double)o.total * sizeof(float) / 65536.0;
+    double budget = device_bytes > 0 ? device_bytes / 4 : 16.0 * 1024 * 1024 * 1024;
+    const bool unfused = !(m.temp.fused && m.feat.fused);
+    if (unfused) budget = std::min(budget, 6.0 * 1024 * 1024 * 1024);   // projections through HBM: a few hundred windows fill the machine
+    int64_t c = (int64_t)(budget / per_window);
+    // (more than 512 features: score matrices of up to 16 MB and projections of up to 4 096 columns per window, ~70 MB of
+    // scratch per window at F = 2048, W = 512 -- fewer than 128 windows fit the budget)
+    const int64_t gran = unfused ? (m.F > 512 ? 8 : 128) : 2048;
+    c = c / gran * gran;
+    return c < gran ? gran : (c > 65536 ? 65536 : c);
+}
 
 int wgrad_slabs(long R, int Mp, int Np) {
     // 128 x 128 output blocks (one workgroup of 4 waves each); enough row slabs for ~4 workgroups per CU
@@ -779,54 +870,44 @@ int wgrad_slabs(long R, int Mp, int Np) {
 }
 
 void plan_tape(const Model& m, int64_t n, Tape& t) {
-    size_t off = 0;
-    auto take = [&](size_t cnt) {
-        size_t o = off;
-        off = align64(off + cnt);
-        return o;
-    };
+    Carver cv;
     const size_t N = (size_t)n;
     const GruPlan& g = m.gru[0];
     const GruPlan& r = m.rec[0];
-    t.hcat = take(N * m.W * m.Dp);
-    t.xct = take(N * m.F * m.Wp);
-    t.att_f = take(N * m.F * m.F);
-    t.att_t = take(N * m.W * m.W);
-    t.hend = take(N * g.Hp);
-    t.gates_g = take(N * m.W * 4 * g.Hp);
-    t.seq_g = take(N * m.W * g.Hp);
-    t.gates_d = take(N * m.W * 4 * r.Hp);
-    t.seq_d = take(N * m.W * r.Hp);
-    t.xdec = take(N * m.W * g.Hp);
-    t.xp = take(N * m.W * 3 * std::max(g.Hp, r.Hp));
+    t.hcat = cv.take(N * m.W * m.Dp);
+    t.xct = cv.take(N * m.F * m.Wp);
+    t.att_f = cv.take(N * m.F * m.F);
+    t.att_t = cv.take(N * m.W * m.W);
+    t.hend = cv.take(N * g.Hp);
+    t.gates_g = cv.take(N * m.W * 4 * g.Hp);
+    t.seq_g = cv.take(N * m.W * g.Hp);
+    t.gates_d = cv.take(N * m.W * 4 * r.Hp);
+    t.seq_d = cv.take(N * m.W * r.Hp);
+    t.xdec = cv.take(N * m.W * g.Hp);
+    t.xp = cv.take(N * m.W * 3 * std::max(g.Hp, r.Hp));
     t.fc_act.clear();
-    for (size_t i = 0; i + 1 < m.fc.size(); ++i) t.fc_act.push_back(take(N * (size_t)m.fc[i].NT * 32));
-    t.vmax = take(64);
-    t.lct = take(m.temp.fused ? 0 : N * m.W * m.temp.ldl);
-    t.rtt = take(m.temp.fused ? 0 : N * m.temp.rt_rows * m.temp.Kp);
-    t.lcf = take(m.feat.fused ? 0 : N * m.F * m.feat.ldl);
-    t.rtf = take(m.feat.fused ? 0 : N * m.feat.rt_rows * m.feat.Kp);
+    for (size_t i = 0; i + 1 < m.fc.size(); ++i) t.fc_act.push_back(cv.take(N * (size_t)m.fc[i].NT * 32));
+    t.vmax = cv.take(64);
+    t.lct = cv.take(m.temp.fused ? 0 : N * m.W * m.temp.ldl);
+    t.rtt = cv.take(m.temp.fused ? 0 : N * m.temp.rt_rows * m.temp.Kp);
+    t.lcf = cv.take(m.feat.fused ? 0 : N * m.F * m.feat.ldl);
+    t.rtf = cv.take(m.feat.fused ? 0 : N * m.feat.rt_rows * m.feat.Kp);
     t.gates_gu.clear(); t.seq_gu.clear(); t.drop_g.clear(); t.gates_du.clear(); t.seq_du.clear(); t.drop_d.clear();
     for (size_t l = 1; l < m.gru.size(); ++l) {
-        t.drop_g.push_back(take(N * m.W * m.gru[l - 1].Hp));
-        t.gates_gu.push_back(take(N * m.W * 4 * m.gru[l].Hp));
-        t.seq_gu.push_back(take(N * m.W * m.gru[l].Hp));
+        t.drop_g.push_back(cv.take(N * m.W * m.gru[l - 1].Hp));
+        t.gates_gu.push_back(cv.take(N * m.W * 4 * m.gru[l].Hp));
+        t.seq_gu.push_back(cv.take(N * m.W * m.gru[l].Hp));
     }
     for (size_t l = 1; l < m.rec.size(); ++l) {
-        t.drop_d.push_back(take(N * m.W * m.rec[l - 1].Hp));
-        t.gates_du.push_back(take(N * m.W * 4 * m.rec[l].Hp));
-        t.seq_du.push_back(take(N * m.W * m.rec[l].Hp));
+        t.drop_d.push_back(cv.take(N * m.W * m.rec[l - 1].Hp));
+        t.gates_du.push_back(cv.take(N * m.W * 4 * m.rec[l].Hp));
+        t.seq_du.push_back(cv.take(N * m.W * m.rec[l].Hp));
     }
-    t.total = off;
+    t.total = cv.off;
 }
 
 void plan_bwd_workspace(const Model& m, int64_t n, BwdWorkspace& w) {
-    size_t off = 0;
-    auto take = [&](size_t cnt) {
-        size_t o = off;
-        off = align64(off + cnt);
-        return o;
-    };
+    Carver cv;
     const size_t N = (size_t)n;
     const GruPlan& g = m.gru[0];
     const GruPlan& r = m.rec[0];
@@ -834,24 +915,24 @@ void plan_bwd_workspace(const Model& m, int64_t n, BwdWorkspace& w) {
     size_t hpmax = std::max(g.Hp, r.Hp);
     for (const GruPlan& q : m.gru) hpmax = std::max(hpmax, (size_t)q.Hp);
     for (const GruPlan& q : m.rec) hpmax = std::max(hpmax, (size_t)q.Hp);
-    w.da = take(N * m.W * 4 * hpmax);
-    w.dhcat = take(N * m.W * m.Dp);
-    w.dhdec = take(N * m.W * hpmax);
-    w.dhend = take(N * g.Hp);
+    w.da = cv.take(N * m.W * 4 * hpmax);
+    w.dhcat = cv.take(N * m.W * m.Dp);
+    w.dhdec = cv.take(N * m.W * hpmax);
+    w.dhend = cv.take(N * g.Hp);
     size_t fcw = 32;
     for (const LinPlan& p : m.fc) fcw = std::max(fcw, (size_t)std::max(p.NT * 32, round_up(p.in_dim, 32)));
-    w.dz0 = take(N * fcw);
-    w.dz1 = take(N * fcw);
-    w.de_f = take(N * m.F * m.F);
-    w.de_t = take(N * m.W * m.W);
-    w.dv_f = take(N * m.F * m.Wp);
-    w.dv_t = take(N * m.W * m.Fp);
+    w.dz0 = cv.take(N * fcw);
+    w.dz1 = cv.take(N * fcw);
+    w.de_f = cv.take(N * m.F * m.F);
+    w.de_t = cv.take(N * m.W * m.W);
+    w.dv_f = cv.take(N * m.F * m.Wp);
+    w.dv_t = cv.take(N * m.W * m.Fp);
     // (GAT v1 reuses these regions for its per-window partials [sum dc_i v_i | sum dd_j v_j | sc sd]: 2 D + 2 floats per window)
-    w.dlr_f = take(std::max(N * m.F * 2 * b.gat[0].Ep, m.cfg.use_gatv2 ? (size_t)0 : N * (2 * (size_t)m.W + 2)));
-    w.dlr_t = take(std::max(N * m.W * 2 * b.gat[1].Ep, m.cfg.use_gatv2 ? (size_t)0 : N * (2 * (size_t)m.F + 2)));
-    w.dap_f = take(N * b.gat[0].Ep);
-    w.dap_t = take(N * b.gat[1].Ep);
-    w.dpre = take(N * m.W * m.Fp);
+    w.dlr_f = cv.take(std::max(N * m.F * 2 * b.gat[0].Ep, m.cfg.use_gatv2 ? (size_t)0 : N * (2 * (size_t)m.W + 2)));
+    w.dlr_t = cv.take(std::max(N * m.W * 2 * b.gat[1].Ep, m.cfg.use_gatv2 ? (size_t)0 : N * (2 * (size_t)m.F + 2)));
+    w.dap_f = cv.take(N * b.gat[0].Ep);
+    w.dap_t = cv.take(N * b.gat[1].Ep);
+    w.dpre = cv.take(N * m.W * m.Fp);
     {   // wide attention layers (mtadgat_bwdw.hip), one layer at a time
         size_t ds = 0, lr = 0;
         for (int which = 0; which < 2; ++which) {
@@ -862,7 +943,7 @@ void plan_bwd_workspace(const Model& m, int64_t n, BwdWorkspace& w) {
             if (!b.gat[which].wide) continue;
             ds = std::max(ds, N * gp.K * (size_t)round_up(gp.D, 4));
         }
-        w.wds = take(ds); w.wlr = take(lr);          // (no transposed copy of d e since round 6: the score backward is one pass)
+        w.wds = cv.take(ds); w.wlr = cv.take(lr);          // (no transposed copy of d e since round 6: the score backward is one pass)
     }
     // partial sums of the weight-gradient GEMMs: one region each (round 6), so that their reductions can wait for ONE batched launch
     // at the end of the backward (the GEMMs used to share a region, each followed by its own reduction launch: twelve per step)
@@ -879,17 +960,85 @@ void plan_bwd_workspace(const Model& m, int64_t n, BwdWorkspace& w) {
     need(b.recfc_wg, RW);
     for (const WgradPlan& p : b.fc_wg) need(p, (long)n);
     w.wpart_floats = wp;
-    w.wpart = take(wp);
+    w.wpart = cv.take(wp);
     const size_t pv = 2 * (size_t)std::max(m.F, m.W) + 2;             // GAT (v1): per-window partials [p1 | p2 | sc sd]
-    w.v1s = take(4 * pv);
+    w.v1s = cv.take(4 * pv);
     const size_t smax = std::max(std::max((size_t)m.W * m.W, pv), std::max((size_t)m.F * m.F, (size_t)std::max(b.gat[0].Ep, b.gat[1].Ep)));
-    w.sums = take(sum_rows_scratch(n, (int)smax));
+    w.sums = cv.take(sum_rows_scratch(n, (int)smax));
     for (int which = 0; which < 2; ++which) {
         const size_t K = which == 0 ? (size_t)m.F : (size_t)m.W;
-        w.sums_q[2 * which] = m.cfg.use_gatv2 ? take(sum_rows_scratch(n, (int)(K * K))) : 0;
-        w.sums_q[2 * which + 1] = m.cfg.use_gatv2 ? take(sum_rows_scratch(n, b.gat[which].Ep)) : 0;
+        w.sums_q[2 * which] = m.cfg.use_gatv2 ? cv.take(sum_rows_scratch(n, (int)(K * K))) : 0;
+        w.sums_q[2 * which + 1] = m.cfg.use_gatv2 ? cv.take(sum_rows_scratch(n, b.gat[which].Ep)) : 0;
     }
-    w.total = off;
+    w.total = cv.off;
+}
+
+// mean mode: at most 2^26 floats (256 MB) of per-window maps per chunk (MSL's temporal layer: 6 710 windows of 100 x 100)
+static constexpr int64_t ATT_MAPS_FLOATS = int64_t(1) << 26;
+void plan_attention(const Model& m, int64_t batch, bool reduce, AttPlan& p) {
+    Carver cv;
+    const int64_t kk = std::max<int64_t>((int64_t)m.F * m.F, (int64_t)m.W * m.W);
+    p.chunk = reduce ? std::min<int64_t>(m.chunk, std::max<int64_t>(1, ATT_MAPS_FLOATS / kk)) : m.chunk;
+    const int64_t n = std::min<int64_t>(batch, p.chunk);
+    const size_t N = (size_t)n;
+    p.hcat = cv.take(N * m.W * m.Dp);
+    p.xct = cv.take(m.feat.fused ? 0 : N * m.F * m.Wp);
+    p.lct = cv.take(m.temp.fused ? 0 : N * m.W * m.temp.ldl);
+    p.rtt = cv.take(m.temp.fused ? 0 : N * m.temp.rt_rows * m.temp.Kp);
+    p.lcf = cv.take(m.feat.fused ? 0 : N * m.F * m.feat.ldl);
+    p.rtf = cv.take(m.feat.fused ? 0 : N * m.feat.rt_rows * m.feat.Kp);
+    p.slabs_f = reduce ? att_mean_slabs(n, m.F) : 0;
+    p.slabs_t = reduce ? att_mean_slabs(n, m.W) : 0;
+    p.maps = cv.take(reduce ? N * (size_t)kk : 0);
+    p.ps_f = cv.take((size_t)p.slabs_f * m.F * m.F);
+    p.pc_f = cv.take((size_t)p.slabs_f * m.F * m.F);
+    p.ps_t = cv.take((size_t)p.slabs_t * m.W * m.W);
+    p.pc_t = cv.take((size_t)p.slabs_t * m.W * m.W);
+    p.total = cv.off;
+}
+
+// the chunk's scratch stays below 4 GiB (MSL shape: ~2 300 windows; BASELINE config 4: ~190), and below mtadgat_chunk_windows()
+static constexpr double ATTR_WS_BYTES = 4.0 * 1024 * 1024 * 1024;
+void plan_attribution(const Model& m, int64_t count, int steps, AttrPlan& p) {
+    const int W = m.W, F = m.F, od = m.cfg.out_dim;
+    const int64_t U = count * std::max(steps, 1);
+    Tape t;
+    plan_tape(m, 64, t);
+    BwdWorkspace w;
+    plan_bwd_workspace(m, 64, w);
+    const double per_window = ((double)(t.total + w.total) / 64 + 2.0 * W * F + 2.0 * (W + 1) * od + 2.0 * od) * sizeof(float);
+    int64_t win = std::min<int64_t>(m.chunk, (int64_t)(ATTR_WS_BYTES / per_window));
+    win = std::max<int64_t>(2, win / 2 * 2);
+    p.units = std::max<int64_t>(1, std::min<int64_t>(U, win / 2));
+    const size_t n = (size_t)(2 * p.units), nu = (size_t)p.units;
+    Carver cv;
+    p.x = cv.take(n * W * F);
+    p.y = cv.take(nu * od);
+    p.preds = cv.take(n * od);
+    p.recons = cv.take(n * W * od);
+    p.dpreds = cv.take(n * od);
+    p.drecons = cv.take(n * W * od);
+    p.gy = cv.take(nu * od);
+    p.dx = cv.take(n * W * F);
+    plan_tape(m, (int64_t)n, t);
+    plan_bwd_workspace(m, (int64_t)n, w);
+    p.tape_floats = t.total;
+    p.bws_floats = w.total;
+    p.tape = cv.take(t.total);
+    p.bws = cv.take(w.total);
+    p.total = cv.off;
+}
+
+// the push workspace of the streaming scorer: its own regions (rounded to 4 floats), the forward's workspace behind them
+StreamWs stream_ws(const Model& m, int64_t windows) {
+    const size_t od = ((size_t)windows * m.cfg.out_dim + 3) / 4 * 4;
+    StreamWs w;
+    w.preds = 0;
+    w.last = od;
+    w.starts = 2 * od;
+    w.fwd = w.starts + ((size_t)windows * 2 + 3) / 4 * 4;          // (an int64 per window)
+    w.total = w.fwd + plan_forward(m, windows).total_floats;
+    return w;
 }
 
 // embedding columns with a'_k = (1 - alpha)/2 a_k >= 0 first (padded to a multiple of 8), then the negative ones

@@ -1,5 +1,5 @@
 """forward() walks a large call in pieces that alternate between the caller's stream and the handle's second lane
-(mtadgat_capi.cpp forward_schedule): the results are those of forward() on each piece, whatever stream the caller is on,
+(mtadgat_pack.cpp plan_forward): the results are those of forward() on each piece, whatever stream the caller is on,
 call after call on the same workspace; option "lanes" = 1 keeps everything on the caller's stream."""
 import pytest
 import torch
@@ -124,6 +124,33 @@ def test_small_calls_run_independent_stages_side_by_side(name, n, gpu_device):
     k = case.x.shape[0]
     gate(p[:k], case.preds, case.preds64, what=f"{name} predictions (two-stream small call)")
     gate(r[:k], case.recons, case.recons64, what=f"{name} recons (two-stream small call)")
+
+
+@pytest.mark.parametrize("n,last", [(9000, (8192, 808, 1)), (4096, (0, 4096, 0))])
+def test_last_conv_max_reads_the_last_pieces_lane(n, last, gpu_device):
+    """mtadgat_last_conv_max finds its word in the workspace part of the lane that ran the call's last piece -- at 9000 windows
+    (8192 + 808) the second lane's.  The convolution kernel is chosen by the piece's size and the maximum is an integer atomic max of
+    float bits (order does not matter): the value equals, bit for bit, that of the last piece run alone on one lane."""
+    case = Case("msl")
+    model = case.build_model().to(gpu_device)
+    model.check_weight_contents = False
+    g = torch.Generator().manual_seed(n)
+    x = torch.rand(n, case.kwargs["window_size"], case.kwargs["n_features"], generator=g).to(gpu_device)
+    with torch.no_grad():
+        model(x[:1])
+        eng = model._engine
+        plan = eng.forward_plan(n)
+        assert plan["pieces"][-1] == last and (plan["lane_floats"][1] > 0) == bool(last[2])
+        model(x)
+        a = eng.last_conv_max(n, gpu_device)
+        eng.set_option("lanes", 1)
+        try:
+            assert eng.forward_plan(last[1])["pieces"] == [(0, last[1], 0)]
+            model(x[-last[1]:])
+            b = eng.last_conv_max(last[1], gpu_device)
+        finally:
+            eng.set_option("lanes", 0)
+    assert a == b and a > 0, (a, b)
 
 
 def test_unchanged_weights_do_not_hold_the_call_up(gpu_device):

@@ -137,7 +137,8 @@ def test_recurrence_kernel_bands_on_random_shapes(idx, gpu_device):
 
 def test_config4_chunked_batch_against_the_oracle(gpu_device):
     """BASELINE config 4 (F = 512, W = 256, out_dim = 512; the un-fused wide attention path: projections through HBM,
-    k_gat_wide) on a batch that the library walks in several chunks (64 = 24 + 24 + 16 windows), every window against
+    k_gat_wide) on a batch that the library walks in several pieces (64 = 32 + 24 + 8 windows on lanes 0, 1, 0: chunks of 24 windows
+    alternate between the lanes behind a first piece of half a chunk, which is at least 32 windows), every window against
     oracle.forward_chunked (the reference's algorithm on the CPU, two windows at a time: it materialises 0.8 GB of pairwise
     inputs per window)."""
     from mtad_gat import MTAD_GAT
