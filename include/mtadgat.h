@@ -160,7 +160,7 @@ int mtadgat_read_packed(mtadgat_handle h, float* dst_host, int64_t n_floats, voi
  *   out[4]  the input products of all steps are hoisted into a launch in front
  *   out[5]  the layer's split packs are needed (derived on first use after an upload)
  *   out[6]  the per-step Linear of the decoder rides inside the recurrence
- *   out[7]  the stack takes the small-batch kernels (what the heads and the backward ask; equals out[0] in {1, 2} for layer 0)
+ *   out[7]  the stack takes the small-batch kernels (what the heads and the training forward ask; equals out[0] in {1, 2} for layer 0)
  * Returns 0, or MTADGAT_ERR_INVALID. */
 int mtadgat_gru_route(mtadgat_handle h, int stack, int layer, int64_t n, int training, int compute_units, int* out);
 /* Test hook (host only: needs neither a GPU nor loaded weights): which kernels run the front end -- window convolution, temporal
@@ -200,6 +200,23 @@ int mtadgat_front_route(mtadgat_handle h, int kind, int source, int64_t n, int f
  *   out[5 + 3 i .. 8 + 3 i)  piece i: its first window, its window count, its lane
  * Returns the count of values written, or MTADGAT_ERR_INVALID (a NULL argument, batch < 1, max_n too small: nothing is written). */
 int mtadgat_forward_plan(mtadgat_handle h, int64_t batch, int64_t* out, int max_n);
+/* Test hook (host only: needs neither a GPU nor loaded weights): which kernels run the recurrence layers and the attention layers of
+ * a training step (mtadgat_forward_train + mtadgat_backward) of n windows.  The answer is the one the library's own dispatch uses
+ * under the handle's current mtadgat_set_precision mode and "gru_kernel" option; the backward's recurrence kernel is derived from
+ * the forward's, whose tape it reads.  Writes 3 * (gru_n_layers + recon_n_layers) + 5 ints:
+ *   per layer of the GRU stack, then per layer of the decoder, counted from the input:
+ *     [0]  first kernel of the training forward (the codes of mtadgat_gru_route's out[0])
+ *     [1]  kernel of the backward: 0 k_gru1_bwd (partner of k_gru1), 1 k_gru16_bwd (partner of k_gru16), 2 k_gru_bwd (partner of
+ *          k_gru_split on either operand build)
+ *     [2]  k_gru_bwd multiplies on three bf16 pieces per operand (its split pack is derived on first use after an upload)
+ *   then 1 when the decoder's per-step Linear runs inside the top decoder layer's recurrence in this call (its partial sums fit the
+ *   hidden-tile-split kernel's LDS and the decoder is not on the small-batch kernels), 0 when it is a row GEMM over the kept states
+ *   then for the feature and for the temporal attention layer:
+ *     [0]  the backward goes through the generic wide-layer kernels (the layer is not fused)
+ *     [1]  the score backward is GAT (v1)'s (use_gatv2 == 0)
+ * Returns the count of values written, or MTADGAT_ERR_INVALID (a NULL argument, n < 1, max_n too small: nothing is written),
+ * MTADGAT_ERR_UNSUPPORTED (the configuration has no HIP backward). */
+int mtadgat_train_route(mtadgat_handle h, int64_t n, int* out, int max_n);
 /* Test hook (host only): does a row GEMM over `rows` rows take split-bf16 operands (k_rowgemm_x3) under the handle's precision mode
  * and "rowgemm_kernel" option?  has_pack: a split pack was planned for its weights; backward: a site of mtadgat_backward (there
  * "rowgemm_kernel" = 2 forces the split pack in every mode, in the forward only in the "fp32" mode).  Returns 1 / 0, negative: error. */

@@ -37,6 +37,8 @@ PROFILE_SLOTS = 6
 GRU_ROUTE_FIELDS = ("first", "fallback", "build", "two", "hoist", "split_packs", "fc_rides", "small_stack")
 GRU_KERNELS = ("none", "k_gru1", "k_gru16", "k_gru_split", "k_gru_split_x3", "k_gru_cm", "k_gru")
 GRU_BUILDS = ("fp32", "bf16", "x3_hi", "x3_lo")
+# mtadgat_train_route: the backward kernel codes (GruBwdKernel of csrc/mtadgat_host.h)
+GRU_BWD_KERNELS = ("k_gru1_bwd", "k_gru16_bwd", "k_gru_bwd")
 # mtadgat_front_route: the integers it writes (include/mtadgat.h) and the codes of csrc/mtadgat_host.h
 FRONT_ROUTE_FIELDS = ("conv", "conv_build", "conv_split_pack", "range",
                       "temp_kernel", "temp_build", "temp_fp16", "temp_split_gemm", "temp_split_pack",
@@ -101,6 +103,7 @@ def load_library():
     lib.mtadgat_gru_route.argtypes = [vp, ctypes.c_int, ctypes.c_int, i64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
     lib.mtadgat_front_route.argtypes = [vp, ctypes.c_int, ctypes.c_int, i64, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
     lib.mtadgat_forward_plan.argtypes = [vp, i64, ctypes.POINTER(i64), ctypes.c_int]
+    lib.mtadgat_train_route.argtypes = [vp, i64, ctypes.POINTER(ctypes.c_int), ctypes.c_int]
     lib.mtadgat_rowgemm_split.argtypes = [vp, ctypes.c_int, i64, ctypes.c_int]
     lib.mtadgat_workspace_bytes.argtypes = [vp, i64]
     lib.mtadgat_workspace_bytes.restype = sz
@@ -487,6 +490,20 @@ class Engine:
             _check(got, "mtadgat_forward_plan")
         v = [int(x) for x in buf[:got]]
         return dict(fork=bool(v[1]), lane_floats=(v[2], v[3]), total_floats=v[4], pieces=[tuple(v[i:i + 3]) for i in range(5, got, 3)])
+
+    def train_route(self, n):
+        """Which kernels run the recurrence and attention layers of a training step of n windows under the current precision and
+        "gru_kernel" option (host only) -- mtadgat_train_route (include/mtadgat.h): dict of gru / rec [(forward kernel, backward
+        kernel, x3) per layer], rec_fc_rides, feat / temp (wide, v1)."""
+        lg, ld = self.cfg.gru_n_layers, self.cfg.recon_n_layers
+        cap = 3 * (lg + ld) + 5
+        buf = (ctypes.c_int * cap)()
+        got = self.lib.mtadgat_train_route(self.handle, int(n), buf, cap)
+        if got != cap:
+            _check(got or -1, "mtadgat_train_route")
+        v = [int(x) for x in buf]
+        layers = [tuple(v[3 * i:3 * i + 3]) for i in range(lg + ld)]
+        return dict(gru=layers[:lg], rec=layers[lg:], rec_fc_rides=v[-5], feat=tuple(v[-4:-2]), temp=tuple(v[-2:]))
 
     def load_weights(self, sd, device, allow_device_pack=True):
         """sd: reference-format state_dict (any device).  The first load packs on the host and uploads on the current

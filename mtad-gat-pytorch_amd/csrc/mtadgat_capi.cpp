@@ -909,6 +909,31 @@ int mtadgat_forward_plan(mtadgat_handle h, int64_t batch, int64_t* out, int max_
     return (int)v.size();
 }
 
+/* Read-only test hook (no GPU, no weights): the recurrence and attention routes of a training step of n windows under the handle's
+ * precision and "gru_kernel" option; include/mtadgat.h defines the values written.  Returns their count. */
+int mtadgat_train_route(mtadgat_handle h, int64_t n, int* out, int max_n) {
+    if (!h || !out) return fail(MTADGAT_ERR_INVALID, "null argument");
+    if (n < 1) return fail(MTADGAT_ERR_INVALID, "the route needs at least one window");
+    const Model& m = h->m;
+    if (!m.bw.supported) return fail(MTADGAT_ERR_UNSUPPORTED, "no HIP backward for this configuration: " + m.bw.why);
+    std::vector<int> v;
+    bool fc_rides = false;
+    for (int decoder = 0; decoder < 2; ++decoder) {
+        const std::vector<GruPlan>& st = decoder ? m.rec : m.gru;
+        for (int l = 0; l < (int)st.size(); ++l) {
+            const GruRoute f = gru_route(m, st, l, n, XP_PLAN_CUS, gru_call_facts(m, decoder != 0, l, n, true));
+            const GruBwdRoute r = gru_bwd_route(m, decoder != 0, l, n);
+            v.insert(v.end(), {f.first, r.kernel, r.x3});
+            fc_rides = f.fc_rides;          // (of the last decoder layer when the loops end)
+        }
+    }
+    v.push_back(fc_rides);
+    for (int which = 0; which < 2; ++which) v.insert(v.end(), {m.bw.gat[which].wide, !m.cfg.use_gatv2});
+    if ((int64_t)v.size() > max_n) return fail(MTADGAT_ERR_INVALID, "route array too small");
+    std::copy(v.begin(), v.end(), out);
+    return (int)v.size();
+}
+
 /* Read-only test hook: rowgemm_split under the handle's precision and "rowgemm_kernel" option (1 / 0, negative: error) */
 int mtadgat_rowgemm_split(mtadgat_handle h, int has_pack, int64_t rows, int backward) {
     return h ? (int)rowgemm_split(h->m, has_pack != 0, rows, backward != 0) : fail(MTADGAT_ERR_INVALID, "null handle");
@@ -1476,8 +1501,8 @@ struct WgradQueue {
     }
 };
 int run_wgrad(Model& m, const WgradPlan& p, const WgradIn& in, WgradQueue& wq, float* outW, float* outB, hipStream_t s) {
-    const int nslab_ = wgrad_slabs(in.R, p.Mp, p.Np);
-    const size_t need_ = ((size_t)nslab_ * p.Mp * p.Np + 63) & ~(size_t)63;
+    const int nslab = wgrad_slabs(in.R, p.Mp, p.Np);
+    const size_t need_ = ((size_t)nslab * p.Mp * p.Np + 63) & ~(size_t)63;
     if (need_ > wq.cap) return fail(MTADGAT_ERR_WORKSPACE, "internal: weight-gradient partial region too small");
     if (wq.used + need_ > wq.cap || wq.n == WGRAD_BATCH_MAX)
         if (int rc_ = wq.flush()) return rc_;
@@ -1488,7 +1513,7 @@ int run_wgrad(Model& m, const WgradPlan& p, const WgradIn& in, WgradQueue& wq, f
     a.B = in.B; a.ldb = in.ldb; a.N = p.N; a.bmode = in.bmode; a.bshift = in.bshift;
     a.T = in.T; a.F = m.F; a.taps = m.taps; a.pad = m.pad;
     a.R = in.R;
-    a.nslab = wgrad_slabs(in.R, p.Mp, p.Np);
+    a.nslab = nslab;
     long rps = (in.R + a.nslab - 1) / a.nslab;
     rps = (rps + 15) / 16 * 16;
     a.rows_per_slab = rps;
@@ -1516,6 +1541,119 @@ int run_sum_rows_queued(const float* src, long ld, long R, int N, float* scratch
     r.P = scratch; r.nslab = nslab; r.Mp = 1; r.Np = N; r.M = 1; r.N = N;
     r.outW = dst;
     wq.pend[wq.n++] = r;
+    return 0;
+}
+
+// The training forward of one recurrence stack (modules.py:235-238 / :276-283): every layer keeps its gates and states; between
+// stacked layers nn.GRU's dropout (training only; modules.py:232-233 / :253) -- the dropped sequence is what the next layer reads
+// and is kept as well.  What the two stacks differ in:
+struct StackFwd {
+    int slot; const char* name; unsigned drop0;     // profile slot, "gru" / "decoder", dropout stream of layer 0's states
+    const float* x; long ldx; int kx;               // what layer 0 reads
+    float* xp = nullptr;                            // layer 0: room for hoisted input products (the small-batch kernels need it) ...
+    const unsigned* vmax = nullptr;                 // ... and the convolution's recorded range
+    float* hend = nullptr;                          // the top layer's last states
+    const LinPlan* fc = nullptr;                    // a per-step Linear on the top layer's states into yfc: inside its recurrence
+    bool rides = false;                             // (rides), otherwise a row GEMM over the kept states
+    float* yfc = nullptr;
+};
+int walk_stack_forward(Model& m, const std::vector<GruPlan>& stack, const std::vector<TapeLayer>& tl, float* T, StackFwd f,
+                       const DropArgs& drop, int64_t n, hipStream_t s) {
+    const int L = (int)stack.size();
+    const std::string drop_what = std::string(f.name) + " inter-layer dropout";
+    for (int l = 0; l < L; ++l) {
+        const GruPlan& g = stack[l];
+        const bool top = l == L - 1;
+        float* seq = T + tl[l].seq;
+        GruIo io;
+        io.x = f.x; io.ldx = f.ldx; io.kx = f.kx; io.seq = seq; io.gates = T + tl[l].gates;
+        io.hend = top ? f.hend : nullptr; io.ldhe = f.hend ? g.Hp : 0;
+        if (l == 0) { io.xp = f.xp; io.vmax = f.vmax; }
+        if (top && f.rides) { io.fc = f.fc; io.yfc = f.yfc; }
+        if (int rc = run_gru_layer(m, f.slot, stack, l, io, n, s)) return rc;
+        if (!top) {
+            float* dr = T + tl[l].drop;
+            K_TRY(launch_seq_dropout(seq, dr, n, m.W, g.H, g.Hp, drop, f.drop0 + (unsigned)l, s), drop_what.c_str());
+            f.x = dr; f.ldx = g.Hp; f.kx = g.H;
+        } else if (f.fc && !f.rides) {
+            Scope sc(m, f.slot, s);
+            K_TRY(launch_rowgemm(lin_rows(m, *f.fc, seq, g.Hp, n * (int64_t)m.W, f.yfc), s), "reconstruction Linear (training)");
+        }
+    }
+    return 0;
+}
+
+// What the steps of one backward call share.  grads == nullptr: the data path only.
+struct BwdCall {
+    Model& m; const float* T; int64_t n; const DropArgs& drop; float* grads; WgradQueue& wq;
+    float* da;        // gate gradients of every step of the layer at hand
+    float* dhdec;     // gradient of every state of the layer below it
+    hipStream_t s;
+};
+// The backward of one recurrence stack from the top layer down.  Per layer: BPTT with the kernel gru_bwd_route names (gate
+// gradients of every step into `da`), the layer's weight gradients, and d (rows the layer read) = d a W_ih -- above layer 0 into
+// dhdec and through the dropout's adjoint: the gradient of the states of the layer below.  What the two stacks differ in:
+struct StackBwd {
+    bool decoder; const char* name; unsigned drop0;
+    const float* x0; float* d0; long ld0;           // layer 0: the rows it read, where their gradient goes, the row stride of both
+    const float* dh_seq; const float* dh_end;       // top layer: gradient of every state / of the last state only (nullptr: none)
+};
+int walk_stack_backward(const BwdCall& c, const std::vector<TapeLayer>& tl, const StackBwd& sb) {
+    Model& m = c.m;
+    const std::vector<GruPlan>& stack = sb.decoder ? m.rec : m.gru;
+    const std::vector<GruBwdPlan>& plans = sb.decoder ? m.bw.rec : m.bw.gru;
+    const GradLayout& gl = m.bw.gl;
+    const std::vector<int64_t>&o_wih = sb.decoder ? gl.rec_wih : gl.gru_wih, &o_whh = sb.decoder ? gl.rec_whh : gl.gru_whh,
+                              &o_bih = sb.decoder ? gl.rec_bih : gl.gru_bih, &o_bhh = sb.decoder ? gl.rec_bhh : gl.gru_bhh;
+    const int W = m.W, L = (int)stack.size();
+    const int64_t n = c.n;
+    const long RW = (long)n * W;
+    const std::string what = std::string(sb.name) + " backward", drop_what = std::string(sb.name) + " inter-layer dropout (adjoint)";
+    hipStream_t s = c.s;
+    float* da = c.da;
+    for (int l = L - 1; l >= 0; --l) {
+        const GruPlan& q = stack[l];
+        const GruBwdPlan& qb = plans[l];
+        const bool top = l == L - 1;
+        const float* gates = c.T + tl[l].gates;
+        const float* seq = c.T + tl[l].seq;
+        const float* xin = l == 0 ? sb.x0 : c.T + tl[l - 1].drop;
+        const long ldxin = l == 0 ? sb.ld0 : stack[l - 1].Hp;
+        const float* dhseq = top ? sb.dh_seq : c.dhdec;
+        const float* dhend = top ? sb.dh_end : nullptr;
+        const GruBwdRoute r = gru_bwd_route(m, sb.decoder, l, n);
+        if (r.kernel != GRU_BWD_SPLIT) {
+            Gru16BwdArgs ga{};
+            ga.Gates = gates; ga.Seq = seq; ga.DHseq = dhseq; ga.lddh = q.Hp; ga.DHend = dhend; ga.ldde = q.Hp;
+            ga.W16T = m.packed_dev + (r.kernel == GRU_BWD_WINDOW ? q.g1T_off : q.g16T_off);
+            ga.DA = da; ga.Hp = q.Hp; ga.KS = q.KS16; ga.NT16 = q.NT16; ga.T = W; ga.B = n; ga.H = q.H;
+            if (r.kernel == GRU_BWD_WINDOW) K_TRY(launch_gru1_bwd(ga, s), what.c_str());
+            else K_TRY(launch_gru16_bwd(ga, s), what.c_str());
+        } else {
+            GruBwdArgs ga{};
+            ga.Gates = gates; ga.Seq = seq; ga.DHseq = dhseq; ga.lddh = q.Hp; ga.DHend = dhend; ga.ldde = q.Hp;
+            if (r.split_pack)
+                if (int rc_ = ensure(m, qb.split, s)) return rc_;
+            ga.WhT = reinterpret_cast<const f32x4*>(m.packed_dev + (r.x3 ? qb.whT3_off : qb.whT_off));
+            ga.x3 = r.x3 ? 1 : 0;
+            ga.DA = da; ga.Hp = q.Hp; ga.H = q.H; ga.T = W; ga.NCG = q.NCG; ga.B = n;
+            K_TRY(launch_gru_bwd(ga, s), what.c_str());
+        }
+        if (c.grads) {
+            WgradIn hh;
+            hh.A = da + q.Hp; hh.lda = 4L * q.Hp; hh.bshift = 1; hh.B = seq; hh.ldb = q.Hp; hh.R = RW; hh.T = W;
+            if (int rc = run_wgrad(m, qb.wg_hh, hh, c.wq, c.grads + o_whh[l], c.grads + o_bhh[l], s)) return rc;
+            WgradIn ih;
+            ih.A = da; ih.lda = 4L * q.Hp; ih.B = xin; ih.ldb = ldxin; ih.R = RW; ih.T = W;
+            if (int rc = run_wgrad(m, qb.wg_ih, ih, c.wq, c.grads + o_wih[l], c.grads + o_bih[l], s)) return rc;
+        }
+        if (l > 0) {
+            const GruPlan& lo = stack[l - 1];
+            if (int rc = run_rowgemm_T(m, qb.wihT, da, 4L * q.Hp, RW, c.dhdec, lo.Hp, lo.Hp, false, nullptr, 0, 1.f, s)) return rc;
+            K_TRY(launch_seq_dropout(c.dhdec, c.dhdec, n, W, lo.H, lo.Hp, c.drop, sb.drop0 + (unsigned)(l - 1), s), drop_what.c_str());
+        } else if (int rc = run_rowgemm_T(m, qb.wihT, da, 4L * q.Hp, RW, sb.d0, sb.ld0, (int)sb.ld0, false, nullptr, 0, 1.f, s))
+            return rc;
+    }
     return 0;
 }
 
@@ -1564,8 +1702,8 @@ int mtadgat_train_layout(mtadgat_handle h, int64_t batch, int64_t* out, int max_
     plan_tape(h->m, batch, t);
     BwdWorkspace w;
     plan_bwd_workspace(h->m, batch, w);
-    std::vector<int64_t> v = {(int64_t)t.hcat, (int64_t)t.xct, (int64_t)t.att_f, (int64_t)t.att_t, (int64_t)t.hend, (int64_t)t.gates_g,
-                              (int64_t)t.seq_g, (int64_t)t.gates_d, (int64_t)t.seq_d, (int64_t)t.xdec,
+    std::vector<int64_t> v = {(int64_t)t.hcat, (int64_t)t.xct, (int64_t)t.att_f, (int64_t)t.att_t, (int64_t)t.hend, (int64_t)t.gru[0].gates,
+                              (int64_t)t.gru[0].seq, (int64_t)t.rec[0].gates, (int64_t)t.rec[0].seq, (int64_t)t.xdec,
                               (int64_t)w.da, (int64_t)w.dhcat, (int64_t)w.dhdec, (int64_t)w.dhend, (int64_t)w.dz0, (int64_t)w.dz1,
                               (int64_t)w.de_f, (int64_t)w.de_t, (int64_t)w.dv_f, (int64_t)w.dv_t, (int64_t)w.dlr_f, (int64_t)w.dlr_t,
                               (int64_t)w.dap_f, (int64_t)w.dap_t, (int64_t)w.dpre};
@@ -1602,31 +1740,12 @@ int mtadgat_forward_train(mtadgat_handle h, const float* x, int64_t batch, int64
     feat.att = T + t.att_f; feat.drop = &drop; feat.drop_stream = DROP_FEAT; feat.vmax = vmax;
     if ((rc = run_gat_layer(m, m.temp, fr.temp, temp, n, s))) return rc;
     if ((rc = run_gat_layer(m, m.feat, fr.feat, feat, n, s))) return rc;
-    // GRU stack (modules.py:235-238): every layer keeps its gates and states; between stacked layers nn.GRU's dropout
-    // (training only; reference modules.py:232-233): the dropped sequence is what the next layer reads and is kept as well
-    const int Lg = (int)m.gru.size(), Ld = (int)m.rec.size();
-    const GruPlan& g = m.gru.back();                 // the layer that produces h_end
+    // GRU stack (modules.py:235-238): layer 0 behind the convolution's recorded range, the top layer produces h_end
+    const GruPlan& g = m.gru.back();
     float* hend = T + t.hend;
-    {
-        const float* xin = hcat;
-        long ldin = m.Dp;
-        int kx = 3 * F;
-        for (int l = 0; l < Lg; ++l) {
-            const GruPlan& gl_ = m.gru[l];
-            const bool last = l == Lg - 1;
-            float* seq = T + (l == 0 ? t.seq_g : t.seq_gu[l - 1]);
-            float* gates = T + (l == 0 ? t.gates_g : t.gates_gu[l - 1]);
-            GruIo io;
-            io.x = xin; io.ldx = ldin; io.kx = kx; io.hend = last ? hend : nullptr; io.ldhe = gl_.Hp; io.seq = seq; io.gates = gates;
-            if (l == 0) { io.xp = T + t.xp; io.vmax = vmax; }
-            if ((rc = run_gru_layer(m, S_GRU, m.gru, l, io, n, s))) return rc;
-            if (!last) {
-                float* dr = T + t.drop_g[l];
-                K_TRY(launch_seq_dropout(seq, dr, n, W, gl_.H, gl_.Hp, drop, DROP_GRU0 + (unsigned)l, s), "gru inter-layer dropout");
-                xin = dr; ldin = gl_.Hp; kx = gl_.H;
-            }
-        }
-    }
+    StackFwd gs{S_GRU, "gru", DROP_GRU0, hcat, m.Dp, 3 * F};
+    gs.xp = T + t.xp; gs.vmax = vmax; gs.hend = hend;
+    if ((rc = walk_stack_forward(m, m.gru, t.gru, T, gs, drop, n, s))) return rc;
     // forecasting head: ReLU + dropout on the hidden layers (modules.py:307-311), activations kept
     {
         Scope sc(m, S_FC, s);
@@ -1646,41 +1765,15 @@ int mtadgat_forward_train(mtadgat_handle h, const float* x, int64_t batch, int64
             xin = a.Y; ld = a.ldy;
         }
     }
-    // reconstruction decoder, all steps kept
-    const GruPlan& r = m.rec[0];
-    if (gru_stack_small(m, m.rec, n, true)) {
-        GruIo io;
-        io.x = hend; io.ldx = g.Hp; io.kx = m.cfg.gru_hid_dim; io.seq = T + t.seq_d; io.gates = T + t.gates_d; io.xp = T + t.xp;
-        if ((rc = run_gru_layer(m, S_RECON, m.rec, 0, io, n, s))) return rc;
-        Scope sc(m, S_RECON, s);
-        K_TRY(launch_rowgemm(lin_rows(m, m.rec_fc, T + t.seq_d, r.Hp, n * (int64_t)W, recons), s), "reconstruction Linear (training)");
-    } else {
-        // layer 0 reads the repeated h_end (modules.py:279), the layers above the (dropped-out) states of the one below; the
-        // per-step Linear (modules.py:282) rides in the last layer while its weights fit beside the state in 64 KB of LDS
-        // (launch_gru_split), otherwise it is a row GEMM over the kept states -- as in the small-batch branch above
-        const float* xin = hend;
-        long ldin = g.Hp;
-        int kx = m.cfg.gru_hid_dim;
-        const bool fc_rides = rec_fc_rides_train(m);
-        for (int l = 0; l < Ld; ++l) {
-            const GruPlan& rl = m.rec[l];
-            const bool last = l == Ld - 1, fused = last && fc_rides;
-            float* seq = T + (l == 0 ? t.seq_d : t.seq_du[l - 1]);
-            float* gates = T + (l == 0 ? t.gates_d : t.gates_du[l - 1]);
-            GruIo io;
-            io.x = xin; io.ldx = ldin; io.kx = kx; io.seq = seq; io.gates = gates;
-            if (fused) { io.fc = &m.rec_fc; io.yfc = recons; }
-            if ((rc = run_gru_layer(m, S_RECON, m.rec, l, io, n, s))) return rc;
-            if (!last) {
-                float* dr = T + t.drop_d[l];
-                K_TRY(launch_seq_dropout(seq, dr, n, W, rl.H, rl.Hp, drop, DROP_REC0 + (unsigned)l, s), "decoder inter-layer dropout");
-                xin = dr; ldin = rl.Hp; kx = rl.H;
-            } else if (!fused) {
-                Scope sc(m, S_RECON, s);
-                K_TRY(launch_rowgemm(lin_rows(m, m.rec_fc, seq, rl.Hp, n * (int64_t)W, recons), s), "reconstruction Linear (training)");
-            }
-        }
-    }
+    // reconstruction decoder, all steps kept: layer 0 reads the repeated h_end (modules.py:279).  Small batches: one layer on the
+    // small-batch kernels behind its hoisted input products.  Otherwise the per-step Linear (modules.py:282) rides in the last layer
+    // while its weights fit beside the state in 64 KB of LDS (launch_gru_split); where it does not ride it is a row GEMM over the
+    // kept states
+    const bool dec_small = gru_stack_small(m, m.rec, n, true);
+    StackFwd ds{S_RECON, "decoder", DROP_REC0, hend, g.Hp, m.cfg.gru_hid_dim};
+    ds.xp = dec_small ? T + t.xp : nullptr;
+    ds.fc = &m.rec_fc; ds.rides = !dec_small && rec_fc_rides_train(m); ds.yfc = recons;
+    if ((rc = walk_stack_forward(m, m.rec, t.rec, T, ds, drop, n, s))) return rc;
     K_TRY(launch_xdec(hend, g.Hp, m.cfg.gru_hid_dim, W, n, T + t.xdec, g.Hp, s), "decoder input");
     return 0;
 }
@@ -1718,7 +1811,6 @@ int backward_impl(mtadgat_handle h, const float* x, int64_t batch, int64_t windo
     const int64_t n = batch;
     const long RW = (long)n * W;
     const DropArgs drop = make_drop(dropout_p, seed, window0);
-    const int Lg = (int)m.gru.size(), Ld = (int)m.rec.size();
     const GruPlan& g = m.gru.back();                 // the layer that produced h_end (all GRU layers share the hidden size)
     const GruPlan& r = m.rec.back();                 // the decoder layer under the per-step Linear
     const float* hcat = T + t.hcat;
@@ -1745,109 +1837,43 @@ int backward_impl(mtadgat_handle h, const float* x, int64_t batch, int64_t windo
             dy = y; lddy = ldy;
         }
     }
-    // One recurrence layer backward: BPTT (gate gradients of every step into `da`) and the layer's weight gradients.
-    // dhseq: gradient of every state (nullptr: none); dhend_: of the last state only (nullptr: none); xin: the rows the layer read.
-    float* da = ws + w.da;
-    auto layer_bwd = [&](const GruPlan& q, const GruBwdPlan& qb, bool small, const float* gates, const float* seq, const float* dhseq,
-                         const float* dhend_, const float* xin, long ldxin, int64_t o_wih, int64_t o_whh, int64_t o_bih, int64_t o_bhh,
-                         const char* what) -> int {
-        if (small) {
-            Gru16BwdArgs ga{};
-            ga.Gates = gates; ga.Seq = seq; ga.DHseq = dhseq; ga.lddh = q.Hp; ga.DHend = dhend_; ga.ldde = q.Hp;
-            ga.W16T = m.packed_dev + q.g16T_off; ga.DA = da; ga.Hp = q.Hp; ga.KS = q.KS16; ga.NT16 = q.NT16; ga.T = W; ga.B = n; ga.H = q.H;
-            if (n <= G1_MAX_WINDOWS) {                       // as the forward (gru_route): one window per workgroup at a time
-                ga.W16T = m.packed_dev + q.g1T_off;
-                K_TRY(launch_gru1_bwd(ga, s), what);
-            } else
-                K_TRY(launch_gru16_bwd(ga, s), what);
-        } else {
-            GruBwdArgs ga{};
-            ga.Gates = gates; ga.Seq = seq; ga.DHseq = dhseq; ga.lddh = q.Hp; ga.DHend = dhend_; ga.ldde = q.Hp;
-            ga.WhT = reinterpret_cast<const f32x4*>(m.packed_dev + qb.whT_off);
-            if (m.precision == 2 && qb.whT3_off) {       // default arithmetic: three bf16 pieces per operand (split on first use after an upload)
-                if (int rc_ = ensure(m, qb.split, s)) return rc_;
-                ga.WhT = reinterpret_cast<const f32x4*>(m.packed_dev + qb.whT3_off);
-                ga.x3 = 1;
-            }
-            ga.DA = da; ga.Hp = q.Hp; ga.H = q.H; ga.T = W; ga.NCG = q.NCG; ga.B = n;
-            K_TRY(launch_gru_bwd(ga, s), what);
-        }
-        if (!wg) return 0;
-        int rc2;
-        WgradIn hh;
-        hh.A = da + q.Hp; hh.lda = 4L * q.Hp; hh.bshift = 1; hh.B = seq; hh.ldb = q.Hp; hh.R = RW; hh.T = W;
-        if ((rc2 = run_wgrad(m, qb.wg_hh, hh, wpart, grads + o_whh, grads + o_bhh, s))) return rc2;
-        WgradIn ih;
-        ih.A = da; ih.lda = 4L * q.Hp; ih.B = xin; ih.ldb = ldxin; ih.R = RW; ih.T = W;
-        return run_wgrad(m, qb.wg_ih, ih, wpart, grads + o_wih, grads + o_bih, s);
-    };
-    // ---- 2. reconstruction model (modules.py:276-283): per-step Linear, decoder layers from the top, decoder input
     float* dhdec = ws + w.dhdec;
+    const BwdCall call{m, T, n, drop, grads, wpart, ws + w.da, dhdec, s};
+    // ---- 2. reconstruction model (modules.py:276-283): per-step Linear, decoder layers from the top, decoder input
     {
-        const float* seq_top = T + (Ld == 1 ? t.seq_d : t.seq_du[Ld - 2]);
         if ((rc = run_rowgemm_T(m, b.recfcT, d_recons, od, RW, dhdec, r.Hp, r.Hp, false, nullptr, 0, 1.f, s))) return rc;
         WgradIn in;
-        in.A = d_recons; in.lda = od; in.B = seq_top; in.ldb = r.Hp; in.R = RW; in.T = W;
+        in.A = d_recons; in.lda = od; in.B = T + t.rec.back().seq; in.ldb = r.Hp; in.R = RW; in.T = W;
         if (wg && (rc = run_wgrad(m, b.recfc_wg, in, wpart, grads + gl.rec_fc_w, grads + gl.rec_fc_b, s))) return rc;
-        for (int l = Ld - 1; l >= 0; --l) {
-            const GruPlan& q = m.rec[l];
-            const float* gates = T + (l == 0 ? t.gates_d : t.gates_du[l - 1]);
-            const float* seq = T + (l == 0 ? t.seq_d : t.seq_du[l - 1]);
-            const float* xin = l == 0 ? T + t.xdec : T + t.drop_d[l - 1];
-            const long ldxin = l == 0 ? m.gru.back().Hp : m.rec[l - 1].Hp;
-            if ((rc = layer_bwd(q, b.rec[l], gru_stack_small(m, m.rec, n, true), gates, seq, dhdec, nullptr, xin, ldxin, gl.rec_wih[l],
-                                gl.rec_whh[l], gl.rec_bih[l], gl.rec_bhh[l], "decoder backward"))) return rc;
-            if (l > 0) {
-                // d (dropped states of the layer below), then through the dropout: the gradient of that layer's states
-                const GruPlan& lo = m.rec[l - 1];
-                if ((rc = run_rowgemm_T(m, b.rec[l].wihT, da, 4L * q.Hp, RW, dhdec, lo.Hp, lo.Hp, false, nullptr, 0, 1.f, s))) return rc;
-                K_TRY(launch_seq_dropout(dhdec, dhdec, n, W, lo.H, lo.Hp, drop, DROP_REC0 + (unsigned)(l - 1), s), "decoder inter-layer dropout (adjoint)");
-            } else {
-                // d (decoder input) -> d h_end through the repeat_interleave / view of modules.py:279
-                if ((rc = run_rowgemm_T(m, b.rec[0].wihT, da, 4L * q.Hp, RW, dhdec, g.Hp, g.Hp, false, nullptr, 0, 1.f, s))) return rc;
-                K_TRY(launch_xdec_bwd(dhdec, g.Hp, m.cfg.gru_hid_dim, W, n, dhend, g.Hp, s), "decoder input adjoint");
-            }
-        }
+        // layer 0: d (decoder input) -> d h_end through the repeat_interleave / view of modules.py:279
+        if ((rc = walk_stack_backward(call, t.rec, {true, "decoder", DROP_REC0, T + t.xdec, dhdec, g.Hp, dhdec, nullptr}))) return rc;
+        K_TRY(launch_xdec_bwd(dhdec, g.Hp, m.cfg.gru_hid_dim, W, n, dhend, g.Hp, s), "decoder input adjoint");
     }
     // ---- 3. GRU layers from the top (modules.py:235-238): the last one receives d h_end, the others the gradient of their states
     float* dhcat = ws + w.dhcat;
-    for (int l = Lg - 1; l >= 0; --l) {
-        const GruPlan& q = m.gru[l];
-        const float* gates = T + (l == 0 ? t.gates_g : t.gates_gu[l - 1]);
-        const float* seq = T + (l == 0 ? t.seq_g : t.seq_gu[l - 1]);
-        const float* xin = l == 0 ? hcat : T + t.drop_g[l - 1];
-        const long ldxin = l == 0 ? m.Dp : m.gru[l - 1].Hp;
-        const bool top = l == Lg - 1;
-        if ((rc = layer_bwd(q, b.gru[l], gru_stack_small(m, m.gru, n, true), gates, seq, top ? nullptr : dhdec, top ? dhend : nullptr, xin, ldxin,
-                            gl.gru_wih[l], gl.gru_whh[l], gl.gru_bih[l], gl.gru_bhh[l], "gru backward"))) return rc;
-        if (l > 0) {
-            const GruPlan& lo = m.gru[l - 1];
-            if ((rc = run_rowgemm_T(m, b.gru[l].wihT, da, 4L * q.Hp, RW, dhdec, lo.Hp, lo.Hp, false, nullptr, 0, 1.f, s))) return rc;
-            K_TRY(launch_seq_dropout(dhdec, dhdec, n, W, lo.H, lo.Hp, drop, DROP_GRU0 + (unsigned)(l - 1), s), "gru inter-layer dropout (adjoint)");
-        } else if ((rc = run_rowgemm_T(m, b.gru[0].wihT, da, 4L * q.Hp, RW, dhcat, m.Dp, m.Dp, false, nullptr, 0, 1.f, s)))
-            return rc;
-    }
+    if ((rc = walk_stack_backward(call, t.gru, {false, "gru", DROP_GRU0, hcat, dhcat, m.Dp, nullptr, dhend}))) return rc;
     // ---- 4. the two graph-attention layers (modules.py:65-95, :166-193)
     for (int which = 1; which >= 0; --which) {
         const GatPlan& gp = which == 0 ? m.feat : m.temp;
         const GatBwdPlan& gb = b.gat[which];
-        const int K = gp.K;
+        const int K = gp.K, D = gp.D, Ep = gb.Ep;
         float* de = ws + (which == 0 ? w.de_f : w.de_t);
         float* dv = ws + (which == 0 ? w.dv_f : w.dv_t);
         float* dlr = ws + (which == 0 ? w.dlr_f : w.dlr_t);
         float* dap = ws + (which == 0 ? w.dap_f : w.dap_t);
         const int lddv = which == 0 ? m.Wp : m.Fp;
         const int colofs = which == 0 ? F : 2 * F;
+        const long so_w = (long)W * m.Dp, so_i = which == 0 ? 1 : m.Dp, so_d = which == 0 ? m.Dp : 1;
+        const float* att = T + (which == 0 ? t.att_f : t.att_t);
+        const unsigned dstream = which == 0 ? DROP_FEAT : DROP_TEMP;
+        const float* Vn = which == 0 ? T + t.xct : hcat;          // node rows: xc^T rows (feature layer) / h_cat rows (temporal layer)
+        const long ldv = which == 0 ? m.Wp : m.Dp;
+        const int vt = which == 0 ? 1 : 0;                        // fused kernels read the nodes from h_cat: the feature layer's from its columns
+        // scores and aggregation: d e (through the softmax and the dropout of the attention rows) and the aggregation's share of d V
         if (gb.wide) {
             // wide layer (mtadgat_bwdw.hip): every matrix through memory, generic in K and D
-            const long so_w = (long)W * m.Dp, so_i = which == 0 ? 1 : m.Dp, so_d = which == 0 ? m.Dp : 1;
-            const float* att = T + (which == 0 ? t.att_f : t.att_t);
-            const unsigned dstream = which == 0 ? DROP_FEAT : DROP_TEMP;
-            const float* Vn = which == 0 ? T + t.xct : hcat;          // node rows: xc^T rows (feature layer) / h_cat rows (temporal layer)
-            const long ldv = which == 0 ? m.Wp : m.Dp;
-            const int D = gp.D, ldS = round_up(D, 4), Ep = gb.Ep;
+            const int ldS = round_up(D, 4);
             float* dS = ws + w.wds;
-            float* LR = ws + w.wlr;
             K_TRY(launch_bw_ds(hcat + colofs, dhcat + colofs, so_w, so_i, so_d, n, K, D, dS, ldS, s), "attention backward (d S)");
             // d V (aggregation path) = att'^T d S, att' = dropout(att)
             K_TRY(launch_bgemm(att, (long)K * K, 1, K, dS, (long)K * ldS, ldS, 1, dv, (long)K * lddv, lddv, K, D, K, n, &drop, dstream, K, s),
@@ -1856,55 +1882,28 @@ int backward_impl(mtadgat_handle h, const float* x, int64_t batch, int64_t windo
             K_TRY(launch_bgemm(dS, (long)K * ldS, ldS, 1, Vn, (long)K * ldv, 1, ldv, de, (long)K * K, K, K, K, D, n, nullptr, 0, 0, s),
                   "attention backward (d att)");
             K_TRY(launch_bw_softmax(att, de, n, K, drop, dstream, s), "attention backward (softmax)");
-            if (!m.cfg.use_gatv2) {
-                // GAT (v1), round 6: the score backward is linear in the node vectors below d s -- k_gat_bwd_v1's algebra with the
-                // node rows read from memory (k_bw_v1); prep and finish are the fused path's
-                const int E = gp.E, PV = 2 * D + 2;
-                float* u = ws + w.v1s + (size_t)which * 2 * (2 * std::max(m.F, m.W) + 2);
-                float* P = u + (2 * std::max(m.F, m.W) + 2);
-                const float* Wm = m.packed_dev + gb.w1_off;
-                const float* bv = m.packed_dev + gb.b1_off;
-                const float* av = m.packed_dev + gb.a_off;
-                K_TRY(launch_gat_v1_prep(Wm, bv, av, E, D, u, s), "attention backward (v1 vectors)");
-                K_TRY(launch_bw_v1(Vn, ldv, D, K, u, de, m.cfg.alpha, dv, lddv, dlr, n, s), "attention backward (v1 scores, wide)");
-                if (!wg) continue;
-                HIP_TRY(hipMemsetAsync(P, 0, (size_t)PV * sizeof(float), s));
-                K_TRY(launch_sum_rows(dlr, PV, n, PV, ws + w.sums, P, s), "attention backward (v1 sums)");
-                K_TRY(launch_gat_v1_finish(P, Wm, bv, av, E, D, grads + gl.lin_w[which], grads + gl.lin_b[which], grads + gl.a[which], s),
-                      "attention parameter gradients (v1)");
-                K_TRY(launch_sum_rows(de, (long)K * K, n, K * K, ws + w.sums, grads + gl.bias[which], s), "attention bias gradient");
-                continue;
-            }
-            // un-scaled projections [L | R] of the node rows, then the score backward
-            if ((rc = run_bwd_projection(m, gp, gb, Vn, ldv, (long)n * K, LR, s))) return rc;
-            K_TRY(launch_bw_pair(LR, 2 * Ep, Ep, m.packed_dev + gb.a_off, de, K, m.cfg.alpha, dlr, dap, n, s), "attention backward (pairs)");
-            const long RK = (long)n * K;
-            if ((rc = run_rowgemm_T(m, gb.lrT, dlr, 2L * Ep, RK, dv, lddv, gp.D, true, nullptr, 0, 1.f, s))) return rc;
-            WgradIn in;
-            in.A = dlr; in.lda = 2L * Ep; in.R = RK; in.T = 1; in.B = Vn; in.ldb = ldv;
-            if (wg && (rc = run_wgrad(m, gb.wg, in, wpart, grads + gl.lin_w[which], grads + gl.lin_b[which], s))) return rc;
-            if (wg && (rc = run_sum_rows_queued(de, (long)K * K, n, K * K, ws + w.sums_q[2 * which], grads + gl.bias[which], wpart, s))) return rc;
-            if (wg && (rc = run_sum_rows_queued(dap, Ep, n, gp.E, ws + w.sums_q[2 * which + 1], grads + gl.a[which], wpart, s))) return rc;
-            continue;
+        } else {
+            GatBwdAttArgs aa{};
+            aa.V = hcat; aa.ldv = m.Dp; aa.D = D; aa.K = K; aa.vt = vt; aa.vld = gp.f_vld;
+            aa.H = hcat + colofs; aa.dH = dhcat + colofs;
+            aa.so_w = so_w; aa.so_i = so_i; aa.so_d = so_d;
+            aa.ATT = att;
+            aa.DE = de; aa.DV = dv; aa.lddv = lddv; aa.nwin = n;
+            aa.drop = drop; aa.drop_stream = dstream;
+            K_TRY(launch_gat_bwd_att(aa, gp.f_IBL, gp.f_JPL, gp.f_RJ, gp.f_nw, gb.att_lds, s), "attention backward (scores)");
         }
-        GatBwdAttArgs aa{};
-        aa.V = hcat; aa.ldv = m.Dp; aa.D = gp.D; aa.K = K; aa.vt = which == 0 ? 1 : 0; aa.vld = gp.f_vld;
-        aa.H = hcat + colofs; aa.dH = dhcat + colofs;
-        aa.so_w = (long)W * m.Dp; aa.so_i = which == 0 ? 1 : m.Dp; aa.so_d = which == 0 ? m.Dp : 1;
-        aa.ATT = T + (which == 0 ? t.att_f : t.att_t);
-        aa.DE = de; aa.DV = dv; aa.lddv = lddv; aa.nwin = n;
-        aa.drop = drop; aa.drop_stream = which == 0 ? DROP_FEAT : DROP_TEMP;
-        K_TRY(launch_gat_bwd_att(aa, gp.f_IBL, gp.f_JPL, gp.f_RJ, gp.f_nw, gb.att_lds, s), "attention backward (scores)");
         if (!m.cfg.use_gatv2) {
-            // GAT (v1) scores: linear in the node vectors below d s (mtadgat_bwd.hip)
-            const int E = gp.E, D = gp.D, PV = 2 * D + 2;
+            // GAT (v1) scores: linear in the node vectors below d s -- the fused layers' kernel reads them from h_cat
+            // (k_gat_bwd_v1, mtadgat_bwd.hip), the wide layers' the same algebra from the node rows in memory (k_bw_v1)
+            const int E = gp.E, PV = 2 * D + 2;
             float* u = ws + w.v1s + (size_t)which * 2 * (2 * std::max(m.F, m.W) + 2);
             float* P = u + (2 * std::max(m.F, m.W) + 2);
             const float* Wm = m.packed_dev + gb.w1_off;
             const float* bv = m.packed_dev + gb.b1_off;
             const float* av = m.packed_dev + gb.a_off;
             K_TRY(launch_gat_v1_prep(Wm, bv, av, E, D, u, s), "attention backward (v1 vectors)");
-            K_TRY(launch_gat_bwd_v1(hcat, m.Dp, D, K, aa.vt, u, de, m.cfg.alpha, dv, lddv, dlr, n, s), "attention backward (v1 scores)");
+            if (gb.wide) K_TRY(launch_bw_v1(Vn, ldv, D, K, u, de, m.cfg.alpha, dv, lddv, dlr, n, s), "attention backward (v1 scores, wide)");
+            else K_TRY(launch_gat_bwd_v1(hcat, m.Dp, D, K, vt, u, de, m.cfg.alpha, dv, lddv, dlr, n, s), "attention backward (v1 scores)");
             if (!wg) continue;
             HIP_TRY(hipMemsetAsync(P, 0, (size_t)PV * sizeof(float), s));
             K_TRY(launch_sum_rows(dlr, PV, n, PV, ws + w.sums, P, s), "attention backward (v1 sums)");
@@ -1913,21 +1912,18 @@ int backward_impl(mtadgat_handle h, const float* x, int64_t batch, int64_t windo
             K_TRY(launch_sum_rows(de, (long)K * K, n, K * K, ws + w.sums, grads + gl.bias[which], s), "attention bias gradient");
             continue;
         }
-        // round 6: the un-scaled projections [L | R] of the node rows as one row GEMM, then the one-pass score backward (k_bw_pair,
-        // mtadgat_bwdw.hip) -- for fused layers too: the per-window kernel that re-projected L, R inside the workgroup is gone
-        {
-            float* LR = ws + w.wlr;
-            if ((rc = run_bwd_projection(m, gp, gb, which == 0 ? T + t.xct : hcat, which == 0 ? m.Wp : m.Dp, (long)n * K, LR, s))) return rc;
-            K_TRY(launch_bw_pair(LR, 2 * gb.Ep, gb.Ep, m.packed_dev + gb.a_off, de, K, m.cfg.alpha, dlr, dap, n, s), "attention backward (pairs)");
-        }
+        // GATv2: the un-scaled projections [L | R] of the node rows as one row GEMM, then the one-pass score backward (k_bw_pair,
+        // mtadgat_bwdw.hip) -- for fused layers too
+        float* LR = ws + w.wlr;
         const long RK = (long)n * K;
-        if ((rc = run_rowgemm_T(m, gb.lrT, dlr, 2L * gb.Ep, RK, dv, lddv, gp.D, true, nullptr, 0, 1.f, s))) return rc;
+        if ((rc = run_bwd_projection(m, gp, gb, Vn, ldv, RK, LR, s))) return rc;
+        K_TRY(launch_bw_pair(LR, 2 * Ep, Ep, m.packed_dev + gb.a_off, de, K, m.cfg.alpha, dlr, dap, n, s), "attention backward (pairs)");
+        if ((rc = run_rowgemm_T(m, gb.lrT, dlr, 2L * Ep, RK, dv, lddv, D, true, nullptr, 0, 1.f, s))) return rc;
         WgradIn in;
-        in.A = dlr; in.lda = 2L * gb.Ep; in.R = RK; in.T = 1;
-        if (which == 0) { in.B = T + t.xct; in.ldb = m.Wp; } else { in.B = hcat; in.ldb = m.Dp; }
+        in.A = dlr; in.lda = 2L * Ep; in.R = RK; in.T = 1; in.B = Vn; in.ldb = ldv;
         if (wg && (rc = run_wgrad(m, gb.wg, in, wpart, grads + gl.lin_w[which], grads + gl.lin_b[which], s))) return rc;
         if (wg && (rc = run_sum_rows_queued(de, (long)K * K, n, K * K, ws + w.sums_q[2 * which], grads + gl.bias[which], wpart, s))) return rc;
-        if (wg && (rc = run_sum_rows_queued(dap, gb.Ep, n, gp.E, ws + w.sums_q[2 * which + 1], grads + gl.a[which], wpart, s))) return rc;
+        if (wg && (rc = run_sum_rows_queued(dap, Ep, n, gp.E, ws + w.sums_q[2 * which + 1], grads + gl.a[which], wpart, s))) return rc;
     }
     // ---- 5. convolution (modules.py:18-22)
     {
@@ -1984,8 +1980,7 @@ int mtadgat_backward_data(mtadgat_handle h, const float* x, int64_t batch, int64
     return input_gradient(h->m, batch, static_cast<const float*>(ws_), w, dx, (hipStream_t)stream);
 }
 
-/* The keep-masks of nn.GRU's dropout between stacked layers (reference modules.py:233 / :253): mask_gru (gru_n_layers - 1, batch, W, H),
- * mask_rec (recon_n_layers - 1, batch, W, recon_hid_dim); either may be NULL */
+/* d x of the chunk whose mtadgat_backward left its convolution pre-activation gradients in `ws` */
 int mtadgat_backward_input(mtadgat_handle h, int64_t batch, const void* ws_, size_t ws_bytes, float* dx, void* stream) {
     int rc = check_train(h, batch, 0.f);
     if (rc) return rc;
@@ -2059,6 +2054,8 @@ int mtadgat_score_attribution(mtadgat_handle h, const float* series, int64_t n_r
     return 0;
 }
 
+/* The keep-masks of nn.GRU's dropout between stacked layers (reference modules.py:233 / :253): mask_gru (gru_n_layers - 1, batch, W, H),
+ * mask_rec (recon_n_layers - 1, batch, W, recon_hid_dim); either may be NULL */
 int mtadgat_dropout_masks_rnn(mtadgat_handle h, int64_t batch, int64_t window0, float dropout_p, uint64_t seed, float* mask_gru,
                               float* mask_rec, void* stream) {
     if (!h) return fail(MTADGAT_ERR_INVALID, "null handle");

@@ -135,7 +135,8 @@ inline bool gru_xp_serves(int64_t n, int cu) { return n <= XP_WINDOWS_PER_CU * c
 
 // ---- recurrence routes ---------------------------------------------------------------------------------------------------------
 // Which kernels run one GRU / decoder layer of one call.  gru_route (mtadgat_pack.cpp) is the only place that decides; run_gru_layer
-// (mtadgat_capi.cpp) launches what it names, the callers ask gru_stack_small for the stack-level question.  DESIGN.md section 4 has
+// (mtadgat_capi.cpp) launches what it names, the forward's callers ask gru_stack_small for the stack-level question, the backward asks
+// gru_bwd_route.  DESIGN.md section 4 has
 // the table of bands.
 enum GruKernel : int {
     GRU_NONE = 0,
@@ -172,6 +173,15 @@ GruRoute gru_route(const Model& m, const std::vector<GruPlan>& stack, int layer,
 // the facts of layer `layer` of the GRU stack (decoder = false) or the decoder in a whole forward() (predictions and reconstructions
 // wanted, n windows in one piece) or training forward: what mtadgat_gru_route reports
 GruCall gru_call_facts(const Model& m, bool decoder, int layer, int64_t n, bool training);
+// The backward of a recurrence layer reads the tape the training forward's route wrote; gru_bwd_route derives its kernel from that
+// route (layer `layer` of the GRU stack or the decoder, n windows), so the pair cannot drift.
+enum GruBwdKernel : int { GRU_BWD_WINDOW = 0 /* k_gru1_bwd */, GRU_BWD_GROUP16 = 1 /* k_gru16_bwd */, GRU_BWD_SPLIT = 2 /* k_gru_bwd */ };
+struct GruBwdRoute {
+    GruBwdKernel kernel = GRU_BWD_SPLIT;
+    bool x3 = false;             // GRU_BWD_SPLIT on three bf16 pieces per operand (GruBwdPlan::whT3_off)
+    bool split_pack = false;     // the layer's backward split pack must be current (ensure)
+};
+GruBwdRoute gru_bwd_route(const Model& m, bool decoder, int layer, int64_t n);
 
 // ---- front-end routes ----------------------------------------------------------------------------------------------------------
 // Which kernels run the window convolution and the two attention layers of one call.  front_route (mtadgat_pack.cpp) is the only
@@ -379,13 +389,14 @@ struct Workspace {
 };
 
 // activations kept between the training forward and the backward (caller-owned "tape"), offsets in floats
+struct TapeLayer { size_t gates, seq, drop; };   // of one recurrence layer: gate activations and states of every step, and the dropped-out
+                                                 // copy of the states that the layer above reads (nn.GRU's inter-layer dropout,
+                                                 // modules.py:233 / :253; unused for the top layer)
 struct Tape {
-    size_t hcat, xct, att_f, att_t, hend, gates_g, seq_g, gates_d, seq_d, xdec, xp, total;
+    size_t hcat, xct, att_f, att_t, hend, xdec, xp, total;
     size_t vmax;         // one word: bits of the largest convolution output (range guard of the split-operand recurrences)
     size_t lct, rtt, lcf, rtf;   // wide attention layers: the projections L' / R'^T of the training forward (zero-sized for fused layers)
-    // stacked recurrences: gates / state sequences of the layers above the first, and the (dropped-out) state sequences
-    // that feed them (nn.GRU's inter-layer dropout, modules.py:233 / :253)
-    std::vector<size_t> gates_gu, seq_gu, drop_g, gates_du, seq_du, drop_d;
+    std::vector<TapeLayer> gru, rec;   // per layer of the GRU stack / the decoder
     std::vector<size_t> fc_act;     // outputs of the hidden forecasting layers (after ReLU + dropout)
 };
 // scratch of the backward

@@ -589,6 +589,18 @@ GruCall gru_call_facts(const Model& m, bool decoder, int layer, int64_t n, bool 
     return c;
 }
 
+// The forward's kernel decides the backward's: k_gru1 / k_gru16 keep the tape k_gru1_bwd / k_gru16_bwd read, every other training
+// route is the hidden-tile-split kernel's, read by k_gru_bwd.  A training route's small / large answer does not depend on the
+// compute-unit count -- gru_route returns from its small-batch and training branches before `cu` is read -- so any count serves.
+GruBwdRoute gru_bwd_route(const Model& m, bool decoder, int layer, int64_t n) {
+    const GruKernel fwd = gru_route(m, decoder ? m.rec : m.gru, layer, n, XP_PLAN_CUS, gru_call_facts(m, decoder, layer, n, true)).first;
+    GruBwdRoute r;
+    r.kernel = fwd == GRU_WINDOW ? GRU_BWD_WINDOW : fwd == GRU_GROUP16 ? GRU_BWD_GROUP16 : GRU_BWD_SPLIT;
+    // default arithmetic: three bf16 pieces per operand (split on first use after an upload)
+    r.x3 = r.split_pack = r.kernel == GRU_BWD_SPLIT && m.precision == 2 && (decoder ? m.bw.rec : m.bw.gru)[layer].whT3_off != 0;
+    return r;
+}
+
 // The one rule "this row GEMM takes split-bf16 operands": the split-operand arithmetic (mode 2) from 65 536 rows on (below that the
 // product is a few tens of microseconds either way and the pack would be re-split after every optimizer step for nothing);
 // "rowgemm_kernel" = 1 keeps the fp32 MFMA, 2 takes the split pack at any size.  The forward and the backward sites differ and
@@ -879,10 +891,13 @@ void plan_tape(const Model& m, int64_t n, Tape& t) {
     t.att_f = cv.take(N * m.F * m.F);
     t.att_t = cv.take(N * m.W * m.W);
     t.hend = cv.take(N * g.Hp);
-    t.gates_g = cv.take(N * m.W * 4 * g.Hp);
-    t.seq_g = cv.take(N * m.W * g.Hp);
-    t.gates_d = cv.take(N * m.W * 4 * r.Hp);
-    t.seq_d = cv.take(N * m.W * r.Hp);
+    // layer 0 of each stack first, the layers above (the dropped-out states below them, their gates, their states) at the end
+    t.gru.assign(m.gru.size(), TapeLayer{});
+    t.rec.assign(m.rec.size(), TapeLayer{});
+    t.gru[0].gates = cv.take(N * m.W * 4 * g.Hp);
+    t.gru[0].seq = cv.take(N * m.W * g.Hp);
+    t.rec[0].gates = cv.take(N * m.W * 4 * r.Hp);
+    t.rec[0].seq = cv.take(N * m.W * r.Hp);
     t.xdec = cv.take(N * m.W * g.Hp);
     t.xp = cv.take(N * m.W * 3 * std::max(g.Hp, r.Hp));
     t.fc_act.clear();
@@ -892,17 +907,15 @@ void plan_tape(const Model& m, int64_t n, Tape& t) {
     t.rtt = cv.take(m.temp.fused ? 0 : N * m.temp.rt_rows * m.temp.Kp);
     t.lcf = cv.take(m.feat.fused ? 0 : N * m.F * m.feat.ldl);
     t.rtf = cv.take(m.feat.fused ? 0 : N * m.feat.rt_rows * m.feat.Kp);
-    t.gates_gu.clear(); t.seq_gu.clear(); t.drop_g.clear(); t.gates_du.clear(); t.seq_du.clear(); t.drop_d.clear();
-    for (size_t l = 1; l < m.gru.size(); ++l) {
-        t.drop_g.push_back(cv.take(N * m.W * m.gru[l - 1].Hp));
-        t.gates_gu.push_back(cv.take(N * m.W * 4 * m.gru[l].Hp));
-        t.seq_gu.push_back(cv.take(N * m.W * m.gru[l].Hp));
-    }
-    for (size_t l = 1; l < m.rec.size(); ++l) {
-        t.drop_d.push_back(cv.take(N * m.W * m.rec[l - 1].Hp));
-        t.gates_du.push_back(cv.take(N * m.W * 4 * m.rec[l].Hp));
-        t.seq_du.push_back(cv.take(N * m.W * m.rec[l].Hp));
-    }
+    auto upper = [&](const std::vector<GruPlan>& stack, std::vector<TapeLayer>& tl) {
+        for (size_t l = 1; l < stack.size(); ++l) {
+            tl[l - 1].drop = cv.take(N * m.W * stack[l - 1].Hp);
+            tl[l].gates = cv.take(N * m.W * 4 * stack[l].Hp);
+            tl[l].seq = cv.take(N * m.W * stack[l].Hp);
+        }
+    };
+    upper(m.gru, t.gru);
+    upper(m.rec, t.rec);
     t.total = cv.off;
 }
 

@@ -149,6 +149,46 @@ def test_gradients_match_autograd_above_the_small_batch_kernels(name, gpu_device
     assert not bad, "\n".join(bad)
 
 
+_WINDOW_EDGE = {}
+
+
+def _window_edge_step(n, device):
+    """One eval-mode HIP step on the first n of 1793 fixed windows of `small_v2` and its autograd reference, computed once per n."""
+    if n not in _WINDOW_EDGE:
+        kw, _ = CONFIGS["small_v2"]
+        model = _model(kw, device).eval()
+        g = torch.Generator().manual_seed(16)
+        x = torch.rand(1793, kw["window_size"], kw["n_features"], generator=g)[:n].to(device)
+        y = torch.rand(1793, kw["out_dim"], generator=g)[:n].to(device)
+        pr_ref, rc_ref, ref = _reference_grads(model, x, y)
+        pr, rc = model(x)
+        assert model.grad_path == "hip", model.grad_path
+        _loss(pr, rc, x, y).backward()
+        rows, bad = _grad_report(model, ref)
+        route = model._engine.train_route(n)
+        _WINDOW_EDGE[n] = (pr.detach(), rc.detach(), pr_ref, rc_ref, rows, bad, route)
+    return _WINDOW_EDGE[n]
+
+
+@pytest.mark.parametrize("n", [1792, 1793])
+def test_gradients_match_autograd_on_both_sides_of_the_window_kernel_edge(n, gpu_device):
+    """Up to 1792 windows the single-layer stacks run one window per workgroup at a time (k_gru1 / k_gru1_bwd), from 1793 on in
+    16-window groups (k_gru16 / k_gru16_bwd): the file's gate against autograd on either side, on the smallest shape whose
+    stacks take these kernels, and the two calls against each other on the windows they share."""
+    pr, rc, pr_ref, rc_ref, rows, bad, route = _window_edge_step(n, gpu_device)
+    kernels = (1, 0, 0) if n <= 1792 else (2, 1, 0)             # (forward, backward, x3): k_gru1 + k_gru1_bwd | k_gru16 + k_gru16_bwd
+    assert route["gru"] == [kernels] and route["rec"] == [kernels], route
+    dp, dr = (pr - pr_ref).abs().max().item(), (rc - rc_ref).abs().max().item()
+    print(f"n={n}: |preds - ref| = {dp:.3e}, |recons - ref| = {dr:.3e}")
+    print("\n".join(rows))
+    assert dp <= 1e-5 and dr <= 1e-5
+    assert not bad, "\n".join(bad)
+    po, ro = _window_edge_step(1792 + 1793 - n, gpu_device)[:2]
+    dp, dr = (pr[:1792] - po[:1792]).abs().max().item(), (rc[:1792] - ro[:1792]).abs().max().item()
+    print(f"n={n}: the other call on the first 1792 windows: |preds| {dp:.3e}, |recons| {dr:.3e}")
+    assert dp <= 1e-5 and dr <= 1e-5
+
+
 def test_gradients_above_the_fp16_range_guard(gpu_device):
     """From 2561 windows on the training forward's recurrences run on split operands, with two fp16 pieces for the
     convolution's channels -- unless the convolution recorded outputs of 2^15 and more: then the device-side guard hands the
