@@ -538,6 +538,62 @@ int mtadgat_eval_run_stats(const float* score_dev, int64_t n, const int64_t* sta
 int mtadgat_eval_first_hit(const float* score_dev, const unsigned char* label_dev, int64_t n, double threshold, int compare_f32,
                            const int64_t* start_dev, const int64_t* end_dev, int64_t count, int64_t* first_dev, void* stream);
 
+/* ---- series made of parts (csrc/mtadgat_parts.hip; evaluation.score_parts, adjust_part_scores, moving_average(parts=),
+ * find_epsilon_parts, part_predictions) -------------------------------------------------------------------------------------
+ * A series that is a concatenation of independent entities (the channels of MSL / SMAP, the machines of SMD), scored part by
+ * part: what the reference's adjust_anomaly_scores (utils.py:210-255) does around the seams, and the moving average and
+ * find_epsilon restarted per part.  tests/part_refs.py states the definitions in numpy.
+ *
+ * Conventions of the event calls above: no atomics, no library kernels, bitwise reproducible (float64 partials of fixed row
+ * blocks added in block order: the bits do not depend on the launch shape); scratch is 8-byte aligned, at least what the
+ * _scratch function returns (0 for invalid sizes), and need not be initialised; status 0 / -1 / -3 / -5 with a
+ * mtadgat_last_error() message; nothing is launched when validation fails.  1 <= n <= 2^31 - 1, indices are int64.  The
+ * number of launches does not depend on `count`.
+ *
+ * The parts are `count` >= 1 spans [start_k, end_k) of score indices on the device, disjoint and ascending (empty spans are
+ * fine), bounds cut to [0, n].  The arrays live on the device, so this is the caller's promise and is not checked.  A score
+ * that no span covers belongs to no part: adjust writes it through (blanked if transitional), the moving average gives NaN,
+ * its flag is 0 and the moments and tables do not see it.
+ *
+ * mtadgat_eval_part_adjust: x_dev is (n, d) float32 with row stride ld >= d (1-D: d = ld = 1), d <= 2048; out_dev likewise with
+ * ld_out.  A score i with t - before <= i <= t + after for one of the n_seams seams t (seam_dev, int64, ascending, on the
+ * device; NULL with n_seams = 0) becomes +0.0 in every column.  With normalize, every (part, column) is then mapped to
+ * (x - lo) / (hi - lo), evaluated in float64 and rounded once, lo / hi being the minimum / maximum of its non-NaN values after
+ * blanking; NaN stays NaN, +-inf are ordinary values, and where hi <= lo (a constant, all-NaN or empty part) every non-NaN value
+ * becomes +0.0.  lohi_dev (NULL, or (count, d, 2) float64 on the device, only with normalize) receives lo and hi (+inf and -inf
+ * where the part has no non-NaN value).  Without normalize only the blanking is done and scratch may be NULL.  out_dev may be
+ * x_dev itself (with ld_out = ld), and must not overlap it otherwise.  Asynchronous on `stream`, nothing is read back.
+ *
+ * mtadgat_eval_ewm_parts: mtadgat_eval_ewm restarted at every span start: inside span [s, e) N_t = x_t + (1 - alpha) N_{t-1}
+ * with N_{s-1} = 0, D_t = (1 - (1 - alpha)^(t - s + 1)) / alpha, y_t = N_t / D_t.  The scan carries (sum, "a span started")
+ * pairs, so no part's sum is ever subtracted from a later one; with one span [0, n) the bits are mtadgat_eval_ewm's.
+ * out_dev may be x_dev.  Asynchronous on `stream`.
+ *
+ * mtadgat_eval_part_epsilon_moments / _table: the two device passes of find_epsilon for every part at once, each ending in one
+ * small copy to the host (they synchronise the stream).  moments: out_host count x [sum, sum of squares, maximum] (0, 0, -inf
+ * for an empty part; the maximum is NaN if the part holds a NaN).  table: eps_host count x nz thresholds (1 <= nz <= 64),
+ * out_host count x nz x [pruned sum, pruned sum of squares, pruned count, dilated count] as mtadgat_eval_epsilon_table defines
+ * them, the +-halo dilation (0 <= halo <= 128) never looking outside the part.  Both take the same scratch,
+ * mtadgat_eval_part_epsilon_scratch(n, count, nz).
+ *
+ * mtadgat_eval_part_flags: flags_dev[i] (uint8) = x_i > thr_dev[part(i)], thr_dev (count) float64 on the device, compared in
+ * float64; NaN and equality are not flagged.  Asynchronous on `stream`. */
+size_t mtadgat_eval_part_adjust_scratch(int64_t n, int d, int64_t count);
+int mtadgat_eval_part_adjust(const float* x_dev, int64_t n, int d, int64_t ld, const int64_t* start_dev, const int64_t* end_dev,
+                             int64_t count, const int64_t* seam_dev, int64_t n_seams, int64_t before, int64_t after, int normalize,
+                             void* scratch_dev, size_t scratch_bytes, float* out_dev, int64_t ld_out, double* lohi_dev, void* stream);
+size_t mtadgat_eval_ewm_parts_scratch(int64_t n);
+int mtadgat_eval_ewm_parts(const float* x_dev, int64_t n, const int64_t* start_dev, const int64_t* end_dev, int64_t count, double alpha,
+                           void* scratch_dev, size_t scratch_bytes, float* out_dev, void* stream);
+size_t mtadgat_eval_part_epsilon_scratch(int64_t n, int64_t count, int nz);
+int mtadgat_eval_part_epsilon_moments(const float* x_dev, int64_t n, const int64_t* start_dev, const int64_t* end_dev, int64_t count,
+                                      int nz, void* scratch_dev, size_t scratch_bytes, double* out_host, void* stream);
+int mtadgat_eval_part_epsilon_table(const float* x_dev, int64_t n, const int64_t* start_dev, const int64_t* end_dev, int64_t count,
+                                    const double* eps_host, int nz, int halo, void* scratch_dev, size_t scratch_bytes,
+                                    double* out_host, void* stream);
+int mtadgat_eval_part_flags(const float* x_dev, int64_t n, const int64_t* start_dev, const int64_t* end_dev, int64_t count,
+                            const double* thr_dev, unsigned char* flags_dev, void* stream);
+
 /* ---- ranking curves (csrc/mtadgat_curves.hip; evaluation.score_order, ranking_curve, ranking_metrics) -------------------
  * Conventions of the event calls above: no atomics, no library kernels, bitwise reproducible; scratch is 8-byte aligned, at
  * least what the _scratch function returns (0 for invalid sizes) and need not be initialised; status 0 / -1 / -3 / -5 with a

@@ -36,6 +36,14 @@ Threshold-free quality of a score array (csrc/mtadgat_curves.hip, tests/test_gpu
   ranking_curve                     every distinct threshold with its cumulative TP / FP, for the raw scores, the reference's point
                                     adjust or PA%K (Kim et al., AAAI 2022), adjusted and ranked without the scores leaving the device
   ranking_metrics                   exact AUROC, average precision and the best-F1 point of that curve, from one small copy
+Series that are concatenations of independent parts -- the channels of MSL / SMAP, the machines of SMD (csrc/mtadgat_parts.hip,
+tests/test_gpu_parts.py; tests/part_refs.py is the specification; the reference's adjust_anomaly_scores, utils.py:210-255):
+  score_parts                       where the parts lie among the scores: spans, seams and the transition blanked around a seam
+  adjust_part_scores                the scores around every seam set to 0, then min-max normalisation per part (and per column)
+  moving_average(parts=)            the exponentially weighted mean restarted at every part: a segmented float64 scan
+  find_epsilon_parts /              find_epsilon of every part's slice in two launches and two small copies whatever the number
+  part_predictions                  of parts, and scores > the threshold of their own part
+  predict_anomalies(parts=)         the above inside the one-call pipeline, with one global or one threshold per part
 The fit follows the paper, not the reference's vendored spot.py (its optimiser-based root search cannot be reproduced bit for
 bit): tests/spot_refs.py is the specification, csrc/mtadgat_spot.h spells it out.
 """
@@ -98,6 +106,17 @@ def _lib():
         lib.mtadgat_eval_curve_scratch.argtypes = [i64, ci]
         lib.mtadgat_eval_curve_scratch.restype = sz
         lib.mtadgat_eval_curve.argtypes = [vp, vp, i64, ci, ci, vp, sz, vp, vp, vp, ctypes.POINTER(ctypes.c_int64), vp]
+        lib.mtadgat_eval_part_adjust_scratch.argtypes = [i64, ci, i64]
+        lib.mtadgat_eval_part_adjust_scratch.restype = sz
+        lib.mtadgat_eval_part_adjust.argtypes = [vp, i64, ci, i64, vp, vp, i64, vp, i64, i64, i64, ci, vp, sz, vp, i64, vp, vp]
+        lib.mtadgat_eval_ewm_parts_scratch.argtypes = [i64]
+        lib.mtadgat_eval_ewm_parts_scratch.restype = sz
+        lib.mtadgat_eval_ewm_parts.argtypes = [vp, i64, vp, vp, i64, f64, vp, sz, vp, vp]
+        lib.mtadgat_eval_part_epsilon_scratch.argtypes = [i64, i64, ci]
+        lib.mtadgat_eval_part_epsilon_scratch.restype = sz
+        lib.mtadgat_eval_part_epsilon_moments.argtypes = [vp, i64, vp, vp, i64, ci, vp, sz, _c_double_p, vp]
+        lib.mtadgat_eval_part_epsilon_table.argtypes = [vp, i64, vp, vp, i64, _c_double_p, ci, ci, vp, sz, _c_double_p, vp]
+        lib.mtadgat_eval_part_flags.argtypes = [vp, i64, vp, vp, i64, vp, vp, vp]
         lib.mtadgat_last_error.restype = ctypes.c_char_p
         lib._eval_bound = True
     return lib
@@ -293,9 +312,11 @@ def scale_scores(per_dim):
     return (per_dim - q[1]) / (1.0 + (q[2] - q[0]))
 
 
-def moving_average(scores, span):
+def moving_average(scores, span, parts=None):
     """pandas.DataFrame(scores).ewm(span=span).mean() (prediction.py:99-103) of a 1-D GPU tensor: (n,) float32.
-    Accumulated in float64 on the device, stored as float32; bitwise reproducible."""
+    Accumulated in float64 on the device, stored as float32; bitwise reproducible.
+    With parts (a ScoreParts with parts.n == len(scores)) the average restarts at the first score of every part, so that no part is
+    smoothed into the next: ewm(span).mean() of every part's slice on its own.  The reference smooths across the seams."""
     if not span >= 1:
         raise ValueError(f"span must be >= 1, got {span!r}")
     lib = _lib()
@@ -303,6 +324,16 @@ def moving_average(scores, span):
     n = x.numel()
     if n < 1:
         raise ValueError("scores is empty")
+    if parts is not None:
+        start, end, _ = _parts_on(parts, x, n)
+        scratch = _scratch(lib.mtadgat_eval_ewm_parts_scratch(n), x.device)
+        out = _native._empty((n,), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            rc = lib.mtadgat_eval_ewm_parts(x.data_ptr(), n, start.data_ptr(), end.data_ptr(), parts.n_parts, 2.0 / (float(span) + 1.0),
+                                            scratch.data_ptr(), scratch.numel() * 8, out.data_ptr(), _stream(x))
+        if rc != 0:
+            _fail(lib, rc, "eval_ewm_parts")
+        return out
     scratch = _scratch(lib.mtadgat_eval_ewm_scratch(n), x.device)
     out = _native._empty((n,), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
@@ -394,6 +425,163 @@ def bf_search(score, label, start, end=None, step_num=1, display_freq=1, verbose
 
 
 _sweep = bf_search       # predict_anomalies has a keyword of that name
+
+
+# ---- series made of parts ----------------------------------------------------------------------------------------------------------
+class ScoreParts:
+    """Where the parts of a concatenated series lie among its scores (made by score_parts).  Score i (0 <= i < n = N - W) targets
+    row i + W and belongs to the part of that row, so part p owns the scores [start[p], end[p]) with
+    start[p] = max(o_p - W, 0), end[p] = max(o_{p+1} - W, 0), o the row offsets of the parts: disjoint, ascending, covering
+    [0, n), some possibly empty.  `seams` are the positions o_p - W (1 <= p < P) that fall inside [0, n): the first score of a
+    new part, around which `transition` = (before, after) scores are blanked by adjust_part_scores.
+      lengths, window_size, transition, n, n_parts      as given / derived
+      start_host, end_host, seams_host                  int64 numpy arrays
+      start, end, seams                                 the same as int64 tensors on `device` (seams is None without a seam)"""
+
+    def __init__(self, lengths, window_size, transition, device):
+        self.lengths, self.window_size, self.transition = lengths, window_size, transition
+        offsets = np.concatenate(([0], np.cumsum(lengths, dtype=np.int64)))
+        self.n = int(offsets[-1]) - window_size
+        self.n_parts = len(lengths)
+        cut = np.maximum(offsets - window_size, 0)
+        self.start_host, self.end_host = np.ascontiguousarray(cut[:-1]), np.ascontiguousarray(cut[1:])
+        t = offsets[1:-1] - window_size
+        self.seams_host = np.ascontiguousarray(t[(t >= 0) & (t < self.n)])
+        self.device = torch.device("cpu" if device is None else device)
+        self._on = {}
+        self.start, self.end, self.seams = self.tensors(self.device)
+
+    def tensors(self, device):
+        """(start, end, seams) on `device`, copied there once."""
+        key = str(torch.device(device))
+        if key not in self._on:
+            put = lambda a: torch.from_numpy(a).to(device) if a.size else None
+            self._on[key] = (put(self.start_host), put(self.end_host), put(self.seams_host))
+        return self._on[key]
+
+    def part_of(self, i):
+        """The part that owns score i (an int or an array of ints in [0, n)): an int or an int64 array."""
+        idx = np.asarray(i, dtype=np.int64)
+        if idx.size and (idx.min() < 0 or idx.max() >= self.n):
+            raise IndexError(f"score index outside [0, {self.n})")
+        p = np.searchsorted(self.end_host, idx, side="right")
+        return int(p) if np.ndim(i) == 0 else p
+
+
+def score_parts(lengths, window_size, transition=(19, 19), device=None):
+    """Describe a series of N rows that is the concatenation of len(lengths) independent parts (the channels of MSL / SMAP, the
+    machines of SMD) with `lengths` rows each, for a model of window `window_size`: a ScoreParts for the N - window_size scores.
+    transition = (before, after): the scores t - before .. t + after around every seam t are blanked by adjust_part_scores; the
+    default is the reference's buffer of 19 (utils.py:210-255), and after = window_size - 1 blanks every window that straddles two
+    parts.  device: where the span arrays are kept (they are copied to the scores' device on first use otherwise).
+    Raises ValueError on negative lengths, a negative transition or sum(lengths) <= window_size."""
+    ls = np.asarray(lengths)
+    if ls.ndim != 1 or ls.size < 1 or not np.issubdtype(ls.dtype, np.integer):
+        raise ValueError(f"lengths must be a non-empty 1-D sequence of integers, got {lengths!r}")
+    ls = ls.astype(np.int64)
+    if ls.min() < 0:
+        raise ValueError("lengths must be >= 0")
+    if isinstance(window_size, bool) or int(window_size) != window_size or window_size < 1:
+        raise ValueError(f"window_size must be a positive integer, got {window_size!r}")
+    if len(transition) != 2 or any(isinstance(t, bool) or int(t) != t or t < 0 for t in transition):
+        raise ValueError(f"transition must be two integers >= 0, got {transition!r}")
+    if int(ls.sum()) <= window_size:
+        raise ValueError(f"the parts hold {int(ls.sum())} rows, which leaves no score for window_size {window_size}")
+    return ScoreParts(ls, int(window_size), (int(transition[0]), int(transition[1])), device)
+
+
+def _parts_on(parts, x, n):
+    """parts' arrays on the device of x, after checking that parts describe n scores."""
+    if not isinstance(parts, ScoreParts):
+        raise TypeError("parts must be a ScoreParts (score_parts)")
+    if n != parts.n:
+        raise ValueError(f"parts describe {parts.n} scores, got {n}")
+    return parts.tensors(x.device)
+
+
+def adjust_part_scores(scores, parts, normalize=True):
+    """The seam handling of the reference's adjust_anomaly_scores (utils.py:210-255) for (n,) or (n, d) scores on the GPU: the
+    scores in parts.transition around every seam become +0.0 (a window that straddles two parts cannot be predicted), then, with
+    normalize, every part's stretch (per column) is min-max normalised on its own: (x - lo) / (hi - lo) in float64, rounded once,
+    lo / hi over the part's non-NaN values after blanking.  NaN stays NaN; +-inf are ordinary values.  Returns a new float32 tensor
+    of the input's shape; asynchronous, bitwise reproducible.
+    Departures from the reference (whose source could not be run here to pin it; tests/part_refs.py is the specification): a constant,
+    all-NaN or empty part maps to +0.0 where the reference divides 0 by 0; the parts are half-open, where the reference's slices
+    [c_start : c_end + 1] share one sample that is normalised twice."""
+    lib = _lib()
+    one_d = isinstance(scores, torch.Tensor) and scores.ndim == 1
+    x = _dev2d(scores, "scores")
+    n, d = x.shape
+    start, end, seams = _parts_on(parts, x, n)
+    out = _native._empty((n, d), dtype=torch.float32, device=x.device)
+    scratch = _scratch(lib.mtadgat_eval_part_adjust_scratch(n, d, parts.n_parts), x.device) if normalize else None
+    with torch.cuda.device(x.device):
+        rc = lib.mtadgat_eval_part_adjust(x.data_ptr(), n, d, x.stride(0), start.data_ptr(), end.data_ptr(), parts.n_parts, _ptr(seams),
+                                          0 if seams is None else seams.numel(), parts.transition[0], parts.transition[1],
+                                          1 if normalize else 0, _ptr(scratch), 0 if scratch is None else scratch.numel() * 8,
+                                          out.data_ptr(), d, None, _stream(x))
+    if rc != 0:
+        _fail(lib, rc, "eval_part_adjust")
+    return out.reshape(-1) if one_d else out
+
+
+def find_epsilon_parts(scores, parts, reg_level=1):
+    """find_epsilon of every part's slice of a 1-D score array: a float64 array (P,).  Moments, the 19 z values and the +-49 dilation
+    never look outside the part; a part where no z qualifies gets its maximum, an empty part +inf.  Two device passes over all
+    parts and two small copies to the host, whatever P is."""
+    lib = _lib()
+    x = _dev1d(scores, torch.float32, "scores")
+    n = x.numel()
+    start, end, _ = _parts_on(parts, x, n)
+    P, zs = parts.n_parts, _EPSILON_ZS
+    nz = len(zs)
+    scratch = _scratch(lib.mtadgat_eval_part_epsilon_scratch(n, P, nz), x.device)
+    mom = np.empty((P, 3), dtype=np.float64)
+    with torch.cuda.device(x.device):
+        rc = lib.mtadgat_eval_part_epsilon_moments(x.data_ptr(), n, start.data_ptr(), end.data_ptr(), P, nz, scratch.data_ptr(),
+                                                   scratch.numel() * 8, mom.ctypes.data_as(_c_double_p), _stream(x))
+    if rc != 0:
+        _fail(lib, rc, "eval_part_epsilon_moments")
+    count = parts.end_host - parts.start_host
+    eps = np.full((P, nz), np.nan)
+    means, sds = np.full(P, np.nan), np.full(P, np.nan)
+    for p in range(P):
+        if count[p] > 0:
+            means[p] = mom[p, 0] / count[p]
+            sds[p] = math.sqrt(max(mom[p, 1] / count[p] - means[p] * means[p], 0.0))
+            eps[p] = means[p] + sds[p] * zs
+    tab = np.empty((P, 4 * nz), dtype=np.float64)
+    with torch.cuda.device(x.device):
+        rc = lib.mtadgat_eval_part_epsilon_table(x.data_ptr(), n, start.data_ptr(), end.data_ptr(), P, eps.ctypes.data_as(_c_double_p), nz,
+                                                 _EPSILON_HALO, scratch.data_ptr(), scratch.numel() * 8, tab.ctypes.data_as(_c_double_p),
+                                                 _stream(x))
+    if rc != 0:
+        _fail(lib, rc, "eval_part_epsilon_table")
+    out = np.full(P, np.inf)
+    for p in range(P):
+        if count[p] > 0:
+            best = _choose_epsilon(int(count[p]), float(means[p]), float(sds[p]), eps[p], tab[p], reg_level)
+            out[p] = mom[p, 2] if best is None else best
+    return out
+
+
+def part_predictions(scores, parts, thresholds):
+    """flags[i] = scores[i] > thresholds[part of i], compared in float64 (NaN and equality are not flagged: flag_runs' convention):
+    (n,) uint8 on the device.  thresholds: (P,) numbers, as find_epsilon_parts returns them."""
+    lib = _lib()
+    x = _dev1d(scores, torch.float32, "scores")
+    n = x.numel()
+    start, end, _ = _parts_on(parts, x, n)
+    thr = torch.as_tensor(np.asarray(thresholds, dtype=np.float64).reshape(-1)).to(x.device)
+    if thr.numel() != parts.n_parts:
+        raise ValueError(f"{thr.numel()} thresholds for {parts.n_parts} parts")
+    flags = torch.empty(n, dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = lib.mtadgat_eval_part_flags(x.data_ptr(), n, start.data_ptr(), end.data_ptr(), parts.n_parts, thr.data_ptr(), flags.data_ptr(),
+                                         _stream(x))
+    if rc != 0:
+        _fail(lib, rc, "eval_part_flags")
+    return flags
 
 
 # ---- peaks over threshold ----------------------------------------------------------------------------------------------------------
@@ -527,7 +715,7 @@ def pot_eval(init_scores, scores, labels, q=1e-3, level=0.98, dynamic=False, max
 
 
 def predict_anomalies(model, train, test, labels=None, target_dims=None, gamma=1.0, scale_scores=False, use_mov_av=False, reg_level=1,
-                      bf_search=None, events=None, pot=None, curves=None):
+                      bf_search=None, events=None, pot=None, curves=None, parts=None):
     """What Predictor.predict_anomalies (prediction.py:106-165) derives from a train and a test series, with every score array
     staying on the device.  train, test: device-resident (N, F) series; labels: the test labels for rows window_size.. (one
     per score) or None; bf_search: (start, end, step_num) for the best-F1 sweep, run when labels are given too.
@@ -544,12 +732,44 @@ def predict_anomalies(model, train, test, labels=None, target_dims=None, gamma=1
                                   SPOT calibrated on the training scores; without labels its threshold only
       curve_result                only with curves=dict(adjust=) (or an empty dict): ranking_metrics(test_scores, labels, adjust), or None
                                   without labels
-    Not included: `adjust_anomaly_scores` for MSL / SMAP, which needs the datasets' channel metadata files and the reference
-    source to pin its behaviour, neither of which this package ships."""
-    train_scores, train_per_dim = model.anomaly_scores(train, target_dims=target_dims, gamma=gamma, scale_scores=scale_scores,
-                                                       use_mov_av=use_mov_av)
-    test_scores, test_per_dim = model.anomaly_scores(test, target_dims=target_dims, gamma=gamma, scale_scores=scale_scores,
-                                                     use_mov_av=use_mov_av)
+      part_result                 only with parts=dict(..., thresholds="per_part"), see below
+    parts=dict(train_lengths=, test_lengths=, transition=, normalize=, thresholds=) (any subset) scores series that are
+    concatenations of independent parts (the channels of MSL / SMAP, the machines of SMD) part by part, the reference's
+    adjust_anomaly_scores (utils.py:210-255): train_lengths / test_lengths are the parts' row counts (left out: one part),
+    transition and normalize as in score_parts and adjust_part_scores.  Train and test scores then come from
+    model.anomaly_scores(..., parts=): smoothed per part when use_mov_av, blanked around the seams, min-max normalised per part;
+    the per-dimension scores are as without parts.  thresholds="global" (the default) leaves everything else as it is, now on
+    the adjusted scores; "per_part" adds part_result, a dict of
+      thresholds   find_epsilon_parts of the train scores -- of the test scores when train and test differ in their number of parts
+      preds        part_predictions(test_scores, ...): (n,) uint8 on the device
+      f1, precision, recall, TP, TN, FP, FN, latency      with labels: the point-adjusted counts of those flags
+    Three departures from the reference, whose own function could not be run here to pin it (tests/part_refs.py is the specification):
+    a constant part maps to 0 where the reference has 0 / 0; the parts are half-open where the reference's slices share a sample
+    that is normalised twice; the moving average restarts per part where the reference smooths across the seams.  Events
+    (events=) may still merge across a seam; with both sides blanked that takes merge_gap >= before + after.
+    Without parts every returned value is what it was before parts existed."""
+    part_opts = None
+    if parts is not None:
+        unknown = set(parts) - {"train_lengths", "test_lengths", "transition", "normalize", "thresholds"}
+        if unknown:
+            raise ValueError(f"parts takes train_lengths, test_lengths, transition, normalize and thresholds, got {sorted(unknown)}")
+        part_opts = dict(transition=(19, 19), normalize=True, thresholds="global", train_lengths=None, test_lengths=None)
+        part_opts.update(parts)
+        if part_opts["thresholds"] not in ("global", "per_part"):
+            raise ValueError(f"parts' thresholds must be 'global' or 'per_part', got {part_opts['thresholds']!r}")
+    score_kw = dict(target_dims=target_dims, gamma=gamma, scale_scores=scale_scores, use_mov_av=use_mov_av)
+    if part_opts is None:
+        train_scores, train_per_dim = model.anomaly_scores(train, **score_kw)
+        test_scores, test_per_dim = model.anomaly_scores(test, **score_kw)
+    else:
+        def described(values, lengths):
+            return score_parts([values.shape[0]] if lengths is None else lengths, model.window_size, part_opts["transition"], values.device)
+        train_parts, test_parts = described(train, part_opts["train_lengths"]), described(test, part_opts["test_lengths"])
+        for name, values, sp in (("train", train, train_parts), ("test", test, test_parts)):
+            if sp.n != values.shape[0] - model.window_size:
+                raise ValueError(f"{name}_lengths add up to {sp.n + model.window_size} rows, the {name} series has {values.shape[0]}")
+        train_scores, train_per_dim = model.anomaly_scores(train, parts=train_parts, normalize_parts=part_opts["normalize"], **score_kw)
+        test_scores, test_per_dim = model.anomaly_scores(test, parts=test_parts, normalize_parts=part_opts["normalize"], **score_kw)
     eps_result = bf_result = None
     if labels is not None:
         eps_result = epsilon_eval(train_scores, test_scores, labels, reg_level)
@@ -559,6 +779,15 @@ def predict_anomalies(model, train, test, labels=None, target_dims=None, gamma=1
     thr, preds = feature_predictions(train_per_dim, test_per_dim, reg_level)
     out = {"epsilon_result": eps_result, "bf_result": bf_result, "feature_thresholds": thr, "train_scores": train_scores,
            "test_scores": test_scores, "test_per_dim": test_per_dim, "feature_preds": preds}
+    if part_opts is not None and part_opts["thresholds"] == "per_part":
+        same = train_parts.n_parts == test_parts.n_parts
+        part_thr = find_epsilon_parts(train_scores, train_parts, reg_level) if same else find_epsilon_parts(test_scores, test_parts, reg_level)
+        part_preds = part_predictions(test_scores, test_parts, part_thr)
+        out["part_result"] = {"thresholds": part_thr, "preds": part_preds}
+        if labels is not None:
+            metrics = _result(point_adjust_counts(part_preds.float(), labels, [0.5])[0], None)
+            del metrics["threshold"]
+            out["part_result"].update(metrics)
     if pot is not None:
         unknown = set(pot) - {"q", "level", "dynamic"}
         if unknown:

@@ -522,7 +522,8 @@ class MTAD_GAT(nn.Module):
                                        lambda eng: eng.forward_series(vf, None, 0, 1, n + 1, want_recons=False, want_last=True))
         return p[:n], last[1:n + 1]
 
-    def anomaly_scores(self, values, target_dims=None, gamma=1.0, scale_scores=False, use_mov_av=False, smoothing_span=None):
+    def anomaly_scores(self, values, target_dims=None, gamma=1.0, scale_scores=False, use_mov_av=False, smoothing_span=None, parts=None,
+                       normalize_parts=True):
         """The per-timestamp anomaly score of `Predictor.get_score` (reference prediction.py:65-103) for a
         whole series (N, F), computed on the device from `score_series`:
             a_i[d] = |y_hat_i[d] - x_{i+W}[d]| + gamma * |recon_i[d] - x_{i+W}[d]|
@@ -532,6 +533,11 @@ class MTAD_GAT(nn.Module):
         the span is `smoothing_span`, or the reference's int(256 * window_size * 0.05) -- its Predictor's
         hard-coded batch size of 256 -- and a span below 1 raises ValueError).  target_dims as in the reference
         (`utils.get_target_dims`): None = all features, an int or a list of column indices.
+        `parts` (an evaluation.ScoreParts for this series and window, from evaluation.score_parts) treats the series as a
+        concatenation of independent parts, the reference's adjust_anomaly_scores (utils.py:210-255): the global score is
+        smoothed part by part when `use_mov_av` (evaluation.moving_average(parts=)), then the scores around every seam are
+        set to 0 and, with `normalize_parts`, every part is min-max normalised on its own (evaluation.adjust_part_scores).
+        The per-dimension scores are returned exactly as without `parts`.
         Returns (scores (N-W,), per-dimension scores (N-W, out_dim)), both on the device; the per-dimension
         scores are never smoothed, as in the reference."""
         span = None
@@ -553,7 +559,10 @@ class MTAD_GAT(nn.Module):
         scores = a.mean(dim=1)
         if use_mov_av:
             import evaluation
-            scores = evaluation.moving_average(scores, span)
+            scores = evaluation.moving_average(scores, span, parts=parts)
+        if parts is not None:
+            import evaluation
+            scores = evaluation.adjust_part_scores(scores, parts, normalize=normalize_parts)
         return scores, a
 
     # -- which inputs pushed a score up: gradient attribution of anomaly_scores ---------------------------------------------------
