@@ -146,6 +146,24 @@ int64_t mtadgat_packed_floats(mtadgat_handle h);
  * the number only. */
 int mtadgat_derived_regions(mtadgat_handle h, int64_t* out_pairs, int max_pairs);
 int mtadgat_read_packed(mtadgat_handle h, float* dst_host, int64_t n_floats, void* stream);
+/* Test hook (host only: needs neither a GPU nor loaded weights): the table of steps that derive the split packs from the fp32
+ * packs of the image, over all groups in group order, then step order.  A record is 10 int64:
+ *   [group, op, scale, src, dst, n, Qs, Qd, arg, ord]
+ *   op     0 ZERO_SCALE, 1 ABSMAX, 2 SCALE_FROM_MAX, 3 SPLIT3, 4 SPLIT2H, 5 SPLIT2H_GATH, 6 SPLIT_X, 7 REORDER_XQ
+ *   scale  offset (floats) of the group's scale slot [bits of max |W|, S, 1 / S, 0] (0: the step uses none)
+ *   src, dst  offsets (floats) of the pack read and of the region written
+ *   n      ABSMAX: floats of src; the others: outer count (tiles; SPLIT2H_GATH: tiles per side)
+ *   Qs, Qd  chunks per tile of src / dst
+ *   arg    SPLIT2H: words per chunk (gates); SPLIT_X: leading chunks on three bf16 pieces; SPLIT2H_GATH: embedding columns E
+ *   ord    SPLIT2H_GATH: offset of the layer's column order [P8, PT, npos, 0] (ints)
+ * Returns the number of steps; at most max_steps records are written (out == NULL with max_steps == 0 returns the number only).
+ * mtadgat_split_n_infer: groups [0, n_infer) are what an inference call may read (mtadgat_read_packed derives those), the rest
+ * belong to the training backward. */
+int mtadgat_split_steps(mtadgat_handle h, int64_t* out, int max_steps);
+int mtadgat_split_n_infer(mtadgat_handle h);
+/* Test hook: derives every stale split group, the training backward's included, on `stream` -- what the kernels' callers do lazily,
+ * group by group.  Needs loaded weights.  mtadgat_read_packed afterwards shows every pack current. */
+int mtadgat_derive_split_packs(mtadgat_handle h, void* stream);
 /* Test hook (host only: needs neither a GPU nor loaded weights): which kernels run one recurrence layer.  stack 0: the GRU stack,
  * 1: the reconstruction decoder; `layer` counts from the input; n: windows of the call (one piece of a forward(), or one training
  * forward); compute_units: of the device the call would run on (256 on MI355X).  The answer is the one the library's own dispatch

@@ -100,6 +100,9 @@ def load_library():
     lib.mtadgat_packed_floats.restype = i64
     lib.mtadgat_read_packed.argtypes = [vp, vp, i64, vp]
     lib.mtadgat_derived_regions.argtypes = [vp, ctypes.POINTER(i64), ctypes.c_int]
+    lib.mtadgat_split_steps.argtypes = [vp, ctypes.POINTER(i64), ctypes.c_int]
+    lib.mtadgat_split_n_infer.argtypes = [vp]
+    lib.mtadgat_derive_split_packs.argtypes = [vp, vp]
     lib.mtadgat_gru_route.argtypes = [vp, ctypes.c_int, ctypes.c_int, i64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
     lib.mtadgat_front_route.argtypes = [vp, ctypes.c_int, ctypes.c_int, i64, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
     lib.mtadgat_forward_plan.argtypes = [vp, i64, ctypes.POINTER(i64), ctypes.c_int]
@@ -156,6 +159,22 @@ def load_library():
         raise RuntimeError("libmtadgat.so ABI version mismatch")
     _lib = lib
     return lib
+
+
+# mtadgat_split_steps: SplitStep::Op of csrc/mtadgat_host.h and the fields of a record
+SPLIT_OPS = ("ZERO_SCALE", "ABSMAX", "SCALE_FROM_MAX", "SPLIT3", "SPLIT2H", "SPLIT2H_GATH", "SPLIT_X", "REORDER_XQ")
+SPLIT_STEP_FIELDS = ("group", "op", "scale", "src", "dst", "n", "Qs", "Qd", "arg", "ord")
+
+
+def split_steps(lib, handle):
+    """mtadgat_split_steps of a handle as a list of dicts (needs no GPU: the host tests call it on a bare handle)."""
+    n = lib.mtadgat_split_steps(handle, None, 0)
+    buf = (ctypes.c_int64 * (10 * n))()
+    n = lib.mtadgat_split_steps(handle, buf, n)
+    steps = [dict(zip(SPLIT_STEP_FIELDS, (int(v) for v in buf[10 * i:10 * i + 10]))) for i in range(n)]
+    for s in steps:
+        s["op"] = SPLIT_OPS[s["op"]]
+    return steps
 
 
 def _check(rc, what):
@@ -460,6 +479,22 @@ class Engine:
         buf = (ctypes.c_int64 * (2 * n))()
         n = self.lib.mtadgat_derived_regions(self.handle, buf, n)
         return [(int(buf[2 * i]), int(buf[2 * i + 1])) for i in range(n)]
+
+    def split_steps(self):
+        """The steps that derive the split packs (host only), in group then step order: dicts of the ten fields of
+        mtadgat_split_steps (include/mtadgat.h), the op as its name (SPLIT_OPS)."""
+        return split_steps(self.lib, self.handle)
+
+    def split_n_infer(self):
+        """Groups [0, n) of split_steps() are the ones an inference call may read; the rest are the training backward's."""
+        return int(self.lib.mtadgat_split_n_infer(self.handle))
+
+    def derive_split_packs(self, device):
+        """Diagnostic: derive every split group, the backward's included, on the current stream (read_packed derives the
+        inference groups only)."""
+        with torch.cuda.device(device):
+            stream = torch.cuda.current_stream().cuda_stream
+            _check(self.lib.mtadgat_derive_split_packs(self.handle, ctypes.c_void_p(stream)), "derive_split_packs")
 
     def gru_route(self, stack, layer, n, training=False, compute_units=256):
         """Which kernels run recurrence layer `layer` of the GRU stack (stack 0) or the decoder (1) at n windows, under the current

@@ -863,6 +863,36 @@ int mtadgat_derived_regions(mtadgat_handle h, int64_t* out, int max_pairs) {
     return (int)r.size();
 }
 
+/* Read-only test hook (no GPU, no weights): the steps that derive the split packs (SplitTable), over all groups in group order then
+ * step order, 10 int64 per step: [group, op (SplitStep::Op), scale, src, dst, n, Qs, Qd, arg, ord]; at most max_steps records are
+ * written, the number of steps is returned.  mtadgat_split_n_infer: the groups [0, n_infer) are the ones an inference call may read. */
+int mtadgat_split_steps(mtadgat_handle h, int64_t* out, int max_steps) {
+    if (!h || (!out && max_steps > 0)) return 0;
+    int k = 0;
+    const std::vector<SplitGroup>& groups = h->m.split.groups;
+    for (size_t g = 0; g < groups.size(); ++g)
+        for (const SplitStep& t : groups[g].steps) {
+            if (k < max_steps) {
+                const int64_t v[10] = {(int64_t)g, (int64_t)t.op, (int64_t)t.scale, (int64_t)t.src, (int64_t)t.dst, (int64_t)t.n, t.Qs, t.Qd, t.arg, (int64_t)t.ord};
+                std::copy(v, v + 10, out + 10 * (size_t)k);
+            }
+            ++k;
+        }
+    return k;
+}
+int mtadgat_split_n_infer(mtadgat_handle h) { return h ? h->m.split.n_infer : 0; }
+
+/* Test hook: derives every split group that is stale, the training backward's included, on `stream` (what the consumers do lazily,
+ * group by group); mtadgat_read_packed then shows all of them */
+int mtadgat_derive_split_packs(mtadgat_handle h, void* stream) {
+    if (!h) return fail(MTADGAT_ERR_INVALID, "null argument");
+    Model& m = h->m;
+    if (!m.have_weights || !m.packed_dev) return fail(MTADGAT_ERR_NOWEIGHTS, "no weights loaded");
+    for (int i = 0; i < (int)m.split.groups.size(); ++i)
+        if (int rc_ = ensure(m, i, (hipStream_t)stream)) return rc_;
+    return 0;
+}
+
 /* Read-only test hook (no GPU, no weights): the recurrence route (gru_route) of layer `layer` of the GRU stack (stack 0) or the decoder
  * (stack 1) for a whole forward() / training forward of n windows on a device of `compute_units` CUs, under the handle's current
  * precision and "gru_kernel" option: out[0 .. 8) = first kernel, fallback kernel (GruKernel), operand build (GruBuild), two groups

@@ -1,5 +1,6 @@
 """Host-side checks of the split-pack regions the library reports (mtadgat_derived_regions), against the C ABI library; no GPU
-needed.  The device re-pack tests mask exactly these regions, so the list must be complete."""
+needed.  The device re-pack tests mask exactly these regions, so the list must be complete: tests/test_host_split_table.py proves that
+every step that derives a split pack writes inside exactly one of them (and that each has one writer); this file counts them."""
 import ctypes
 
 import pytest
