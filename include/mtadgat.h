@@ -584,14 +584,16 @@ int mtadgat_eval_first_hit(const float* score_dev, const unsigned char* label_de
  *
  * mtadgat_eval_ewm_parts: mtadgat_eval_ewm restarted at every span start: inside span [s, e) N_t = x_t + (1 - alpha) N_{t-1}
  * with N_{s-1} = 0, D_t = (1 - (1 - alpha)^(t - s + 1)) / alpha, y_t = N_t / D_t.  The scan carries (sum, "a span started")
- * pairs, so no part's sum is ever subtracted from a later one; with one span [0, n) the bits are mtadgat_eval_ewm's.
+ * pairs, so no part's sum is ever subtracted from a later one; with one span [0, n) the bits are mtadgat_eval_ewm's (the two are
+ * instantiations of one scan, csrc/mtadgat_evalcol.hip).
  * out_dev may be x_dev.  Asynchronous on `stream`.
  *
  * mtadgat_eval_part_epsilon_moments / _table: the two device passes of find_epsilon for every part at once, each ending in one
  * small copy to the host (they synchronise the stream).  moments: out_host count x [sum, sum of squares, maximum] (0, 0, -inf
  * for an empty part; the maximum is NaN if the part holds a NaN).  table: eps_host count x nz thresholds (1 <= nz <= 64),
  * out_host count x nz x [pruned sum, pruned sum of squares, pruned count, dilated count] as mtadgat_eval_epsilon_table defines
- * them, the +-halo dilation (0 <= halo <= 128) never looking outside the part.  Both take the same scratch,
+ * them (one tile routine computes both, csrc/mtadgat_scan.h), the +-halo dilation (0 <= halo <= 128) never looking outside the
+ * part.  Both take the same scratch,
  * mtadgat_eval_part_epsilon_scratch(n, count, nz).
  *
  * mtadgat_eval_part_flags: flags_dev[i] (uint8) = x_i > thr_dev[part(i)], thr_dev (count) float64 on the device, compared in

@@ -3,7 +3,8 @@
 // ("point adjust") + calc_point2point for one or many thresholds (epsilon_eval, bf_search; eval_methods.py:6-236).
 // O(N) work per threshold on 1-D arrays; the scalar bookkeeping (picking the best z / threshold, F1 from the
 // confusion counts) stays on the host in float64 exactly as the reference writes it.
-#include "mtadgat_device.h"
+// Every kernel here is launched with 256 threads; block_sum and epsilon_tile come from mtadgat_scan.h.
+#include "mtadgat_scan.h"
 
 namespace mtadgat {
 
@@ -21,19 +22,6 @@ __global__ void k_eval_scores(const float* __restrict__ preds, const float* __re
         acc += a;
     }
     if (global) global[i] = acc / (float)d;
-}
-
-__device__ __forceinline__ double block_sum(double v, double* sm) {
-    const int tid = threadIdx.x;
-    sm[tid] = v;
-    __syncthreads();
-    for (int s = blockDim.x >> 1; s > 0; s >>= 1) {
-        if (tid < s) sm[tid] += sm[tid + s];
-        __syncthreads();
-    }
-    const double r = sm[0];
-    __syncthreads();
-    return r;
 }
 
 // column blockIdx.y of an (n, d) array with row stride ld (a 1-D array: d = ld = 1): out[2 col] += sum e, out[2 col + 1] += sum e^2  (double)
@@ -55,46 +43,33 @@ __global__ void k_eval_moments(const float* __restrict__ e, long n, long ld, dou
 }
 
 // find_epsilon, one z per blockIdx.y and one column per blockIdx.z: epsilon = mean + sd * z, eps[col * nz + z];
-//   out[col * nz + z] = { sum of e < eps, sum of squares, count of e < eps, |{ i : some |k| <= 49 has e[i + k] >= eps }| }
-// Each step of the grid-stride loop stages its 256 rows and their halo once in LDS as the flags e >= eps, so the dilation reads
-// LDS and the array is read once per z instead of 2 halo + 1 times (halo <= EPS_HALO_MAX; wider halos read memory directly).
-constexpr int EPS_HALO_MAX = 128;
-__global__ void k_eval_epsilon(const float* __restrict__ e, long n, long ld, const double* __restrict__ eps, int halo, double* __restrict__ out) {
+//   out[col * nz + z] = { sum of e < eps, sum of squares, count of e < eps, |{ i : some |k| <= halo has e[i + k] >= eps }| }
+// The column is walked grid-stride in tiles of SPAN_RB rows, each through epsilon_tile with the range [0, n): the array is read once
+// per z instead of 2 halo + 1 times.  The partial sums are carried across the trips, then one block_sum and one atomic per quantity.
+__global__ void __launch_bounds__(256) k_eval_epsilon(const float* __restrict__ e, long n, long ld, const double* __restrict__ eps, int halo,
+                                                       double* __restrict__ out) {
     __shared__ double sm[256];
-    __shared__ unsigned char hot[256 + 2 * EPS_HALO_MAX];
+    __shared__ unsigned long long hot[EPS_TILE_WORDS];
     e += blockIdx.z;
     const long cell = (long)blockIdx.z * gridDim.y + blockIdx.y;
     const double ez = eps[cell];
-    const bool tiled = halo <= EPS_HALO_MAX;
+    const long tiles = (n + SPAN_RB - 1) / SPAN_RB;
     double s = 0.0, s2 = 0.0, cnt = 0.0, dil = 0.0;
-    for (long base = (long)blockIdx.x * blockDim.x; base < n; base += (long)gridDim.x * blockDim.x) {   // block-uniform trip count
-        const long i = base + threadIdx.x;
-        if (tiled) {
-            __syncthreads();                              // the previous step's reads of `hot` are done
-            for (int t = threadIdx.x; t < 256 + 2 * halo; t += 256) {
-                const long k = base - halo + t;
-                hot[t] = (k >= 0 && k < n) ? ((double)e[k * ld] >= ez) : 0;
-            }
-            __syncthreads();
-        }
-        if (i < n) {
-            const double v = e[i * ld];
-            if (v < ez) { s += v; s2 += v * v; cnt += 1.0; }
-            bool any = false;
-            if (tiled) {
-                for (int t = 0; t <= 2 * halo; ++t) any = any || hot[threadIdx.x + t];
-            } else {
-                const long lo = i - halo < 0 ? 0 : i - halo, hi = i + halo >= n ? n - 1 : i + halo;
-                for (long k = lo; k <= hi; ++k) any = any || ((double)e[k * ld] >= ez);
-            }
-            dil += any ? 1.0 : 0.0;
-        }
+    for (long t = blockIdx.x; t < tiles; t += gridDim.x) {               // block-uniform trip count
+        const long r0 = t * SPAN_RB;
+        __syncthreads();                                                  // the previous trip's reads of `hot` are done
+        epsilon_tile(e, ld, 0, n, r0, n - r0 < SPAN_RB ? (int)(n - r0) : SPAN_RB, ez, halo, hot, s, s2, cnt, dil);
     }
     s = block_sum(s, sm); s2 = block_sum(s2, sm); cnt = block_sum(cnt, sm); dil = block_sum(dil, sm);
     if (threadIdx.x == 0) {
         double* o = out + 4 * cell;
         atomicAdd(&o[0], s); atomicAdd(&o[1], s2); atomicAdd(&o[2], cnt); atomicAdd(&o[3], dil);
     }
+}
+// workgroups per (z, column) of k_eval_epsilon: one per tile, 128 at the most
+static unsigned epsilon_grid(int64_t n) {
+    const int64_t tiles = (n + SPAN_RB - 1) / SPAN_RB;
+    return (unsigned)(tiles < 128 ? tiles : 128);
 }
 
 // runs of label > 0: seg[2 k] = first index, seg[2 k + 1] = last index; *nseg counts them (unordered)
@@ -181,7 +156,7 @@ int mtadgat_eval_epsilon_table(const float* e_dev, int64_t n, const double* eps_
     double* tab = scratch_dev + 64;              // 4 * nz
     if (hipMemcpyAsync(eps_dev, eps_host, nz * sizeof(double), hipMemcpyHostToDevice, s) != hipSuccess) return -3;
     if (hipMemsetAsync(tab, 0, 4 * nz * sizeof(double), s) != hipSuccess) return -3;
-    hipLaunchKernelGGL(k_eval_epsilon, dim3(128, nz), dim3(256), 0, s, e_dev, (long)n, 1L, eps_dev, halo, tab);
+    hipLaunchKernelGGL(k_eval_epsilon, dim3(epsilon_grid(n), nz), dim3(256), 0, s, e_dev, (long)n, 1L, eps_dev, halo, tab);
     if (hipMemcpyAsync(out_host, tab, 4 * nz * sizeof(double), hipMemcpyDeviceToHost, s) != hipSuccess) return -3;
     return hipStreamSynchronize(s) == hipSuccess ? 0 : -3;
 }
@@ -213,8 +188,7 @@ int mtadgat_eval_epsilon_table_columns(const float* e_dev, int64_t n, int d, int
     if (hipMemcpyAsync(eps_dev, eps_host, cells * sizeof(double), hipMemcpyHostToDevice, s) != hipSuccess)
         return record_error(-3, "epsilon_table_columns: copy failed");
     if (hipMemsetAsync(tab, 0, 4 * cells * sizeof(double), s) != hipSuccess) return record_error(-3, "epsilon_table_columns: memset failed");
-    const long bx = (n + 255) / 256;
-    hipLaunchKernelGGL(k_eval_epsilon, dim3((unsigned)(bx < 128 ? bx : 128), nz, d), dim3(256), 0, s, e_dev, (long)n, (long)ld, eps_dev, halo, tab);
+    hipLaunchKernelGGL(k_eval_epsilon, dim3(epsilon_grid(n), nz, d), dim3(256), 0, s, e_dev, (long)n, (long)ld, eps_dev, halo, tab);
     if (hipMemcpyAsync(out_host, tab, 4 * cells * sizeof(double), hipMemcpyDeviceToHost, s) != hipSuccess)
         return record_error(-3, "epsilon_table_columns: copy failed");
     return hipStreamSynchronize(s) == hipSuccess ? 0 : record_error(-3, "epsilon_table_columns: stream failed");

@@ -1,14 +1,16 @@
 // Per-column order statistics and the exponentially weighted mean of the anomaly scores (reference prediction.py:65-165:
 // --scale_scores, --use_mov_av), so that the Predictor's post-processing stays on the device with the scores.
 //
-//   Shared primitives (the wave sum, the order bits of a float, the scratch carver) come from mtadgat_scan.h.
+//   Shared primitives (the wave sum, the order bits of a float, the spans, the scratch carver) come from mtadgat_scan.h.
 //   k_eval_colq_*: np.percentile ("linear") of every column of an (n, d) array for nq probabilities at once.  The two order
 //       statistics each probability needs are EXACT: a most-significant-digit radix select (four 8-bit digits) on the
 //       order-preserving 32-bit key of the float, all columns and all 2 nq ranks per pass.  Histograms are built with integer
 //       atomics in LDS and merged with integer atomics in memory -- integer sums do not depend on their order, so two runs give
 //       the same bits -- and the digit of every (column, rank) is chosen on the device between the passes.  Nothing is sorted.
-//   k_eval_ewm_*: pandas' ewm(span).mean() (adjust=True) as a blocked scan in float64: chunk-local scans, one wave that
-//       composes the chunk carries in chunk order, and a pass that applies carry and closed-form denominator.  No atomics.
+//   k_ewm_chunk / _carry / _apply: pandas' ewm(span).mean() (adjust=True) as a blocked scan in float64: chunk-local scans, one wave
+//       that composes the chunk carries in chunk order, and a pass that applies carry and closed-form denominator.  No atomics.
+//       One template, instantiated for the whole array (mtadgat_eval_ewm) and restarted at every span of a concatenated series
+//       (mtadgat_eval_ewm_parts).
 #include "mtadgat_scan.h"
 
 namespace mtadgat {
@@ -146,79 +148,139 @@ __global__ void k_eval_colq_interp(const float* __restrict__ ord, const double* 
 }
 
 // ---- exponentially weighted mean -------------------------------------------------------------------------------------------------
+// One scan, instantiated twice.  SEG: the mean restarts at the start of every span [start, end) (disjoint and ascending,
+// mtadgat_scan.h; a score outside every span is a span of its own and gives NaN): the scan carries (sum, "a span started inside")
+// pairs, so a part never sees its predecessor's sum -- nothing is subtracted.  !SEG: one span [0, n) -- no span arrays are read,
+// every flag is a compile-time false and F is never touched; the arithmetic, and so the bits, are those of SEG with that one span.
 constexpr int EWM_L = 1024;      // elements per chunk: 256 threads x 4
 
-// N just before this thread's four elements, for the recurrence N_t = x_t + b N_{t-1} started from `carry` before the chunk.
-// Wave scan by shuffles (factor b^(4 off) at distance off), then the four wave totals composed in order.
-__device__ __forceinline__ double ewm_thread_prefix(const double (&x)[4], double b, double carry, double* sm) {
+// this thread's four elements: the value, whether a span starts there and the start of its span (-1: outside every span)
+template <bool SEG>
+__device__ __forceinline__ void ewm_load(const float* __restrict__ x, long n, long base, const long* __restrict__ start,
+                                         const long* __restrict__ end, long count, double (&v)[4], bool (&rs)[4], long (&st)[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const long i = base + j;
+        v[j] = 0.0; rs[j] = false; st[j] = 0;
+        if constexpr (!SEG) {
+            v[j] = i < n ? (double)x[i] : 0.0;
+        } else if (i < n) {
+            v[j] = (double)x[i];
+            long s = 0;
+            const long p = span_find(start, end, count, i, s);
+            rs[j] = p < 0 || i == s;
+            st[j] = p < 0 ? -1 : s;
+        }
+    }
+}
+
+// N just before this thread's four elements for N_t = x_t + b N_{t-1}, N = 0 before a span start, started from `carry` before the
+// chunk.  Wave scan by shuffles (factor b^(4 off) at distance off) on (sum, flag) pairs -- a piece in which a span starts ignores
+// what precedes it -- then the four wave totals composed in order.  *any: a span starts somewhere in the chunk.
+// sm: 4 doubles, smf: 4 ints (SEG only).
+template <bool SEG>
+__device__ __forceinline__ double ewm_prefix(const double (&x)[4], const bool (&rs)[4], double b, double carry, double* sm, int* smf,
+                                             bool* any) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double s = ((x[0] * b + x[1]) * b + x[2]) * b + x[3];
+    double s = x[0];
+    int fl = SEG && rs[0];
+#pragma unroll
+    for (int j = 1; j < 4; ++j) {
+        s = (SEG && rs[j] ? 0.0 : s) * b + x[j];
+        fl |= SEG && rs[j];
+    }
     double f = (b * b) * (b * b);
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
         const double t = __shfl_up(s, off);
-        if (lane >= off) s = t * f + s;
+        const int tf = SEG ? __shfl_up(fl, off) : 0;
+        if (lane >= off) {
+            if (!fl) s = t * f + s;
+            fl |= tf;
+        }
         f *= f;
     }                                                   // f = b^256
-    if (lane == 63) sm[wave] = s;
+    if (lane == 63) {
+        sm[wave] = s;
+        if constexpr (SEG) smf[wave] = fl;
+    }
     double ex = __shfl_up(s, 1);
-    if (lane == 0) ex = 0.0;
+    int exf = SEG ? __shfl_up(fl, 1) : 0;
+    if (lane == 0) { ex = 0.0; exf = 0; }
     __syncthreads();
     double in = carry;
-    for (int w = 0; w < wave; ++w) in = in * f + sm[w];
-    return ex + in * pow(b, (double)(4 * lane));
+    for (int w = 0; w < wave; ++w) in = (SEG && smf[w] ? 0.0 : in) * f + sm[w];
+    *any = SEG && (smf[0] | smf[1] | smf[2] | smf[3]) != 0;
+    return ex + (exf ? 0.0 : in) * pow(b, (double)(4 * lane));
 }
 
-__device__ __forceinline__ void ewm_load(const float* __restrict__ x, long n, long base, double (&v)[4]) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = base + j < n ? (double)x[base + j] : 0.0;
-}
-
-// S[c] = N at the end of chunk c when nothing precedes it
-__global__ void __launch_bounds__(256) k_eval_ewm_chunk(const float* __restrict__ x, long n, double b, double* __restrict__ S) {
+// S[c] = N at the end of chunk c when nothing precedes it, F[c] = a span starts inside chunk c (SEG only)
+template <bool SEG>
+__global__ void __launch_bounds__(256) k_ewm_chunk(const float* __restrict__ x, long n, const long* __restrict__ start,
+                                                    const long* __restrict__ end, long count, double b, double* __restrict__ S,
+                                                    int* __restrict__ F) {
     __shared__ double sm[4];
+    __shared__ int smf[4];
     double v[4];
-    ewm_load(x, n, (long)blockIdx.x * EWM_L + 4 * threadIdx.x, v);
-    double s = ewm_thread_prefix(v, b, 0.0, sm);
+    bool rs[4], any;
+    long st[4];
+    ewm_load<SEG>(x, n, (long)blockIdx.x * EWM_L + 4 * threadIdx.x, start, end, count, v, rs, st);
+    double s = ewm_prefix<SEG>(v, rs, b, 0.0, sm, smf, &any);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) s = s * b + v[j];
-    if (threadIdx.x == 255) S[blockIdx.x] = s;
+    for (int j = 0; j < 4; ++j) s = (rs[j] ? 0.0 : s) * b + v[j];
+    if (threadIdx.x == 255) {
+        S[blockIdx.x] = s;
+        if constexpr (SEG) F[blockIdx.x] = any ? 1 : 0;
+    }
 }
 
-// carry[c] = N just before chunk c: carry[c] = carry[c-1] b^L + S[c-1], 64 chunks per step of one wave, in chunk order
-__global__ void __launch_bounds__(64) k_eval_ewm_carry(const double* __restrict__ S, long nchunks, double fL, double* __restrict__ carry) {
+// carry[c] = N just before chunk c: carry[c] = (F[c-1] ? 0 : carry[c-1] b^L) + S[c-1], 64 chunks per step of one wave, in chunk order
+template <bool SEG>
+__global__ void __launch_bounds__(64) k_ewm_carry(const double* __restrict__ S, const int* __restrict__ F, long nchunks, double fL,
+                                                   double* __restrict__ carry) {
     const int lane = threadIdx.x;
     const double fl = pow(fL, (double)lane);
     double run = 0.0;
     for (long base = 0; base < nchunks; base += 64) {
         const long i = base + lane;
         double s = i < nchunks ? S[i] : 0.0;
+        int g = SEG && i < nchunks ? F[i] : 0;
         double f = fL;
 #pragma unroll
         for (int off = 1; off < 64; off <<= 1) {
             const double t = __shfl_up(s, off);
-            if (lane >= off) s = t * f + s;
+            const int tg = SEG ? __shfl_up(g, off) : 0;
+            if (lane >= off) {
+                if (!g) s = t * f + s;
+                g |= tg;
+            }
             f *= f;
         }                                               // f = fL^64
         double ex = __shfl_up(s, 1);
-        if (lane == 0) ex = 0.0;
-        if (i < nchunks) carry[i] = run * fl + ex;
-        run = run * f + __shfl(s, 63);
+        int exg = SEG ? __shfl_up(g, 1) : 0;
+        if (lane == 0) { ex = 0.0; exg = 0; }
+        if (i < nchunks) carry[i] = (exg ? 0.0 : run) * fl + ex;
+        run = (SEG && __shfl(g, 63) ? 0.0 : run) * f + __shfl(s, 63);
     }
 }
 
-// y[t] = N_t / D_t, D_t = (1 - b^(t+1)) / alpha
-__global__ void __launch_bounds__(256) k_eval_ewm_apply(const float* __restrict__ x, long n, double b, double alpha,
-                                                         const double* __restrict__ carry, float* __restrict__ y) {
+// y[t] = N_t / D_t, D_t = (1 - b^(t - s + 1)) / alpha with s the start of t's span; NaN outside every span.  y may be x.
+template <bool SEG>
+__global__ void __launch_bounds__(256) k_ewm_apply(const float* x, long n, const long* __restrict__ start, const long* __restrict__ end,
+                                                    long count, double b, double alpha, const double* __restrict__ carry, float* y) {
     __shared__ double sm[4];
+    __shared__ int smf[4];
     double v[4];
+    bool rs[4], any;
+    long st[4];
     const long base = (long)blockIdx.x * EWM_L + 4 * threadIdx.x;
-    ewm_load(x, n, base, v);
-    double s = ewm_thread_prefix(v, b, carry[blockIdx.x], sm);
+    ewm_load<SEG>(x, n, base, start, end, count, v, rs, st);
+    double s = ewm_prefix<SEG>(v, rs, b, carry[blockIdx.x], sm, smf, &any);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        s = s * b + v[j];
-        if (base + j < n) y[base + j] = (float)(s / ((1.0 - pow(b, (double)(base + j + 1))) / alpha));
+        s = (rs[j] ? 0.0 : s) * b + v[j];
+        if (base + j < n)
+            y[base + j] = st[j] < 0 ? __builtin_nanf("") : (float)(s / ((1.0 - pow(b, (double)(base + j - st[j] + 1))) / alpha));
     }
 }
 
@@ -258,6 +320,36 @@ void colq_passes(const float* a_dev, long n, int d, long ld, int R, unsigned* st
                            state, hist, nanflag);
         hipLaunchKernelGGL(k_eval_colq_pick, dim3((unsigned)cells), dim3(64), 0, s, state, hist, shift, ord);
     }
+}
+
+constexpr int64_t N_MAX = 2147483647LL;
+
+// S and carry: one double per chunk each (mtadgat_eval_ewm: 16 bytes per chunk); the segmented scan adds one int per chunk
+struct EwmScratch {
+    double *S, *carry;
+    int* F;
+    long nchunks;
+};
+EwmScratch ewm_scratch(ScratchCarver& c, int64_t n, bool seg) {
+    EwmScratch l;
+    l.nchunks = (long)((n + EWM_L - 1) / EWM_L);
+    l.S = c.take<double>(l.nchunks);
+    l.carry = c.take<double>(l.nchunks);
+    l.F = seg ? c.take<int>(l.nchunks) : nullptr;
+    return l;
+}
+
+// chunk-local scans, one wave that composes the chunk carries, the pass that applies carry and denominator; false: a launch failed
+template <bool SEG>
+bool launch_ewm(const float* x, int64_t n, const long* st, const long* en, long count, double alpha, const EwmScratch& l, float* out,
+                hipStream_t s) {
+    const double b = 1.0 - alpha;
+    hipLaunchKernelGGL(k_ewm_chunk<SEG>, dim3((unsigned)l.nchunks), dim3(256), 0, s, x, (long)n, st, en, count, b, l.S, l.F);
+    hipLaunchKernelGGL(k_ewm_carry<SEG>, dim3(1), dim3(64), 0, s, (const double*)l.S, (const int*)l.F, l.nchunks, pow(b, (double)EWM_L),
+                       l.carry);
+    hipLaunchKernelGGL(k_ewm_apply<SEG>, dim3((unsigned)l.nchunks), dim3(256), 0, s, x, (long)n, st, en, count, b, alpha,
+                       (const double*)l.carry, out);
+    return hipGetLastError() == hipSuccess;
 }
 
 }  // namespace
@@ -322,24 +414,39 @@ int mtadgat_eval_column_quantiles(const float* a_dev, int64_t n, int d, int64_t 
 
 size_t mtadgat_eval_ewm_scratch(int64_t n) {
     if (n < 1) return 0;
-    return 16 * (size_t)((n + EWM_L - 1) / EWM_L);
+    return scratch_bytes_of([&](ScratchCarver& c) { ewm_scratch(c, n, false); });
 }
 
 int mtadgat_eval_ewm(const float* x_dev, int64_t n, double alpha, void* scratch_dev, size_t scratch_bytes, float* out_dev, void* stream) {
     if (!x_dev || !scratch_dev || !out_dev) return record_error(-1, "ewm: null pointer");
-    if (n < 1 || n > 2147483647LL) return record_error(-1, "ewm: n must lie in [1, 2^31 - 1]");
+    if (n < 1 || n > N_MAX) return record_error(-1, "ewm: n must lie in [1, 2^31 - 1]");
     if (!(alpha > 0.0 && alpha <= 1.0)) return record_error(-1, "ewm: alpha outside (0, 1]");
-    if (scratch_bytes < mtadgat_eval_ewm_scratch(n)) return record_error(-5, "ewm: scratch too small (see mtadgat_eval_ewm_scratch)");
+    ScratchCarver carver(scratch_dev);
+    const EwmScratch l = ewm_scratch(carver, n, false);
+    if (scratch_bytes < carver.bytes()) return record_error(-5, "ewm: scratch too small (see mtadgat_eval_ewm_scratch)");
     if ((uintptr_t)scratch_dev & 7) return record_error(-5, "ewm: scratch must be 8-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    const long nchunks = (long)((n + EWM_L - 1) / EWM_L);
-    double* S = static_cast<double*>(scratch_dev);
-    double* carry = S + nchunks;
-    const double b = 1.0 - alpha;
-    hipLaunchKernelGGL(k_eval_ewm_chunk, dim3((unsigned)nchunks), dim3(256), 0, s, x_dev, (long)n, b, S);
-    hipLaunchKernelGGL(k_eval_ewm_carry, dim3(1), dim3(64), 0, s, S, nchunks, pow(b, (double)EWM_L), carry);
-    hipLaunchKernelGGL(k_eval_ewm_apply, dim3((unsigned)nchunks), dim3(256), 0, s, x_dev, (long)n, b, alpha, carry, out_dev);
-    return hipGetLastError() == hipSuccess ? 0 : record_error(-3, "ewm: kernel launch failed");
+    if (!launch_ewm<false>(x_dev, n, nullptr, nullptr, 0, alpha, l, out_dev, (hipStream_t)stream)) return record_error(-3, "ewm: kernel launch failed");
+    return 0;
+}
+
+size_t mtadgat_eval_ewm_parts_scratch(int64_t n) {
+    if (n < 1 || n > N_MAX) return 0;
+    return scratch_bytes_of([&](ScratchCarver& c) { ewm_scratch(c, n, true); });
+}
+
+int mtadgat_eval_ewm_parts(const float* x_dev, int64_t n, const int64_t* start_dev, const int64_t* end_dev, int64_t count, double alpha,
+                           void* scratch_dev, size_t scratch_bytes, float* out_dev, void* stream) {
+    if (!x_dev || !start_dev || !end_dev || !scratch_dev || !out_dev) return record_error(-1, "ewm_parts: null pointer");
+    if (n < 1 || n > N_MAX) return record_error(-1, "ewm_parts: n must lie in [1, 2^31 - 1]");
+    if (count < 1 || count > N_MAX) return record_error(-1, "ewm_parts: count must lie in [1, 2^31 - 1]");
+    if (!(alpha > 0.0 && alpha <= 1.0)) return record_error(-1, "ewm_parts: alpha outside (0, 1]");
+    ScratchCarver carver(scratch_dev);
+    const EwmScratch l = ewm_scratch(carver, n, true);
+    if (scratch_bytes < carver.bytes()) return record_error(-5, "ewm_parts: scratch too small (see mtadgat_eval_ewm_parts_scratch)");
+    if ((uintptr_t)scratch_dev & 7) return record_error(-5, "ewm_parts: scratch must be 8-byte aligned");
+    const long *st = reinterpret_cast<const long*>(start_dev), *en = reinterpret_cast<const long*>(end_dev);
+    if (!launch_ewm<true>(x_dev, n, st, en, (long)count, alpha, l, out_dev, (hipStream_t)stream)) return record_error(-3, "ewm_parts: kernel launch failed");
+    return 0;
 }
 
 }  // extern "C"

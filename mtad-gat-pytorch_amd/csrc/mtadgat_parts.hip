@@ -1,39 +1,21 @@
 // Part-aware score passes for series that are concatenations of independent entities (MSL / SMAP channels, SMD machines): what the
-// reference's adjust_anomaly_scores (utils.py:210-255) does at the seams, plus the moving average and the Hundman threshold restarted
-// per part.  evaluation.score_parts describes the parts; tests/part_refs.py is the specification.
+// reference's adjust_anomaly_scores (utils.py:210-255) does at the seams, plus the Hundman threshold restarted per part (the moving
+// average restarted per part is the segmented instantiation of the scan in mtadgat_evalcol.hip).  evaluation.score_parts describes the
+// parts; tests/part_refs.py is the specification.
 //
 //   A part is a span [start, end) of score indices; the spans are disjoint and ascending (mtadgat_scan.h) and the kernels find the
-//   part of an index by a binary search over the span ends.  A score that no span covers belongs to no part.
+//   part of an index by a binary search over the span ends (span_find).  A score that no span covers belongs to no part.
 //   Reductions run over fixed row blocks of SPAN_RB with one slot per (part, block) and are combined in block order by one wave per
 //   part: no atomics, the bits depend on the input alone.  No launch count depends on the number of parts.
 //
 //   k_part_minmax / k_part_minmax_final / k_part_adjust   blank the transitions around the seams, then min-max normalise per part
-//   k_part_ewm_chunk / _carry / _apply                    k_eval_ewm_* (mtadgat_evalcol.hip) with a reset at every span start: the scan
-//                                                         carries (sum, "a span started inside") pairs, so a part never sees its
-//                                                         predecessor's sum -- nothing is subtracted
 //   k_part_moments / k_part_moments_final                 sum, sum of squares and maximum per part
-//   k_part_epsilon / k_part_epsilon_final                 find_epsilon's z table per part, the +-halo dilation clipped to the span
+//   k_part_epsilon / k_part_epsilon_final                 find_epsilon's z table per part, the +-halo dilation clipped to the span:
+//                                                         epsilon_tile (mtadgat_scan.h), which k_eval_epsilon runs over a whole column
 //   k_part_flags                                          score_i > eps[part(i)]
 #include "mtadgat_scan.h"
 
 namespace mtadgat {
-
-constexpr int PART_EWM_L = 1024;     // elements per chunk of the segmented scan: 256 threads x 4, as EWM_L
-constexpr int PART_HALO_MAX = 128;   // widest dilation halo the epsilon table stages in LDS
-
-// the part of score i (0 <= i < n): the first span whose end lies beyond i, if it starts at or before i; -1: no span covers i.
-// s: that span's start cut to 0.
-__device__ __forceinline__ long span_find(const long* __restrict__ start, const long* __restrict__ end, long count, long i, long& s) {
-    long lo = 0, hi = count;
-    while (lo < hi) {
-        const long mid = (lo + hi) >> 1;
-        if (end[mid] <= i) lo = mid + 1;
-        else hi = mid;
-    }
-    if (lo >= count) return -1;
-    s = start[lo] < 0 ? 0 : start[lo];
-    return s <= i ? lo : -1;
-}
 
 // score i lies in [t - before, t + after] of some seam t: the first seam >= i - after is at most i + before (seams ascending)
 __device__ __forceinline__ bool in_transition(const long* __restrict__ seam, long nseams, long i, long before, long after) {
@@ -155,139 +137,7 @@ __global__ void __launch_bounds__(256) k_part_adjust(const float* x, long n, int
     }
 }
 
-// ---- segmented exponentially weighted mean -----------------------------------------------------------------------------------------
-// this thread's four elements: the value, whether a span starts there (a score outside every span is a span of its own) and the
-// start of its span (-1: outside every span)
-__device__ __forceinline__ void part_ewm_load(const float* __restrict__ x, long n, long base, const long* __restrict__ start,
-                                              const long* __restrict__ end, long count, double (&v)[4], bool (&rs)[4], long (&st)[4]) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const long i = base + j;
-        v[j] = 0.0; rs[j] = false; st[j] = 0;
-        if (i < n) {
-            v[j] = (double)x[i];
-            long s = 0;
-            const long p = span_find(start, end, count, i, s);
-            rs[j] = p < 0 || i == s;
-            st[j] = p < 0 ? -1 : s;
-        }
-    }
-}
-
-// N just before this thread's four elements for N_t = x_t + b N_{t-1}, N = 0 before a span start, started from `carry` before the
-// chunk.  ewm_thread_prefix (mtadgat_evalcol.hip) on (sum, flag) pairs: a piece in which a span starts ignores what precedes it.
-// *any: a span starts somewhere in the chunk.  sm: 4 doubles, smf: 4 ints.
-__device__ __forceinline__ double part_ewm_prefix(const double (&x)[4], const bool (&rs)[4], double b, double carry, double* sm, int* smf,
-                                                  bool* any) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double s = x[0];
-    int fl = rs[0];
-#pragma unroll
-    for (int j = 1; j < 4; ++j) {
-        s = (rs[j] ? 0.0 : s) * b + x[j];
-        fl |= rs[j];
-    }
-    double f = (b * b) * (b * b);
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const double t = __shfl_up(s, off);
-        const int tf = __shfl_up(fl, off);
-        if (lane >= off) {
-            if (!fl) s = t * f + s;
-            fl |= tf;
-        }
-        f *= f;
-    }                                                   // f = b^256
-    if (lane == 63) { sm[wave] = s; smf[wave] = fl; }
-    double ex = __shfl_up(s, 1);
-    int exf = __shfl_up(fl, 1);
-    if (lane == 0) { ex = 0.0; exf = 0; }
-    __syncthreads();
-    double in = carry;
-    for (int w = 0; w < wave; ++w) in = (smf[w] ? 0.0 : in) * f + sm[w];
-    *any = (smf[0] | smf[1] | smf[2] | smf[3]) != 0;
-    return ex + (exf ? 0.0 : in) * pow(b, (double)(4 * lane));
-}
-
-// S[c] = N at the end of chunk c when nothing precedes it, F[c] = a span starts inside chunk c
-__global__ void __launch_bounds__(256) k_part_ewm_chunk(const float* __restrict__ x, long n, const long* __restrict__ start,
-                                                         const long* __restrict__ end, long count, double b, double* __restrict__ S,
-                                                         int* __restrict__ F) {
-    __shared__ double sm[4];
-    __shared__ int smf[4];
-    double v[4];
-    bool rs[4], any;
-    long st[4];
-    part_ewm_load(x, n, (long)blockIdx.x * PART_EWM_L + 4 * threadIdx.x, start, end, count, v, rs, st);
-    double s = part_ewm_prefix(v, rs, b, 0.0, sm, smf, &any);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) s = (rs[j] ? 0.0 : s) * b + v[j];
-    if (threadIdx.x == 255) { S[blockIdx.x] = s; F[blockIdx.x] = any ? 1 : 0; }
-}
-
-// carry[c] = N just before chunk c: carry[c] = (F[c-1] ? 0 : carry[c-1] b^L) + S[c-1], 64 chunks per step of one wave, in chunk order
-__global__ void __launch_bounds__(64) k_part_ewm_carry(const double* __restrict__ S, const int* __restrict__ F, long nchunks, double fL,
-                                                        double* __restrict__ carry) {
-    const int lane = threadIdx.x;
-    const double fl = pow(fL, (double)lane);
-    double run = 0.0;
-    for (long base = 0; base < nchunks; base += 64) {
-        const long i = base + lane;
-        double s = i < nchunks ? S[i] : 0.0;
-        int g = i < nchunks ? F[i] : 0;
-        double f = fL;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const double t = __shfl_up(s, off);
-            const int tg = __shfl_up(g, off);
-            if (lane >= off) {
-                if (!g) s = t * f + s;
-                g |= tg;
-            }
-            f *= f;
-        }                                               // f = fL^64
-        double ex = __shfl_up(s, 1);
-        int exg = __shfl_up(g, 1);
-        if (lane == 0) { ex = 0.0; exg = 0; }
-        if (i < nchunks) carry[i] = (exg ? 0.0 : run) * fl + ex;
-        run = (__shfl(g, 63) ? 0.0 : run) * f + __shfl(s, 63);
-    }
-}
-
-// y[t] = N_t / D_t, D_t = (1 - b^(t - s + 1)) / alpha with s the start of t's span; NaN outside every span
-__global__ void __launch_bounds__(256) k_part_ewm_apply(const float* x, long n, const long* __restrict__ start,
-                                                         const long* __restrict__ end, long count, double b, double alpha,
-                                                         const double* __restrict__ carry, float* y) {
-    __shared__ double sm[4];
-    __shared__ int smf[4];
-    double v[4];
-    bool rs[4], any;
-    long st[4];
-    const long base = (long)blockIdx.x * PART_EWM_L + 4 * threadIdx.x;
-    part_ewm_load(x, n, base, start, end, count, v, rs, st);
-    double s = part_ewm_prefix(v, rs, b, carry[blockIdx.x], sm, smf, &any);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        s = (rs[j] ? 0.0 : s) * b + v[j];
-        if (base + j < n)
-            y[base + j] = st[j] < 0 ? __builtin_nanf("") : (float)(s / ((1.0 - pow(b, (double)(base + j - st[j] + 1))) / alpha));
-    }
-}
-
 // ---- per-part moments and epsilon table --------------------------------------------------------------------------------------------
-// the sum of v over a 256-thread workgroup by a fixed tree; sm: 256 doubles (barriers inside)
-__device__ __forceinline__ double part_block_sum(double v, double* sm) {
-    const int tid = threadIdx.x;
-    sm[tid] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) sm[tid] += sm[tid + s];
-        __syncthreads();
-    }
-    const double r = sm[0];
-    __syncthreads();
-    return r;
-}
 // the larger of m and v; a NaN wins and stays (numpy's max)
 __device__ __forceinline__ float nan_max(float m, float v) { return (v > m || v != v) ? v : m; }
 
@@ -315,8 +165,8 @@ __global__ void __launch_bounds__(256) k_part_moments(const float* __restrict__ 
             q += v * v;
             m = nan_max(m, f);
         }
-        a = part_block_sum(a, sm);
-        q = part_block_sum(q, sm);
+        a = block_sum(a, sm);
+        q = block_sum(q, sm);
         smf[tid] = m;
         __syncthreads();
         for (int st = 128; st > 0; st >>= 1) {
@@ -351,17 +201,13 @@ __global__ void __launch_bounds__(64) k_part_moments_final(long n, const long* _
     if (lane == 0) { mom[3 * k] = a; mom[3 * k + 1] = q; mom[3 * k + 2] = (double)m; }
 }
 
-// grid (part, slice, z): for threshold eps[part * nz + z], per row block of the part
+// grid (part, slice, z): for threshold eps[part * nz + z], per row block of the part, epsilon_tile's four sums with the part as the range
 //   { sum of x < eps, its sum of squares, the count of x < eps, |{ i in the part : some |j| <= halo, i + j in the part, has x[i + j] >= eps }| }
-// The block's rows and their halo, cut to the part, are staged once in LDS as the flags x >= eps, one bit each (a wave's __ballot
-// is a 64-bit word of them), so a row's window of 2 halo + 1 flags is at most five masked words.
 __global__ void __launch_bounds__(256) k_part_epsilon(const float* __restrict__ x, long n, const long* __restrict__ start,
                                                        const long* __restrict__ end, const double* __restrict__ eps, int nz, int halo,
                                                        double* __restrict__ ptab) {
-    constexpr int WORDS = (SPAN_RB + 2 * PART_HALO_MAX) / 64;
     __shared__ double sm[256];
-    __shared__ unsigned long long hot[WORDS];
-    const int tid = threadIdx.x, lane = threadIdx.x & 63;
+    __shared__ unsigned long long hot[EPS_TILE_WORDS];
     const long k = blockIdx.x;
     const int z = blockIdx.z;
     const double ez = eps[k * nz + z];
@@ -371,32 +217,13 @@ __global__ void __launch_bounds__(256) k_part_epsilon(const float* __restrict__ 
     const long slot0 = span_slot0(s, k);
     for (long b = blockIdx.y; b < nb; b += gridDim.y) {
         const long r0 = s + b * SPAN_RB;
-        const int rows = e - r0 < SPAN_RB ? (int)(e - r0) : SPAN_RB;
-        for (int t0 = tid - lane; t0 < rows + 2 * halo; t0 += 256) {        // wave-uniform: bit t of the tile is sample r0 - halo + t
-            const long at = r0 - halo + t0 + lane;
-            const unsigned long long m = __ballot(at >= s && at < e && (double)x[at] >= ez);
-            if (lane == 0) hot[t0 >> 6] = m;
-        }
-        __syncthreads();
         double a = 0.0, q = 0.0, cnt = 0.0, dil = 0.0;
-        for (int r = tid; r < rows; r += 256) {
-            const double v = (double)x[r0 + r];
-            if (v < ez) { a += v; q += v * v; cnt += 1.0; }
-            const int lo = r, hi = r + 2 * halo;                             // the window of row r, in tile bits
-            bool any = false;
-            for (int w = lo >> 6; w <= hi >> 6; ++w) {
-                unsigned long long mask = ~0ull;
-                if (w == lo >> 6) mask &= ~0ull << (lo & 63);
-                if (w == hi >> 6) mask &= ~0ull >> (63 - (hi & 63));
-                any = any || (hot[w] & mask) != 0ull;
-            }
-            dil += any ? 1.0 : 0.0;
-        }
-        a = part_block_sum(a, sm);                      // its barriers also close the reads of `hot`
-        q = part_block_sum(q, sm);
-        cnt = part_block_sum(cnt, sm);
-        dil = part_block_sum(dil, sm);
-        if (tid == 0) {
+        epsilon_tile(x, 1, s, e, r0, e - r0 < SPAN_RB ? (int)(e - r0) : SPAN_RB, ez, halo, hot, a, q, cnt, dil);
+        a = block_sum(a, sm);                           // its barriers also close the reads of `hot`
+        q = block_sum(q, sm);
+        cnt = block_sum(cnt, sm);
+        dil = block_sum(dil, sm);
+        if (threadIdx.x == 0) {
             double* o = ptab + ((slot0 + b) * nz + z) * 4;
             o[0] = a; o[1] = q; o[2] = cnt; o[3] = dil;
         }
@@ -455,20 +282,6 @@ AdjustScratch adjust_scratch(ScratchCarver& c, int64_t n, int64_t count, int d) 
     l.lohi = c.take<double>((size_t)count * (size_t)d * 2);
     l.plo = c.take<float>(cells);
     l.phi = c.take<float>(cells);
-    return l;
-}
-
-struct EwmScratch {
-    double *S, *carry;
-    int* F;
-    long nchunks;
-};
-EwmScratch ewm_scratch(ScratchCarver& c, int64_t n) {
-    EwmScratch l;
-    l.nchunks = (long)((n + PART_EWM_L - 1) / PART_EWM_L);
-    l.S = c.take<double>(l.nchunks);
-    l.carry = c.take<double>(l.nchunks);
-    l.F = c.take<int>(l.nchunks);
     return l;
 }
 
@@ -542,33 +355,6 @@ int mtadgat_eval_part_adjust(const float* x_dev, int64_t n, int d, int64_t ld, c
     return hipGetLastError() == hipSuccess ? 0 : record_error(-3, "part_adjust: kernel launch failed");
 }
 
-size_t mtadgat_eval_ewm_parts_scratch(int64_t n) {
-    if (n < 1 || n > N_MAX) return 0;
-    return scratch_bytes_of([&](ScratchCarver& c) { ewm_scratch(c, n); });
-}
-
-int mtadgat_eval_ewm_parts(const float* x_dev, int64_t n, const int64_t* start_dev, const int64_t* end_dev, int64_t count, double alpha,
-                           void* scratch_dev, size_t scratch_bytes, float* out_dev, void* stream) {
-    if (!x_dev || !start_dev || !end_dev || !scratch_dev || !out_dev) return record_error(-1, "ewm_parts: null pointer");
-    if (n < 1 || n > N_MAX) return record_error(-1, "ewm_parts: n must lie in [1, 2^31 - 1]");
-    if (count < 1 || count > N_MAX) return record_error(-1, "ewm_parts: count must lie in [1, 2^31 - 1]");
-    if (!(alpha > 0.0 && alpha <= 1.0)) return record_error(-1, "ewm_parts: alpha outside (0, 1]");
-    ScratchCarver carver(scratch_dev);
-    const EwmScratch l = ewm_scratch(carver, n);
-    if (scratch_bytes < carver.bytes()) return record_error(-5, "ewm_parts: scratch too small (see mtadgat_eval_ewm_parts_scratch)");
-    if ((uintptr_t)scratch_dev & 7) return record_error(-5, "ewm_parts: scratch must be 8-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    const long* st = reinterpret_cast<const long*>(start_dev);
-    const long* en = reinterpret_cast<const long*>(end_dev);
-    const double b = 1.0 - alpha;
-    hipLaunchKernelGGL(k_part_ewm_chunk, dim3((unsigned)l.nchunks), dim3(256), 0, s, x_dev, (long)n, st, en, (long)count, b, l.S, l.F);
-    hipLaunchKernelGGL(k_part_ewm_carry, dim3(1), dim3(64), 0, s, (const double*)l.S, (const int*)l.F, l.nchunks, pow(b, (double)PART_EWM_L),
-                       l.carry);
-    hipLaunchKernelGGL(k_part_ewm_apply, dim3((unsigned)l.nchunks), dim3(256), 0, s, x_dev, (long)n, st, en, (long)count, b, alpha,
-                       (const double*)l.carry, out_dev);
-    return hipGetLastError() == hipSuccess ? 0 : record_error(-3, "ewm_parts: kernel launch failed");
-}
-
 size_t mtadgat_eval_part_epsilon_scratch(int64_t n, int64_t count, int nz) {
     if (!sizes_ok(n, count) || nz < 1 || nz > 64) return 0;
     return scratch_bytes_of([&](ScratchCarver& c) { eps_scratch(c, n, count, nz); });
@@ -604,7 +390,7 @@ int mtadgat_eval_part_epsilon_table(const float* x_dev, int64_t n, const int64_t
     if (n < 1 || n > N_MAX) return record_error(-1, "part_epsilon_table: n must lie in [1, 2^31 - 1]");
     if (count < 1 || count > N_MAX) return record_error(-1, "part_epsilon_table: count must lie in [1, 2^31 - 1]");
     if (nz < 1 || nz > 64) return record_error(-1, "part_epsilon_table: nz must lie in [1, 64]");
-    if (halo < 0 || halo > PART_HALO_MAX) return record_error(-1, "part_epsilon_table: halo must lie in [0, 128]");
+    if (halo < 0 || halo > EPS_HALO_MAX) return record_error(-1, "part_epsilon_table: halo must lie in [0, 128]");
     ScratchCarver carver(scratch_dev);
     const EpsScratch l = eps_scratch(carver, n, count, nz);
     if (scratch_bytes < carver.bytes()) return record_error(-5, "part_epsilon_table: scratch too small (see mtadgat_eval_part_epsilon_scratch)");

@@ -1,11 +1,15 @@
-// Scan, rank and layout primitives of the evaluation kernels (mtadgat_events.hip, mtadgat_curves.hip, mtadgat_evalcol.hip): what
-// at least two of their kernels or entry points share.  Everything is an integer operation in a fixed order -- no atomics --
-// so a result is a function of the input alone.
+// Scan, rank, reduction and layout primitives of the evaluation kernels (mtadgat_eval.hip, mtadgat_evalcol.hip, mtadgat_events.hip,
+// mtadgat_curves.hip, mtadgat_parts.hip): what at least two of their kernels or entry points share.  Everything runs in a fixed
+// order -- no atomics -- so a result is a function of the input alone.
 //
 //   blocked scan of counts: per-chunk totals (chunk_rank), one wave that turns the totals into the chunks' starting ranks in
 //       chunk order (k_scan_carry), and a pass that recomputes the predicate and places every item at start + rank inside the
 //       chunk (chunk_rank again).  Within a wave the rank is the population count of the __ballot mask below the lane.
+//   block_sum: the float64 sum over a 256-thread workgroup by a fixed tree.
 //   spans: runs or segments [start, end) that are disjoint and ascending, reduced in fixed row blocks with one slot per block.
+//   epsilon_tile: find_epsilon's four sums for a tile of SPAN_RB rows under one threshold, the dilation from ballot words in LDS --
+//       the body of both k_eval_epsilon (mtadgat_eval.hip: a column, the tiles walked grid-stride) and k_part_epsilon
+//       (mtadgat_parts.hip: a span, one slot per tile).
 //   ScratchCarver: one description of a scratch layout for the size query and for the call.
 #ifndef MTADGAT_SCAN_H
 #define MTADGAT_SCAN_H
@@ -52,6 +56,20 @@ __device__ __forceinline__ unsigned block_exclusive(unsigned mine, unsigned* sm,
     total = (sm[0] + sm[1]) + (sm[2] + sm[3]);
     __syncthreads();
     return before + s - mine;
+}
+
+// the sum of v over a 256-thread workgroup by a fixed tree; sm: 256 doubles (barriers inside)
+__device__ __forceinline__ double block_sum(double v, double* sm) {
+    const int tid = threadIdx.x;
+    sm[tid] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) sm[tid] += sm[tid + s];
+        __syncthreads();
+    }
+    const double r = sm[0];
+    __syncthreads();
+    return r;
 }
 
 // C[i] = T[0] + .. + T[i - 1] (C may be T), 64 entries per step of one wave in entry order; *total (may be null) = the sum.
@@ -137,6 +155,19 @@ __device__ __forceinline__ void span_bounds(const long* __restrict__ start, cons
     if (e > n) e = n;
     if (e < s) e = s;
 }
+// the span of index i (0 <= i < n): the first span whose end lies beyond i, if it starts at or before i; -1: no span covers i.
+// s: that span's start cut to 0.
+__device__ __forceinline__ long span_find(const long* __restrict__ start, const long* __restrict__ end, long count, long i, long& s) {
+    long lo = 0, hi = count;
+    while (lo < hi) {
+        const long mid = (lo + hi) >> 1;
+        if (end[mid] <= i) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo >= count) return -1;
+    s = start[lo] < 0 ? 0 : start[lo];
+    return s <= i ? lo : -1;
+}
 // slot of row block b of span k: spans are disjoint and ascending, so floor(s / SPAN_RB) + k + b is different for every (k, b)
 // and stays below n / SPAN_RB + count + 1
 __device__ __forceinline__ long span_slot0(long s, long k) { return s / SPAN_RB + k; }
@@ -149,6 +180,49 @@ inline long span_slices(int64_t n, int64_t count, long per_slice) {
     long slices = 8192 / count;
     slices = slices < 4 ? 4 : (slices > 1024 ? 1024 : slices);
     return slices > most ? most : slices;
+}
+
+// ---- find_epsilon's z table, one tile ------------------------------------------------------------------------------------------------
+constexpr int EPS_HALO_MAX = 128;                                    // widest dilation halo staged in LDS
+constexpr int EPS_TILE_WORDS = (SPAN_RB + 2 * EPS_HALO_MAX) / 64;    // `hot` of epsilon_tile: 64-bit words
+
+// Rows [r0, r0 + rows) (rows <= SPAN_RB) of the range [lo, hi) of an array with row stride ld, under the threshold ez.  Added to this
+// thread's partial sums, rows r = tid, tid + 256, ... in that order:
+//   a += x, q += x^2, cnt += 1 where x < ez;  dil += 1 where some |j| <= halo with lo <= row + j < hi has x[row + j] >= ez
+// The tile's rows and their halo, cut to [lo, hi), are staged once in `hot` as the flags x >= ez, one bit each (a wave's __ballot is a
+// 64-bit word of them: bit t is sample r0 - halo + t), so a row's window of 2 halo + 1 flags is at most five masked words.  A halo
+// beyond EPS_HALO_MAX reads the window from memory.  Every thread of a 256-thread workgroup calls it (one barrier inside); the caller
+// puts a barrier between a tile's reads of `hot` and the next call.
+__device__ __forceinline__ void epsilon_tile(const float* __restrict__ x, long ld, long lo, long hi, long r0, int rows, double ez, int halo,
+                                             unsigned long long* hot, double& a, double& q, double& cnt, double& dil) {
+    const int tid = threadIdx.x, lane = threadIdx.x & 63;
+    const bool staged = halo <= EPS_HALO_MAX;
+    if (staged) {
+        for (int t0 = tid - lane; t0 < rows + 2 * halo; t0 += 256) {         // wave-uniform
+            const long at = r0 - halo + t0 + lane;
+            const unsigned long long m = __ballot(at >= lo && at < hi && (double)x[at * ld] >= ez);
+            if (lane == 0) hot[t0 >> 6] = m;
+        }
+    }
+    __syncthreads();
+    for (int r = tid; r < rows; r += 256) {
+        const double v = (double)x[(r0 + r) * ld];
+        if (v < ez) { a += v; q += v * v; cnt += 1.0; }
+        bool any = false;
+        if (staged) {
+            const int b0 = r, b1 = r + 2 * halo;                              // the window of row r, in tile bits
+            for (int w = b0 >> 6; w <= b1 >> 6; ++w) {
+                unsigned long long mask = ~0ull;
+                if (w == b0 >> 6) mask &= ~0ull << (b0 & 63);
+                if (w == b1 >> 6) mask &= ~0ull >> (63 - (b1 & 63));
+                any = any || (hot[w] & mask) != 0ull;
+            }
+        } else {
+            const long k0 = r0 + r - halo < lo ? lo : r0 + r - halo, k1 = r0 + r + halo >= hi ? hi - 1 : r0 + r + halo;
+            for (long k = k0; k <= k1; ++k) any = any || ((double)x[k * ld] >= ez);
+        }
+        dil += any ? 1.0 : 0.0;
+    }
 }
 
 // ---- scratch layouts ---------------------------------------------------------------------------------------------------------------

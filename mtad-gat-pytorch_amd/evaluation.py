@@ -6,13 +6,15 @@ epsilon_eval :164-186, bf_search :117-158) and the score arithmetic of `Predicto
 +-49-sample dilation, point-adjusted confusion counts for one threshold or a whole sweep -- are HIP kernels
 (csrc/mtadgat_eval.hip behind the `mtadgat_eval_*` C entry points); the scalar bookkeeping on top (which z /
 threshold wins, precision / recall / F1 from the counts) is done here in float64 exactly as the reference writes
-it.  Results equal the reference's dictionaries (tests/test_gpu_eval.py: the shipped MSL run's summary.txt).
+it -- find_epsilon's host half once (_epsilon_thresholds, _chosen_epsilons) for an array, its columns and its parts.
+Results equal the reference's dictionaries (tests/test_gpu_eval.py: the shipped MSL run's summary.txt).
 
 The Predictor's options on top of the raw score (prediction.py:65-165) stay on the device too
 (csrc/mtadgat_evalcol.hip, tests/test_gpu_score_pipeline.py):
   column_quantiles / scale_scores   --scale_scores: (a - median) / (1 + IQR) per output dimension; np.percentile's linear
                                     quantiles of all columns from one exact radix select (no sort, any n < 2^31)
-  moving_average                    --use_mov_av: pandas' ewm(span).mean() as a float64 blocked scan
+  moving_average                    --use_mov_av: pandas' ewm(span).mean() as a float64 blocked scan; with parts= the same scan
+                                    restarted at every part (one kernel template, two entry points)
   find_epsilon_columns /            the per-feature thresholds and predictions (prediction.py:140-154): both find_epsilon
   feature_predictions               passes over all columns in one launch each
   predict_anomalies                 what Predictor.predict_anomalies computes from a train and a test series, in one call
@@ -36,7 +38,8 @@ Threshold-free quality of a score array (csrc/mtadgat_curves.hip, tests/test_gpu
   ranking_curve                     every distinct threshold with its cumulative TP / FP, for the raw scores, the reference's point
                                     adjust or PA%K (Kim et al., AAAI 2022), adjusted and ranked without the scores leaving the device
   ranking_metrics                   exact AUROC, average precision and the best-F1 point of that curve, from one small copy
-Series that are concatenations of independent parts -- the channels of MSL / SMAP, the machines of SMD (csrc/mtadgat_parts.hip,
+Series that are concatenations of independent parts -- the channels of MSL / SMAP, the machines of SMD (csrc/mtadgat_parts.hip, the
+segmented scan of csrc/mtadgat_evalcol.hip and the epsilon tile of csrc/mtadgat_scan.h that find_epsilon shares;
 tests/test_gpu_parts.py; tests/part_refs.py is the specification; the reference's adjust_anomaly_scores, utils.py:210-255):
   score_parts                       where the parts lie among the scores: spans, seams and the transition blanked around a seam
   adjust_part_scores                the scores around every seam set to 0, then min-max normalisation per part (and per column)
@@ -231,6 +234,24 @@ _EPSILON_ZS = np.arange(2.5, 12, 0.5)
 _EPSILON_HALO = 49
 
 
+def _epsilon_thresholds(sums, squares, counts):
+    """The host half of find_epsilon between its two device passes, for P problems at once: from (sum, sum of squares, count) per
+    problem the mean and sd (float64, (P,)) and the (P, nz) thresholds mean + sd * z.  A problem without samples: NaN throughout."""
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+    means, sds = np.full(counts.size, np.nan), np.full(counts.size, np.nan)
+    for p in np.flatnonzero(counts > 0):
+        means[p] = sums[p] / counts[p]
+        sds[p] = math.sqrt(max(squares[p] / counts[p] - means[p] * means[p], 0.0))
+    return means, sds, np.ascontiguousarray(means[:, None] + sds[:, None] * _EPSILON_ZS)
+
+
+def _chosen_epsilons(counts, means, sds, eps, tab, reg_level):
+    """_choose_epsilon of every problem that has samples, from the (P, 4 nz) table rows: a list of thresholds, None where no z
+    qualifies or there is no sample (the callers differ in what they fall back to)."""
+    return [_choose_epsilon(int(counts[p]), float(means[p]), float(sds[p]), eps[p], tab[p], reg_level) if counts[p] > 0 else None
+            for p in range(len(eps))]
+
+
 def find_epsilon(errors, reg_level=1):
     """Threshold of Hundman et al. as the reference computes it (eval_methods.py:189-236)."""
     lib = _lib()
@@ -240,18 +261,13 @@ def find_epsilon(errors, reg_level=1):
     mom = (ctypes.c_double * 2)()
     with torch.cuda.device(e.device):
         _check(lib.mtadgat_eval_moments(e.data_ptr(), n, scratch.data_ptr(), mom, _stream(e)), "eval_moments")
-    mean = mom[0] / n
-    sd = math.sqrt(max(mom[1] / n - mean * mean, 0.0))
-    zs = _EPSILON_ZS
-    eps = mean + sd * zs
-    tab = (ctypes.c_double * (4 * len(zs)))()
+    means, sds, eps = _epsilon_thresholds(mom[0:1], mom[1:2], [n])
+    tab = np.empty((1, 4 * eps.shape[1]), dtype=np.float64)
     with torch.cuda.device(e.device):
-        _check(lib.mtadgat_eval_epsilon_table(e.data_ptr(), n, eps.ctypes.data_as(_c_double_p), len(zs), _EPSILON_HALO,
-                                              scratch.data_ptr(), tab, _stream(e)), "eval_epsilon_table")
-    best = _choose_epsilon(n, mean, sd, eps, tab, reg_level)
-    if best is None:
-        best = float(e.max().item())
-    return best
+        _check(lib.mtadgat_eval_epsilon_table(e.data_ptr(), n, eps.ctypes.data_as(_c_double_p), eps.shape[1], _EPSILON_HALO,
+                                              scratch.data_ptr(), tab.ctypes.data_as(_c_double_p), _stream(e)), "eval_epsilon_table")
+    best = _chosen_epsilons([n], means, sds, eps, tab, reg_level)[0]
+    return float(e.max().item()) if best is None else best
 
 
 def find_epsilon_columns(errors, reg_level=1):
@@ -262,27 +278,23 @@ def find_epsilon_columns(errors, reg_level=1):
     e = _dev2d(errors, "errors")
     n, d = e.shape
     ld = e.stride(0)
-    zs = _EPSILON_ZS
-    nz = len(zs)
+    nz = len(_EPSILON_ZS)
     scratch = _native._empty(max(2 * d, 5 * d * nz), dtype=torch.float64, device=e.device)
-    mom = (ctypes.c_double * (2 * d))()
+    mom = np.empty((d, 2), dtype=np.float64)
     with torch.cuda.device(e.device):
-        _check(lib.mtadgat_eval_moments_columns(e.data_ptr(), n, d, ld, scratch.data_ptr(), mom, _stream(e)), "eval_moments_columns")
-    means = [mom[2 * c] / n for c in range(d)]
-    sds = [math.sqrt(max(mom[2 * c + 1] / n - means[c] * means[c], 0.0)) for c in range(d)]
-    eps = np.ascontiguousarray(np.stack([means[c] + sds[c] * zs for c in range(d)]))
-    tab = (ctypes.c_double * (4 * nz * d))()
+        _check(lib.mtadgat_eval_moments_columns(e.data_ptr(), n, d, ld, scratch.data_ptr(), mom.ctypes.data_as(_c_double_p), _stream(e)),
+               "eval_moments_columns")
+    counts = [n] * d
+    means, sds, eps = _epsilon_thresholds(mom[:, 0], mom[:, 1], counts)
+    tab = np.empty((d, 4 * nz), dtype=np.float64)
     with torch.cuda.device(e.device):
         _check(lib.mtadgat_eval_epsilon_table_columns(e.data_ptr(), n, d, ld, eps.ctypes.data_as(_c_double_p), nz, _EPSILON_HALO,
-                                                      scratch.data_ptr(), tab, _stream(e)), "eval_epsilon_table_columns")
-    out, col_max = [], None
-    for c in range(d):
-        best = _choose_epsilon(n, means[c], sds[c], eps[c], tab[4 * nz * c:4 * nz * (c + 1)], reg_level)
-        if best is None:
-            if col_max is None:
-                col_max = e.max(dim=0).values.cpu()
-            best = float(col_max[c])
-        out.append(best)
+                                                      scratch.data_ptr(), tab.ctypes.data_as(_c_double_p), _stream(e)),
+               "eval_epsilon_table_columns")
+    out = _chosen_epsilons(counts, means, sds, eps, tab, reg_level)
+    if None in out:
+        col_max = e.max(dim=0).values.cpu()
+        out = [float(col_max[c]) if best is None else best for c, best in enumerate(out)]
     return out
 
 
@@ -324,23 +336,18 @@ def moving_average(scores, span, parts=None):
     n = x.numel()
     if n < 1:
         raise ValueError("scores is empty")
-    if parts is not None:
-        start, end, _ = _parts_on(parts, x, n)
-        scratch = _scratch(lib.mtadgat_eval_ewm_parts_scratch(n), x.device)
-        out = _native._empty((n,), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            rc = lib.mtadgat_eval_ewm_parts(x.data_ptr(), n, start.data_ptr(), end.data_ptr(), parts.n_parts, 2.0 / (float(span) + 1.0),
-                                            scratch.data_ptr(), scratch.numel() * 8, out.data_ptr(), _stream(x))
-        if rc != 0:
-            _fail(lib, rc, "eval_ewm_parts")
-        return out
-    scratch = _scratch(lib.mtadgat_eval_ewm_scratch(n), x.device)
+    alpha = 2.0 / (float(span) + 1.0)
     out = _native._empty((n,), dtype=torch.float32, device=x.device)
+    if parts is None:
+        what, spans = "eval_ewm", ()
+    else:
+        start, end, _ = _parts_on(parts, x, n)
+        what, spans = "eval_ewm_parts", (start.data_ptr(), end.data_ptr(), parts.n_parts)
+    scratch = _scratch(getattr(lib, f"mtadgat_{what}_scratch")(n), x.device)
     with torch.cuda.device(x.device):
-        rc = lib.mtadgat_eval_ewm(x.data_ptr(), n, 2.0 / (float(span) + 1.0), scratch.data_ptr(), scratch.numel() * 8, out.data_ptr(),
-                                  _stream(x))
+        rc = getattr(lib, f"mtadgat_{what}")(x.data_ptr(), n, *spans, alpha, scratch.data_ptr(), scratch.numel() * 8, out.data_ptr(), _stream(x))
     if rc != 0:
-        _fail(lib, rc, "eval_ewm")
+        _fail(lib, rc, what)
     return out
 
 
@@ -533,8 +540,7 @@ def find_epsilon_parts(scores, parts, reg_level=1):
     x = _dev1d(scores, torch.float32, "scores")
     n = x.numel()
     start, end, _ = _parts_on(parts, x, n)
-    P, zs = parts.n_parts, _EPSILON_ZS
-    nz = len(zs)
+    P, nz = parts.n_parts, len(_EPSILON_ZS)
     scratch = _scratch(lib.mtadgat_eval_part_epsilon_scratch(n, P, nz), x.device)
     mom = np.empty((P, 3), dtype=np.float64)
     with torch.cuda.device(x.device):
@@ -543,13 +549,7 @@ def find_epsilon_parts(scores, parts, reg_level=1):
     if rc != 0:
         _fail(lib, rc, "eval_part_epsilon_moments")
     count = parts.end_host - parts.start_host
-    eps = np.full((P, nz), np.nan)
-    means, sds = np.full(P, np.nan), np.full(P, np.nan)
-    for p in range(P):
-        if count[p] > 0:
-            means[p] = mom[p, 0] / count[p]
-            sds[p] = math.sqrt(max(mom[p, 1] / count[p] - means[p] * means[p], 0.0))
-            eps[p] = means[p] + sds[p] * zs
+    means, sds, eps = _epsilon_thresholds(mom[:, 0], mom[:, 1], count)
     tab = np.empty((P, 4 * nz), dtype=np.float64)
     with torch.cuda.device(x.device):
         rc = lib.mtadgat_eval_part_epsilon_table(x.data_ptr(), n, start.data_ptr(), end.data_ptr(), P, eps.ctypes.data_as(_c_double_p), nz,
@@ -558,9 +558,8 @@ def find_epsilon_parts(scores, parts, reg_level=1):
     if rc != 0:
         _fail(lib, rc, "eval_part_epsilon_table")
     out = np.full(P, np.inf)
-    for p in range(P):
+    for p, best in enumerate(_chosen_epsilons(count, means, sds, eps, tab, reg_level)):
         if count[p] > 0:
-            best = _choose_epsilon(int(count[p]), float(means[p]), float(sds[p]), eps[p], tab[p], reg_level)
             out[p] = mom[p, 2] if best is None else best
     return out
 

@@ -1,6 +1,8 @@
 """Reference arithmetic of the threshold-evaluation kernels of csrc/mtadgat_eval.hip (k_eval_moments, k_eval_epsilon,
-k_eval_segments + k_eval_adjust, k_eval_scores) in numpy / float64, table by table, straight from the definitions; the gates
-the GPU tests hold the kernels to; and the seeded inputs those tests and tests/test_host_eval.py share.  No torch, no GPU.
+k_eval_segments + k_eval_adjust, k_eval_scores) and of the per-part tables of csrc/mtadgat_parts.hip (k_part_moments,
+k_part_epsilon) in numpy / float64, table by table, straight from the definitions; the gates the GPU tests hold the kernels to; and
+the seeded inputs those tests and tests/test_host_eval.py share.  No torch, no GPU.
+Both epsilon kernels run epsilon_tile (csrc/mtadgat_scan.h): tiles of 1024 rows, the hot flags staged as 64-bit ballot words.
 
 The gates return the largest error / bound ratio they met, so a caller can report how much room a derived bound leaves."""
 import math
@@ -162,8 +164,13 @@ def check_scores(got, want, d=None):
 MOMENT_SIZES = (1, 255, 256, 257, 65535, 65536, 65537, 131073)       # k_eval_moments: 256 x 256 rows per trip of the grid
 MOMENT_COLUMNS = (1, 3, 65)
 EPS_HALOS = (0, 1, 49, 127, 128, 129, 300)                            # 128 = EPS_HALO_MAX: 129 and 300 read memory directly
-EPS_TRIP = 128 * 256                                                  # rows of k_eval_epsilon per trip of the grid
-EPS_COLUMN_SIZES = (257, 32769, 65793)
+EPS_TILE = 1024                                                       # rows of epsilon_tile (SPAN_RB), staged as words of 64 flags
+EPS_TRIP = 128 * EPS_TILE                                             # rows of k_eval_epsilon per trip of the grid (at most 128 tiles)
+EPS_OLD_TILE, EPS_OLD_TRIP = 256, 128 * 256                           # the byte-flag tile k_eval_epsilon had: its sizes stay in the lists
+EPS_THREE_TRIPS = (2 * EPS_TRIP + EPS_TILE + 1, 49)                   # the one (n, halo) at which every block makes three trips
+EPS_COLUMN_SIZES = (257, 1025, 32769, 65793, EPS_TRIP + 1)
+PART_TABLE_SCORES = (13, 0, 300, 1023, 1024, 1025, 2500)              # scores per part of the per-part table test: around EPS_TILE
+PART_TABLE_HALOS = (0, 49, 128)
 EPS_NZ = 64
 ADJUST_SIZES = (1, 2, 255, 256, 257, 4099)
 ADJUST_LABELS = ("none", "all", "alternating", "one_at_0", "longer_at_0", "ending_at_end", "spanning_250_520", "random")
@@ -174,7 +181,11 @@ SCORE_ACTUAL_COLUMNS = 70
 
 
 def eps_sizes(halo):
-    ns = (1, 2, halo, halo + 1, 2 * halo + 1, 255, 256, 257, 256 + halo, EPS_TRIP - 1, EPS_TRIP, EPS_TRIP + 1, EPS_TRIP + 257 + halo)
+    """n one below, at and one above a tile and a trip, and a tile / a trip and a partial tile with its halo more; the same around
+    the earlier tile of 256 rows, which is four words."""
+    ns = (1, 2, halo, halo + 1, 2 * halo + 1)
+    for tile, trip in ((EPS_OLD_TILE, EPS_OLD_TRIP), (EPS_TILE, EPS_TRIP)):
+        ns += (tile - 1, tile, tile + 1, tile + halo, trip - 1, trip, trip + 1, trip + tile + 1 + halo)
     return sorted({n for n in ns if n >= 1})
 
 
@@ -185,15 +196,18 @@ def moment_columns(n, d, seed=0):
 
 
 def spike_indices(n, halo):
-    """Where epsilon_case puts its isolated spikes, tallest first: a dilation window then ends exactly on a tile edge (256) or a
-    trip edge (32768) of k_eval_epsilon, or one sample short of / past it."""
-    want = (0, 256, n - 1, 255, EPS_TRIP, EPS_TRIP - 1, 256 + halo + 1, 256 - halo - 1, 256 + halo, 256 - halo, EPS_TRIP + halo,
-            EPS_TRIP - halo)
+    """Where epsilon_case puts its isolated spikes, tallest first, twelve at the most: a dilation window then ends exactly on a tile
+    edge (1024) or a trip edge (131072) of k_eval_epsilon, or one sample short of / past it.  A tile's flag t is sample
+    r0 - halo + t, so the spikes at 1024 - halo and 1024 - halo - 1 are bit 0 of one 64-bit word and bit 63 of the word before it.
+    Below n = 1024 the places around 256 (a multiple of the word as well) take over."""
+    T, R, t = EPS_TILE, EPS_TRIP, EPS_OLD_TILE
+    want = (0, T, n - 1, T - 1, R, R - 1, T + halo + 1, T - halo - 1, T + halo, T - halo, R + halo, R - halo,
+            t, t - 1, t + halo + 1, t - halo - 1, t + halo, t - halo)
     out = []
     for i in want:
         if 0 <= i < n and i not in out:
             out.append(i)
-    return out
+    return out[:12]
 
 
 def epsilon_case(n, halo, seed=0, nonfinite=False):
@@ -226,6 +240,15 @@ def epsilon_case(n, halo, seed=0, nonfinite=False):
 
 
 EPS_ROW_BELOW, EPS_ROW_ABOVE, EPS_ROW_NAN, EPS_ROW_OWN = 19, 20, 21, 22      # rows of epsilon_case's thresholds
+
+
+def part_table_case(halo):
+    """The per-part tables' case: parts of PART_TABLE_SCORES scores side by side, part p holding epsilon_case(count, halo, seed p)
+    with its own 64 thresholds (an empty part: a NaN row).  Every part has spikes on its first and last score, so a dilation that
+    looked across a seam would count the neighbour's.  Returns (x (n,) float32, start, end, eps (P, 64) float64)."""
+    cases = [epsilon_case(c, halo, seed=p) if c else (np.zeros(0, np.float32), np.full(EPS_NZ, np.nan)) for p, c in enumerate(PART_TABLE_SCORES)]
+    end = np.cumsum(PART_TABLE_SCORES, dtype=np.int64)
+    return np.concatenate([c[0] for c in cases]), end - np.asarray(PART_TABLE_SCORES, np.int64), end, np.stack([c[1] for c in cases])
 
 
 def adjust_labels(kind, n, rng):

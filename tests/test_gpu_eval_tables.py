@@ -1,8 +1,9 @@
-"""The kernels of csrc/mtadgat_eval.hip (k_eval_moments, k_eval_epsilon, k_eval_segments + k_eval_adjust, k_eval_scores) table by
-table against the float64 specification of tests/eval_refs.py: every row of the z table, not only the threshold find_epsilon
-picks from it; at the sizes where a tile (256 rows), a trip of the grid-stride loops or the staged / direct dilation paths
-change; contiguous and as a column slice of a wider tensor.  The bounds are derived in eval_refs.check_*; each test prints the
-largest error / bound it met (pytest -s).  Scratch buffers have the sizes evaluation.py allocates."""
+"""The kernels of csrc/mtadgat_eval.hip (k_eval_moments, k_eval_epsilon, k_eval_segments + k_eval_adjust, k_eval_scores) and the
+per-part tables of csrc/mtadgat_parts.hip (k_part_moments, k_part_epsilon) table by table against the float64 specification of
+tests/eval_refs.py: every row of the z table, not only the threshold find_epsilon picks from it; at the sizes where a tile of
+epsilon_tile (csrc/mtadgat_scan.h: 1024 rows, flags in 64-bit words), a trip of the grid-stride loops or the staged / direct
+dilation paths change; contiguous and as a column slice of a wider tensor.  The bounds are derived in eval_refs.check_*; each test
+prints the largest error / bound it met (pytest -s).  Scratch buffers have the sizes evaluation.py allocates."""
 import ctypes
 import functools
 
@@ -107,7 +108,7 @@ def _epsilon_table(ev, x, n, eps, halo):
     return out
 
 
-@pytest.mark.parametrize("n,halo", [(n, h) for h in er.EPS_HALOS for n in er.eps_sizes(h)])
+@pytest.mark.parametrize("n,halo", [(n, h) for h in er.EPS_HALOS for n in er.eps_sizes(h)] + [er.EPS_THREE_TRIPS])
 def test_epsilon_table(n, halo, gpu_device):
     import evaluation as ev
     e, eps, tab, absum = _eps_ref(n, halo)
@@ -128,10 +129,10 @@ def test_epsilon_table_nan_and_inf_samples(gpu_device):
     _note("epsilon_table with NaN and +inf samples", 1, _check_table(got, tab, absum, n, finite=False))
 
 
-@pytest.mark.parametrize("n,halo", [(257, 49), (32769, 49), (65793, 49), (257, 129), (32769, 129)])
+@pytest.mark.parametrize("n,halo", [(257, 49), (32769, 49), (65793, 49), (257, 129), (32769, 129), (1025, 49), (131073, 49), (1025, 129)])
 def test_epsilon_table_columns(n, halo, gpu_device):
-    """Three columns of a six-column tensor, each with its own data and thresholds; at n = 65793 the grid cap min(ceil(n / 256), 128)
-    holds and every block makes three trips."""
+    """Three columns of a six-column tensor, each with its own data and thresholds; at n = 131073 the grid cap
+    min(ceil(n / 1024), 128) holds and the first block makes a second trip (three trips: test_epsilon_table at EPS_THREE_TRIPS)."""
     import evaluation as ev
     lib = ev._lib()
     d, ld, nz = 3, 6, er.EPS_NZ
@@ -155,6 +156,46 @@ def test_epsilon_table_columns(n, halo, gpu_device):
         except AssertionError as err:
             raise AssertionError(f"column {c}: {err}") from None
     _note(f"epsilon_table_columns n={n} halo={halo}", d, worst)
+
+
+def _check_part_rows(mom, tab, x, start, end, eps, halo):
+    """Every part's moments and table rows against the reference of its slice alone; the largest error / bound."""
+    worst = 0.0
+    for p, (s, e) in enumerate(zip(start, end)):
+        part, n = x[s:e], int(e - s)
+        try:
+            if n == 0:
+                assert mom[p].tolist() == [0.0, 0.0, -np.inf] and not tab[p].any()
+                continue
+            ref, absum = er.epsilon_table(part, eps[p], halo, with_abs=True)
+            worst = max(worst, _check_table(tab[p], ref, absum, n), _check_moments(mom[p, :2], er.moments(part) + (er.abs_sum(part),), n))
+            assert mom[p, 2] == float(part.max())
+        except AssertionError as err:
+            raise AssertionError(f"part {p} of {n} scores: {err}") from None
+    return worst
+
+
+@pytest.mark.parametrize("halo", er.PART_TABLE_HALOS)
+def test_part_epsilon_table(halo, gpu_device):
+    """mtadgat_eval_part_epsilon_moments / _table called directly: parts on both sides of a tile and an empty one, each under its own
+    64 thresholds.  The dilation never looks outside a part, so the part's slice alone is the reference; counts exact, sums inside
+    the bound of eval_refs.check_sums with n = the row's pruned count."""
+    import evaluation as ev
+    lib = ev._lib()
+    x, start, end, eps = er.part_table_case(halo)
+    P, nz, n = len(start), er.EPS_NZ, x.size
+    xd, sd, ed = _dev(x, gpu_device), _dev(start, gpu_device), _dev(end, gpu_device)
+    scratch = ev._scratch(lib.mtadgat_eval_part_epsilon_scratch(n, P, nz), gpu_device)
+    mom, tab = np.empty((P, 3)), np.empty((P, 4 * nz))
+    eps = np.ascontiguousarray(eps)
+    with torch.cuda.device(gpu_device):
+        rc = lib.mtadgat_eval_part_epsilon_moments(xd.data_ptr(), n, sd.data_ptr(), ed.data_ptr(), P, nz, scratch.data_ptr(),
+                                                   scratch.numel() * 8, mom.ctypes.data_as(_dp), ev._stream(xd))
+        assert rc == 0, lib.mtadgat_last_error()
+        rc = lib.mtadgat_eval_part_epsilon_table(xd.data_ptr(), n, sd.data_ptr(), ed.data_ptr(), P, eps.ctypes.data_as(_dp), nz, halo,
+                                                 scratch.data_ptr(), scratch.numel() * 8, tab.ctypes.data_as(_dp), ev._stream(xd))
+        assert rc == 0, lib.mtadgat_last_error()
+    _note(f"part_epsilon_table halo={halo}", P, _check_part_rows(mom, tab, x, start, end, eps, halo))
 
 
 # ---- (c) point adjust ------------------------------------------------------------------------------------------------------------------

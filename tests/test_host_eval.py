@@ -187,10 +187,11 @@ def test_gates_catch_a_strict_hot_flag():
 
 
 def test_gates_catch_one_pruned_count_and_the_sample_at_a_tile_edge():
+    T = er.EPS_TILE
     for halo in er.EPS_HALOS:
-        n = 256 + halo
-        if n <= 256:
-            n = 257
+        n = T + halo
+        if n <= T:
+            n = T + 1
         e, eps = er.epsilon_case(n, halo)
         want = er.epsilon_table(e, eps, halo)
         got = want.copy()
@@ -198,13 +199,29 @@ def test_gates_catch_one_pruned_count_and_the_sample_at_a_tile_edge():
         with pytest.raises(AssertionError, match="count row 7"):
             er.check_counts(got[:, 2:], want[:, 2:])
 
-        def without_256(e32, ez):
+        def without_edge(e32, ez):
             hot = er.hot_flags(e32, ez).copy()
-            hot[256] = False
+            hot[T] = False
             return hot
-        assert er.spike_indices(n, halo)[:2] == [0, 256]      # the row of the second spike's own value: 0 and 256 alone are hot
+        assert er.spike_indices(n, halo)[:2] == [0, T]        # the row of the second spike's own value: 0 and T alone are hot
         with pytest.raises(AssertionError, match="count row"):
-            er.check_counts(er.epsilon_table(e, eps, halo, hot=without_256)[:, 2:], want[:, 2:])
+            er.check_counts(er.epsilon_table(e, eps, halo, hot=without_edge)[:, 2:], want[:, 2:])
+
+
+def test_the_part_table_references_keep_the_row_conventions():
+    """What tests/test_gpu_eval_tables.py asserts of the per-part rows holds for the reference alone, on every part's slice."""
+    for halo in er.PART_TABLE_HALOS:
+        x, start, end, eps = er.part_table_case(halo)
+        assert (end - start).tolist() == list(er.PART_TABLE_SCORES) and x.size == end[-1]
+        for s, e, row in zip(start, end, eps):
+            n = int(e - s)
+            tab = er.epsilon_table(x[s:e], row, halo)
+            assert tab[er.EPS_ROW_NAN].tolist() == [0.0, 0.0, 0.0, 0.0]
+            if n == 0:
+                assert not tab.any() and er.moments(x[s:e]) == (0.0, 0.0)
+                continue
+            assert tab[er.EPS_ROW_BELOW].tolist() == [0.0, 0.0, 0.0, float(n)] and tab[er.EPS_ROW_ABOVE, 2:].tolist() == [float(n), 0.0]
+            assert er.spike_indices(n, halo)[:2] == ([0, n - 1] if n > 1 and n <= er.EPS_TILE else [0, er.EPS_TILE][:n])
 
 
 def test_gates_catch_a_sum_outside_its_bound():
