@@ -328,3 +328,18 @@ def straddling_indices(count, steps, units):
     """Positions p whose step range [p m, (p + 1) m) (m = max(steps, 1)) crosses a chunk boundary of attribution_chunks."""
     m = max(steps, 1)
     return [p for p in range(count) if (p * m) // units != ((p + 1) * m - 1) // units]
+
+
+# ---- which recurrence kernels a GPU call runs (tests that claim a kernel assert it) ----------------------------------------------------
+def device_compute_units(device):
+    return torch.cuda.get_device_properties(device).multi_processor_count
+
+
+def call_routes(eng, n, compute_units):
+    """(piece sizes, ["GRU 0 | ... | decoder 0 | ..." per piece]) of an inference call of n windows under the engine's current
+    precision, chunk size and options: Engine.forward_plan and Engine.gru_route, each route spelled as tests/test_host_gru_route.py's
+    `_describe` spells it, "+" joining a first kernel to its range-guard fallback."""
+    from test_host_gru_route import _describe
+    pieces = [p for _, p, _ in eng.forward_plan(n)["pieces"]]
+    layers = [(0, l) for l in range(eng.cfg.gru_n_layers)] + [(1, l) for l in range(eng.cfg.recon_n_layers)]
+    return pieces, [" | ".join("+".join(_describe(eng.gru_route(s, l, p, compute_units=compute_units))) for s, l in layers) for p in pieces]

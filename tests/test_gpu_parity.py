@@ -3,7 +3,7 @@ golden vectors generated from the reference itself (tests/golden/make_golden.py)
 import pytest
 import torch
 
-from helpers import ALL_CASES, SHIPPED_CASES, Case, gate
+from helpers import ALL_CASES, SHIPPED_CASES, Case, call_routes, device_compute_units, gate
 from oracle import mtad_gat_oracle as oracle
 
 pytestmark = pytest.mark.gpu
@@ -165,12 +165,24 @@ def test_split_operand_kernels_track_the_fp32_mfma_kernels_at_any_input_scale(sc
             assert (pa - pb).abs().max().item() <= tol and (ra - rb).abs().max().item() <= tol, (scale, wmul)
 
 
+# What test_full_machine_batch_matches runs, hand-written (256 compute units): the 65 573 windows go as a piece of 65 536 and one of 37.
+FULL_MACHINE_ROUTES = {
+    ("msl", "fp32"): "cm+tile:x3_hi:2 | cm:fc",
+    ("msl", "fp32_strict"): "tile:fp32:2 | tile:fp32:2:fc",
+    ("syn_v2_embed", "fp32"): "cm+tile:x3_lo:2 | cm:fc",
+    ("syn_v2_embed", "fp32_strict"): "tile:fp32:2 | tile:fp32:2:fc",
+}
+
+
 @pytest.mark.parametrize("precision", ["fp32", "fp32_strict"])
 @pytest.mark.parametrize("name", ["msl", "syn_v2_embed"])
 def test_full_machine_batch_matches(name, precision, gpu_device):
-    """From 65 536 windows on, the GRU kernels take two 32-window groups per wave (one wave per SIMD); a
-    ragged batch of that size must still carry the fixture windows and agree with a small-batch run -- in the default
-    arithmetic (split-bf16 operands in k_gru and the feature layer's projection) and in "fp32_strict"."""
+    """A ragged batch of 65 536 + 37 windows runs as two pieces: 65 536 windows on the large-batch kernels -- "fp32_strict": the
+    tile-major kernel with two 32-window groups per wave (one wave per SIMD); the default arithmetic: the chunk-major kernel, the
+    two-group tile-major kernel on split operands behind its range guard -- and the last 37 on the window-per-workgroup kernel.  The
+    fixture windows are embedded twice, at the end of the call (the 37-window piece) and at the end of the 65 536-window piece (its
+    last wave); both copies must match the reference, and the large piece must agree with a small-batch run.  (A ragged last wave
+    under two groups per wave: tests/test_gpu_gru_routes.py.)"""
     case = Case(name)
     model = case.build_model().to(gpu_device)
     model.precision = precision
@@ -179,13 +191,19 @@ def test_full_machine_batch_matches(name, precision, gpu_device):
     n_big = 65536 + 37
     x = torch.rand(n_big, W, F, generator=g)
     n = case.x.shape[0]
-    x[-n:] = case.x                                   # the last, partially filled wave
+    assert n <= 37
+    x[-n:] = case.x                                   # the last piece
+    x[65536 - n:65536] = case.x                       # the last windows of the 65 536-window piece
     x = x.to(gpu_device)
     with torch.no_grad():
         p_big, r_big = model(x)
+        pieces, routes = call_routes(model._sync_engine(gpu_device), n_big, device_compute_units(gpu_device))
         p_small, r_small = model(x[40000:40100].contiguous())
+    assert pieces == [65536, 37] and routes == [FULL_MACHINE_ROUTES[name, precision], "gru1 | gru1"], (pieces, routes)
     gate(p_big[-n:], case.preds, case.preds64, what="preds at the end of a 65573-window batch")
     gate(r_big[-n:], case.recons, case.recons64, what="recons at the end of a 65573-window batch")
+    gate(p_big[65536 - n:65536], case.preds, case.preds64, what="preds at the end of the 65536-window piece")
+    gate(r_big[65536 - n:65536], case.recons, case.recons64, what="recons at the end of the 65536-window piece")
     assert (p_big[40000:40100] - p_small).abs().max().item() <= 2e-6
     assert (r_big[40000:40100] - r_small).abs().max().item() <= 2e-6
 
@@ -366,13 +384,33 @@ def test_short_last_chunk_is_planned_for_its_own_size(gpu_device):
     assert torch.equal(p, torch.cat([p1, p2])) and torch.equal(r, torch.cat([r1, r2]))
 
 
+# What test_mid_size_batches_match runs, hand-written (256 compute units, one piece each): the automatic choice, the calls forced with
+# "gru_kernel" = 1 / 2 at n_mid windows (3000 / 8192), and the 10 273-window call forced with "gru_kernel" = 1 on one lane.  Up to 8192
+# windows nothing forces the tile-major kernel onto a layer of two or more hidden tiles: "gru_kernel" = 1 only refuses the split-operand
+# kernels there, and at 3000 windows values 1 and 2 leave the 16-window-group kernel in place.  (syn_v1_small: v1 attention records no
+# convolution range and its decoder has one hidden tile: no split-operand kernel applies, the option changes nothing.)
+MID_ROUTES = {
+    "msl": dict(auto="splitx3+tile:x3_hi | splitx3:fc", k1=("gru16 | gru16", "split:fp32:xp | split:fp32:fc"),
+                k2=("gru16 | gru16", "cm+tile:x3_hi | cm:fc"), tile="tile:x3_hi | tile:x3_hi:fc"),
+    "smd_1_1": dict(auto="splitx3+tile:x3_hi | splitx3", k1=("gru16 | gru16", "split:fp32:xp | split:fp32"),
+                    k2=("gru16 | gru16", "cm+tile:x3_hi | cm"), tile="tile:x3_hi | tile:x3_hi"),
+    "syn_v2_embed": dict(auto="splitx3+tile:x3_lo | splitx3:fc", k1=("gru16 | gru16", "split:fp32:xp | split:fp32:fc"),
+                         k2=("gru16 | gru16", "cm+tile:x3_lo | cm:fc"), tile="tile:x3_lo | tile:x3_lo:fc"),
+    "syn_v1_small": dict(auto="split:fp32:xp | tile:fp32 | tile:fp32 | tile:fp32", k1=("split:fp32:xp | tile:fp32 | tile:fp32 | tile:fp32",) * 2,
+                         k2=("split:fp32:xp | tile:fp32 | tile:fp32 | tile:fp32",) * 2, tile="tile:x3_lo | tile:x3_lo | tile:x3_lo | tile:x3_lo"),
+}
+N_TILE = 10273                                        # more than 1.25 32-window groups per compute unit, the last group of one window
+
+
 @pytest.mark.parametrize("n_mid", [3000, 8192])
 @pytest.mark.parametrize("name", ["msl", "smd_1_1", "syn_v2_embed", "syn_v1_small"])
 def test_mid_size_batches_match(name, n_mid, gpu_device):
     """2 561 - 8 192 windows: the hidden-tile-split recurrence on split operands (two fp16 pieces per value, one workgroup
     of NCG waves per 32 windows) -- fixture windows embedded in such a batch match the reference, the batch agrees with the
     same windows run as a small batch (16-window-group / window-per-workgroup kernels) and, forced through the engine's
-    measurement hook, with the chunk-major and the tile-major kernels."""
+    measurement hook, with the kernels MID_ROUTES names: "gru_kernel" = 1 (3000 windows: the 16-window-group kernel, 8192: the
+    hidden-tile split on fp32 operands), 2 (3000: the same, 8192: the chunk-major kernel) and 3 (the automatic choice); and with the
+    tile-major kernel on split operands, which takes these windows as the head of a 10 273-window call on one lane."""
     case = Case(name)
     model = case.build_model().to(gpu_device)
     g = torch.Generator().manual_seed(19)
@@ -381,17 +419,29 @@ def test_mid_size_batches_match(name, n_mid, gpu_device):
     n = case.x.shape[0]
     x[100:100 + n] = case.x
     x = x.to(gpu_device)
+    cus = device_compute_units(gpu_device)
     with torch.no_grad():
         p_mid, r_mid = model(x)
         p_small, r_small = model(x[1000:1300].contiguous())
         eng = model._sync_engine(gpu_device)
-        outs = {}
+        outs, routes = {}, {0: call_routes(eng, n_mid, cus)}
         try:
             for k in (1, 2, 3):
                 eng.set_option("gru_kernel", k)
+                routes[k] = call_routes(eng, n_mid, cus)
                 outs[k] = model(x)
+            eng.set_option("gru_kernel", 1)
+            eng.set_option("lanes", 1)
+            routes["tile"] = call_routes(eng, N_TILE, cus)
+            x_tile = torch.cat([x] * (N_TILE // n_mid + 1))[:N_TILE].contiguous()
+            outs["tile"] = model(x_tile)
         finally:
             eng.set_option("gru_kernel", 0)
+            eng.set_option("lanes", 0)
+    want, i = MID_ROUTES[name], (3000, 8192).index(n_mid)
+    assert routes[0] == ([n_mid], [want["auto"]]) and routes[3] == routes[0], routes
+    assert routes[1] == ([n_mid], [want["k1"][i]]) and routes[2] == ([n_mid], [want["k2"][i]]), routes
+    assert routes["tile"] == ([N_TILE], [want["tile"]]), routes
     gate(p_mid[100:100 + n], case.preds, case.preds64, what=f"preds in a {n_mid}-window batch")
     gate(r_mid[100:100 + n], case.recons, case.recons64, what=f"recons in a {n_mid}-window batch")
     assert (p_mid[1000:1300] - p_small).abs().max().item() <= 2e-6
@@ -399,3 +449,6 @@ def test_mid_size_batches_match(name, n_mid, gpu_device):
     assert torch.equal(outs[3][0], p_mid) and torch.equal(outs[3][1], r_mid)       # the automatic choice in this band
     for k in (1, 2):
         assert (outs[k][0] - p_mid).abs().max().item() <= 2e-6 and (outs[k][1] - r_mid).abs().max().item() <= 2e-6, k
+    gate(outs["tile"][0][100:100 + n], case.preds, case.preds64, what="preds, tile-major kernel on split operands")
+    gate(outs["tile"][1][100:100 + n], case.recons, case.recons64, what="recons, tile-major kernel on split operands")
+    assert (outs["tile"][0][:n_mid] - p_mid).abs().max().item() <= 2e-6 and (outs["tile"][1][:n_mid] - r_mid).abs().max().item() <= 2e-6

@@ -4,7 +4,7 @@ blocks, v1 and v2 attention.  Tolerance 1e-5 (north_star)."""
 import pytest
 import torch
 
-from helpers import gate
+from helpers import call_routes, device_compute_units, gate
 from oracle import mtad_gat_oracle as oracle
 
 pytestmark = pytest.mark.gpu
@@ -47,14 +47,25 @@ def test_shape_against_oracle(kw, gpu_device):
         gate(r, r_ref, what=f"recons b={b}")
 
 
+# What test_large_and_small_batch_kernels_on_odd_shapes runs, hand-written (256 compute units, one piece each): 20 000 windows, 70 000
+# windows on one lane (":2": two window groups per wave of the tile-major kernel), 40 windows.
+ODD_ROUTES = {
+    "F4W5": ("tile:x3_lo | cm | tile:x3_lo | tile:x3_lo:fc", "tile:x3_lo:2 | cm | tile:x3_lo:2 | tile:x3_lo:2:fc",
+             "split:fp32:xp | split:fp32 | split:fp32 | split:fp32:fc"),
+    "F7W12": ("cm+tile:x3_lo | cm", "cm+tile:x3_lo:2 | cm", "gru1 | gru1"),
+}
+
+
 @pytest.mark.parametrize("kw", [
     # decoder input spread over more than 8 h_end entries per step (3-chunk folded input), stacked layers
     dict(n_features=4, window_size=5, out_dim=2, kernel_size=3, gru_hid_dim=96, recon_hid_dim=40, gru_n_layers=2, recon_n_layers=2),
     dict(n_features=7, window_size=12, out_dim=7, kernel_size=5, gru_hid_dim=33, recon_hid_dim=65, use_gatv2=False),
 ], ids=["F4W5", "F7W12"])
 def test_large_and_small_batch_kernels_on_odd_shapes(kw, gpu_device):
-    """20 000 windows go through the register-resident GRU kernels (70 000: two window groups per wave), 40
-    through the hidden-tile-split ones; all must match the oracle."""
+    """20 000 windows go through the large-batch GRU kernels (tile-major on split operands, chunk-major), 70 000 in one piece on one
+    lane through the tile-major kernel with two window groups per wave (automatic lanes cut that call into pieces of 32 768 windows,
+    none of which has the 65 505 windows two groups per wave start at: run as well), 40 through the hidden-tile-split and
+    window-per-workgroup ones; all must match the oracle.  ODD_ROUTES names the kernels."""
     from mtad_gat import MTAD_GAT
     torch.manual_seed(23)
     model = MTAD_GAT(**kw).eval()
@@ -62,17 +73,36 @@ def test_large_and_small_batch_kernels_on_odd_shapes(kw, gpu_device):
         model.feature_gat.bias.normal_()
         model.temporal_gat.bias.normal_()
     x = torch.rand(70000, kw["window_size"], kw["n_features"])
+    cus = device_compute_units(gpu_device)
     with torch.no_grad():
         p_ref, r_ref = oracle.forward(x[:40], model.state_dict(), alpha=kw.get("alpha", 0.2))
         m = model.to(gpu_device)
         p_big, r_big = m(x[:20000].to(gpu_device))
-        m._engine.set_chunk_windows(1 << 17)                       # keep the 70 000 windows in one launch
+        eng = m._engine
+        routes = [call_routes(eng, 20000, cus)]
+        eng.set_chunk_windows(1 << 17)                             # keep the 70 000 windows in one chunk
         p_huge, r_huge = m(x.to(gpu_device))
+        pieces_auto = call_routes(eng, 70000, cus)[0]
+        eng.set_option("lanes", 1)
+        try:
+            routes.append(call_routes(eng, 70000, cus))
+            p_two, r_two = m(x.to(gpu_device))                     # ... and in one piece
+        finally:
+            eng.set_option("lanes", 0)
         p_small, r_small = m(x[:40].to(gpu_device))
+        routes.append(call_routes(eng, 40, cus))
+    name = "F%dW%d" % (kw["n_features"], kw["window_size"])
+    assert pieces_auto == [32768, 32768, 4464], pieces_auto
+    assert routes == [([n], [r]) for n, r in zip((20000, 70000, 40), ODD_ROUTES[name])], routes
+    assert all(":2" in r for r in ODD_ROUTES[name][1].split(" | ") if "tile" in r)
     gate(p_big[:40], p_ref, what="preds, large batch")
     gate(r_big[:40], r_ref, what="recons, large batch")
-    gate(p_huge[:40], p_ref, what="preds, full-machine batch")
-    gate(r_huge[:40], r_ref, what="recons, full-machine batch")
+    gate(p_huge[:40], p_ref, what="preds, full-machine batch in three pieces")
+    gate(r_huge[:40], r_ref, what="recons, full-machine batch in three pieces")
+    gate(p_two[:40], p_ref, what="preds, full-machine batch, two groups per wave")
+    gate(r_two[:40], r_ref, what="recons, full-machine batch, two groups per wave")
+    tol = 2e-6 * max(1.0, r_huge.abs().max().item(), p_huge.abs().max().item())
+    assert (p_two - p_huge).abs().max().item() <= tol and (r_two - r_huge).abs().max().item() <= tol    # every window, the ragged last wave too
     gate(p_small, p_ref, what="preds, small batch")
     gate(r_small, r_ref, what="recons, small batch")
 
@@ -101,10 +131,28 @@ def _random_shapes(count, seed):
     return out
 
 
+# What the 9 000-window call of test_recurrence_kernel_bands_on_random_shapes runs on one lane, hand-written per shape (256 compute
+# units): the chunk-major kernel on every layer it fits (hidden sizes of 2 .. 5 tiles on a recorded range, a Linear inside of at most
+# 4 outputs).  With automatic lanes the same windows go as 8192 + 808 and never reach it.
+CM_ROUTES_9000 = [
+    "cm+tile:x3_lo | cm:fc",
+    "split:fp32:xp | cm:fc",
+    "split:fp32:xp | cm:fc",
+    "cm+tile:x3_lo | cm | cm",
+    "cm+tile:x3_lo | cm | cm",
+    "cm+tile:x3_hi | split:fp32",
+    "split:fp32:xp | cm | cm | split:fp32:fc",
+    "cm+tile:x3_lo | cm",
+    "cm+tile:x3_hi | cm | split:fp32",
+    "cm+tile:x3_lo | cm:fc",
+]
+
+
 @pytest.mark.parametrize("idx", list(range(10)))
 def test_recurrence_kernel_bands_on_random_shapes(idx, gpu_device):
     """Random model shapes through every band of the batch-size dispatch of the default arithmetic -- 3 000 windows
-    (hidden-tile split on split operands), 8 192 (its largest batch), 9 000 (chunk-major), also as stride-1 windows of a series
+    (hidden-tile split on split operands where it fits), 8 192 (its largest batch), 9 000 (two pieces, 8 192 + 808: the same kernel and
+    the small-batch ones) and 9 000 on one lane (one piece: chunk-major, CM_ROUTES_9000), also as stride-1 windows of a series
     (shared convolution rows) -- against precision = "fp32_strict" (fp32-MFMA kernels, themselves pinned to the oracle at
     small batches by the tests above): <= 2e-6 of the output scale, and the first windows against the oracle."""
     from mtad_gat import MTAD_GAT
@@ -116,18 +164,28 @@ def test_recurrence_kernel_bands_on_random_shapes(idx, gpu_device):
         model.temporal_gat.bias.normal_()
     W, F = kw["window_size"], kw["n_features"]
     series = torch.rand(W + 9000 - 1, F)
+    cus = device_compute_units(gpu_device)
     with torch.no_grad():
         x_head = torch.stack([series[i:i + W] for i in range(6)])
         p_ref, r_ref = oracle.forward(x_head, model.state_dict(), alpha=kw["alpha"])
         m = model.to(gpu_device)
         sd = series.to(gpu_device)
-        for n in (3000, 8192, 9000):
+        for n, lanes in ((3000, 0), (8192, 0), (9000, 0), (9000, 1)):
             x = torch.stack([sd[i:i + W] for i in range(n)])
             m.precision = "fp32_strict"
             ps, rs = m(x)
             m.precision = "fp32"
-            pd, rd = m(x)
-            pser, rser = m.forward_series(sd, start=0, stride=1, count=n)
+            eng = m._sync_engine(gpu_device)
+            eng.set_option("lanes", lanes)
+            try:
+                pieces, routes = call_routes(eng, n, cus)
+                pd, rd = m(x)
+                pser, rser = m.forward_series(sd, start=0, stride=1, count=n)
+            finally:
+                eng.set_option("lanes", 0)
+            assert pieces == ([8192, 808] if (n, lanes) == (9000, 0) else [n]), (kw, n, lanes, pieces)
+            if lanes:
+                assert routes == [CM_ROUTES_9000[idx]], (kw, routes)
             tol = 2e-6 * max(1.0, rs.abs().max().item(), ps.abs().max().item())
             assert (pd - ps).abs().max().item() <= tol and (rd - rs).abs().max().item() <= tol, (kw, n)
             assert torch.equal(pser, pd) and torch.equal(rser, rd), (kw, n)
