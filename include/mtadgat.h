@@ -597,7 +597,32 @@ int mtadgat_eval_first_hit(const float* score_dev, const unsigned char* label_de
  * mtadgat_eval_part_epsilon_scratch(n, count, nz).
  *
  * mtadgat_eval_part_flags: flags_dev[i] (uint8) = x_i > thr_dev[part(i)], thr_dev (count) float64 on the device, compared in
- * float64; NaN and equality are not flagged.  Asynchronous on `stream`. */
+ * float64; NaN and equality are not flagged.  Asynchronous on `stream`.
+ *
+ * mtadgat_eval_part_quantiles: np.percentile(a[start_k : end_k], 100 q, axis=0) ("linear") for every part k of a_dev, (n, d) float32
+ * with row stride ld >= d, d <= 2048, and the nq probabilities q_host (1 <= nq <= 8, each in [0, 1]; they travel in the kernel
+ * arguments: no copy, q_host is free on return).  out_dev is (nq, count, d) float32.  Per (part, column) the semantics are
+ * mtadgat_eval_column_quantiles' with the part's length: the two order statistics each probability needs are exact (a
+ * most-significant-digit radix select on the order bits, nothing is sorted), interpolated in float64 and rounded once; a (part,
+ * column) that holds a NaN gives NaN for every q and touches no other; an empty part gives NaN, a part of one row that row.
+ * Histogram bins are integer atomics (integer sums do not depend on their order), there are no float atomics: bitwise
+ * reproducible.  A part of at most mtadgat_eval_partq_long() rows is selected inside one workgroup, its bins never leaving LDS;
+ * a longer one runs the passes of mtadgat_eval_column_quantiles restricted to its rows, its bins in scratch slot
+ * floor(start / mtadgat_eval_partq_long()).  Scratch (16-byte aligned, need not be initialised) is
+ * (n / partq_long + 1) d 2 nq KiB of bins and select state (none for n <= partq_long) plus 8 nq + 4 bytes per (part, column).
+ * Asynchronous on `stream`.
+ *
+ * mtadgat_eval_part_scale: out[i, c] = (a[i, c] - median) / (1 + (q75 - q25)) with q_dev (3, count, d) float32 = q25, median, q75
+ * of the part that owns row i, as mtadgat_eval_part_quantiles writes them for q = 0.25, 0.5, 0.75.  float32, every operation
+ * rounded on its own.  A row that no span covers gives NaN.  out_dev (row stride ld_out >= d) may be a_dev itself (with
+ * ld_out = ld), and must not overlap it otherwise.  One launch, no scratch, asynchronous on `stream`. */
+size_t mtadgat_eval_part_quantiles_scratch(int64_t n, int d, int64_t count, int nq);
+int mtadgat_eval_part_quantiles(const float* a_dev, int64_t n, int d, int64_t ld, const int64_t* start_dev, const int64_t* end_dev,
+                                int64_t count, const double* q_host, int nq, void* scratch_dev, size_t scratch_bytes,
+                                float* out_dev /* (nq, count, d) */, void* stream);
+int mtadgat_eval_partq_long(void);
+int mtadgat_eval_part_scale(const float* a_dev, int64_t n, int d, int64_t ld, const int64_t* start_dev, const int64_t* end_dev,
+                            int64_t count, const float* q_dev /* (3, count, d) */, float* out_dev, int64_t ld_out, void* stream);
 size_t mtadgat_eval_part_adjust_scratch(int64_t n, int d, int64_t count);
 int mtadgat_eval_part_adjust(const float* x_dev, int64_t n, int d, int64_t ld, const int64_t* start_dev, const int64_t* end_dev,
                              int64_t count, const int64_t* seam_dev, int64_t n_seams, int64_t before, int64_t after, int normalize,

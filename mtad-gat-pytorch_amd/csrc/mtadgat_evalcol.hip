@@ -7,6 +7,12 @@
 //       order-preserving 32-bit key of the float, all columns and all 2 nq ranks per pass.  Histograms are built with integer
 //       atomics in LDS and merged with integer atomics in memory -- integer sums do not depend on their order, so two runs give
 //       the same bits -- and the digit of every (column, rank) is chosen on the device between the passes.  Nothing is sorted.
+//   k_partq_* and the segmented instantiations of k_eval_colq_hist / _pick: the same select for every (part, column) of a
+//       concatenated series (mtadgat_eval_part_quantiles), by two routes chosen per part on the device.  A part of at most PARTQ_LONG
+//       rows is selected inside one workgroup, bins, prefixes and ranks in LDS (k_partq_short).  A longer part runs the four passes
+//       with bins in memory, its rows cut into chunks of PARTQ_LONG, one workgroup per (chunk, column tile); its bins are slot
+//       floor(start / PARTQ_LONG) -- long parts are disjoint and longer than PARTQ_LONG, so no two share a slot, and the slots
+//       number n / PARTQ_LONG + 1 whatever the number of parts.
 //   k_ewm_chunk / _carry / _apply: pandas' ewm(span).mean() (adjust=True) as a blocked scan in float64: chunk-local scans, one wave
 //       that composes the chunk carries in chunk order, and a pass that applies carry and closed-form denominator.  No atomics.
 //       One template, instantiated for the whole array (mtadgat_eval_ewm) and restarted at every span of a concatenated series
@@ -71,12 +77,15 @@ __global__ void k_eval_colq_init_rank(unsigned rank, int d, unsigned* __restrict
     }
 }
 
-// One radix pass: for every (column, rank) the histogram of digit (key >> shift) & 255 over the keys whose higher digits equal
-// the rank's prefix.  grid = (column tiles, row slices, rank groups); the rows are walked grid-stride.
-__global__ void __launch_bounds__(256) k_eval_colq_hist(const float* __restrict__ a, long n, int d, long ld, int R, int shift,
-                                                         const unsigned* __restrict__ state, unsigned* __restrict__ hist,
-                                                         unsigned* __restrict__ nanflag) {
-    __shared__ unsigned h[CQ_RT * CQ_CT * 256];
+constexpr int PARTQ_LONG = 16 * SPAN_RB;     // a part longer than this many rows takes the route with bins in memory
+
+// One radix pass over the rows first, first + step, .. below `last` of the workgroup's CQ_CT columns: for every (column, rank) the
+// histogram of digit (key >> shift) & 255 over the keys whose higher digits equal the rank's prefix, built in `h` and merged into
+// `hist`.  state / hist start at the cell of (column 0, rank 0), nanflag at column 0.  Every thread of the workgroup calls it
+// (barriers inside; one more before `h` is used again).
+__device__ __forceinline__ void colq_hist_rows(const float* __restrict__ a, int d, long ld, int R, int shift, long first, long last, long step,
+                                               const unsigned* __restrict__ state, unsigned* __restrict__ hist,
+                                               unsigned* __restrict__ nanflag, unsigned* h) {
     const int tid = threadIdx.x;
     const int c = tid & (CQ_CT - 1);
     const int col = blockIdx.x * CQ_CT + c;
@@ -90,7 +99,7 @@ __global__ void __launch_bounds__(256) k_eval_colq_hist(const float* __restrict_
     __syncthreads();
     if (col < d) {
         bool seen_nan = false;
-        for (long row = (long)blockIdx.y * CQ_ROWS + (tid >> 3); row < n; row += (long)gridDim.y * CQ_ROWS) {
+        for (long row = first; row < last; row += step) {
             const float v = a[row * ld + col];
             seen_nan = seen_nan || (v != v);
             const unsigned key = colq_key(v);
@@ -109,28 +118,207 @@ __global__ void __launch_bounds__(256) k_eval_colq_hist(const float* __restrict_
     }
 }
 
-// One wave per (column, rank): the digit whose bin holds the rank, appended to the prefix; the bins are cleared for the next pass.
-// After the last digit the prefix is the key of the order statistic.
-__global__ void __launch_bounds__(64) k_eval_colq_pick(unsigned* __restrict__ state, unsigned* __restrict__ hist, int shift,
-                                                        float* __restrict__ ord) {
-    const long idx = blockIdx.x;
-    const int lane = threadIdx.x;
-    uint4* bins = reinterpret_cast<uint4*>(hist + idx * 256) + lane;
-    const uint4 b = *bins;
-    *bins = make_uint4(0u, 0u, 0u, 0u);
+// One pass, instantiated twice.  !SEG: the whole column, grid = (column tiles, row slices, rank groups), the rows walked grid-stride;
+// no span array is read.  SEG: grid = (column tiles, chunks of PARTQ_LONG rows, rank groups); a chunk meets at most two long parts --
+// the one that covers its first row and the one that starts inside it, which is the owner of slot `chunk` -- and adds its rows of
+// each to that part's bins.  Chunks that meet no long part leave at once.
+template <bool SEG>
+__global__ void __launch_bounds__(256) k_eval_colq_hist(const float* __restrict__ a, long n, int d, long ld, int R, int shift,
+                                                         const unsigned* __restrict__ state, unsigned* __restrict__ hist,
+                                                         unsigned* __restrict__ nanflag, const long* __restrict__ start,
+                                                         const long* __restrict__ end, long count, const int* __restrict__ slotmap) {
+    __shared__ unsigned h[CQ_RT * CQ_CT * 256];
+    const long sub = threadIdx.x >> 3;                    // CQ_ROWS rows at a time
+    if constexpr (!SEG) {
+        colq_hist_rows(a, d, ld, R, shift, (long)blockIdx.y * CQ_ROWS + sub, n, (long)gridDim.y * CQ_ROWS, state, hist, nanflag, h);
+    } else {
+        const long cells = (long)d * R;
+        for (long b = blockIdx.y; b <= n / PARTQ_LONG; b += gridDim.y) {
+            const long c0 = b * PARTQ_LONG, c1 = c0 + PARTQ_LONG;
+            for (int which = 0; which < 2; ++which) {
+                long p = -1, s = 0, e = 0;
+                if (which == 0) {
+                    if (c0 < n) p = span_find(start, end, count, c0, s);
+                } else {
+                    p = slotmap[b];
+                }
+                if (p < 0) continue;
+                span_bounds(start, end, p, n, s, e);
+                if (e - s <= PARTQ_LONG || (which == 1 && s == c0)) continue;      // short; or met as the part that covers c0
+                const long slot = s / PARTQ_LONG;
+                const long lo = s > c0 ? s : c0, hi = e < c1 ? e : c1;
+                colq_hist_rows(a, d, ld, R, shift, lo + sub, hi, (long)CQ_ROWS, state + 2 * slot * cells, hist + slot * cells * 256,
+                               nanflag + p * d, h);
+                __syncthreads();
+            }
+        }
+    }
+}
+
+// One wave on the 256 bins at `bins` that hold more than state[1] keys in all: the digit whose bin holds that rank is appended to the
+// prefix state[0], the rank made relative to the bin.  Lane l brings the bins 4 l .. 4 l + 3.  True in the one lane that chose, with
+// the new prefix in *key.
+__device__ __forceinline__ bool colq_pick_digit(const uint4 b, unsigned prefix, unsigned k, int shift, unsigned* key, unsigned* rest) {
+    const int lane = threadIdx.x & 63;
     const unsigned mine = b.x + b.y + b.z + b.w;
     const unsigned incl = wave_inclusive_sum(mine);
-    const unsigned k = state[2 * idx + 1];
     unsigned below = incl - mine;
-    if (below <= k && k < incl) {                       // exactly one lane: the bins hold more than k keys in all
-        unsigned digit = 4u * lane;
-        if (k >= below + b.x) { below += b.x; ++digit;
-            if (k >= below + b.y) { below += b.y; ++digit;
-                if (k >= below + b.z) { below += b.z; ++digit; } } }
-        const unsigned key = state[2 * idx] | (digit << shift);
-        state[2 * idx] = key;
-        state[2 * idx + 1] = k - below;
-        if (shift == 0) ord[idx] = colq_value(key);
+    if (!(below <= k && k < incl)) return false;
+    unsigned digit = 4u * lane;
+    if (k >= below + b.x) { below += b.x; ++digit;
+        if (k >= below + b.y) { below += b.y; ++digit;
+            if (k >= below + b.z) { below += b.z; ++digit; } } }
+    *key = prefix | (digit << shift);
+    *rest = k - below;
+    return true;
+}
+
+// One wave per (column, rank): the digit whose bin holds the rank, appended to the prefix; the bins are cleared for the next pass.
+// After the last digit the prefix is the key of the order statistic.  SEG: grid = (column x rank, slots); the cells of a slot that
+// a long part owns, the order statistic written to that part's place; a free slot is skipped.
+template <bool SEG>
+__global__ void __launch_bounds__(64) k_eval_colq_pick(unsigned* __restrict__ state, unsigned* __restrict__ hist, int shift,
+                                                        float* __restrict__ ord, long cells, long nslots, const int* __restrict__ slotmap) {
+    const int lane = threadIdx.x;
+    for (long b = SEG ? blockIdx.y : 0; b < (SEG ? nslots : 1); b += SEG ? gridDim.y : 1) {
+        long idx = blockIdx.x, at = blockIdx.x;
+        if constexpr (SEG) {
+            const long p = slotmap[b];
+            if (p < 0) continue;
+            idx = b * cells + blockIdx.x;
+            at = p * cells + blockIdx.x;
+        }
+        uint4* bins = reinterpret_cast<uint4*>(hist + idx * 256) + lane;
+        const uint4 bv = *bins;
+        *bins = make_uint4(0u, 0u, 0u, 0u);
+        unsigned key, rest;
+        if (colq_pick_digit(bv, state[2 * idx], state[2 * idx + 1], shift, &key, &rest)) {      // exactly one lane
+            state[2 * idx] = key;
+            state[2 * idx + 1] = rest;
+            if (shift == 0) ord[at] = colq_value(key);
+        }
+    }
+}
+
+// ---- quantiles per part ----------------------------------------------------------------------------------------------------------
+// ord[((part * d + col) * nq + qi) * 2] = { s[lo], s[hi] } of the part's slice of the column, nanflag[part * d + col] as for a column.
+__global__ void k_partq_free(int* __restrict__ slotmap, long nslots) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nslots; i += (long)gridDim.x * blockDim.x) slotmap[i] = -1;
+}
+
+// The workgroup that meets a long part writes it into its slot, clears the slot's bins and the part's NaN flags and sets the ranks to
+// find; the parts are walked grid-stride.
+__global__ void __launch_bounds__(256) k_partq_slots(long n, int d, const long* __restrict__ start, const long* __restrict__ end, long count,
+                                                      ColqProbs pv, int nq, int* __restrict__ slotmap, unsigned* __restrict__ state,
+                                                      unsigned* __restrict__ hist, unsigned* __restrict__ nanflag) {
+    const int tid = threadIdx.x, R = 2 * nq;
+    const long cells = (long)d * R;
+    for (long k = blockIdx.x; k < count; k += gridDim.x) {
+        long s, e;
+        span_bounds(start, end, k, n, s, e);
+        const long len = e - s;
+        if (len <= PARTQ_LONG) continue;
+        const long slot = s / PARTQ_LONG;
+        if (tid == 0) slotmap[slot] = (int)k;
+        uint4* bins = reinterpret_cast<uint4*>(hist + slot * cells * 256);
+        for (long i = tid; i < cells * 64; i += 256) bins[i] = make_uint4(0u, 0u, 0u, 0u);
+        for (long i = tid; i < cells; i += 256) {
+            const int r = (int)(i % R);
+            const unsigned lo = colq_rank(pv.v[r >> 1], len, nullptr);
+            const unsigned hi = (long)lo + 1 < len ? lo + 1 : (unsigned)(len - 1);
+            state[2 * (slot * cells + i)] = 0u;
+            state[2 * (slot * cells + i) + 1] = (r & 1) ? hi : lo;
+        }
+        for (int c = tid; c < d; c += 256) nanflag[k * d + c] = 0u;
+    }
+}
+
+// grid = (part, column tile): the whole select of a part of 1 .. PARTQ_LONG rows for ct columns (a power of two <= CQ_CT, chosen from
+// d: at d = 1 all 256 threads walk rows) and CQ_RT ranks at a time.  Four digit passes over the part's rows -- the first from memory,
+// the rest from L2 -- with the bins in LDS; between them one wave per (column, rank) picks the digit.  A bin of column c sits at
+// bin ^ 4 c of its histogram: the ct columns of a row that share a digit, as the leading digits of scores do, fall into ct
+// different banks, and the four bins a lane picks from stay one 16-byte word.  Nothing of the histogram reaches memory.
+__global__ void __launch_bounds__(256) k_partq_short(const float* __restrict__ a, long n, int d, long ld, const long* __restrict__ start,
+                                                      const long* __restrict__ end, ColqProbs pv, int nq, int ct, float* __restrict__ ord,
+                                                      unsigned* __restrict__ nanflag) {
+    __shared__ __attribute__((aligned(16))) unsigned h[CQ_RT * CQ_CT * 256];
+    __shared__ unsigned spfx[CQ_RT * CQ_CT], srank[CQ_RT * CQ_CT], snan[CQ_CT];
+    const long k = blockIdx.x;
+    long s, e;
+    span_bounds(start, end, k, n, s, e);
+    const long len = e - s;
+    if (len < 1 || len > PARTQ_LONG) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int c = tid & (ct - 1), rsub = tid / ct, rp = 256 / ct;
+    const int col0 = blockIdx.y * ct, col = col0 + c;
+    const int R = 2 * nq;
+    if (tid < CQ_CT) snan[tid] = 0u;
+    for (int r0 = 0; r0 < R; r0 += CQ_RT) {
+        const int nr = R - r0 < CQ_RT ? R - r0 : CQ_RT;
+        for (int i = tid; i < nr * ct; i += 256) {
+            const int r = r0 + i / ct;
+            const unsigned lo = colq_rank(pv.v[r >> 1], len, nullptr);
+            const unsigned hi = (long)lo + 1 < len ? lo + 1 : (unsigned)(len - 1);
+            spfx[i] = 0u;
+            srank[i] = (r & 1) ? hi : lo;
+        }
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            for (int i = tid; i < nr * ct * 256; i += 256) h[i] = 0u;
+            __syncthreads();
+            const unsigned high = shift == 24 ? 0u : (0xffffffffu << (shift + 8));
+            unsigned pfx[CQ_RT];
+#pragma unroll
+            for (int r = 0; r < CQ_RT; ++r) pfx[r] = r < nr ? spfx[r * ct + c] : 0u;
+            if (col < d) {
+                bool seen_nan = false;
+                for (long row = rsub; row < len; row += rp) {
+                    const float v = a[(s + row) * ld + col];
+                    seen_nan = seen_nan || (v != v);
+                    const unsigned key = colq_key(v);
+                    const unsigned bin = ((key >> shift) & 255u) ^ (unsigned)(c << 2);
+#pragma unroll
+                    for (int r = 0; r < CQ_RT; ++r)
+                        if (r < nr && ((key ^ pfx[r]) & high) == 0u) atomicAdd(&h[(r * ct + c) * 256 + bin], 1u);
+                }
+                if (seen_nan && shift == 24 && r0 == 0) atomicOr(&snan[c], 1u);
+            }
+            __syncthreads();
+            for (int pair = wave; pair < nr * ct; pair += 4) {
+                const uint4 bv = reinterpret_cast<const uint4*>(h + pair * 256)[lane ^ (pair & (ct - 1))];
+                unsigned key, rest;
+                if (colq_pick_digit(bv, spfx[pair], srank[pair], shift, &key, &rest)) {
+                    spfx[pair] = key;
+                    srank[pair] = rest;
+                }
+            }
+            __syncthreads();
+        }
+        for (int i = tid; i < nr * ct; i += 256) {
+            const int cc = col0 + (i & (ct - 1));
+            if (cc < d) ord[(k * d + cc) * R + r0 + i / ct] = colq_value(spfx[i]);
+        }
+        __syncthreads();
+    }
+    if (tid < ct && col < d) nanflag[k * d + col] = snan[tid];
+}
+
+// out[qi][part][col], interpolated as for a column with the part's length; NaN for an empty part (whose ord was never written)
+__global__ void k_partq_interp(const float* __restrict__ ord, ColqProbs pv, const unsigned* __restrict__ nanflag, long n, int d, int nq,
+                               const long* __restrict__ start, const long* __restrict__ end, long count, float* __restrict__ out) {
+    const long per_q = count * d, total = per_q * nq;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int qi = (int)(i / per_q);
+        const long cell = i - qi * per_q;               // part * d + col
+        long s, e;
+        span_bounds(start, end, cell / d, n, s, e);
+        float r = __builtin_nanf("");
+        if (e > s && !nanflag[cell]) {
+            double frac;
+            colq_rank(pv.v[qi], e - s, &frac);
+            const double lo = ord[(cell * nq + qi) * 2], hi = ord[(cell * nq + qi) * 2 + 1];
+            r = (float)(lo + (hi - lo) * frac);
+        }
+        out[i] = r;
     }
 }
 
@@ -316,10 +504,29 @@ void colq_passes(const float* a_dev, long n, int d, long ld, int R, unsigned* st
     const long cap = 1024 / ((long)tiles * groups) > 0 ? 1024 / ((long)tiles * groups) : 1;
     if (slices > cap) slices = cap;
     for (int shift = 24; shift >= 0; shift -= 8) {
-        hipLaunchKernelGGL(k_eval_colq_hist, dim3(tiles, (unsigned)slices, groups), dim3(256), 0, s, a_dev, (long)n, d, (long)ld, R, shift,
-                           state, hist, nanflag);
-        hipLaunchKernelGGL(k_eval_colq_pick, dim3((unsigned)cells), dim3(64), 0, s, state, hist, shift, ord);
+        hipLaunchKernelGGL(k_eval_colq_hist<false>, dim3(tiles, (unsigned)slices, groups), dim3(256), 0, s, a_dev, (long)n, d, (long)ld, R, shift,
+                           (const unsigned*)state, hist, nanflag, (const long*)nullptr, (const long*)nullptr, 0L, (const int*)nullptr);
+        hipLaunchKernelGGL(k_eval_colq_pick<false>, dim3((unsigned)cells), dim3(64), 0, s, state, hist, shift, ord, cells, 1L, (const int*)nullptr);
     }
+}
+
+// per part: the order statistics and the NaN flags; per slot of the long route: the owner, the select's state and the bins
+struct PartqScratch {
+    unsigned *hist, *state, *nanflag;
+    float* ord;
+    int* slotmap;
+    long nslots;
+};
+PartqScratch partq_scratch(ScratchCarver& c, int64_t n, int64_t d, int64_t count, int64_t nq) {
+    const size_t cells = (size_t)d * 2 * (size_t)nq;
+    PartqScratch l;
+    l.nslots = n > PARTQ_LONG ? (long)(n / PARTQ_LONG + 1) : 0;     // no part of n <= PARTQ_LONG rows is long
+    l.hist = c.take<unsigned>((size_t)l.nslots * cells * 256, 16);
+    l.state = c.take<unsigned>((size_t)l.nslots * cells * 2, 4);
+    l.slotmap = c.take<int>((size_t)l.nslots, 4);
+    l.nanflag = c.take<unsigned>((size_t)count * (size_t)d, 4);
+    l.ord = c.take<float>((size_t)count * cells, 4);
+    return l;
 }
 
 constexpr int64_t N_MAX = 2147483647LL;
@@ -410,6 +617,58 @@ int mtadgat_eval_column_quantiles(const float* a_dev, int64_t n, int d, int64_t 
     hipLaunchKernelGGL(k_eval_colq_interp, dim3((unsigned)((outs + 255) / 256)), dim3(256), 0, s, (const float*)l.ord, (const double*)l.q,
                        (const unsigned*)l.nanflag, (long)n, d, nq, out_dev);
     return hipGetLastError() == hipSuccess ? 0 : record_error(-3, "column_quantiles: kernel launch failed");
+}
+
+int mtadgat_eval_partq_long(void) { return PARTQ_LONG; }
+
+size_t mtadgat_eval_part_quantiles_scratch(int64_t n, int d, int64_t count, int nq) {
+    if (n < 1 || n > N_MAX || count < 1 || count > N_MAX || d < 1 || d > 2048 || nq < 1 || nq > CQ_INLINE) return 0;
+    return scratch_bytes_of([&](ScratchCarver& c) { partq_scratch(c, n, d, count, nq); });
+}
+
+int mtadgat_eval_part_quantiles(const float* a_dev, int64_t n, int d, int64_t ld, const int64_t* start_dev, const int64_t* end_dev, int64_t count,
+                                const double* q_host, int nq, void* scratch_dev, size_t scratch_bytes, float* out_dev, void* stream) {
+    if (!a_dev || !start_dev || !end_dev || !q_host || !scratch_dev || !out_dev) return record_error(-1, "part_quantiles: null pointer");
+    if (n < 1 || n > N_MAX) return record_error(-1, "part_quantiles: n must lie in [1, 2^31 - 1]");
+    if (count < 1 || count > N_MAX) return record_error(-1, "part_quantiles: count must lie in [1, 2^31 - 1]");
+    if (d < 1 || d > 2048) return record_error(-1, "part_quantiles: d must lie in [1, 2048]");
+    if (ld < d) return record_error(-1, "part_quantiles: ld < d");
+    if (nq < 1 || nq > CQ_INLINE) return record_error(-1, "part_quantiles: nq must lie in [1, 8]");
+    ColqProbs pv = {};
+    for (int i = 0; i < nq; ++i) {
+        if (!(q_host[i] >= 0.0 && q_host[i] <= 1.0)) return record_error(-1, "part_quantiles: q outside [0, 1]");
+        pv.v[i] = q_host[i];
+    }
+    ScratchCarver carver(scratch_dev);
+    const PartqScratch l = partq_scratch(carver, n, d, count, nq);
+    if (scratch_bytes < carver.bytes()) return record_error(-5, "part_quantiles: scratch too small (see mtadgat_eval_part_quantiles_scratch)");
+    if ((uintptr_t)scratch_dev & 15) return record_error(-5, "part_quantiles: scratch must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const long *st = reinterpret_cast<const long*>(start_dev), *en = reinterpret_cast<const long*>(end_dev);
+    const int R = 2 * nq;
+    const long cells = (long)d * R;
+    int ct = 1;
+    while (ct < d && ct < CQ_CT) ct <<= 1;
+    hipLaunchKernelGGL(k_partq_short, dim3((unsigned)count, (unsigned)((d + ct - 1) / ct)), dim3(256), 0, s, a_dev, (long)n, d, (long)ld, st, en, pv,
+                       nq, ct, l.ord, l.nanflag);
+    if (l.nslots > 0) {
+        const unsigned ys = (unsigned)(l.nslots < 65535 ? l.nslots : 65535);
+        const int tiles = (d + CQ_CT - 1) / CQ_CT, groups = (R + CQ_RT - 1) / CQ_RT;
+        hipLaunchKernelGGL(k_partq_free, dim3((unsigned)((l.nslots + 255) / 256)), dim3(256), 0, s, l.slotmap, l.nslots);
+        hipLaunchKernelGGL(k_partq_slots, dim3((unsigned)(count < 4096 ? count : 4096)), dim3(256), 0, s, (long)n, d, st, en, (long)count, pv, nq,
+                           l.slotmap, l.state, l.hist, l.nanflag);
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            hipLaunchKernelGGL(k_eval_colq_hist<true>, dim3(tiles, ys, groups), dim3(256), 0, s, a_dev, (long)n, d, (long)ld, R, shift,
+                               (const unsigned*)l.state, l.hist, l.nanflag, st, en, (long)count, (const int*)l.slotmap);
+            hipLaunchKernelGGL(k_eval_colq_pick<true>, dim3((unsigned)cells, ys), dim3(64), 0, s, l.state, l.hist, shift, l.ord, cells, l.nslots,
+                               (const int*)l.slotmap);
+        }
+    }
+    const long outs = (long)nq * count * d;
+    const long blocks = (outs + 255) / 256;
+    hipLaunchKernelGGL(k_partq_interp, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, s, (const float*)l.ord, pv,
+                       (const unsigned*)l.nanflag, (long)n, d, nq, st, en, (long)count, out_dev);
+    return hipGetLastError() == hipSuccess ? 0 : record_error(-3, "part_quantiles: kernel launch failed");
 }
 
 size_t mtadgat_eval_ewm_scratch(int64_t n) {

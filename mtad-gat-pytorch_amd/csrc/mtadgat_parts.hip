@@ -13,6 +13,8 @@
 //   k_part_epsilon / k_part_epsilon_final                 find_epsilon's z table per part, the +-halo dilation clipped to the span:
 //                                                         epsilon_tile (mtadgat_scan.h), which k_eval_epsilon runs over a whole column
 //   k_part_flags                                          score_i > eps[part(i)]
+//   k_part_scale                                          (a - median) / (1 + IQR) with the quantiles of the row's part, which
+//                                                         mtadgat_eval_part_quantiles (mtadgat_evalcol.hip) selects
 #include "mtadgat_scan.h"
 
 namespace mtadgat {
@@ -264,6 +266,37 @@ __global__ void __launch_bounds__(256) k_part_flags(const float* __restrict__ x,
     }
 }
 
+// ---- scale ---------------------------------------------------------------------------------------------------------------------------
+// out = (a - median) / (1 + (q75 - q25)) with the quantiles q[(j * count + part) * d + col] (j = 0, 1, 2: q25, median, q75) of the
+// row's part, in float32 with every operation rounded on its own; NaN for a row outside every span.  out may be a.
+__global__ void __launch_bounds__(256) k_part_scale(const float* a, long n, int d, long ld, const long* __restrict__ start,
+                                                     const long* __restrict__ end, long count, const float* __restrict__ q, float* out,
+                                                     long ld_out) {
+    __shared__ int owner[256];                          // the part of each of the block's rows: one search per row, not per element
+    const int tid = threadIdx.x;
+    const long per_q = count * d;
+    for (long r0 = (long)blockIdx.x * 256; r0 < n; r0 += (long)gridDim.x * 256) {
+        const int rows = n - r0 < 256 ? (int)(n - r0) : 256;
+        if (tid < rows) {
+            long s;
+            owner[tid] = (int)span_find(start, end, count, r0 + tid, s);
+        }
+        __syncthreads();
+        for (int j = tid; j < rows * d; j += 256) {
+            const int r = j / d, col = j - r * d;
+            const long p = owner[r];
+            float v = __builtin_nanf("");
+            if (p >= 0) {
+                const float* qc = q + p * d + col;
+                const float iqr = __fsub_rn(qc[2 * per_q], qc[0]);
+                v = __fdiv_rn(__fsub_rn(a[(r0 + r) * ld + col], qc[per_q]), __fadd_rn(1.f, iqr));
+            }
+            out[(r0 + r) * ld_out + col] = v;
+        }
+        __syncthreads();
+    }
+}
+
 }  // namespace mtadgat
 
 using namespace mtadgat;
@@ -419,6 +452,19 @@ int mtadgat_eval_part_flags(const float* x_dev, int64_t n, const int64_t* start_
     hipLaunchKernelGGL(k_part_flags, dim3(capped_grid((long)n)), dim3(256), 0, (hipStream_t)stream, x_dev, (long)n,
                        reinterpret_cast<const long*>(start_dev), reinterpret_cast<const long*>(end_dev), (long)count, thr_dev, flags_dev);
     return hipGetLastError() == hipSuccess ? 0 : record_error(-3, "part_flags: kernel launch failed");
+}
+
+int mtadgat_eval_part_scale(const float* a_dev, int64_t n, int d, int64_t ld, const int64_t* start_dev, const int64_t* end_dev, int64_t count,
+                            const float* q_dev, float* out_dev, int64_t ld_out, void* stream) {
+    if (!a_dev || !start_dev || !end_dev || !q_dev || !out_dev) return record_error(-1, "part_scale: null pointer");
+    if (n < 1 || n > N_MAX) return record_error(-1, "part_scale: n must lie in [1, 2^31 - 1]");
+    if (count < 1 || count > N_MAX) return record_error(-1, "part_scale: count must lie in [1, 2^31 - 1]");
+    if (d < 1 || d > 2048) return record_error(-1, "part_scale: d must lie in [1, 2048]");
+    if (ld < d || ld_out < d) return record_error(-1, "part_scale: ld < d");
+    hipLaunchKernelGGL(k_part_scale, dim3(capped_grid((long)n)), dim3(256), 0, (hipStream_t)stream, a_dev, (long)n, d, (long)ld,
+                       reinterpret_cast<const long*>(start_dev), reinterpret_cast<const long*>(end_dev), (long)count, q_dev, out_dev,
+                       (long)ld_out);
+    return hipGetLastError() == hipSuccess ? 0 : record_error(-3, "part_scale: kernel launch failed");
 }
 
 }  // extern "C"

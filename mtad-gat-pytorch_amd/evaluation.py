@@ -46,7 +46,12 @@ tests/test_gpu_parts.py; tests/part_refs.py is the specification; the reference'
   moving_average(parts=)            the exponentially weighted mean restarted at every part: a segmented float64 scan
   find_epsilon_parts /              find_epsilon of every part's slice in two launches and two small copies whatever the number
   part_predictions                  of parts, and scores > the threshold of their own part
-  predict_anomalies(parts=)         the above inside the one-call pipeline, with one global or one threshold per part
+  part_quantiles /                  np.percentile of every (part, column) from one segmented exact radix select: short parts wholly
+  scale_scores(parts=)              inside one workgroup, long ones through the column select's passes restricted to their rows; then
+                                    (a - median) / (1 + IQR) with every row's own part's quantiles (tests/test_gpu_part_scale.py;
+                                    tests/part_scale_refs.py is the specification)
+  predict_anomalies(parts=)         the above inside the one-call pipeline, with one global or one threshold per part, and with
+                                    scale_scores="per_part" the per-dimension scores scaled part by part
 The fit follows the paper, not the reference's vendored spot.py (its optimiser-based root search cannot be reproduced bit for
 bit): tests/spot_refs.py is the specification, csrc/mtadgat_spot.h spells it out.
 """
@@ -120,6 +125,12 @@ def _lib():
         lib.mtadgat_eval_part_epsilon_moments.argtypes = [vp, i64, vp, vp, i64, ci, vp, sz, _c_double_p, vp]
         lib.mtadgat_eval_part_epsilon_table.argtypes = [vp, i64, vp, vp, i64, _c_double_p, ci, ci, vp, sz, _c_double_p, vp]
         lib.mtadgat_eval_part_flags.argtypes = [vp, i64, vp, vp, i64, vp, vp, vp]
+        lib.mtadgat_eval_part_quantiles_scratch.argtypes = [i64, ci, i64, ci]
+        lib.mtadgat_eval_part_quantiles_scratch.restype = sz
+        lib.mtadgat_eval_part_quantiles.argtypes = [vp, i64, ci, i64, vp, vp, i64, _c_double_p, ci, vp, sz, vp, vp]
+        lib.mtadgat_eval_partq_long.argtypes = []
+        lib.mtadgat_eval_partq_long.restype = ci
+        lib.mtadgat_eval_part_scale.argtypes = [vp, i64, ci, i64, vp, vp, i64, vp, vp, i64, vp]
         lib.mtadgat_last_error.restype = ctypes.c_char_p
         lib._eval_bound = True
     return lib
@@ -318,10 +329,51 @@ def column_quantiles(a, qs):
     return out
 
 
-def scale_scores(per_dim):
-    """(a - median) / (1 + IQR) per column (prediction.py:84-88), quantiles from column_quantiles."""
-    q = column_quantiles(per_dim, [0.25, 0.5, 0.75])
-    return (per_dim - q[1]) / (1.0 + (q[2] - q[0]))
+def part_quantiles(a, qs, parts):
+    """np.percentile(a[start[p]:end[p]], 100 * qs, axis=0) for every part p of an (n,) or (n, d) float32 GPU tensor (parts: a
+    ScoreParts with parts.n == n), (len(qs), P, d) float32 on the device.  Per (part, column) as column_quantiles: exact order
+    statistics, interpolated in float64 and rounded once; a NaN makes its own (part, column) NaN and no other; an empty part gives
+    NaN, a part of one row that row.  At most 8 probabilities.  A column slice of a wider tensor is read in place.  The number of
+    launches does not depend on P; asynchronous, bitwise reproducible."""
+    lib = _lib()
+    a = _dev2d(a, "a")
+    n, d = a.shape
+    start, end, _ = _parts_on(parts, a, n)
+    q = np.ascontiguousarray(np.asarray(qs, dtype=np.float64).reshape(-1))
+    if q.size < 1 or q.size > 8 or not np.all((q >= 0.0) & (q <= 1.0)):
+        raise ValueError(f"1 to 8 quantile probabilities in [0, 1] are needed, got {qs!r}")
+    P = parts.n_parts
+    scratch = _scratch(lib.mtadgat_eval_part_quantiles_scratch(n, d, P, q.size), a.device)
+    out = _native._empty((q.size, P, d), dtype=torch.float32, device=a.device)
+    with torch.cuda.device(a.device):
+        rc = lib.mtadgat_eval_part_quantiles(a.data_ptr(), n, d, a.stride(0), start.data_ptr(), end.data_ptr(), P, q.ctypes.data_as(_c_double_p),
+                                             q.size, scratch.data_ptr(), scratch.numel() * 8, out.data_ptr(), _stream(a))
+    if rc != 0:
+        _fail(lib, rc, "eval_part_quantiles")
+    return out
+
+
+def scale_scores(per_dim, parts=None):
+    """(a - median) / (1 + IQR) per column (prediction.py:84-88), quantiles from column_quantiles.
+    With parts (a ScoreParts with parts.n == len(per_dim)) every part's rows are scaled by the part's own median and IQR
+    (part_quantiles), in float32 with every operation rounded on its own: one noisy part no longer sets the scale of the others.
+    Returns a new float32 tensor of the input's shape."""
+    if parts is None:
+        q = column_quantiles(per_dim, [0.25, 0.5, 0.75])
+        return (per_dim - q[1]) / (1.0 + (q[2] - q[0]))
+    lib = _lib()
+    one_d = isinstance(per_dim, torch.Tensor) and per_dim.ndim == 1
+    a = _dev2d(per_dim, "per_dim")
+    n, d = a.shape
+    start, end, _ = _parts_on(parts, a, n)
+    q = part_quantiles(a, [0.25, 0.5, 0.75], parts)
+    out = _native._empty((n, d), dtype=torch.float32, device=a.device)
+    with torch.cuda.device(a.device):
+        rc = lib.mtadgat_eval_part_scale(a.data_ptr(), n, d, a.stride(0), start.data_ptr(), end.data_ptr(), parts.n_parts, q.data_ptr(),
+                                         out.data_ptr(), d, _stream(a))
+    if rc != 0:
+        _fail(lib, rc, "eval_part_scale")
+    return out.reshape(-1) if one_d else out
 
 
 def moving_average(scores, span, parts=None):
@@ -737,7 +789,9 @@ def predict_anomalies(model, train, test, labels=None, target_dims=None, gamma=1
     adjust_anomaly_scores (utils.py:210-255): train_lengths / test_lengths are the parts' row counts (left out: one part),
     transition and normalize as in score_parts and adjust_part_scores.  Train and test scores then come from
     model.anomaly_scores(..., parts=): smoothed per part when use_mov_av, blanked around the seams, min-max normalised per part;
-    the per-dimension scores are as without parts.  thresholds="global" (the default) leaves everything else as it is, now on
+    the per-dimension scores are as without parts, unless scale_scores="per_part": then every series' per-dimension scores are
+    scaled by the median and IQR of its own parts (scale_scores(parts=)) instead of the whole series' (scale_scores=True keeps
+    meaning that); "per_part" without parts raises ValueError.  thresholds="global" (the default) leaves everything else as it is, now on
     the adjusted scores; "per_part" adds part_result, a dict of
       thresholds   find_epsilon_parts of the train scores -- of the test scores when train and test differ in their number of parts
       preds        part_predictions(test_scores, ...): (n,) uint8 on the device
@@ -748,6 +802,10 @@ def predict_anomalies(model, train, test, labels=None, target_dims=None, gamma=1
     (events=) may still merge across a seam; with both sides blanked that takes merge_gap >= before + after.
     Without parts every returned value is what it was before parts existed."""
     part_opts = None
+    if isinstance(scale_scores, str) and scale_scores != "per_part":
+        raise ValueError(f"scale_scores must be False, True or 'per_part', got {scale_scores!r}")
+    if isinstance(scale_scores, str) and parts is None:
+        raise ValueError("scale_scores='per_part' needs parts=")
     if parts is not None:
         unknown = set(parts) - {"train_lengths", "test_lengths", "transition", "normalize", "thresholds"}
         if unknown:

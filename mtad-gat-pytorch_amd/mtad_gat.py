@@ -537,9 +537,17 @@ class MTAD_GAT(nn.Module):
         concatenation of independent parts, the reference's adjust_anomaly_scores (utils.py:210-255): the global score is
         smoothed part by part when `use_mov_av` (evaluation.moving_average(parts=)), then the scores around every seam are
         set to 0 and, with `normalize_parts`, every part is min-max normalised on its own (evaluation.adjust_part_scores).
-        The per-dimension scores are returned exactly as without `parts`.
+        The per-dimension scores are returned exactly as without `parts`, unless `scale_scores="per_part"`: then every part's
+        per-dimension scores are scaled by the part's own median and IQR (evaluation.scale_scores(parts=); GPU only) before the
+        mean over the dimensions, and the returned per-dimension scores are those per-part-scaled ones.  `scale_scores=True` keeps
+        its meaning -- the quantiles of the whole series -- with or without `parts`; "per_part" without `parts`, and any other
+        string, raise ValueError.
         Returns (scores (N-W,), per-dimension scores (N-W, out_dim)), both on the device; the per-dimension
         scores are never smoothed, as in the reference."""
+        if isinstance(scale_scores, str) and scale_scores != "per_part":
+            raise ValueError(f"scale_scores must be False, True or 'per_part', got {scale_scores!r}")
+        if isinstance(scale_scores, str) and parts is None:
+            raise ValueError("scale_scores='per_part' needs parts= (evaluation.score_parts)")
         span = None
         if use_mov_av:
             span = int(256 * self.window_size * 0.05) if smoothing_span is None else smoothing_span
@@ -553,7 +561,10 @@ class MTAD_GAT(nn.Module):
         if actual.shape[1] != preds.shape[1]:
             raise RuntimeError(f"target_dims select {actual.shape[1]} columns but the model has out_dim={preds.shape[1]}")
         a = (preds - actual).abs() + gamma * (recons - actual).abs()
-        if scale_scores:
+        if scale_scores == "per_part":
+            import evaluation
+            a = evaluation.scale_scores(a, parts=parts)
+        elif scale_scores:
             q = _column_quantiles(a, [0.25, 0.5, 0.75])
             a = (a - q[1]) / (1.0 + (q[2] - q[0]))
         scores = a.mean(dim=1)
@@ -577,7 +588,8 @@ class MTAD_GAT(nn.Module):
           a_i(S) = sum_d w_d * ( |yhat_A[d] - y[d]| + gamma * |r_B[W-1, d] - y[d]| ),  yhat_A = preds of A, r_B = recons of B
         which equals anomaly_scores(values, target_dims, gamma, scale_scores)[0][i] (reference prediction.py:65-91).
           w_d = 1/|dims|; with scale_scores=True w_d = 1/(|dims| (1 + IQR_d)), IQR_d from the whole series' per-dimension scores as
-          anomaly_scores computes them, held constant (the median drops out of the gradient).
+          anomaly_scores computes them, held constant (the median drops out of the gradient).  scale_scores="per_part" raises
+          ValueError: the weights are one vector per call, not one per part.
         The model is the eval-mode function (no dropout) whatever self.training is; the arithmetic is fp32.
           method="gradient":   attr = d a_i / d S, shape (W+1, F), including the direct dependence through the target row
                                (sign(0) = 0, as torch's abs backward)
@@ -588,6 +600,9 @@ class MTAD_GAT(nn.Module):
         chunked, under no_grad); self.training, the precision setting and every p.grad are left as they were.  CPU tensors go
         through the torch-op algebra with torch.autograd.grad with respect to the slices only."""
         W, F = self.window_size, self.n_features
+        if isinstance(scale_scores, str):
+            raise ValueError(f"score_attribution takes scale_scores=False or True, got {scale_scores!r}: per-part scaling "
+                             "(anomaly_scores(scale_scores='per_part')) is not attributed yet, the weights are one vector per call")
         if values.dim() != 2 or values.shape[1] != F:
             raise RuntimeError(f"values must have shape (N, {F}), got {tuple(values.shape)}")
         if method not in ("gradient", "integrated"):
