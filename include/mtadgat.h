@@ -387,6 +387,26 @@ int mtadgat_attention_series_mean(mtadgat_handle h, const float* series_dev, int
                                   int64_t start0, int64_t stride, int64_t batch, float* mean_feat_dev, float* mean_temp_dev,
                                   void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ---- forecast and reconstruction errors of a series ------------------------------------------------
+ * What Trainer.evaluate (training.py:188-228) computes from model(x), for the windows of mtadgat_forward_series, without the
+ * (batch, W, out_dim) reconstructions ever existing in full: the windows are cut into consecutive chunks of
+ * L = mtadgat_series_losses_chunk(h) windows -- min(mtadgat_chunk_windows(h), max(1, 2^26 / (W out_dim))) -- and for each chunk
+ * the forward writes preds and recons into the workspace and mtadgat_eval_window_sse (below, with its arithmetic and its
+ * definitions) reduces them against the series, accumulate = (chunk > 0):
+ *   window_sse_dev (batch, 2) float64 and dim_sse_dev (2, out_dim) float64 (may be NULL), both out.
+ *   dims_dev (out_dim) int32: the series columns the outputs are compared with (NULL: 0 .. out_dim - 1, which needs out_dim <= F).
+ * Chunk c's preds and recons are bit for bit what mtadgat_forward_series returns for that chunk's windows called on its own, in
+ * the handle's current precision mode.  The call leaves no state behind: a later mtadgat_forward on the handle returns what it
+ * returned before, bit for bit.  Identical calls give identical bits for a given chunk size.
+ * batch >= 1; every window's target row must exist: with starts_dev NULL, start0 + (batch - 1) stride + W <= n_rows - 1 is
+ * checked on the host.  Workspace: mtadgat_series_losses_workspace_bytes(h, batch), 16-byte aligned -- the forward workspace
+ * of min(batch, L) windows, one chunk of preds and recons, and the reduction's scratch: it does not grow with batch beyond L. */
+int64_t mtadgat_series_losses_chunk(mtadgat_handle h);
+size_t mtadgat_series_losses_workspace_bytes(mtadgat_handle h, int64_t batch);
+int mtadgat_series_losses(mtadgat_handle h, const float* series_dev, int64_t n_rows, const int64_t* starts_dev, int64_t start0,
+                          int64_t stride, int64_t batch, const int32_t* dims_dev, double* window_sse_dev, double* dim_sse_dev,
+                          void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* ---- training step --------------------------------------------------------------------------------
  * Replaces what autograd does for the reference around MTAD_GAT.forward in Trainer.fit
  * (training.py:106-127: preds, recons = model(x); loss.backward()): a forward that keeps the
@@ -638,6 +658,40 @@ int mtadgat_eval_part_epsilon_table(const float* x_dev, int64_t n, const int64_t
                                     double* out_host, void* stream);
 int mtadgat_eval_part_flags(const float* x_dev, int64_t n, const int64_t* start_dev, const int64_t* end_dev, int64_t count,
                             const double* thr_dev, unsigned char* flags_dev, void* stream);
+
+/* ---- squared errors of windows against their series (csrc/mtadgat_losses.hip; evaluation.window_sse) ---------------------
+ * What the reference's Trainer.evaluate (training.py:188-228) reduces model(x) to.  Conventions of the part calls above: no
+ * atomics, bitwise reproducible, status 0 / -1 / -3 / -5 with a mtadgat_last_error() message, nothing touches the device when
+ * validation fails, asynchronous on `stream`.
+ *
+ * mtadgat_eval_window_sse: for window w of the call, first row s_w = starts_dev[w] or start0 + w * stride of series_dev
+ * ((n_rows, F) float32, row stride ld_series >= F), and column dims_dev[d] (NULL: d) for output dimension d:
+ *   window_sse_dev[w, 0] = sum_d        (preds_dev[w, d]     - series[s_w + W, dims[d]])^2
+ *   window_sse_dev[w, 1] = sum_{t < W} sum_d (recons_dev[w, t, d] - series[s_w + t, dims[d]])^2
+ *   dim_sse_dev[0, d], dim_sse_dev[1, d]   the same squares summed over the windows (and time steps) instead of over d
+ * Every difference is ONE float32 subtraction (numpy's float32 a - b), converted to float64 and squared there -- exact -- and
+ * the squares are summed in float64 in a fixed order.  A window's pair depends on that window's data alone.  The per-dimension
+ * sums are a two-stage reduction (per-slab partials, then one wave per entry); their bits depend on the inputs and on how the
+ * caller cut the windows into calls, on nothing else.  accumulate = 0: the per-dimension sums start at 0; 1: they continue the
+ * sums the previous call with a non-NULL dim_sse_dev left in the SAME scratch (any batch whose scratch need is not larger), and
+ * dim_sse_dev receives the total so far.  dim_sse_dev may be NULL: only window_sse_dev is written.
+ * Limits: 1 <= batch <= 2^31 - 1, 1 <= out_dim <= 2048, 1 <= W <= 512, ld_series >= F >= 1, out_dim <= F when dims_dev is NULL,
+ * n_rows >= W + 1.  With starts_dev NULL the progression is checked on the host: start0 >= 0, stride >= 0 and
+ * start0 + (batch - 1) stride + W <= n_rows - 1 (the target row exists); starts_dev and dims_dev are the caller's to check.
+ * Scratch: 16-byte aligned, at least mtadgat_eval_window_sse_scratch(batch, out_dim) bytes (0 for refused sizes; non-decreasing
+ * in batch), need not be initialised for accumulate = 0.
+ *
+ * mtadgat_eval_group_sums: out_dev[g, c] = sum of x_dev[i, c] over the rows i of group g = [g group, min((g + 1) group, n)) of
+ * x_dev (n, cols) float64 -- ceil(n / group) groups, the last one may be short --, in float64 in a fixed order.
+ * 1 <= n <= 2^31 - 1, 1 <= cols <= 64, group >= 1. */
+size_t mtadgat_eval_window_sse_scratch(int64_t batch, int out_dim);
+int mtadgat_eval_window_sse(const float* preds_dev /* (batch, out_dim) */, const float* recons_dev /* (batch, W, out_dim) */,
+                            int64_t batch, int W, int out_dim, const float* series_dev, int64_t n_rows, int F, int64_t ld_series,
+                            const int64_t* starts_dev, int64_t start0, int64_t stride, const int32_t* dims_dev, int accumulate,
+                            double* window_sse_dev /* (batch, 2) */, double* dim_sse_dev /* (2, out_dim) or NULL */,
+                            void* scratch_dev, size_t scratch_bytes, void* stream);
+int mtadgat_eval_group_sums(const double* x_dev, int64_t n, int cols, int64_t group, double* out_dev /* (groups, cols) */,
+                            void* stream);
 
 /* ---- ranking curves (csrc/mtadgat_curves.hip; evaluation.score_order, ranking_curve, ranking_metrics) -------------------
  * Conventions of the event calls above: no atomics, no library kernels, bitwise reproducible; scratch is 8-byte aligned, at

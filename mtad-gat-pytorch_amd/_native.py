@@ -130,6 +130,11 @@ def load_library():
     lib.mtadgat_attention_mean.argtypes = [vp, vp, i64, vp, vp, vp, sz, vp]
     lib.mtadgat_attention_series.argtypes = [vp, vp, i64, vp, i64, i64, i64, vp, vp, vp, sz, vp]
     lib.mtadgat_attention_series_mean.argtypes = [vp, vp, i64, vp, i64, i64, i64, vp, vp, vp, sz, vp]
+    lib.mtadgat_series_losses_chunk.argtypes = [vp]
+    lib.mtadgat_series_losses_chunk.restype = i64
+    lib.mtadgat_series_losses_workspace_bytes.argtypes = [vp, i64]
+    lib.mtadgat_series_losses_workspace_bytes.restype = sz
+    lib.mtadgat_series_losses.argtypes = [vp, vp, i64, vp, i64, i64, i64, vp, vp, vp, vp, sz, vp]
     u64, f32 = ctypes.c_uint64, ctypes.c_float
     lib.mtadgat_backward_supported.argtypes = [vp]
     lib.mtadgat_tape_bytes.argtypes = [vp, i64]
@@ -722,6 +727,41 @@ class Engine:
                    _dev_ptr(af, "att_feat") if feat else None, _dev_ptr(at, "att_temp") if temp else None,
                    _dev_ptr(ws, "workspace") if b else None, need)
         return af, at
+
+    # -- forecast / reconstruction errors of a series (Trainer.evaluate's reduction, chunk by chunk) -----------------------
+    def series_losses_chunk(self):
+        """Windows per chunk of series_losses (mtadgat_series_losses_chunk)."""
+        return int(self.lib.mtadgat_series_losses_chunk(self.handle))
+
+    def series_losses_workspace_bytes(self, batch):
+        return int(self.lib.mtadgat_series_losses_workspace_bytes(self.handle, int(batch)))
+
+    def series_losses(self, series, starts=None, start0=0, stride=1, count=None, dims=None):
+        """Squared errors of the windows of forward_series() against the series itself, the (b, W, out) reconstructions never
+        leaving the library's workspace: (window_sse (b, 2) float64 -- forecast against row s_w + W, reconstruction against rows
+        s_w .. s_w + W - 1 --, dim_sse (2, out_dim) float64).  dims: int32 device tensor of the out_dim series columns compared
+        with (None: 0 .. out_dim - 1).  count defaults to the windows whose target row exists."""
+        c = self.cfg
+        W = c.window_size
+        if starts is None and count is None:
+            count = max(0, (series.shape[0] - 1 - W - start0) // max(stride, 1) + 1)
+        sp, n_rows, stp, b = self._series_windows(series, starts, start0, stride, count)
+        if b < 1:
+            raise RuntimeError("series_losses needs at least one window with a target row")
+        if starts is not None and int(starts.max()) + W > n_rows - 1:
+            raise RuntimeError("a window's target row does not lie inside the series")
+        dev = series.device
+        if dims is not None:
+            if dims.dtype != torch.int32 or dims.device != dev or not dims.is_contiguous() or tuple(dims.shape) != (c.out_dim,):
+                raise RuntimeError(f"dims must be a contiguous int32 tensor of {c.out_dim} columns on the series' device")
+        wsse = _empty((b, 2), dtype=torch.float64, device=dev)
+        dsse = _empty((2, c.out_dim), dtype=torch.float64, device=dev)
+        need = self.series_losses_workspace_bytes(b)
+        ws = _empty((need + 3) // 4, dtype=torch.float32, device=dev)
+        self._call(self.lib.mtadgat_series_losses, "series_losses", dev, sp, n_rows, stp, int(start0), int(stride), b,
+                   ctypes.c_void_p(dims.data_ptr()) if dims is not None else None, ctypes.c_void_p(wsse.data_ptr()),
+                   ctypes.c_void_p(dsse.data_ptr()), _dev_ptr(ws, "workspace"), need)
+        return wsse, dsse
 
     def conv(self, x):
         c = self.cfg

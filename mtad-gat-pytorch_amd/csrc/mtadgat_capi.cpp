@@ -1406,6 +1406,56 @@ int mtadgat_attention_series_mean(mtadgat_handle h, const float* series, int64_t
     return attention_series(h, series, n_rows, starts, start0, stride, batch, true, mean_feat, mean_temp, ws, ws_bytes, stream);
 }
 
+// ---- forecast / reconstruction errors of a series (Trainer.evaluate, training.py:188-228; scratch: plan_losses) -------------------
+// Chunk by chunk: the forward of that chunk's windows alone into the workspace, then mtadgat_eval_window_sse over them.
+int64_t mtadgat_series_losses_chunk(mtadgat_handle h) {
+    if (!h) return 0;
+    LossPlan p;
+    plan_losses(h->m, 1, p);
+    return p.chunk;
+}
+
+size_t mtadgat_series_losses_workspace_bytes(mtadgat_handle h, int64_t batch) {
+    if (!h || batch <= 0) return 0;
+    LossPlan p;
+    plan_losses(h->m, batch, p);
+    return p.total * sizeof(float);
+}
+
+int mtadgat_series_losses(mtadgat_handle h, const float* series, int64_t n_rows, const int64_t* starts, int64_t start0, int64_t stride,
+                          int64_t batch, const int32_t* dims, double* window_sse, double* dim_sse, void* ws_, size_t ws_bytes,
+                          void* stream) {
+    if (!h) return fail(MTADGAT_ERR_INVALID, "null handle");
+    if (batch < 1 || batch > 2147483647LL) return fail(MTADGAT_ERR_INVALID, "series losses need between 1 and 2^31 - 1 windows");
+    if (!h->m.have_weights) return fail(MTADGAT_ERR_NOWEIGHTS, "mtadgat_load_weights has not been called");
+    if (!series || !window_sse) return fail(MTADGAT_ERR_INVALID, "null tensor");
+    Model& m = h->m;
+    const int W = m.W, od = m.cfg.out_dim;
+    if (n_rows < (int64_t)W + 1) return fail(MTADGAT_ERR_INVALID, "series shorter than one window and its target row");
+    if (!dims && od > m.F) return fail(MTADGAT_ERR_INVALID, "out_dim > n_features needs dims_dev");
+    if (!starts && (stride < 0 || start0 < 0 || start0 + W > n_rows - 1 || (stride > 0 && batch - 1 > (n_rows - 1 - W - start0) / stride)))
+        return fail(MTADGAT_ERR_INVALID, "windows start0 + w*stride .. +W and their target rows do not lie inside the series");
+    if (!ws_) return fail(MTADGAT_ERR_WORKSPACE, "workspace is NULL");
+    if (!aligned16(ws_)) return fail(MTADGAT_ERR_WORKSPACE, "workspace must be 16-byte aligned");
+    LossPlan p;
+    plan_losses(m, batch, p);
+    if (ws_bytes < p.total * sizeof(float)) return fail(MTADGAT_ERR_WORKSPACE, "workspace too small");
+    float* ws = static_cast<float*>(ws_);
+    for (int64_t c0 = 0; c0 < batch; c0 += p.chunk) {
+        const int64_t n = std::min<int64_t>(p.chunk, batch - c0);
+        XSource src;
+        src.x = series; src.gather = 1; src.stride = stride;
+        src.starts = starts ? starts + c0 : nullptr;
+        src.start0 = start0 + c0 * stride;
+        int rc = forward_impl(h, src, n, ws + p.preds, ws + p.recons, nullptr, nullptr, ws, p.fwd_floats * sizeof(float), stream);
+        if (rc) return rc;
+        rc = mtadgat_eval_window_sse(ws + p.preds, ws + p.recons, n, W, od, series, n_rows, m.F, m.F, src.starts, src.start0, stride, dims,
+                                     c0 > 0, window_sse + 2 * c0, dim_sse, ws + p.scratch, p.scratch_bytes, stream);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
 int mtadgat_profile_enable(mtadgat_handle h, int on) {
     if (!h) return fail(MTADGAT_ERR_INVALID, "null handle");
     h->m.profile = on != 0;

@@ -52,6 +52,12 @@ tests/test_gpu_parts.py; tests/part_refs.py is the specification; the reference'
                                     tests/part_scale_refs.py is the specification)
   predict_anomalies(parts=)         the above inside the one-call pipeline, with one global or one threshold per part, and with
                                     scale_scores="per_part" the per-dimension scores scaled part by part
+The reference's Trainer.evaluate (training.py:188-228) on the device (csrc/mtadgat_losses.hip, tests/test_gpu_losses.py; tests/loss_refs.py
+is the specification):
+  window_sse                        per window the squared forecast and reconstruction error against the series the windows were cut
+                                    from, and the same squares per output dimension: float32 differences, float64 sums, fixed order
+  group_sums / group_losses         sums over consecutive loader batches of windows, and the reference's epoch losses from them
+                                    (MTAD_GAT.series_losses runs the forward and these without the reconstructions leaving the library)
 The fit follows the paper, not the reference's vendored spot.py (its optimiser-based root search cannot be reproduced bit for
 bit): tests/spot_refs.py is the specification, csrc/mtadgat_spot.h spells it out.
 """
@@ -131,6 +137,10 @@ def _lib():
         lib.mtadgat_eval_partq_long.argtypes = []
         lib.mtadgat_eval_partq_long.restype = ci
         lib.mtadgat_eval_part_scale.argtypes = [vp, i64, ci, i64, vp, vp, i64, vp, vp, i64, vp]
+        lib.mtadgat_eval_window_sse_scratch.argtypes = [i64, ci]
+        lib.mtadgat_eval_window_sse_scratch.restype = sz
+        lib.mtadgat_eval_window_sse.argtypes = [vp, vp, i64, ci, ci, vp, i64, ci, i64, vp, i64, i64, vp, ci, vp, vp, vp, sz, vp]
+        lib.mtadgat_eval_group_sums.argtypes = [vp, i64, ci, i64, vp, vp]
         lib.mtadgat_last_error.restype = ctypes.c_char_p
         lib._eval_bound = True
     return lib
@@ -1170,3 +1180,112 @@ def ranking_metrics(scores, labels, adjust=None):
             res["latency"] = row[4] / (row[5] + 1e-4) if row is not None else None
         out["best"], out["best_index"] = res, best
     return out
+
+
+# ---- forecast / reconstruction losses of a series (csrc/mtadgat_losses.hip; tests/loss_refs.py is the specification) ---------------
+def _target_dims(target_dims, out_dim, n_features):
+    """The series columns the out_dim outputs are compared with, checked as MTAD_GAT.score_attribution checks them."""
+    dims = list(range(n_features)) if target_dims is None else ([target_dims] if isinstance(target_dims, int) else [int(d) for d in target_dims])
+    if len(dims) != out_dim:
+        raise RuntimeError(f"target_dims select {len(dims)} columns but the model has out_dim={out_dim}")
+    if any(d < 0 or d >= n_features for d in dims):
+        raise IndexError(f"target_dims must lie in [0, {n_features})")
+    return dims
+
+
+def window_sse(preds, recons, series, starts=None, start=0, stride=1, dims=None):
+    """Squared errors of model outputs the caller already has against the series their windows were cut from.  preds (n, out) and
+    recons (n, W, out) are the outputs for the windows w = series[s_w : s_w + W], s_w = starts[w] or start + w * stride; output
+    dimension d is compared with series column dims[d] (None: d).  Returns (window_sse (n, 2), dim_sse (2, out)), float64 on the
+    device: window_sse[w, 0] = sum_d (preds[w, d] - series[s_w + W, dims[d]])^2, window_sse[w, 1] = sum_{t, d} (recons[w, t, d] -
+    series[s_w + t, dims[d]])^2, dim_sse the same squares summed over the windows (and time steps) instead of over d.  Every
+    difference is one float32 subtraction, squared and summed in float64 in a fixed order without atomics: a window's pair
+    depends on that window alone, identical calls give identical bits."""
+    lib = _lib()
+    if preds.ndim != 2 or recons.ndim != 3 or recons.shape[0] != preds.shape[0] or recons.shape[2] != preds.shape[1]:
+        raise ValueError(f"preds {tuple(preds.shape)} / recons {tuple(recons.shape)} are not (n, out) / (n, W, out)")
+    n, W, out = recons.shape
+    if n < 1:
+        raise ValueError("window_sse needs at least one window")
+    ser = _dev2d(series, "series")
+    if preds.device != ser.device or recons.device != ser.device:
+        raise RuntimeError("preds, recons and series must be on the same GPU")
+    n_rows, F = ser.shape
+    dims_t = None
+    if dims is not None:
+        dims_t = torch.tensor(_target_dims(dims, out, F), dtype=torch.int32, device=ser.device)
+    elif out > F:
+        raise RuntimeError("out_dim exceeds the number of series columns: pass dims")
+    st = None
+    if starts is not None:
+        st = _dev1d(starts, torch.int64, "starts")
+        if st.numel() != n:
+            raise ValueError(f"starts holds {st.numel()} windows, the outputs {n}")
+        if int(st.min()) < 0 or int(st.max()) + W > n_rows - 1:
+            raise RuntimeError("a window or its target row does not lie inside the series")
+    p, r = preds.detach().float().contiguous(), recons.detach().float().contiguous()
+    wsse = _native._empty((n, 2), dtype=torch.float64, device=ser.device)
+    dsse = _native._empty((2, out), dtype=torch.float64, device=ser.device)
+    need = lib.mtadgat_eval_window_sse_scratch(n, out)
+    if need == 0:
+        raise ValueError(f"window_sse: sizes outside the kernel's limits (n = {n}, out_dim = {out})")
+    scratch = _scratch(need, ser.device)
+    with torch.cuda.device(ser.device):
+        rc = lib.mtadgat_eval_window_sse(p.data_ptr(), r.data_ptr(), n, W, out, ser.data_ptr(), n_rows, F, ser.stride(0),
+                                         st.data_ptr() if st is not None else None, int(start), int(stride),
+                                         dims_t.data_ptr() if dims_t is not None else None, 0, wsse.data_ptr(), dsse.data_ptr(),
+                                         scratch.data_ptr(), need, _stream(ser))
+    if rc:
+        _fail(lib, rc, "eval_window_sse")
+    return wsse, dsse
+
+
+def _ordered_sums(x):
+    """The fixed-order sum over the rows of x (m, cols) float64 that k_group_sums computes: lane t of 256 adds rows t, t + 256, ..
+    in order, then the lanes meet in a halving tree (mtadgat_scan.h: block_sum)."""
+    lanes = np.zeros((256, x.shape[1]), dtype=np.float64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for j in range(0, x.shape[0], 256):
+            blk = x[j:j + 256]
+            lanes[:blk.shape[0]] += blk
+        s = 128
+        while s:
+            lanes[:s] += lanes[s:2 * s]
+            s //= 2
+    return lanes[0].copy()
+
+
+def group_sums(x, group):
+    """Sums of consecutive groups of `group` rows of x (n, cols) float64 -- the last group may be short -- in a fixed order:
+    (ceil(n / group), cols) float64 on x's device (GPU: mtadgat_eval_group_sums; CPU: the same order in numpy)."""
+    if x.ndim != 2 or x.shape[0] < 1 or x.dtype != torch.float64:
+        raise ValueError(f"x must be a float64 (n, cols) tensor with n >= 1, got {tuple(x.shape)} {x.dtype}")
+    group = int(group)
+    if group < 1:
+        raise ValueError(f"group must be >= 1, got {group}")
+    n, cols = x.shape
+    G = (n + group - 1) // group
+    if x.device.type != "cuda":
+        xn = x.detach().contiguous().numpy()
+        return torch.from_numpy(np.stack([_ordered_sums(xn[i:i + group]) for i in range(0, n, group)]))
+    lib = _lib()
+    xc = x.detach().contiguous()
+    out = _native._empty((G, cols), dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = lib.mtadgat_eval_group_sums(xc.data_ptr(), n, cols, group, out.data_ptr(), _stream(xc))
+    if rc:
+        _fail(lib, rc, "eval_group_sums")
+    return out
+
+
+def group_losses(sums, n, W, out, batch_size=None):
+    """(forecast_loss, recon_loss, total_loss) from the (G, 2) host sums of group_sums(window_sse, batch_size or n) over n windows:
+    per group its two MSEs, then sqrt(mean over the groups) -- Trainer.evaluate's epoch value, in which a short last batch
+    weighs as much as a full one; one group gives the global RMSEs."""
+    sums = np.asarray(sums, dtype=np.float64)
+    b = n if batch_size is None else int(batch_size)
+    counts = np.array([min(b, n - i) for i in range(0, n, b)], dtype=np.float64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        f = float(np.sqrt((sums[:, 0] / (counts * out)).mean()))
+        r = float(np.sqrt((sums[:, 1] / (counts * W * out)).mean()))
+    return f, r, f + r

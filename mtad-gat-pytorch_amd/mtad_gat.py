@@ -650,6 +650,101 @@ class MTAD_GAT(nn.Module):
             w_d = dim_w.to(device=dev, dtype=torch.float32)
             return self._checked(dev, False, lambda eng: eng.score_attribution(vf, idx_d, dims_d, w_d, gamma, m, baseline))
 
+    # -- the validation pass: forecast and reconstruction losses of a series ------------------------------------------------------
+    def series_losses(self, values, target_dims=None, batch_size=None, starts=None, start=0, stride=1, count=None):
+        """What the reference's `Trainer.evaluate` (training.py:188-228) computes over `SlidingWindowDataset(values, W)`, in one
+        call on a series (N, F): window w = values[s_w : s_w + W] (s_w = starts[w] or start + w*stride; default the N - W windows
+        0 .. N-W-1, the dataset's length) is run through the model, its forecast compared with row s_w + W and its reconstruction
+        with the window itself, both on the columns `target_dims` (None = all, an int or a list, as in score_attribution).
+        Returns a SeriesLosses:
+          forecast_loss, recon_loss, total_loss   floats.  batch_size=None: the global RMSEs sqrt(sum SSE_f / (n out_dim)) and
+                       sqrt(sum SSE_r / (n W out_dim)).  batch_size=b: the reference's epoch value for a loader of b windows
+                       per batch, sqrt(mean over the batches of the batch's MSE) -- a short last batch weighs as much as a full one.
+          window_sse   (n, 2) float64 on values' device: per window the squared forecast / reconstruction error
+          dim_mse      (2, out_dim) float64: the global mean squared error per output dimension
+          n_windows    n
+        Every difference is one float32 subtraction, squared and summed in float64 (evaluation.window_sse).
+        The model is the EVAL-mode function, under torch.no_grad(), whatever `self.training` is, which is left untouched: a
+        validation pass in the middle of training does not have to flip modes.  GPU tensors run the HIP library
+        (mtadgat_series_losses): the (n, W, out_dim) reconstructions pass through its workspace a chunk at a time and the group
+        sums are formed on the device, one small host copy per call.  CPU tensors run the torch-op forward over batches of
+        `batch_size` windows (256 when None) -- the calls the reference's loader would make."""
+        import evaluation
+        W, F = self.window_size, self.n_features
+        if values.dim() != 2 or values.shape[1] != F:
+            raise RuntimeError(f"values must have shape (N, {F}), got {tuple(values.shape)}")
+        if batch_size is not None and (int(batch_size) != batch_size or batch_size < 1):
+            raise ValueError(f"batch_size must be a positive integer or None, got {batch_size!r}")
+        dims = evaluation._target_dims(target_dims, self.out_dim, F)
+        N = values.shape[0]
+        dev = values.device
+        if starts is not None:
+            starts = torch.as_tensor(starts, dtype=torch.int64).reshape(-1)
+            n = starts.numel()
+            if n and (int(starts.min()) < 0 or int(starts.max()) + W > N - 1):
+                raise RuntimeError("a window or its target row does not lie inside the series")
+        else:
+            if start < 0 or stride < 0:
+                raise RuntimeError("start and stride must not be negative")
+            n = int(count) if count is not None else max(0, (N - 1 - W - start) // max(stride, 1) + 1)
+            if n > 0 and start + (n - 1) * stride + W > N - 1:
+                raise RuntimeError("a window or its target row does not lie inside the series")
+        if n < 1:
+            raise RuntimeError("series_losses needs at least one window whose target row lies inside the series")
+        group = n if batch_size is None else int(batch_size)
+        with torch.no_grad():
+            if dev.type == "cuda":
+                vf = values.detach().contiguous().float()
+                dims_d = None if target_dims is None else torch.tensor(dims, dtype=torch.int32, device=dev)
+                st = None if starts is None else starts.to(dev).contiguous()
+                wsse, dsse = self._checked(dev, self._use_bf16(values), lambda eng: eng.series_losses(vf, st, start, stride, n, dims_d))
+            else:
+                wsse, dsse = self._series_losses_cpu(values.detach().float(), starts, start, stride, n, dims, min(group, n) if batch_size else 256)
+            sums = evaluation.group_sums(wsse, group).cpu().numpy()
+        f, r, t = evaluation.group_losses(sums, n, W, self.out_dim, batch_size)
+        terms = torch.tensor([[n], [n * W]], dtype=torch.float64, device=dsse.device)
+        return SeriesLosses(f, r, t, wsse, dsse / terms, n)
+
+    def _series_losses_cpu(self, values, starts, start, stride, n, dims, batch):
+        """(window_sse, dim_sse) from torch-op forwards over loader batches, with evaluation.window_sse's arithmetic in numpy."""
+        import numpy as np
+        import _torchpath
+        W = self.window_size
+        if starts is None:
+            starts = start + torch.arange(n, dtype=torch.int64) * stride
+        starts = starts.cpu()
+        series = values.numpy()
+        rows, dsse = [], np.zeros((2, self.out_dim), dtype=np.float64)
+        with _torchpath._eval_mode(self):
+            for lo in range(0, n, batch):
+                st = starts[lo:lo + batch]
+                x = values.unfold(0, W, 1)[st].permute(0, 2, 1).contiguous()
+                preds, recons = _torchpath.forward(self, x)
+                s = st.numpy()
+                df = preds.numpy() - series[s + W][:, dims]
+                dr = recons.numpy() - series[s[:, None] + np.arange(W)[None, :]][:, :, dims]
+                with np.errstate(over="ignore", invalid="ignore"):
+                    qf, qr = df.astype(np.float64) ** 2, dr.astype(np.float64) ** 2
+                    rows.append(np.stack([qf.sum(axis=1), qr.reshape(len(s), -1).sum(axis=1)], axis=1))
+                    dsse += np.stack([qf.sum(axis=0), qr.sum(axis=(0, 1))])
+        return torch.from_numpy(np.concatenate(rows)), torch.from_numpy(dsse)
+
+
+class SeriesLosses:
+    """Result of MTAD_GAT.series_losses: Trainer.evaluate's three floats, and the per-window / per-dimension errors behind them."""
+    __slots__ = ("forecast_loss", "recon_loss", "total_loss", "window_sse", "dim_mse", "n_windows")
+
+    def __init__(self, forecast_loss, recon_loss, total_loss, window_sse, dim_mse, n_windows):
+        self.forecast_loss, self.recon_loss, self.total_loss = forecast_loss, recon_loss, total_loss
+        self.window_sse, self.dim_mse, self.n_windows = window_sse, dim_mse, n_windows
+
+    def __iter__(self):                   # forecast_loss, recon_loss, total_loss = model.series_losses(...): Trainer.evaluate's return
+        return iter((self.forecast_loss, self.recon_loss, self.total_loss))
+
+    def __repr__(self):
+        return (f"SeriesLosses(forecast_loss={self.forecast_loss!r}, recon_loss={self.recon_loss!r}, total_loss={self.total_loss!r}, "
+                f"n_windows={self.n_windows})")
+
 
 def _column_quantiles(a, qs):
     """np.percentile's linear quantiles of a column (n,) -> (len(qs),), or of every column of (n, d) -> (len(qs), d).
