@@ -235,6 +235,24 @@ int mtadgat_forward_plan(mtadgat_handle h, int64_t batch, int64_t* out, int max_
  * Returns the count of values written, or MTADGAT_ERR_INVALID (a NULL argument, n < 1, max_n too small: nothing is written),
  * MTADGAT_ERR_UNSUPPORTED (the configuration has no HIP backward). */
 int mtadgat_train_route(mtadgat_handle h, int64_t n, int* out, int max_n);
+/* Test hook (host only: needs neither a GPU nor loaded weights): how the weight-gradient GEMMs (d W = A^T B over the rows of the
+ * call, k_wgrad_lds + one batched reduction) of a backward of n windows -- one chunk of the training step -- are laid out.  The slab
+ * plan is the one the library's own dispatch launches under the handle's current mtadgat_set_precision mode and "wgrad_kernel"
+ * option.  Sites, in this order: the convolution; with GATv2 the projection of the feature layer, then of the temporal layer (GAT v1
+ * has none: its parameter gradients come from column sums); W_ih then W_hh of every GRU layer, then of every decoder layer, counted
+ * from the input; the decoder's per-step Linear; every forecasting Linear from the input.  Ten values per site:
+ *   [0] R     rows: n * window for all but the feature projection (n * n_features) and the forecasting Linears (n)
+ *   [1] M  [2] N      rows and columns of d W (the bias gradient rides as column N: an all-ones column of B)
+ *   [3] Mp [4] Np     the partial blocks' padded sizes
+ *   [5] nslab         row slabs (gridDim.y; a multiple of 8 enables the kernel's XCD-aware block map)
+ *   [6] rows_per_slab a multiple of 16; slabs that start at or beyond R are empty and leave zero partials
+ *   [7] bmode         1: B is the im2col view of the input windows (the convolution)
+ *   [8] bshift        1: B is read one step earlier, masked at the first step of a window (W_hh)
+ *   [9] x3            products from three bf16 pieces per operand, 0: the fp32 MFMA
+ * (Whether a site stages float4 or dword loads depends on the alignment of the call's buffers and is not reported.)
+ * Returns the count of values written, or MTADGAT_ERR_INVALID (a NULL argument, n < 1, max_n too small: nothing is written),
+ * MTADGAT_ERR_UNSUPPORTED (the configuration has no HIP backward). */
+int mtadgat_wgrad_plan(mtadgat_handle h, int64_t n, int64_t* out, int max_n);
 /* Test hook (host only): does a row GEMM over `rows` rows take split-bf16 operands (k_rowgemm_x3) under the handle's precision mode
  * and "rowgemm_kernel" option?  has_pack: a split pack was planned for its weights; backward: a site of mtadgat_backward (there
  * "rowgemm_kernel" = 2 forces the split pack in every mode, in the forward only in the "fp32" mode).  Returns 1 / 0, negative: error. */

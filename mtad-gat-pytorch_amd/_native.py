@@ -43,6 +43,8 @@ GRU_BWD_KERNELS = ("k_gru1_bwd", "k_gru16_bwd", "k_gru_bwd")
 FRONT_ROUTE_FIELDS = ("conv", "conv_build", "conv_split_pack", "range",
                       "temp_kernel", "temp_build", "temp_fp16", "temp_split_gemm", "temp_split_pack",
                       "feat_kernel", "feat_build", "feat_fp16", "feat_split_gemm", "feat_split_pack")
+# mtadgat_wgrad_plan: the ten integers per weight-gradient site (include/mtadgat.h)
+WGRAD_PLAN_FIELDS = ("R", "M", "N", "Mp", "Np", "nslab", "rows_per_slab", "bmode", "bshift", "x3")
 FRONT_KINDS = ("forward", "forward_unfused", "train", "attention", "conv")
 FRONT_SOURCES = ("windows", "windows_bf16", "series_unit", "series")
 FRONT_CONVS = ("in_gath", "k_conv_win", "shared_rows", "launch_conv")
@@ -107,6 +109,7 @@ def load_library():
     lib.mtadgat_front_route.argtypes = [vp, ctypes.c_int, ctypes.c_int, i64, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
     lib.mtadgat_forward_plan.argtypes = [vp, i64, ctypes.POINTER(i64), ctypes.c_int]
     lib.mtadgat_train_route.argtypes = [vp, i64, ctypes.POINTER(ctypes.c_int), ctypes.c_int]
+    lib.mtadgat_wgrad_plan.argtypes = [vp, i64, ctypes.POINTER(i64), ctypes.c_int]
     lib.mtadgat_rowgemm_split.argtypes = [vp, ctypes.c_int, i64, ctypes.c_int]
     lib.mtadgat_workspace_bytes.argtypes = [vp, i64]
     lib.mtadgat_workspace_bytes.restype = sz
@@ -544,6 +547,28 @@ class Engine:
         v = [int(x) for x in buf]
         layers = [tuple(v[3 * i:3 * i + 3]) for i in range(lg + ld)]
         return dict(gru=layers[:lg], rec=layers[lg:], rec_fc_rides=v[-5], feat=tuple(v[-4:-2]), temp=tuple(v[-2:]))
+
+    def wgrad_sites(self):
+        """Names of the weight-gradient sites of a training step in mtadgat_wgrad_plan's order."""
+        c = self.cfg
+        names = ["conv"] + (["feat_lin", "temp_lin"] if c.use_gatv2 else [])
+        for stack, layers in (("gru", c.gru_n_layers), ("rec", c.recon_n_layers)):
+            for l in range(layers):
+                names += [f"{stack}{l}_ih", f"{stack}{l}_hh"]
+        return names + ["rec_fc"] + [f"fc{i}" for i in range(c.forecast_n_linear)]
+
+    def wgrad_plan(self, n):
+        """How the weight-gradient GEMMs of a backward of n windows (one chunk of the training step) are laid out under the
+        current precision and "wgrad_kernel" option (host only) -- mtadgat_wgrad_plan (include/mtadgat.h): {site name: dict of
+        WGRAD_PLAN_FIELDS}, sites in the library's order (wgrad_sites)."""
+        names = self.wgrad_sites()
+        k = len(WGRAD_PLAN_FIELDS)
+        cap = k * len(names)
+        buf = (ctypes.c_int64 * cap)()
+        got = self.lib.mtadgat_wgrad_plan(self.handle, int(n), buf, cap)
+        if got != cap:
+            _check(got if got < 0 else -1, "mtadgat_wgrad_plan")
+        return {name: dict(zip(WGRAD_PLAN_FIELDS, (int(v) for v in buf[k * i:k * i + k]))) for i, name in enumerate(names)}
 
     def load_weights(self, sd, device, allow_device_pack=True):
         """sd: reference-format state_dict (any device).  The first load packs on the host and uploads on the current

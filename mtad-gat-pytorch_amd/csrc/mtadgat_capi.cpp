@@ -964,6 +964,35 @@ int mtadgat_train_route(mtadgat_handle h, int64_t n, int* out, int max_n) {
     return (int)v.size();
 }
 
+/* Read-only test hook (no GPU, no weights): the weight-gradient GEMMs of a training step of n windows (one chunk of the Python step)
+ * in the order of include/mtadgat.h, ten values each; the slab plan is wgrad_slab_plan's, which run_wgrad launches, the rows and
+ * loader modes are those backward_impl / walk_stack_backward hand to run_wgrad.  Returns the count of values written. */
+int mtadgat_wgrad_plan(mtadgat_handle h, int64_t n, int64_t* out, int max_n) {
+    if (!h || !out) return fail(MTADGAT_ERR_INVALID, "null argument");
+    if (n < 1) return fail(MTADGAT_ERR_INVALID, "the plan needs at least one window");
+    const Model& m = h->m;
+    const BwdPlan& b = m.bw;
+    if (!b.supported) return fail(MTADGAT_ERR_UNSUPPORTED, "no HIP backward for this configuration: " + b.why);
+    std::vector<int64_t> v;
+    auto site = [&](const WgradPlan& p, long R, int bmode, int bshift) {
+        const WgradSlabPlan sp = wgrad_slab_plan(m, R, p.Mp, p.Np);
+        v.insert(v.end(), {(int64_t)R, p.M, p.N, p.Mp, p.Np, sp.nslab, (int64_t)sp.rows_per_slab, bmode, bshift, sp.x3});
+    };
+    const long RW = (long)n * m.W;
+    site(b.conv_wg, RW, 1, 0);
+    if (m.cfg.use_gatv2) {
+        site(b.gat[0].wg, (long)n * m.F, 0, 0);
+        site(b.gat[1].wg, RW, 0, 0);
+    }
+    for (const std::vector<GruBwdPlan>* st : {&b.gru, &b.rec})
+        for (const GruBwdPlan& gp : *st) { site(gp.wg_ih, RW, 0, 0); site(gp.wg_hh, RW, 0, 1); }
+    site(b.recfc_wg, RW, 0, 0);
+    for (const WgradPlan& p : b.fc_wg) site(p, (long)n, 0, 0);
+    if ((int64_t)v.size() > max_n) return fail(MTADGAT_ERR_INVALID, "plan array too small");
+    std::copy(v.begin(), v.end(), out);
+    return (int)v.size();
+}
+
 /* Read-only test hook: rowgemm_split under the handle's precision and "rowgemm_kernel" option (1 / 0, negative: error) */
 int mtadgat_rowgemm_split(mtadgat_handle h, int has_pack, int64_t rows, int backward) {
     return h ? (int)rowgemm_split(h->m, has_pack != 0, rows, backward != 0) : fail(MTADGAT_ERR_INVALID, "null handle");
@@ -1581,7 +1610,8 @@ struct WgradQueue {
     }
 };
 int run_wgrad(Model& m, const WgradPlan& p, const WgradIn& in, WgradQueue& wq, float* outW, float* outB, hipStream_t s) {
-    const int nslab = wgrad_slabs(in.R, p.Mp, p.Np);
+    const WgradSlabPlan sp = wgrad_slab_plan(m, in.R, p.Mp, p.Np);
+    const int nslab = sp.nslab;
     const size_t need_ = ((size_t)nslab * p.Mp * p.Np + 63) & ~(size_t)63;
     if (need_ > wq.cap) return fail(MTADGAT_ERR_WORKSPACE, "internal: weight-gradient partial region too small");
     if (wq.used + need_ > wq.cap || wq.n == WGRAD_BATCH_MAX)
@@ -1594,12 +1624,9 @@ int run_wgrad(Model& m, const WgradPlan& p, const WgradIn& in, WgradQueue& wq, f
     a.T = in.T; a.F = m.F; a.taps = m.taps; a.pad = m.pad;
     a.R = in.R;
     a.nslab = nslab;
-    long rps = (in.R + a.nslab - 1) / a.nslab;
-    rps = (rps + 15) / 16 * 16;
-    a.rows_per_slab = rps;
+    a.rows_per_slab = sp.rows_per_slab;
     a.P = wpart; a.Mp = p.Mp; a.Np = p.Np;
-    // default fp32 arithmetic: the products from three bf16 pieces per operand (the fp32 MFMA is 2.7x the matrix time)
-    a.x3 = (m.precision == 2 && m.wgrad_kernel != 1) || m.wgrad_kernel == 2;
+    a.x3 = sp.x3;
     K_TRY(launch_wgrad(a, s), "weight-gradient GEMM");
     WgradReduceArgs r{};
     r.P = wpart; r.nslab = a.nslab; r.Mp = p.Mp; r.Np = p.Np; r.M = p.M; r.N = p.N;

@@ -464,6 +464,11 @@ void plan_attribution(const Model& m, int64_t count, int steps, AttrPlan& p);
 StreamWs stream_ws(const Model& m, int64_t windows);
 int64_t default_chunk(const Model& m, double device_bytes);    // windows per chunk of a new handle (device_bytes 0: assume 16 GB)
 int wgrad_slabs(long R, int Mp, int Np);                       // row slabs of one weight-gradient GEMM
+// How one weight-gradient GEMM over R rows walks them: run_wgrad (mtadgat_capi.cpp) launches what this names, mtadgat_wgrad_plan
+// reports it.  rows_per_slab is a whole number of the kernel's 16-row staging steps, so trailing slabs can start beyond R: they
+// write zero partials.
+struct WgradSlabPlan { int nslab = 1; long rows_per_slab = 16; bool x3 = false; };
+WgradSlabPlan wgrad_slab_plan(const Model& m, long R, int Mp, int Np);
 // packs params into host buffer `out` (size m.packed_floats); returns "" on success
 std::string pack_weights(Model& m, const mtadgat_params& p, std::vector<float>& out);
 

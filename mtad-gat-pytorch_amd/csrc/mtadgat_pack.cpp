@@ -881,6 +881,17 @@ int wgrad_slabs(long R, int Mp, int Np) {
     return (int)(s < 1 ? 1 : s);
 }
 
+WgradSlabPlan wgrad_slab_plan(const Model& m, long R, int Mp, int Np) {
+    WgradSlabPlan p;
+    p.nslab = wgrad_slabs(R, Mp, Np);
+    long rps = (R + p.nslab - 1) / p.nslab;
+    rps = (rps + 15) / 16 * 16;
+    p.rows_per_slab = rps;
+    // default fp32 arithmetic: the products from three bf16 pieces per operand (the fp32 MFMA is 2.7x the matrix time)
+    p.x3 = (m.precision == 2 && m.wgrad_kernel != 1) || m.wgrad_kernel == 2;
+    return p;
+}
+
 void plan_tape(const Model& m, int64_t n, Tape& t) {
     Carver cv;
     const size_t N = (size_t)n;

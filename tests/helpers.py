@@ -238,6 +238,24 @@ def masks_at(eng, windows, p, seed, device, dtype=torch.float64):
     return out
 
 
+def host_masks_at(kwargs, windows, p, seed, dtype=torch.float64):
+    """masks_at without a GPU: the same keep-masks of the given GLOBAL windows from the restated hash (dropout_keep_mask), the
+    masks between stacked recurrence layers included (streams DROP_GRU0 = 64 + l / DROP_REC0 = 96 + l, element t * H + j of a
+    window: k_seq_dropout); None for p = 0.  tests/test_gpu_train_routes.py holds it equal to the library's."""
+    if p <= 0.0:
+        return None
+    W = kwargs["window_size"]
+    parts = [dropout_masks_like_the_library(kwargs, 1, seed, window0=int(w)) for w in windows]
+    out = {"feat": torch.cat([q["feat"] for q in parts]).to(dtype), "temp": torch.cat([q["temp"] for q in parts]).to(dtype),
+           "fc": [torch.cat([q["fc"][i] for q in parts]).to(dtype) for i in range(len(parts[0]["fc"]))]}
+    lg, ld = kwargs.get("gru_n_layers", 1) - 1, kwargs.get("recon_n_layers", 1) - 1
+    if lg > 0 or ld > 0:
+        for key, layers, stream0, H in (("gru", lg, 64, kwargs["gru_hid_dim"]), ("rec", ld, 96, kwargs["recon_hid_dim"])):
+            out[key] = [torch.cat([torch.from_numpy(dropout_keep_mask(seed, stream0 + l, p, 1, W * H, int(w))).reshape(1, W, H)
+                                   for w in windows]).to(dtype) for l in range(layers)]
+    return out
+
+
 def _near_zero(t, rel):
     """bool per window (dim 0): some entry of t within rel * (the window's max |entry|) of zero."""
     t = t.flatten(1).abs()
@@ -284,16 +302,36 @@ def kink_windows(m64, x, masks=None, rel=KINK_REL, gatv2_pairs=False):
     return bad
 
 
-def sample_windows(b, edges=(), n=32, seed=0, groups=(16, 32)):
-    """<= n window indices of a b-window call: 0, 1, the last two, both sides of every edge e (windows e - 1, e) inside the call,
-    of the last `groups`-window group edges, then seeded random windows."""
+def edge_windows(b, edges=(), groups=(16, 32), row_edges=(), window=1):
+    """The windows of a b-window call that sample_windows always takes, sorted: 0, 1, the last two, both sides of every window edge
+    e (windows e - 1, e), of the last `groups`-window group edges, and of every ROW edge r of a (window, step)-row buffer with
+    `window` steps per window -- the windows of rows r - 1 and r and, where the edge falls inside one window, the window before it
+    too, so that a row dropped, duplicated or taken from the neighbouring slab always involves two adjacent sampled windows."""
     must = [0, 1, b - 2, b - 1]
     for e in list(edges) + [(b - 1) // gsz * gsz for gsz in groups]:
         must += [e - 1, e]
-    must = sorted({w for w in must if 0 <= w < b})[:n]
+    for r in row_edges:
+        lo, hi = (r - 1) // window, r // window
+        must += [lo, hi] + ([lo - 1] if lo == hi else [])
+    return sorted({w for w in must if 0 <= w < b})
+
+
+def sample_windows(b, edges=(), n=32, seed=0, groups=(16, 32), row_edges=(), window=1, reject=None):
+    """<= n window indices of a b-window call: edge_windows(...), then seeded random windows.  reject(windows) -> one bool per
+    window: a random window it rejects is replaced by the next seeded one (the edge windows are never replaced)."""
+    must = edge_windows(b, edges, groups, row_edges, window)[:n]
     g = torch.Generator().manual_seed(seed)
-    rest = [w for w in torch.randperm(b, generator=g)[: n + len(must)].tolist() if w not in must][: n - len(must)]
-    return sorted(must + rest)
+    perm = torch.randperm(b, generator=g)
+    if reject is None:
+        rest = [w for w in perm[: n + len(must)].tolist() if w not in must][: n - len(must)]
+        return sorted(must + rest)
+    rest, at = [], 0
+    while len(rest) < n - len(must) and at < b:
+        cand = [w for w in perm[at:at + n].tolist() if w not in must]
+        at += n
+        if cand:
+            rest += [w for w, bad in zip(cand, reject(cand)) if not bad]
+    return sorted(must + rest[: n - len(must)])
 
 
 def window_gate(ours, ref64, ref32_of, what=""):

@@ -138,6 +138,8 @@ def test_gradients_match_autograd_above_the_small_batch_kernels(name, gpu_device
     pr_ref, rc_ref, ref = _reference_grads(model, x, y)
     pr, rc = model(x)
     assert model.grad_path == "hip", model.grad_path
+    route = model._engine.train_route(b)                     # k_gru_split (on either operand build) + k_gru_bwd in every layer
+    assert all(fwd in (3, 4) and bwd == 2 for fwd, bwd, _ in route["gru"] + route["rec"]), route
     assert (pr - pr_ref).abs().max().item() <= 1e-5 and (rc - rc_ref).abs().max().item() <= 1e-5
     with torch.no_grad():
         pe, re_ = model(x)
@@ -190,12 +192,14 @@ def test_gradients_match_autograd_on_both_sides_of_the_window_kernel_edge(n, gpu
 
 
 def test_gradients_above_the_fp16_range_guard(gpu_device):
-    """From 2561 windows on the training forward's recurrences run on split operands, with two fp16 pieces for the
-    convolution's channels -- unless the convolution recorded outputs of 2^15 and more: then the device-side guard hands the
-    launch to the fp32 kernel (both are enqueued, one returns at once).  Un-normalised inputs must give the same gradients
-    as autograd through the torch-op algebra, and the guard must actually have tripped."""
+    """The training forward's recurrences run on split operands (k_gru_split on two fp16 pieces, with two fp16 pieces for the
+    convolution's channels) from 2561 windows where the stack is not on the small-batch kernels -- a single-layer stack like this
+    one leaves them above 4096 windows, hence 4100 -- unless the convolution recorded outputs of 2^15 and more: then the
+    device-side guard hands the launch to the fp32 kernel (both are enqueued, one returns at once).  Un-normalised inputs must
+    give the same gradients as autograd through the torch-op algebra, the route must be the guarded one and the guard must
+    actually have tripped."""
     kw, _ = CONFIGS["odd_shapes"]
-    b = 2600
+    b = 4100
     model = _model(kw, gpu_device).eval()
     g = torch.Generator().manual_seed(14)
     x = (torch.rand(b, kw["window_size"], kw["n_features"], generator=g) * 4e5).to(gpu_device)
@@ -203,6 +207,10 @@ def test_gradients_above_the_fp16_range_guard(gpu_device):
     pr_ref, rc_ref, ref = _reference_grads(model, x, y)
     pr, rc = model(x)
     assert model.grad_path == "hip", model.grad_path
+    route = model._engine.train_route(b)                     # k_gru_split on split operands + k_gru_bwd on three bf16 pieces ...
+    assert route["gru"] == [(4, 2, 1)] and route["rec"] == [(4, 2, 1)], route
+    first = model._engine.gru_route(0, 0, b, training=True, compute_units=torch.cuda.get_device_properties(gpu_device).multi_processor_count)
+    assert (first["first"], first["fallback"]) == (4, 3), first      # ... with k_gru_split on fp32 operands behind the range guard
     # pre-activations of ~1e5: fp32 itself resolves ~1e-2 there, two summation orders differ by ~1e-4 in the outputs
     assert (pr - pr_ref).abs().max().item() <= 5e-4 and (rc - rc_ref).abs().max().item() <= 5e-4
     _loss(pr, rc, x, y).backward()
