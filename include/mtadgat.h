@@ -874,6 +874,66 @@ int mtadgat_stream_reset_spot(mtadgat_handle h, void* state_dev, int64_t n_strea
                               const void* spot_calibrated_dev, int64_t calibrated_columns, int64_t max_peaks,
                               const int64_t* streams_dev, int64_t n, void* stream);
 
+/* ---- preparing raw series: scaler, gap fill, inverse, streams (csrc/mtadgat_prep.hip; preparation.py) ---------------------
+ * The first step of the reference's pipeline (utils.normalize_data: NaN replaced, a MinMaxScaler fitted on the training series and
+ * applied to train and test) for device-resident data, plus a causal fill for sensor drop-outs.  tests/prep_refs.py states the
+ * definitions in numpy.  Conventions of the part calls above: handle-free, no atomics, no library kernels, bitwise reproducible,
+ * status 0 / -1 / -3 / -5 with a mtadgat_last_error() message, every argument is checked before anything touches the device,
+ * asynchronous on `stream`, nothing is read back.  Arrays are (n, d) float32 with a row stride ld >= d, 1 <= n <= 2^31 - 1,
+ * 1 <= d <= 2048, ld < 2^31.  Scratch is 8-byte aligned, at least what the _scratch function returns (0 for refused sizes) and
+ * need not be initialised.  Rows are reduced and scanned in fixed blocks of mtadgat_prep_rows_per_block() rows.
+ *
+ * A GAP is a sample that is not finite: NaN, +inf or -inf (the reference's nan_to_num would turn an infinity into +-3.4e38, which
+ * no scaler survives).
+ *
+ * mtadgat_prep_fit: one record per column of x_dev into scaler_dev (d records on the device).  gaps = 0 (ignore) leaves the gaps
+ * out, sklearn's own behaviour; gaps = 1 (zero) counts every gap as the sample 0.0, the reference's (nan_to_num runs before its
+ * fit).  lo / hi: the exact minimum and maximum of the samples; n_valid their number; mean: their float64 sum -- per row block a
+ * fixed tree, the blocks added in order -- divided once and rounded once to float32.  A column without a sample has lo = hi =
+ * mean = 0.  In float32, every operation rounded on its own: range = hi - lo; scale = 1 / (range < 10 eps32 ? 1 : range);
+ * offset = 0 - lo scale -- MinMaxScaler's scale_ and min_ bit for bit.
+ *
+ * mtadgat_prep_transform: out = fl(fl(v scale) + offset), clipped to [0, 1] when clip != 0, where v is x or, at a gap, by fill:
+ * 0 (none) NaN; 1 (zero) the raw value 0.0; 2 (hold) the raw value of the last valid sample of the column within the row's part,
+ * the column's mean when the part has none before the row.  The parts are `count` disjoint ascending row spans [start_k, end_k)
+ * on the device (int64), as in the part calls above; every span start and every span end is a seam no fill looks across, so rows
+ * that no span covers form stretches of their own; count = 0 (start_dev, end_dev may be NULL): one part.  age_dev (NULL, or (n, d)
+ * int32, contiguous): 0 at a valid sample, k at the k-th consecutive gap row since the last valid one, counted from the part's
+ * first row (i - part_start + 1) where the part has none yet.  fill 0 / 1 without age is one launch and needs no scratch; the hold
+ * fill and the age are a blocked scan of three launches (csrc/mtadgat_prep.hip).  out_dev may be x_dev (with ld_out = ld) and
+ * must not overlap it otherwise.
+ *
+ * mtadgat_prep_inverse: out[i, j] = fl(fl(y[i, j] - offset) / scale) with the record of column dims_dev[j] (int32 on the device;
+ * NULL: column j, then d <= d_scaler) of a scaler of d_scaler columns; NaN where dims_dev[j] lies outside it.
+ *
+ * mtadgat_prep_stream_*: the same fill as per-stream state for rows that arrive a few at a time.  One allocation of
+ * mtadgat_prep_stream_state_bytes() bytes (16-byte aligned) that the host never reads holds, per (stream, column), the last valid
+ * raw value, whether there was one, and the age; _init writes it, _reset returns the selected streams (streams_dev NULL: 0 ..
+ * n - 1) to "nothing heard yet".  _push: rows_dev (n, T, d) float32 for the n distinct streams streams_dev (int64 on the device;
+ * NULL: 0 .. n - 1) in (stream, t) order; out_dev (n, T, d) and age_dev (NULL or (n, T, d) int32) are what mtadgat_prep_transform
+ * gives for the stream's rows so far as one part, however they were cut into pushes.  A stream index outside [0, n_streams)
+ * touches no state and gets NaN (age -1); so does every row when the state was initialised for other sizes. */
+typedef struct mtadgat_prep_column {
+    float   lo, hi, scale, offset, mean;
+    int32_t n_valid;
+} mtadgat_prep_column;
+int mtadgat_prep_rows_per_block(void);
+size_t mtadgat_prep_fit_scratch(int64_t n, int d);
+int mtadgat_prep_fit(const float* x_dev, int64_t n, int d, int64_t ld, int gaps, void* scratch_dev, size_t scratch_bytes,
+                     mtadgat_prep_column* scaler_dev, void* stream);
+size_t mtadgat_prep_transform_scratch(int64_t n, int d, int fill, int want_age);
+int mtadgat_prep_transform(const float* x_dev, int64_t n, int d, int64_t ld, const mtadgat_prep_column* scaler_dev, int fill, int clip,
+                           const int64_t* start_dev, const int64_t* end_dev, int64_t count, void* scratch_dev, size_t scratch_bytes,
+                           float* out_dev, int64_t ld_out, int32_t* age_dev, void* stream);
+int mtadgat_prep_inverse(const float* y_dev, int64_t n, int d, int64_t ld, const mtadgat_prep_column* scaler_dev, int d_scaler,
+                         const int32_t* dims_dev, float* out_dev, int64_t ld_out, void* stream);
+size_t mtadgat_prep_stream_state_bytes(int64_t n_streams, int d);
+int mtadgat_prep_stream_init(void* state_dev, int64_t n_streams, int d, void* stream);
+int mtadgat_prep_stream_push(void* state_dev, int64_t n_streams, int d, const float* rows_dev, const int64_t* streams_dev, int64_t n,
+                             int64_t T, const mtadgat_prep_column* scaler_dev, int fill, int clip, float* out_dev, int32_t* age_dev,
+                             void* stream);
+int mtadgat_prep_stream_reset(void* state_dev, int64_t n_streams, int d, const int64_t* streams_dev, int64_t n, void* stream);
+
 /* Per-kernel launch timing for bench.py's roofline leg: when enabled, forward()
  * brackets each kernel family with hipEvents on `stream`; mtadgat_profile_read
  * synchronises those events and returns accumulated milliseconds + launch counts

@@ -776,7 +776,7 @@ def pot_eval(init_scores, scores, labels, q=1e-3, level=0.98, dynamic=False, max
 
 
 def predict_anomalies(model, train, test, labels=None, target_dims=None, gamma=1.0, scale_scores=False, use_mov_av=False, reg_level=1,
-                      bf_search=None, events=None, pot=None, curves=None, parts=None):
+                      bf_search=None, events=None, pot=None, curves=None, parts=None, prepare=None):
     """What Predictor.predict_anomalies (prediction.py:106-165) derives from a train and a test series, with every score array
     staying on the device.  train, test: device-resident (N, F) series; labels: the test labels for rows window_size.. (one
     per score) or None; bf_search: (start, end, step_num) for the best-F1 sweep, run when labels are given too.
@@ -810,7 +810,23 @@ def predict_anomalies(model, train, test, labels=None, target_dims=None, gamma=1
     a constant part maps to 0 where the reference has 0 / 0; the parts are half-open where the reference's slices share a sample
     that is normalised twice; the moving average restarts per part where the reference smooths across the seams.  Events
     (events=) may still merge across a seam; with both sides blanked that takes merge_gap >= before + after.
-    Without parts every returned value is what it was before parts existed."""
+    Without parts every returned value is what it was before parts existed.
+    prepare=dict(fill=, clip=, gaps=) (any subset; defaults "zero", False, "zero": the reference's normalize_data) takes train and
+    test as RAW series: a preparation.SeriesScaler is fitted on train (fit_scaler(train, gaps)) and both series go through its
+    transform(fill=, clip=) before anything else, a "hold" fill stopping at the seams of parts' train_lengths / test_lengths when
+    those are given; the result gains "scaler".  Without prepare nothing changes."""
+    scaler = None
+    if prepare is not None:
+        import preparation
+        unknown = set(prepare) - {"fill", "clip", "gaps"}
+        if unknown:
+            raise ValueError(f"prepare takes fill, clip and gaps, got {sorted(unknown)}")
+        prep_opts = dict(fill="zero", clip=False, gaps="zero")
+        prep_opts.update(prepare)
+        scaler = preparation.fit_scaler(train, gaps=prep_opts["gaps"])
+        seams = parts or {}
+        train = scaler.transform(train, fill=prep_opts["fill"], clip=prep_opts["clip"], lengths=seams.get("train_lengths"))
+        test = scaler.transform(test, fill=prep_opts["fill"], clip=prep_opts["clip"], lengths=seams.get("test_lengths"))
     part_opts = None
     if isinstance(scale_scores, str) and scale_scores != "per_part":
         raise ValueError(f"scale_scores must be False, True or 'per_part', got {scale_scores!r}")
@@ -846,6 +862,8 @@ def predict_anomalies(model, train, test, labels=None, target_dims=None, gamma=1
     thr, preds = feature_predictions(train_per_dim, test_per_dim, reg_level)
     out = {"epsilon_result": eps_result, "bf_result": bf_result, "feature_thresholds": thr, "train_scores": train_scores,
            "test_scores": test_scores, "test_per_dim": test_per_dim, "feature_preds": preds}
+    if scaler is not None:
+        out["scaler"] = scaler
     if part_opts is not None and part_opts["thresholds"] == "per_part":
         same = train_parts.n_parts == test_parts.n_parts
         part_thr = find_epsilon_parts(train_scores, train_parts, reg_level) if same else find_epsilon_parts(test_scores, test_parts, reg_level)

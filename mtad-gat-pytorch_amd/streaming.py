@@ -82,10 +82,14 @@ class StreamScorer:
     merge_gap,      the event rules of evaluation.flag_runs: flagged runs at most merge_gap samples apart are one event, events
     min_length      shorter than min_length are dropped
     max_block       the most rows per stream one push may carry
+    prepare         None: the rows are scored as they come (a row with a NaN has no score, and poisons a moving average for good);
+                    or a preparation.StreamPreparer for n_streams streams, or a (scaler, fill) pair one is made from: push and
+                    update run the raw rows through it first -- scaled, the gaps filled ("zero" or "hold": no NaN reaches the
+                    history or the moving average) --, reset() resets its streams too
     """
 
     def __init__(self, model, n_streams, threshold, target_dims=None, gamma=1.0, smoothing_span=None, scale=None, merge_gap=0,
-                 min_length=1, max_block=64):
+                 min_length=1, max_block=64, prepare=None):
         F, d = model.n_features, model.out_dim
         if int(n_streams) != n_streams or n_streams < 1:
             raise ValueError(f"n_streams must be a positive integer, got {n_streams!r}")
@@ -130,6 +134,15 @@ class StreamScorer:
         self._state = None
         self._ws = None
         self._spot = self._spot_calibrated = None
+        self._prepare = None
+        if prepare is not None:
+            from preparation import StreamPreparer
+            if not isinstance(prepare, StreamPreparer):
+                scaler, fill = prepare
+                prepare = StreamPreparer(scaler.to(self.device), self.n_streams, fill=fill)
+            if prepare.n_streams != self.n_streams or prepare.scaler.n_columns != F or prepare.device != self.device:
+                raise ValueError(f"prepare must serve {self.n_streams} streams of {F} columns on '{self.device}'")
+            self._prepare = prepare
         if spot is not None:
             if spot.device != self.device:
                 raise ValueError(f"the SpotState is on '{spot.device}', the model on '{self.device}'")
@@ -240,6 +253,8 @@ class StreamScorer:
         rows = self._rows(rows)
         n, T = rows.shape[0], rows.shape[1]
         st, _ = self._select(streams, n)
+        if self._prepare is not None:
+            rows = self._prepare.push(rows, st)
         lib = _lib()
         windows = n * T
 
@@ -274,6 +289,8 @@ class StreamScorer:
             if not isinstance(t, torch.Tensor) or t.device != self.device or t.numel() != n * T * self.out_dim or t.shape[0] != n:
                 raise ValueError(f"{name} must be a ({n}, {T}, {self.out_dim}) tensor on the scorer's device")
             given.append(t.detach().float().contiguous())
+        if self._prepare is not None:
+            rows = self._prepare.push(rows, st)
         eng = self._engine()
         return self._commit(eng, given[0].data_ptr(), given[1].data_ptr(), rows, st, n, T, staged=False)
 
@@ -293,6 +310,8 @@ class StreamScorer:
             self._fail(rc, "stream_flush")
         if reset and self._spot is not None:
             self.reset(streams)
+        elif reset and self._prepare is not None:
+            self._prepare.reset(st)
         return out
 
     def reset(self, streams=None):
@@ -300,6 +319,8 @@ class StreamScorer:
         the calibrated thresholds, counts and excesses."""
         st, n = self._select(streams)
         eng = self._engine()
+        if self._prepare is not None:
+            self._prepare.reset(st)
         sp = st.data_ptr() if st is not None else None
         with torch.cuda.device(self.device):
             if self._spot is not None:
