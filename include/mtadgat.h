@@ -325,6 +325,21 @@ size_t  mtadgat_workspace_bytes(mtadgat_handle h, int64_t batch);
 int64_t mtadgat_chunk_windows(mtadgat_handle h);
 int     mtadgat_set_chunk_windows(mtadgat_handle h, int64_t windows);
 
+/* Non-finite input (every forward entry point below, mtadgat_series_losses, mtadgat_stream_push and mtadgat_forward_train).
+ * A sample is non-finite if it is NaN, +inf or -inf -- a "gap" of mtadgat_prep_*.
+ *   - A window that holds a non-finite sample answers NaN in preds, in EVERY element of recons and in recons_last, in every
+ *     precision mode, for float32 and bfloat16 input: what the reference's float32 algebra gives (the convolution spreads the sample
+ *     over all channels, each attention layer's softmax makes the whole layer output NaN, the GRU carries it to h_end).
+ *   - No other window of the call changes, beyond what a change of kernel allows: a launch-wide range guard may send the launch to
+ *     its fallback kernel (results within the tolerance of the precision mode, not bit-equal).
+ *   - A series: the affected windows are exactly those whose rows [s_w, s_w + W) contain the sample.
+ *   - A stream (mtadgat_stream_push): the affected rows are those of that stream only -- the row itself and the next W rows score
+ *     NaN and are not flagged; the row after that scores again.
+ *   - mtadgat_forward_train's preds / recons follow the same rule, so the loss a caller forms from them is NaN and seen.
+ *   - hend_dev, gradients (mtadgat_backward*), attention maps and attributions of non-finite input are unspecified.
+ * The kernels upstream are not NaN-transparent (ReLU as fmaxf, clamped gate functions): the decision is taken per window at the
+ * input and written over the outputs behind the heads (k_poison_nonfinite). */
+
 /* Replaces MTAD_GAT.forward (mtad_gat.py:64-79), eval mode.
  *   x_dev      (batch, W, F)          in, not modified
  *   preds_dev  (batch, out_dim)       out   (may be NULL: skip both heads if recons_dev is NULL too)

@@ -146,9 +146,10 @@ ConvArgs conv_args(const Model& m, const XSource& src, int64_t c0, int64_t n, in
     a.NT = m.convNT; a.Wpad = m.Wp; a.Dp = m.Dp;
     return a;
 }
-// the convolution launch the route names (CONV_WIN, CONV_LAUNCH); vmax: where the range is recorded when the route says so
+// the convolution launch the route names (CONV_WIN, CONV_LAUNCH); vmax: where the range is recorded when the route says so; bad:
+// where k_conv_win leaves the windows' non-finite flags (run_poison), or null
 int run_conv(Model& m, const FrontRoute& r, const XSource& src, int64_t c0, int64_t n, float* xc, float* xct, float* hcat, float* y,
-             hipStream_t s, unsigned* vmax = nullptr) {
+             hipStream_t s, unsigned* vmax = nullptr, unsigned char* bad = nullptr) {
     Scope sc(m, S_CONV, s);
     ConvArgs a = conv_args(m, src, c0, n, m.W);
     a.XC = xc; a.XCT = xct; a.HCAT = hcat; a.Y = y;
@@ -162,6 +163,7 @@ int run_conv(Model& m, const FrontRoute& r, const XSource& src, int64_t c0, int6
         a.Fq = m.Fp16;
         a.Wp = reinterpret_cast<const f32x4*>(m.packed_dev + m.conv_w2h_off);
         a.wscale = m.packed_dev + m.conv_scale_off + 1;
+        a.bad = bad;
         K_TRY(launch_conv_win(a, s), "conv (window per workgroup)");
         return 0;
     }
@@ -590,6 +592,22 @@ int run_heads(Model& m, const float* hend, long ldh, int64_t n, float* preds, fl
                       "last reconstruction step");
         }
     }
+    return 0;
+}
+
+// The non-finite contract (include/mtadgat.h): NaN over the outputs of the windows from c0 on that hold a NaN / inf sample, behind the
+// heads that wrote them and on their stream.  The outputs are those of these n windows.  bad: the per-window flags the piece's
+// convolution left (k_conv_win, k_gath's CONV build: the large-batch routes) -- one byte read per window.  bad == null (every other
+// convolution, the training forward): the kernel reads the piece's input once more, n * W * F elements -- a third of h_cat, which is
+// written once and read by every layer behind it; 1.4 GB per 65 536 flagship windows, which is why the large-batch routes carry flags.
+int run_poison(const Model& m, const XSource& src, int64_t c0, int64_t n, const unsigned char* bad, float* preds, float* recons,
+               float* recons_last, hipStream_t s) {
+    NonFiniteArgs a{};
+    fill_source(m, src, c0, a);
+    a.bad = bad;
+    a.n = n; a.W = m.W; a.F = m.F; a.od = m.cfg.out_dim;
+    a.preds = preds; a.recons = recons; a.recons_last = recons_last;
+    K_TRY(launch_poison_nonfinite(a, s), "non-finite windows");
     return 0;
 }
 
@@ -1163,6 +1181,7 @@ static int forward_impl(mtadgat_handle h, const XSource& src, int64_t batch, flo
         float* hcat = ws + o.hcat;
         LayerIo temp = hcat_layer(m, true, true, hcat, nullptr, ws + o.lct, ws + o.rtt), feat = hcat_layer(m, false, true, hcat, nullptr, ws + o.lcf, ws + o.rtf);
         temp.sc = feat.sc = ws + o.sc;
+        const unsigned char* bad = nullptr;                   // the windows' non-finite flags, where the convolution leaves them
         if (both_fused) {
             // fused front: conv writes only h_cat[:, :F]; each layer's workgroup stages its window from
             // there (the feature layer transposes on the way into LDS) -- no xc / xc^T / L' / R' in HBM
@@ -1171,14 +1190,16 @@ static int forward_impl(mtadgat_handle h, const XSource& src, int64_t batch, flo
             temp.vmax = feat.vmax = vmax;
             GatConvIn cv{};
             const bool conv_in_gat = r.conv == CONV_IN_GATH;
+            unsigned char* winflag = reinterpret_cast<unsigned char*>(ws + o.winflag);
+            if (conv_in_gat || r.conv == CONV_WIN) bad = winflag;        // these two leave the windows' non-finite flags there
             if (r.conv == CONV_SHARED) {
                 if ((rc = run_conv_shared(m, src, c0, n, hcat, ws + o.cf, ws + o.el, ws + o.er, s, vmax))) return rc;
             } else if (conv_in_gat) {
                 if ((rc = ensure(m, m.conv_split, s))) return rc;
-                cv = fused_conv_args(m, src, c0, hcat, vmax, reinterpret_cast<unsigned char*>(ws + o.winflag));
+                cv = fused_conv_args(m, src, c0, hcat, vmax, winflag);
                 temp.cv = &cv;
                 HIP_TRY(hipMemsetAsync(vmax, 0, sizeof(unsigned), s));
-            } else if ((rc = run_conv(m, r, src, c0, n, nullptr, nullptr, hcat, nullptr, s, vmax))) return rc;
+            } else if ((rc = run_conv(m, r, src, c0, n, nullptr, nullptr, hcat, nullptr, s, vmax, winflag))) return rc;
             if (fork && !conv_in_gat) {                       // the feature layer on the second lane, beside the temporal one
                 HIP_TRY(hipEventRecord(m.fork_ev[0], s));
                 HIP_TRY(hipStreamWaitEvent(m.lane_stream, m.fork_ev[0], 0));
@@ -1207,15 +1228,19 @@ static int forward_impl(mtadgat_handle h, const XSource& src, int64_t batch, flo
             // the forecasting head on the second lane, beside the reconstruction decoder (their scratch regions are disjoint)
             HIP_TRY(hipEventRecord(m.fork_ev[2], s));
             HIP_TRY(hipStreamWaitEvent(m.lane_stream, m.fork_ev[2], 0));
-            if ((rc = run_heads(m, hend, ldh, n, preds + c0 * m.cfg.out_dim, nullptr, nullptr, ws, o, m.lane_stream))) return rc;
-            if ((rc = run_heads(m, hend, ldh, n, nullptr, recons ? recons + c0 * (int64_t)W * m.cfg.out_dim : nullptr,
-                                recons_last ? recons_last + c0 * m.cfg.out_dim : nullptr, ws, o, s)))
-                return rc;
+            float* pr = preds + c0 * m.cfg.out_dim;
+            float* rc_ = recons ? recons + c0 * (int64_t)W * m.cfg.out_dim : nullptr;
+            float* rl = recons_last ? recons_last + c0 * m.cfg.out_dim : nullptr;
+            if ((rc = run_heads(m, hend, ldh, n, pr, nullptr, nullptr, ws, o, m.lane_stream))) return rc;
+            if ((rc = run_poison(m, src, c0, n, bad, pr, nullptr, nullptr, m.lane_stream))) return rc;      // each lane behind its own head
+            if ((rc = run_heads(m, hend, ldh, n, nullptr, rc_, rl, ws, o, s))) return rc;
+            if ((rc = run_poison(m, src, c0, n, bad, nullptr, rc_, rl, s))) return rc;
         } else if (preds || recons || recons_last) {
-            if ((rc = run_heads(m, hend, ldh, n, preds ? preds + c0 * m.cfg.out_dim : nullptr,
-                                recons ? recons + c0 * (int64_t)W * m.cfg.out_dim : nullptr,
-                                recons_last ? recons_last + c0 * m.cfg.out_dim : nullptr, ws, o, s)))
-                return rc;
+            float* pr = preds ? preds + c0 * m.cfg.out_dim : nullptr;
+            float* rc_ = recons ? recons + c0 * (int64_t)W * m.cfg.out_dim : nullptr;
+            float* rl = recons_last ? recons_last + c0 * m.cfg.out_dim : nullptr;
+            if ((rc = run_heads(m, hend, ldh, n, pr, rc_, rl, ws, o, s))) return rc;
+            if ((rc = run_poison(m, src, c0, n, bad, pr, rc_, rl, s))) return rc;
         }
     }
     return 0;
@@ -1882,7 +1907,8 @@ int mtadgat_forward_train(mtadgat_handle h, const float* x, int64_t batch, int64
     ds.fc = &m.rec_fc; ds.rides = !dec_small && rec_fc_rides_train(m); ds.yfc = recons;
     if ((rc = walk_stack_forward(m, m.rec, t.rec, T, ds, drop, n, s))) return rc;
     K_TRY(launch_xdec(hend, g.Hp, m.cfg.gru_hid_dim, W, n, T + t.xdec, g.Hp, s), "decoder input");
-    return 0;
+    // a window with a non-finite sample answers NaN, so that the loss a caller forms from it is NaN (its gradients are unspecified)
+    return run_poison(m, src, 0, n, nullptr, preds, recons, nullptr, s);
 }
 
 }  // extern "C"

@@ -49,7 +49,7 @@ __global__ __launch_bounds__(256 / CW_RT, CW_RT == 1 ? 4 : 3) void k_conv_win(co
     constexpr int MAXU = 6 * CW_RT;                    // 16-byte units per thread held in registers (W F <= 6144: plan)
     f32x4 v[MAXU];
     const int nunit = (total + 3) >> 2;
-    float mx = 0.f;
+    unsigned mxu = 0u;                                 // largest |x| of the window as a bit pattern: a NaN / inf sample wins (wave_max_u)
     // the loader is picked once (wave-uniform) and issues all of a thread's units before anything looks at them: with the choice
     // inside the unit loop each unit was a load, a wait for it, and its maximum -- MAXU memory round trips in a row per window
     const bool whole = vec && (total & 3) == 0;        // every unit is one aligned 16-byte (bf16 input: 8-byte) word
@@ -92,10 +92,10 @@ __global__ __launch_bounds__(256 / CW_RT, CW_RT == 1 ? 4 : 3) void k_conv_win(co
     for (int n = 0; n < MAXU; ++n) {
         const int u = tid + n * NTHR;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) mx = fmaxf(mx, (4 * u + e < total) ? fabsf(v[n][e]) : 0.f);
+        for (int e = 0; e < 4; ++e) mxu = umax2(mxu, (4 * u + e < total) ? (__float_as_uint(v[n][e]) & 0x7fffffffu) : 0u);
     }
-    mx = wave_max(mx);
-    if (lane == 0) red[wave] = mx;
+    mxu = wave_max_u(mxu);
+    if (lane == 0) red[wave] = __uint_as_float(mxu);
     // zero halo rows, the spare row behind them and the channel padding [F, Fq) of the window's rows
     {
         const int hw = pvh >> 1;                       // dwords per row
@@ -119,11 +119,12 @@ __global__ __launch_bounds__(256 / CW_RT, CW_RT == 1 ? 4 : 3) void k_conv_win(co
     __syncthreads();
     if (a.dbg & 4) return;
     if (tid == 0) {
-        float m = red[0];
+        unsigned m = __float_as_uint(red[0]);
 #pragma unroll
-        for (int w2 = 1; w2 < NWV; ++w2) m = fmaxf(m, red[w2]);
+        for (int w2 = 1; w2 < NWV; ++w2) m = umax2(m, __float_as_uint(red[w2]));
+        if (a.bad) a.bad[win] = m >= 0x7f800000u ? 2 : 0;      // the window holds a non-finite sample: for the poisoning behind the heads
         // sx = 2^(13 - floor(log2 m)): exponent field 267 - e (m = 0, denormal or not finite: 1)
-        const unsigned e = (__float_as_uint(m) >> 23) & 0xffu;
+        const unsigned e = (m >> 23) & 0xffu;
         const unsigned es = (e == 0u || e >= 254u) ? 127u : 267u - e;
         const unsigned ec = es < 1u ? 1u : (es > 253u ? 253u : es);
         red[4] = __uint_as_float(ec << 23);

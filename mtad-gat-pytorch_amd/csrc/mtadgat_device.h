@@ -261,6 +261,22 @@ __device__ __forceinline__ float wave_max(float v) {
     v = fmaxf(v, dpp_move<0x140>(v));   // row_mirror
     return fmaxf(fmaxf(lane_value(v, 0), lane_value(v, 16)), fmaxf(lane_value(v, 32), lane_value(v, 48)));
 }
+// wave_max of bit patterns.  Of |x| patterns (sign bit cleared) it is the float maximum while every value is finite, and a NaN or inf
+// pattern (>= 0x7f800000) wins, where fmaxf drops a NaN: the staging passes of k_conv_win / k_gath take the window's scale and
+// its non-finite flag (include/mtadgat.h) from the one reduction
+template <int CTRL>
+__device__ __forceinline__ unsigned dpp_move_u(unsigned v) {
+    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);
+}
+__device__ __forceinline__ unsigned umax2(unsigned a, unsigned b) { return a > b ? a : b; }
+__device__ __forceinline__ unsigned wave_max_u(unsigned v) {
+    v = umax2(v, dpp_move_u<0xB1>(v));
+    v = umax2(v, dpp_move_u<0x4E>(v));
+    v = umax2(v, dpp_move_u<0x141>(v));
+    v = umax2(v, dpp_move_u<0x140>(v));
+    return umax2(umax2((unsigned)__builtin_amdgcn_readlane((int)v, 0), (unsigned)__builtin_amdgcn_readlane((int)v, 16)),
+                 umax2((unsigned)__builtin_amdgcn_readlane((int)v, 32), (unsigned)__builtin_amdgcn_readlane((int)v, 48)));
+}
 __device__ __forceinline__ float wave_sum(float v) {
     v += dpp_move<0xB1>(v);
     v += dpp_move<0x4E>(v);

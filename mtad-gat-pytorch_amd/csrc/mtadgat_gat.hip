@@ -84,7 +84,7 @@ __global__ __launch_bounds__(512, MTADGAT_GAT_MINW) void k_gat(const GatArgs a) 
     bool useh = false;
     if constexpr (X3) useh = a.vmax != nullptr && __uint_as_float(*a.vmax) < 32768.f;
     if (a.winflag) {                                   // behind a CONV launch of k_gath: only the windows it flagged (uniform per workgroup)
-        if (!a.winflag[win]) return;
+        if (!(a.winflag[win] & 1)) return;             // (bit 1 is the window's non-finite flag)
     } else if (X3 && a.skip_h && useh) return;         // k_gath has served this launch (uniform over the grid: no barrier is split)
     const int npw = X3 ? (useh ? 2 : 3) : 1;           // words per weight chunk and lane
     const f32x4* __restrict__ Wbase = (X3 && useh) ? a.Wp2 : a.Wp;

@@ -175,7 +175,8 @@ __global__ __launch_bounds__(512, MTADGAT_GAT_MINW) void k_gath(const GatArgs a)
         constexpr int MAXU = 3;                        // 16-byte units per thread (W F <= 6144, 512 threads: launcher)
         f32x4 v[MAXU];
         const int nunit = (total + 3) >> 2;
-        float mx = 0.f;
+        unsigned mxu = 0u;                             // largest |x| of the window as a bit pattern: a NaN / inf sample wins (wave_max_u)
+        bool nonfin = false;                           // thread 0: the window holds a non-finite sample
         // the loader is picked once (wave-uniform) and issues all of a thread's units before anything looks at them: with the choice
         // inside the unit loop each unit was a load, a wait for it, and its maximum -- three memory round trips in a row per window
         const bool whole = vec && (total & 3) == 0;    // every unit is one aligned 16-byte (bf16 input: 8-byte) word
@@ -220,10 +221,10 @@ __global__ __launch_bounds__(512, MTADGAT_GAT_MINW) void k_gath(const GatArgs a)
         for (int n = 0; n < MAXU; ++n) {
             const int u = tid + n * nthr;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) mx = fmaxf(mx, (4 * u + e < total) ? fabsf(v[n][e]) : 0.f);
+            for (int e = 0; e < 4; ++e) mxu = umax2(mxu, (4 * u + e < total) ? (__float_as_uint(v[n][e]) & 0x7fffffffu) : 0u);
         }
-        mx = wave_max(mx);
-        if (lane == 0) red[wave] = mx;
+        mxu = wave_max_u(mxu);
+        if (lane == 0) red[wave] = __uint_as_float(mxu);
         GATH_STAMP(1);
         {   // zero halo rows, the two spare rows behind them and the channel padding [F, Fq) of the window's rows
             const int hw = pvx >> 1;                   // dwords per row
@@ -246,10 +247,11 @@ __global__ __launch_bounds__(512, MTADGAT_GAT_MINW) void k_gath(const GatArgs a)
         }
         __syncthreads();
         if (tid == 0) {
-            float m = red[0];
-            for (int w2 = 1; w2 < NW; ++w2) m = fmaxf(m, red[w2]);
+            unsigned m = __float_as_uint(red[0]);
+            for (int w2 = 1; w2 < NW; ++w2) m = umax2(m, __float_as_uint(red[w2]));
+            nonfin = m >= 0x7f800000u;
             // sx = 2^(13 - floor(log2 m)): exponent field 267 - e (m = 0, denormal or not finite: 1)
-            const unsigned e = (__float_as_uint(m) >> 23) & 0xffu;
+            const unsigned e = (m >> 23) & 0xffu;
             const unsigned es = (e == 0u || e >= 254u) ? 127u : 267u - e;
             const unsigned ec = es < 1u ? 1u : (es > 253u ? 253u : es);
             red[8] = __uint_as_float(ec << 23);
@@ -408,7 +410,7 @@ __global__ __launch_bounds__(512, MTADGAT_GAT_MINW) void k_gath(const GatArgs a)
         const bool big = !(wmax < 32768.f);
         if (tid == 0) {
             if (c.vmax && !(wmax <= __uint_as_float(*c.vmax))) atomicMax(c.vmax, __float_as_uint(wmax));
-            if (c.flag) c.flag[win] = big ? 1 : 0;
+            if (c.flag) c.flag[win] = (big ? 1 : 0) | (nonfin ? 2 : 0);      // bit 1: for the poisoning behind the heads
         }
         GATH_STAMP(6);
         if (big) return;                               // (uniform) k_gat's bf16-piece build, enqueued behind this kernel, takes the window

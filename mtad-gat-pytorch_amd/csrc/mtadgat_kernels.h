@@ -64,6 +64,7 @@ struct ConvArgs {
     int Fq;              // channel count the MFMA chunks run over: Fp (fp32 build), F rounded up to 16 (bf16 build)
     int bf16;            // 1: Wp is the bf16 pack (k_conv_lds only)
     unsigned* vmax;      // k_conv_lds: bits of the largest output written so far (atomic max), or null
+    unsigned char* bad;  // k_conv_win: (B) 2 = the window holds a non-finite sample, else 0 (k_poison_nonfinite); or null
     int x_bf16;          // 1: X holds bfloat16 (read directly by k_conv_lds; no fp32 copy of the input exists)
     int pvh;             // k_conv_win: LDS pitch of the staged pieces (halfs), set by its launcher
     int dbg;             // k_conv_win measurement hook (bit 0: no MFMA loop, 1: no epilogue, 2: loads + halo only)
@@ -118,7 +119,8 @@ struct GatConvIn {
     const float* wscale; // [S, 1 / S]
     float* HCAT;         // (B*W, Dp): columns [0, F) and the zero padding [3F, Dp) are written
     unsigned* vmax;      // bits of the largest output written so far (atomic max; zeroed by the caller), or null
-    unsigned char* flag; // (B): 1 = the window's outputs reach 2^15 -- k_gat's bf16-piece build has to serve it; or null
+    unsigned char* flag; // (B): bit 0 = the window's outputs reach 2^15 -- k_gat's bf16-piece build has to serve it --, bit 1 = the
+                         // window holds a non-finite sample (k_poison_nonfinite); or null
 };
 
 // fused per-window graph-attention layer (projection + scores + softmax + aggregation in one workgroup)
@@ -492,6 +494,22 @@ int launch_dropmask(const DropArgs& d, unsigned stream, long nwin, long n_per_wi
 // nn.GRU's dropout between stacked layers on a (nwin * T, ld) state sequence (columns >= H are written as zero); also its adjoint
 int launch_seq_dropout(const float* src, float* dst, long nwin, int T, int H, int ld, const DropArgs& d, unsigned stream, hipStream_t s);
 int launch_copy2d(const float* src, long lds, float* dst, long ldd, long R, int ncols, hipStream_t s);
+// NaN over every output element of the windows that hold a non-finite input sample (k_poison_nonfinite); the input is described as
+// for the convolution kernels (fill_source, mtadgat_capi.cpp), the outputs are those of the same n windows, any of them null
+struct NonFiniteArgs {
+    const unsigned char* bad;    // (n) bit 1: the window holds a non-finite sample, written by the call's convolution (k_conv_win,
+                             // k_gath); null: the kernel reads the input itself
+    const float* X;          // windows (n, W, F) -- bfloat16 elements when x_bf16 -- or the series when gather != 0
+    int x_bf16, gather;
+    const long* starts;      // gather: the windows' first rows, or null for start0 + w * stride
+    long start0, stride;
+    long n;
+    int W, F, od;
+    float* preds;            // (n, od)
+    float* recons;           // (n, W, od)
+    float* recons_last;      // (n, od)
+};
+int launch_poison_nonfinite(const NonFiniteArgs& a, hipStream_t s);
 int launch_conv_scatter(const float* cf, const float* el, const float* er, float* hcat, long n, int W, int F, int Fp, int Dp, int pad,
                         hipStream_t s);
 int launch_transpose_win(const float* src, long lds, float* dst, long ldd, long B, int R, int C, hipStream_t s);

@@ -856,6 +856,52 @@ __global__ void k_copy2d(const float* __restrict__ src, long lds, float* __restr
         dst[r * ldd + c] = src[r * lds + c];
     }
 }
+// The non-finite contract of the forward (include/mtadgat.h): a window that holds a NaN, +inf or -inf sample -- exponent bits all
+// set, a "gap" of mtadgat_prep_* -- answers NaN in every output element, as the torch-op algebra does.  The convolution ReLUs, the
+// clamped gate functions and the range reductions upstream drop a NaN (fmaxf, fmed3), so the decision is taken per window at the
+// input and written over the outputs behind the heads.  Clean windows are not written.
+__device__ __forceinline__ void poison_window(const NonFiniteArgs& a, long w, int lane) {
+    const float nanf32 = __builtin_nanf("");
+    if (a.preds)
+        for (int c = lane; c < a.od; c += 64) a.preds[w * a.od + c] = nanf32;
+    if (a.recons_last)
+        for (int c = lane; c < a.od; c += 64) a.recons_last[w * a.od + c] = nanf32;
+    if (a.recons) {
+        const long Wod = (long)a.W * a.od;
+        for (long i = lane; i < Wod; i += 64) a.recons[w * Wod + i] = nanf32;
+    }
+}
+// The windows' flags come from the convolution that staged them (k_conv_win, k_gath: bit 1 of the window's byte, from the integer
+// maximum behind the per-window scale).  grid (ceil(n / 256)) x 256 threads: a lane per window reads its byte, and the wave then
+// writes the flagged windows of its 64 one after the other -- a call without a bad sample costs n bytes and 256 windows per workgroup.
+__global__ void __launch_bounds__(256) k_poison_flagged(NonFiniteArgs a) {
+    const long w = (long)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    unsigned long long m = __ballot(w < a.n && (a.bad[w < a.n ? w : a.n - 1] & 2) != 0);
+    while (m) {                                        // (wave-uniform)
+        const int b = __ffsll((long long)m) - 1;
+        m &= m - 1;
+        poison_window(a, w - lane + b, lane);
+    }
+}
+// No flags (every other convolution, the training forward): one wave per window reads the window's W * F samples once more.
+// grid (ceil(n / 4)) x 256 threads.
+__global__ void __launch_bounds__(256) k_poison_nonfinite(NonFiniteArgs a) {
+    const long w = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (w >= a.n) return;
+    const long WF = (long)a.W * a.F;
+    const long at = (a.gather ? (a.starts ? a.starts[w] : a.start0 + w * a.stride) * a.F : w * WF);
+    bool bad = false;
+    if (a.x_bf16) {
+        const unsigned short* x = reinterpret_cast<const unsigned short*>(a.X) + at;
+        for (long i = lane; i < WF; i += 64) bad |= (x[i] & 0x7f80u) == 0x7f80u;
+    } else {
+        const unsigned* x = reinterpret_cast<const unsigned*>(a.X) + at;
+        for (long i = lane; i < WF; i += 64) bad |= (x[i] & 0x7f800000u) == 0x7f800000u;
+    }
+    if (__ballot(bad) != 0ull) poison_window(a, w, lane);
+}
 // Stride-1 windows of one series share their convolution rows (reference quirk: the zero padding is
 // per WINDOW, modules.py:14,20): row t of window w equals the row s_w + t of the convolution over the whole segment
 // unless a tap leaves the window, i.e. for the first / last `pad` rows.  CF: convolution of the segment as one long
@@ -1018,6 +1064,13 @@ int launch_copy2d(const float* src, long lds, float* dst, long ldd, long R, int 
     const long total = R * ncols;
     if (total <= 0) return 0;
     hipLaunchKernelGGL(k_copy2d, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src, lds, dst, ldd, R, ncols);
+    LAUNCH_CHECK();
+    return 0;
+}
+int launch_poison_nonfinite(const NonFiniteArgs& a, hipStream_t s) {
+    if (a.n <= 0 || (!a.preds && !a.recons && !a.recons_last)) return 0;
+    if (a.bad) hipLaunchKernelGGL(k_poison_flagged, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_poison_nonfinite, dim3((unsigned)((a.n + 3) / 4)), dim3(256), 0, s, a);
     LAUNCH_CHECK();
     return 0;
 }
