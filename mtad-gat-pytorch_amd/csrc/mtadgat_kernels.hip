@@ -1,4 +1,4 @@
-// k_rowgemm (Linear layers), k_conv / k_conv_lds (ConvLayer), small copy kernels + launchers
+// k_rowgemm (Linear layers) and k_conv (ConvLayer) on shared GEMM cores, k_conv_lds, small copy kernels + launchers
 #include <cstdlib>
 #include "mtadgat_device.h"
 
@@ -72,8 +72,167 @@ __device__ __forceinline__ void rowgemm_epilogue(const RowGemmArgs& a, const f32
     }
 }
 
-// XV: the rows are read with 16-byte loads (row stride a multiple of 4 floats) -- a template parameter, not a run-time flag: with
-// both loaders in one body the compiler serialises the chunk's loads on the registers the two paths share
+// ---------------------------------------------------------------------------
+// Operand sources of the GEMM cores below: where a lane's four floats of K group (chunk, half) of its row come from.
+// Two halves, as feat4_raw / feat4_fix: raw() is the 16 bytes from a clamped address, issued chunks ahead; fix() masks that
+// value where it is consumed (looking at it right behind the load would wait for it, and for every load issued before it).
+// KC: features per chunk (8: fp32 MFMA, one K group; 16: split-bf16, two).  A chunk is named by its index q and the source's
+// cursor p for it (a source uses whichever it needs): first() is the cursor of chunk 0, step(p, q, qn) that of chunk qn (q or
+// q + 1) from that of chunk q.
+// ---------------------------------------------------------------------------
+// rows of X, zero beyond kvalid.  XV: 16-byte loads (row stride a multiple of 4 floats) -- a template parameter, not a run-time
+// flag: with both loaders in one body the compiler serialises the chunk's loads on the registers the two paths share
+template <int KC, bool XV>
+struct RowSource {
+    struct Pos {};                                    // (the chunk index says it all)
+    const float* __restrict__ x;
+    int kvalid, g;
+    __device__ __forceinline__ Pos first() const { return {}; }
+    __device__ __forceinline__ Pos step(Pos p, int, int) const { return p; }
+    __device__ __forceinline__ f32x4 raw(int q, Pos, int half) const { return feat4_raw<XV>(x, KC * q + 8 * half + 4 * g, kvalid); }
+    __device__ __forceinline__ f32x4 fix(f32x4 v, int q, Pos, int half) const { return feat4_fix<XV>(v, KC * q + 8 * half + 4 * g, kvalid); }
+};
+// implicit GEMM of the convolution: chunk (tap, cb) of output row t is channels KC cb .. of input row t + tap - pad of the
+// row's window, zero beyond F channels and outside the window.  vec: F and the row stride are multiples of 4 (one 16-byte
+// load: a group is whole or beyond the row); the other shapes take four clamped 4-byte loads.
+template <int KC>
+struct ConvSource {
+    struct Pos { int tap, cb; };
+    const float* __restrict__ xwin;
+    int t;
+    int pad, W, F, QF, g;
+    long ld;
+    bool vec;
+    __device__ __forceinline__ Pos first() const { return {0, 0}; }
+    __device__ __forceinline__ Pos step(Pos p, int q, int qn) const {
+        if (qn != q && ++p.cb == QF) { p.cb = 0; ++p.tap; }
+        return p;
+    }
+    __device__ __forceinline__ f32x4 raw(int, Pos p, int half) const {
+        const int tt = t + p.tap - pad;
+        const int c0 = KC * p.cb + 8 * half + 4 * g;
+        const int ttc = tt < 0 ? 0 : (tt < W ? tt : W - 1);
+        const float* row = xwin + (long)ttc * ld;
+        if (vec) return *reinterpret_cast<const f32x4*>(row + (c0 + 3 < F ? c0 : F - 4));
+        f32x4 v;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) v[s] = row[c0 + s < F ? c0 + s : F - 1];
+        return v;
+    }
+    __device__ __forceinline__ f32x4 fix(f32x4 v, int, Pos p, int half) const {
+        const int tt = t + p.tap - pad;
+        const int c0 = KC * p.cb + 8 * half + 4 * g;
+        const bool tok = tt >= 0 && tt < W;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) v[s] = (tok && c0 + s < F) ? v[s] : 0.f;
+        return v;
+    }
+};
+
+// ---------------------------------------------------------------------------
+// The one-wave GEMM cores.  A wave owns 32 rows; output tiles go NTB at a time, the passes n0 spread over gridDim.y (few rows:
+// so that the launch fills the machine); epi(acc, n0) stores the NTB accumulators.  Which kernel runs on which core:
+//   gemm_core_f32   k_rowgemm<NTB > 1>, k_conv
+//   gemm_core_x3    k_rowgemm_x3, k_conv_x3
+// The workgroup kernels of the split-bf16 mode, k_rowgemm_x3s and k_conv_x3s, are NOT on a shared core: they sit within
+// 3 - 5 registers of their 256-register budget, and built on one core (same ring, same waits, no scratch, 241 / 248 registers)
+// k_rowgemm_x3s ran 4 % slower under a different instruction schedule (profiles/gemm_cores.txt).  They are one pipeline
+// written twice, as the one-wave pairs were: a change to the ring slots, the two prefetch distances or the wait counts goes
+// into both, and both stay bit-identical to gemm_core_x3 (chunk order, terms per output element).
+// ---------------------------------------------------------------------------
+template <int NTB>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[NTB]) {
+#pragma unroll
+    for (int nb = 0; nb < NTB; ++nb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[nb][r] = 0.f;
+}
+// fp32 MFMA, one wave: the weight words ([tile][Q][64]) and the row's raw words of chunk q + 1 are in flight during chunk q
+template <int NTB, class Src, class Epi>
+__device__ __forceinline__ void gemm_core_f32(const f32x4* __restrict__ Wp, int Q, int NT, const Src& src, Epi&& epi) {
+    const int lane = threadIdx.x & 63;
+    for (int n0 = blockIdx.y * NTB; n0 < NT; n0 += NTB * gridDim.y) {
+        f32x16 acc[NTB];
+        zero_acc(acc);
+        typename Src::Pos p = src.first();
+        f32x4 xr = src.raw(0, p, 0);
+        f32x4 w[NTB];
+#pragma unroll
+        for (int nb = 0; nb < NTB; ++nb) {
+            const int n = (n0 + nb < NT) ? n0 + nb : NT - 1;
+            w[nb] = Wp[((long)n * Q) * 64 + lane];
+        }
+        for (int q = 0; q < Q; ++q) {
+            const int qn = (q + 1 < Q) ? q + 1 : q;
+            const typename Src::Pos pn = src.step(p, q, qn);
+            const f32x4 xn = src.raw(qn, pn, 0);
+            const f32x4 xv = src.fix(xr, q, p, 0);
+            f32x4 wn[NTB];
+#pragma unroll
+            for (int nb = 0; nb < NTB; ++nb) {
+                const int n = (n0 + nb < NT) ? n0 + nb : NT - 1;
+                wn[nb] = Wp[((long)n * Q + qn) * 64 + lane];
+            }
+#pragma unroll
+            for (int nb = 0; nb < NTB; ++nb) acc[nb] = mfma4(w[nb], xv, acc[nb]);
+            xr = xn; p = pn;
+#pragma unroll
+            for (int nb = 0; nb < NTB; ++nb) w[nb] = wn[nb];
+        }
+        epi(acc, n0);
+    }
+}
+// split-bf16, one wave: the K loop in 16-feature chunks -- the eight values a lane holds of a chunk are split into three bf16
+// pieces (split3), the weights come pre-split ([tile][Q][piece][64], derived on the device), six v_mfma_f32_32x32x16_bf16 per
+// chunk and tile (mfma_s3): 2.7 x less matrix time than the four fp32 MFMAs of two 8-feature chunks, products of 24-bit
+// significands.
+template <int NTB, class Src, class Epi>
+__device__ __forceinline__ void gemm_core_x3(const f32x4* __restrict__ Wp, int Q, int NT, const Src& src, Epi&& epi) {
+    const int lane = threadIdx.x & 63;
+    for (int n0 = blockIdx.y * NTB; n0 < NT; n0 += NTB * gridDim.y) {
+        f32x16 acc[NTB];
+        zero_acc(acc);
+        typename Src::Pos p = src.first();
+        f32x4 ra = src.raw(0, p, 0), rb = src.raw(0, p, 1);
+        f32x4 w[NTB][3];
+#pragma unroll
+        for (int nb = 0; nb < NTB; ++nb) {
+            const int n = (n0 + nb < NT) ? n0 + nb : NT - 1;
+#pragma unroll
+            for (int pc = 0; pc < 3; ++pc) w[nb][pc] = Wp[(((long)n * Q) * 3 + pc) * 64 + lane];
+        }
+        for (int q = 0; q < Q; ++q) {
+            const int qn = (q + 1 < Q) ? q + 1 : q;
+            const typename Src::Pos pn = src.step(p, q, qn);
+            const f32x4 ran = src.raw(qn, pn, 0), rbn = src.raw(qn, pn, 1);
+            f32x4 xp[3];
+            split3(src.fix(ra, q, p, 0), src.fix(rb, q, p, 1), xp[0], xp[1], xp[2]);
+#pragma unroll
+            for (int nb = 0; nb < NTB; ++nb) {
+                acc[nb] = mfma_s3(w[nb], xp, acc[nb]);
+                const int n = (n0 + nb < NT) ? n0 + nb : NT - 1;
+#pragma unroll
+                for (int pc = 0; pc < 3; ++pc) w[nb][pc] = Wp[(((long)n * Q + qn) * 3 + pc) * 64 + lane];       // the next chunk's words, behind this tile's MFMAs
+            }
+            ra = ran; rb = rbn; p = pn;
+        }
+        epi(acc, n0);
+    }
+}
+
+// workgroup barrier for an LDS hand-off: this wave's LDS traffic is done, vector-memory requests stay in flight
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// LDS-DMA of three consecutive KiB (global_load_lds_dwordx4: 16 bytes per lane from uniform base + per-lane byte offset to LDS byte
+// address M0 + 16 lane; the immediate offset moves source and destination alike -- as in k_gru_cm).  M0 is written and restored here.
+__device__ __forceinline__ void glds3(const void* sbase, unsigned voff, unsigned ldsdst) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
+                 "global_load_lds_dwordx4 %1, %2 offset:1024\n\tglobal_load_lds_dwordx4 %1, %2 offset:2048\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(ldsdst) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+
 template <int NTB, bool XV>
 __global__ __launch_bounds__(64) void k_rowgemm(const RowGemmArgs a) {
     const int lane = threadIdx.x;
@@ -81,18 +240,15 @@ __global__ __launch_bounds__(64) void k_rowgemm(const RowGemmArgs a) {
     const long row = (long)blockIdx.x * 32 + i;
     const long rowc = row < a.R ? row : a.R - 1;
     const float* __restrict__ xrow = a.X + rowc * a.ldx;
-    const f32x4* __restrict__ Wp = a.Wp;
-    const int Q = a.Q;
-
-    // few rows (small batches): the output tiles are spread over gridDim.y waves so that the launch fills the machine
-    for (int n0 = blockIdx.y * NTB; n0 < a.NT; n0 += NTB * gridDim.y) {
-        f32x16 acc[NTB];
-#pragma unroll
-        for (int nb = 0; nb < NTB; ++nb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[nb][r] = 0.f;
-
-        if constexpr (NTB == 1) {
+    if constexpr (NTB > 1) {
+        gemm_core_f32<NTB>(a.Wp, a.Q, a.NT, RowSource<8, XV>{xrow, a.Kvalid, g},
+                           [&](const f32x16 (&acc)[NTB], int n0) { rowgemm_epilogue<NTB>(a, acc, n0, row, rowc, g); });
+    } else {
+        const f32x4* __restrict__ Wp = a.Wp;
+        const int Q = a.Q;
+        for (int n0 = blockIdx.y; n0 < a.NT; n0 += gridDim.y) {
+            f32x16 acc[1];
+            zero_acc(acc);
             // one tile per wave: the launches that use this build are latency chains (a head Linear on 256 rows: a few waves, nothing
             // else on their SIMD), so the chunks go four at a time -- every load of the four issued before the first MFMA, one
             // memory round trip per four chunks instead of one per chunk (19 chunks of a 150-wide layer: 20 -> 8 us per launch)
@@ -110,39 +266,12 @@ __global__ __launch_bounds__(64) void k_rowgemm(const RowGemmArgs a) {
                 for (int u = 0; u < U; ++u)
                     if (q + u < Q) acc[0] = mfma4(w[u], feat4_fix<XV>(xr[u], 8 * (q + u) + 4 * g, a.Kvalid), acc[0]);
             }
-        } else {
-        f32x4 xr = feat4_raw<XV>(xrow, 4 * g, a.Kvalid);
-        f32x4 w[NTB];
-#pragma unroll
-        for (int nb = 0; nb < NTB; ++nb) {
-            const int n = (n0 + nb < a.NT) ? n0 + nb : a.NT - 1;
-            w[nb] = Wp[((long)n * Q) * 64 + lane];
+            rowgemm_epilogue<1>(a, acc, n0, row, rowc, g);
         }
-        for (int q = 0; q < Q; ++q) {
-            const int qn = (q + 1 < Q) ? q + 1 : q;
-            const f32x4 xn = feat4_raw<XV>(xrow, 8 * qn + 4 * g, a.Kvalid);        // raw: looked at one chunk later
-            const f32x4 xv = feat4_fix<XV>(xr, 8 * q + 4 * g, a.Kvalid);
-            f32x4 wn[NTB];
-#pragma unroll
-            for (int nb = 0; nb < NTB; ++nb) {
-                const int n = (n0 + nb < a.NT) ? n0 + nb : a.NT - 1;
-                wn[nb] = Wp[((long)n * Q + qn) * 64 + lane];
-            }
-#pragma unroll
-            for (int nb = 0; nb < NTB; ++nb) acc[nb] = mfma4(w[nb], xv, acc[nb]);
-            xr = xn;
-#pragma unroll
-            for (int nb = 0; nb < NTB; ++nb) w[nb] = wn[nb];
-        }
-        }
-        rowgemm_epilogue<NTB>(a, acc, n0, row, rowc, g);
     }
 }
 
-// split-bf16 build: the same rows / tiles, the K loop in 16-feature chunks -- the eight values a lane holds of a chunk are split
-// into three bf16 pieces (split3), the weights come pre-split ([tile][Q16][piece][64], derived on the device), six
-// v_mfma_f32_32x32x16_bf16 per chunk and tile (mfma_s3): 2.7 x less matrix time than the four fp32 MFMAs of two 8-feature
-// chunks, products of 24-bit significands.  Used by the data-gradient products of mtadgat_backward (d X = d Y W over all
+// split-bf16 build of the same rows / tiles.  Used by the data-gradient products of mtadgat_backward (d X = d Y W over all
 // (window, step) rows), which ran at the fp32-MFMA rate.
 template <int NTB, bool XV>
 __global__ __launch_bounds__(64) void k_rowgemm_x3(const RowGemmArgs a) {
@@ -151,53 +280,9 @@ __global__ __launch_bounds__(64) void k_rowgemm_x3(const RowGemmArgs a) {
     const long row = (long)blockIdx.x * 32 + i;
     const long rowc = row < a.R ? row : a.R - 1;
     const float* __restrict__ xrow = a.X + rowc * a.ldx;
-    const f32x4* __restrict__ Wp = a.Wp3;
-    const int Q = a.Q16;
-    for (int n0 = blockIdx.y * NTB; n0 < a.NT; n0 += NTB * gridDim.y) {
-        f32x16 acc[NTB];
-#pragma unroll
-        for (int nb = 0; nb < NTB; ++nb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[nb][r] = 0.f;
-        f32x4 ra = feat4_raw<XV>(xrow, 4 * g, a.Kvalid), rb = feat4_raw<XV>(xrow, 8 + 4 * g, a.Kvalid);
-        f32x4 w[NTB][3];
-#pragma unroll
-        for (int nb = 0; nb < NTB; ++nb) {
-            const int n = (n0 + nb < a.NT) ? n0 + nb : a.NT - 1;
-#pragma unroll
-            for (int pc = 0; pc < 3; ++pc) w[nb][pc] = Wp[(((long)n * Q) * 3 + pc) * 64 + lane];
-        }
-        for (int q = 0; q < Q; ++q) {
-            const int qn = (q + 1 < Q) ? q + 1 : q;
-            const f32x4 ran = feat4_raw<XV>(xrow, 16 * qn + 4 * g, a.Kvalid), rbn = feat4_raw<XV>(xrow, 16 * qn + 8 + 4 * g, a.Kvalid);    // raw
-            const f32x4 xa = feat4_fix<XV>(ra, 16 * q + 4 * g, a.Kvalid), xb = feat4_fix<XV>(rb, 16 * q + 8 + 4 * g, a.Kvalid);
-            f32x4 xp[3];
-            split3(xa, xb, xp[0], xp[1], xp[2]);
-#pragma unroll
-            for (int nb = 0; nb < NTB; ++nb) {
-                acc[nb] = mfma_s3(w[nb], xp, acc[nb]);
-                const int n = (n0 + nb < a.NT) ? n0 + nb : a.NT - 1;
-#pragma unroll
-                for (int pc = 0; pc < 3; ++pc) w[nb][pc] = Wp[(((long)n * Q + qn) * 3 + pc) * 64 + lane];       // the next chunk's words, behind this tile's MFMAs
-            }
-            ra = ran; rb = rbn;
-        }
-        rowgemm_epilogue<NTB>(a, acc, n0, row, rowc, g);
-    }
+    gemm_core_x3<NTB>(a.Wp3, a.Q16, a.NT, RowSource<16, XV>{xrow, a.Kvalid, g},
+                      [&](const f32x16 (&acc)[NTB], int n0) { rowgemm_epilogue<NTB>(a, acc, n0, row, rowc, g); });
 }
-
-// workgroup barrier for an LDS hand-off: this wave's LDS traffic is done, vector-memory requests stay in flight
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-// LDS-DMA of three consecutive KiB (global_load_lds_dwordx4: 16 bytes per lane from uniform base + per-lane byte offset to LDS byte
-// address M0 + 16 lane; the immediate offset moves source and destination alike -- as in k_gru_cm).  M0 is written and restored here.
-__device__ __forceinline__ void glds3(const void* sbase, unsigned voff, unsigned ldsdst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
-                 "global_load_lds_dwordx4 %1, %2 offset:1024\n\tglobal_load_lds_dwordx4 %1, %2 offset:2048\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(ldsdst) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // Many rows: a workgroup of four waves owns 256 rows (two row tiles per wave) x four output tiles and shares the weight words of a
 // chunk through LDS.  In k_rowgemm_x3 every wave pulls every weight word through the CU's vector L1 itself: 12 KB per 24 MFMAs,
@@ -291,193 +376,98 @@ __global__ __launch_bounds__(256, 2) void k_rowgemm_x3s(const RowGemmArgs a) {
 // Implicit GEMM: data rows = (window, t), K = taps x Fp, loaded straight from x.
 // Writes xc (b*W, Fp), its transpose xcT (b*F, Wp) and columns [0,F) of h_cat.
 // ---------------------------------------------------------------------------
+// element offset of window w in a.X.  gather mode: the window is a view of the device-resident series
+// (SlidingWindowDataset.__getitem__, utils.py:114-117); else the windows lie W rows of ld elements apart
+template <class Args>
+__device__ __forceinline__ long window_offset(const Args& a, long w, long ld) {
+    return a.gather ? (a.starts ? a.starts[w] : a.start0 + w * a.stride) * (long)a.F : w * (long)a.W * ld;
+}
+// zero the alignment padding of an h_cat row (the GRU reads it unguarded)
+__device__ __forceinline__ void zero_hcat_pad(float* __restrict__ hcat, long row, int F, int Dp) {
+    for (int c = 3 * F; c < Dp; ++c) hcat[row * Dp + c] = 0.f;
+}
+struct ConvRow { long row, win; int t; };             // output row, its window (of the row clamped into the batch) and step
+__device__ __forceinline__ ConvRow conv_row(const ConvArgs& a, long row, long R) {
+    const long rowc = row < R ? row : R - 1;
+    const long win = rowc / a.W;
+    return {row, win, (int)(rowc - win * a.W)};
+}
+__device__ __forceinline__ void zero_hcat_pad(const ConvArgs& a, const ConvRow& r, long R, int g) {
+    if (a.HCAT && r.row < R && g == 0) zero_hcat_pad(a.HCAT, r.row, a.F, a.Dp);
+}
+template <int KC>
+__device__ __forceinline__ ConvSource<KC> conv_source(const ConvArgs& a, const ConvRow& r, long ld, int QF, int g) {
+    ConvSource<KC> src;
+    src.xwin = a.X + window_offset(a, r.win, ld); src.t = r.t;
+    src.pad = a.pad; src.W = a.W; src.F = a.F; src.QF = QF; src.g = g;
+    src.ld = ld; src.vec = (a.F & 3) == 0 && (ld & 3) == 0;
+    return src;
+}
+// bias + ReLU (neither under a.linear) and the stores of one row's NTB tiles to whichever of XC / XCT / HCAT / Y are set.
+// STAGED (k_conv_lds): rows of h_cat are 16-byte aligned there -- one store per 4 channels -- and the largest value stored
+// is returned (outputs are >= 0: ReLU)
+template <int NTB, bool STAGED>
+__device__ __forceinline__ float conv_epilogue(const ConvArgs& a, const f32x16 (&acc)[NTB], int n0, const ConvRow& r, long R, int g) {
+    float vmx = 0.f;
+#pragma unroll
+    for (int nb = 0; nb < NTB; ++nb) {
+        if (n0 + nb >= a.NT) break;
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const int col = 32 * (n0 + nb) + 8 * m + 4 * g;
+            const f32x4 bv = a.linear ? f32x4{0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const f32x4*>(a.bias + col);
+            f32x4 v;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) v[s] = a.linear ? acc[nb][4 * m + s] : fmaxf(acc[nb][4 * m + s] + bv[s], 0.f);
+            if (r.row < R) {
+                const bool wide = STAGED && col + 3 < a.F;
+                if constexpr (STAGED) {
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) vmx = (col + s < a.F) ? fmaxf(vmx, v[s]) : vmx;
+                    if (a.HCAT && wide) *reinterpret_cast<f32x4*>(a.HCAT + r.row * a.Dp + col) = v;
+                }
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    const int o = col + s;
+                    if (o < a.F) {
+                        if (a.XC) a.XC[r.row * a.Fp + o] = v[s];
+                        if (a.XCT) a.XCT[(r.win * a.F + o) * (long)a.Wpad + r.t] = v[s];
+                        if (a.HCAT && !wide) a.HCAT[r.row * a.Dp + o] = v[s];
+                        if (a.Y) a.Y[r.row * a.F + o] = v[s];
+                    }
+                }
+            }
+        }
+    }
+    return vmx;
+}
+
+// straight from memory (rows too long for the LDS-staged kernels): fp32 operands.  Also the input gradient of wide windows
+// (launch_conv_dx_gemm: row stride a.ldx, linear epilogue)
 template <int NTB>
 __global__ __launch_bounds__(64) void k_conv(const ConvArgs a) {
     const int lane = threadIdx.x;
-    const int i = lane & 31, g = lane >> 5;
-    const long row = (long)blockIdx.x * 32 + i;
+    const int g = lane >> 5;
     const long R = a.B * a.W;
-    const long rowc = row < R ? row : R - 1;
-    const long win = rowc / a.W;
-    const int t = (int)(rowc - win * a.W);
-    // gather mode: the window is a view of the device-resident series (SlidingWindowDataset.__getitem__, utils.py:114-117)
-    const long ldx = a.ldx ? a.ldx : a.F;
-    const float* __restrict__ xwin = a.gather ? a.X + (a.starts ? a.starts[win] : a.start0 + win * a.stride) * (long)a.F
-                                              : a.X + win * (long)a.W * ldx;
+    const ConvRow r = conv_row(a, (long)blockIdx.x * 32 + (lane & 31), R);
+    zero_hcat_pad(a, r, R, g);
     const int QF = a.Fp >> 3;
-    const int Q = a.taps * QF;
-    const f32x4* __restrict__ Wp = a.Wp;
-
-    if (a.HCAT && row < R && g == 0)      // zero the alignment padding of the h_cat row (the GRU reads it unguarded)
-        for (int c = 3 * a.F; c < a.Dp; ++c) a.HCAT[row * a.Dp + c] = 0.f;
-    // unconditional loads from clamped addresses, masked afterwards (a guarded load is a branch with a full memory
-    // round trip per chunk); one 16-byte load when the rows allow it
-    const bool xvec4 = (a.F & 3) == 0 && (ldx & 3) == 0;
-    auto loadx = [&](int q) -> f32x4 {
-        const int tap = q / QF;
-        const int cb = q - tap * QF;
-        const int tt = t + tap - a.pad;
-        const int c0 = 8 * cb + 4 * g;
-        const bool tok = tt >= 0 && tt < a.W;
-        const int ttc = tt < 0 ? 0 : (tt < a.W ? tt : a.W - 1);
-        const float* p = xwin + (long)ttc * ldx;
-        f32x4 v;
-        if (xvec4) {
-            const int cc = c0 + 3 < a.F ? c0 : a.F - 4;
-            v = *reinterpret_cast<const f32x4*>(p + cc);
-        } else {
-#pragma unroll
-            for (int s4 = 0; s4 < 4; ++s4) v[s4] = p[c0 + s4 < a.F ? c0 + s4 : a.F - 1];
-        }
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) v[s4] = (tok && c0 + s4 < a.F) ? v[s4] : 0.f;
-        return v;
-    };
-
-    for (int n0 = 0; n0 < a.NT; n0 += NTB) {
-        f32x16 acc[NTB];
-#pragma unroll
-        for (int nb = 0; nb < NTB; ++nb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[nb][r] = 0.f;
-
-        f32x4 xv = loadx(0);
-        f32x4 w[NTB];
-#pragma unroll
-        for (int nb = 0; nb < NTB; ++nb) {
-            const int n = (n0 + nb < a.NT) ? n0 + nb : a.NT - 1;
-            w[nb] = Wp[((long)n * Q) * 64 + lane];
-        }
-        for (int q = 0; q < Q; ++q) {
-            const int qn = (q + 1 < Q) ? q + 1 : q;
-            const f32x4 xn = loadx(qn);
-            f32x4 wn[NTB];
-#pragma unroll
-            for (int nb = 0; nb < NTB; ++nb) {
-                const int n = (n0 + nb < a.NT) ? n0 + nb : a.NT - 1;
-                wn[nb] = Wp[((long)n * Q + qn) * 64 + lane];
-            }
-#pragma unroll
-            for (int nb = 0; nb < NTB; ++nb) acc[nb] = mfma4(w[nb], xv, acc[nb]);
-            xv = xn;
-#pragma unroll
-            for (int nb = 0; nb < NTB; ++nb) w[nb] = wn[nb];
-        }
-#pragma unroll
-        for (int nb = 0; nb < NTB; ++nb) {
-            if (n0 + nb >= a.NT) break;
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                const int col = 32 * (n0 + nb) + 8 * m + 4 * g;
-                const f32x4 bv = a.linear ? f32x4{0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const f32x4*>(a.bias + col);
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    const int o = col + s;
-                    const float v = a.linear ? acc[nb][4 * m + s] : fmaxf(acc[nb][4 * m + s] + bv[s], 0.f);
-                    if (row < R && o < a.F) {
-                        if (a.XC) a.XC[row * a.Fp + o] = v;
-                        if (a.XCT) a.XCT[(win * a.F + o) * (long)a.Wpad + t] = v;
-                        if (a.HCAT) a.HCAT[row * a.Dp + o] = v;
-                        if (a.Y) a.Y[row * a.F + o] = v;
-                    }
-                }
-            }
-        }
-    }
+    gemm_core_f32<NTB>(a.Wp, a.taps * QF, a.NT, conv_source<8>(a, r, a.ldx ? a.ldx : a.F, QF, g),
+                       [&](const f32x16 (&acc)[NTB], int n0) { conv_epilogue<NTB, false>(a, acc, n0, r, R, g); });
 }
-
-// conv straight from memory on split-bf16 operands (wide models, whose rows do not fit the LDS-staged kernels): the K loop
-// in 16-channel chunks of one tap, the eight input values a lane holds of a chunk split into three bf16 pieces (split3), the
-// weights pre-split on the device ([tile][taps Fq / 16][3][64], Fq = F rounded up to 16), six v_mfma_f32_32x32x16_bf16 per
-// chunk and tile (mfma_s3) instead of eight v_mfma_f32_32x32x2_f32: 2.7 x less matrix time, products of 24-bit significands.
+// ... on split-bf16 operands: 16-channel chunks of one tap, the weights pre-split on the device ([tile][taps Fq / 16][3][64],
+// Fq = F rounded up to 16)
 template <int NTB>
 __global__ __launch_bounds__(64) void k_conv_x3(const ConvArgs a) {
     const int lane = threadIdx.x;
-    const int i = lane & 31, g = lane >> 5;
-    const long row = (long)blockIdx.x * 32 + i;
+    const int g = lane >> 5;
     const long R = a.B * a.W;
-    const long rowc = row < R ? row : R - 1;
-    const long win = rowc / a.W;
-    const int t = (int)(rowc - win * a.W);
-    const float* __restrict__ xwin = a.gather ? a.X + (a.starts ? a.starts[win] : a.start0 + win * a.stride) * (long)a.F
-                                              : a.X + win * (long)a.W * a.F;
+    const ConvRow r = conv_row(a, (long)blockIdx.x * 32 + (lane & 31), R);
+    zero_hcat_pad(a, r, R, g);
     const int QF = a.Fq >> 4;
-    const int Q = a.taps * QF;
-    const f32x4* __restrict__ Wp = a.Wp3;
-    if (a.HCAT && row < R && g == 0)
-        for (int c = 3 * a.F; c < a.Dp; ++c) a.HCAT[row * a.Dp + c] = 0.f;
-    const bool xvec4 = (a.F & 3) == 0;
-    auto loadx = [&](int q, int half) -> f32x4 {      // channels 16 cb + 8 half + 4 g .. + 3 of input row t + tap - pad
-        const int tap = q / QF;
-        const int cb = q - tap * QF;
-        const int tt = t + tap - a.pad;
-        const int c0 = 16 * cb + 8 * half + 4 * g;
-        const bool tok = tt >= 0 && tt < a.W;
-        const int ttc = tt < 0 ? 0 : (tt < a.W ? tt : a.W - 1);
-        const float* p = xwin + (long)ttc * a.F;
-        f32x4 v;
-        if (xvec4) {
-            const int cc = c0 + 3 < a.F ? c0 : a.F - 4;
-            v = *reinterpret_cast<const f32x4*>(p + cc);
-        } else {
-#pragma unroll
-            for (int s4 = 0; s4 < 4; ++s4) v[s4] = p[c0 + s4 < a.F ? c0 + s4 : a.F - 1];
-        }
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) v[s4] = (tok && c0 + s4 < a.F) ? v[s4] : 0.f;
-        return v;
-    };
-    for (int n0 = 0; n0 < a.NT; n0 += NTB) {
-        f32x16 acc[NTB];
-#pragma unroll
-        for (int nb = 0; nb < NTB; ++nb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[nb][r] = 0.f;
-        f32x4 xa = loadx(0, 0), xb = loadx(0, 1);
-        f32x4 w[NTB][3];
-#pragma unroll
-        for (int nb = 0; nb < NTB; ++nb) {
-            const int n = (n0 + nb < a.NT) ? n0 + nb : a.NT - 1;
-#pragma unroll
-            for (int pc = 0; pc < 3; ++pc) w[nb][pc] = Wp[(((long)n * Q) * 3 + pc) * 64 + lane];
-        }
-        for (int q = 0; q < Q; ++q) {
-            const int qn = (q + 1 < Q) ? q + 1 : q;
-            const f32x4 xan = loadx(qn, 0), xbn = loadx(qn, 1);
-            f32x4 xp[3];
-            split3(xa, xb, xp[0], xp[1], xp[2]);
-#pragma unroll
-            for (int nb = 0; nb < NTB; ++nb) {
-                acc[nb] = mfma_s3(w[nb], xp, acc[nb]);
-                const int n = (n0 + nb < a.NT) ? n0 + nb : a.NT - 1;
-#pragma unroll
-                for (int pc = 0; pc < 3; ++pc) w[nb][pc] = Wp[(((long)n * Q + qn) * 3 + pc) * 64 + lane];
-            }
-            xa = xan; xb = xbn;
-        }
-#pragma unroll
-        for (int nb = 0; nb < NTB; ++nb) {
-            if (n0 + nb >= a.NT) break;
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                const int col = 32 * (n0 + nb) + 8 * m + 4 * g;
-                const f32x4 bv = *reinterpret_cast<const f32x4*>(a.bias + col);
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    const int o = col + s;
-                    const float v = fmaxf(acc[nb][4 * m + s] + bv[s], 0.f);
-                    if (row < R && o < a.F) {
-                        if (a.XC) a.XC[row * a.Fp + o] = v;
-                        if (a.XCT) a.XCT[(win * a.F + o) * (long)a.Wpad + t] = v;
-                        if (a.HCAT) a.HCAT[row * a.Dp + o] = v;
-                        if (a.Y) a.Y[row * a.F + o] = v;
-                    }
-                }
-            }
-        }
-    }
+    gemm_core_x3<NTB>(a.Wp3, a.taps * QF, a.NT, conv_source<16>(a, r, a.F, QF, g),
+                      [&](const f32x16 (&acc)[NTB], int n0) { conv_epilogue<NTB, false>(a, acc, n0, r, R, g); });
 }
-
 // k_conv_x3 for many rows, as k_rowgemm_x3s: a workgroup of four waves owns 256 output rows (two row tiles per wave) x four
 // output tiles, the weight words of a chunk go through LDS once per workgroup and feed two MFMAs per LDS read.  F a multiple of 4.
 // Same chunk order and terms per output element: results are bit-identical to k_conv_x3.
@@ -493,14 +483,10 @@ __global__ __launch_bounds__(256, 2) void k_conv_x3s(const ConvArgs a) {
     const float* __restrict__ xwin[2];
 #pragma unroll
     for (int rt = 0; rt < 2; ++rt) {
-        row[rt] = (long)blockIdx.x * 256 + 64 * wave + 32 * rt + i;
-        const long rowc = row[rt] < R ? row[rt] : R - 1;
-        win[rt] = rowc / a.W;
-        t[rt] = (int)(rowc - win[rt] * a.W);
-        xwin[rt] = a.gather ? a.X + (a.starts ? a.starts[win[rt]] : a.start0 + win[rt] * a.stride) * (long)a.F
-                            : a.X + win[rt] * (long)a.W * a.F;
-        if (a.HCAT && row[rt] < R && g == 0)
-            for (int c = 3 * a.F; c < a.Dp; ++c) a.HCAT[row[rt] * a.Dp + c] = 0.f;
+        const ConvRow r = conv_row(a, (long)blockIdx.x * 256 + 64 * wave + 32 * rt + i, R);
+        row[rt] = r.row; win[rt] = r.win; t[rt] = r.t;
+        xwin[rt] = a.X + window_offset(a, win[rt], a.F);
+        zero_hcat_pad(a, r, R, g);
     }
     const int QF = a.Fq >> 4;
     const int Q = a.taps * QF;
@@ -608,9 +594,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_x3s(const ConvArgs a) {
 // input row `taps` times with 4-byte gathers (PMC: 5-9x FETCH amplification, TA-bound).
 // BF: bf16 operand build -- 16 input channels per chunk (K index = tap * Fq + channel, Fq = F rounded up to 16),
 // the staged fp32 rows are converted on the way into the matrix unit, fp32 accumulation.
-// X3 (with the bf16 chunk geometry): split-bf16 operands -- three weight pieces per chunk, the staged fp32 input split
-// where it is consumed, six bf16 MFMAs per chunk and tile (mtadgat_device.h)
-template <int NTB, bool BF = false, bool X3 = false>
+template <int NTB, bool BF>
 __global__ __launch_bounds__(256) void k_conv_lds(const ConvArgs a) {
     // blockDim.x / 64 independent waves per workgroup, each with its own 32 output rows and LDS slice:
     // one-wave workgroups are launched too slowly to keep the matrix pipes fed at ~50 us per wave
@@ -621,10 +605,8 @@ __global__ __launch_bounds__(256) void k_conv_lds(const ConvArgs a) {
     const int i = lane & 31, g = lane >> 5;
     const long R = a.B * a.W;
     const long r0 = ((long)blockIdx.x * nwv + wv) * 32;
-    const long row = r0 + i;
-    const long rowc = row < R ? row : R - 1;
-    const long win = rowc / a.W;
-    const int t = (int)(rowc - win * a.W);
+    const ConvRow r = conv_row(a, r0 + i, R);
+    const int t = r.t;
     const int Fld = a.Fq + 4;
     const int nrow = 32 + a.taps - 1;
     // source row of LDS row rr: flat row r0 - pad + rr of the (B*W, F) batch; in gather mode the windows
@@ -703,22 +685,11 @@ __global__ __launch_bounds__(256) void k_conv_lds(const ConvArgs a) {
     const int QF = BF ? a.Fq >> 4 : a.Fq >> 3;
     const int Q = a.taps * QF;
     const f32x4* __restrict__ Wp = a.Wp;
-    if (a.HCAT && row < R && g == 0)      // zero the alignment padding of the h_cat row (the GRU reads it unguarded)
-        for (int c = 3 * a.F; c < a.Dp; ++c) a.HCAT[row * a.Dp + c] = 0.f;
+    zero_hcat_pad(a, r, R, g);
     // B operand of chunk (tap, cb): input row i + tap of the staged block, columns 8 cb + 4 g .. +3 (bf16 build: the
     // lane's eight columns of the 16-channel chunk, converted); rows of the neighbouring window count as zero
     // padding (per window, modules.py:14,20)
     const float* __restrict__ xrow = static_cast<const float*>(__builtin_assume_aligned(xs, 16)) + i * Fld + 4 * g;
-    constexpr int NP = X3 ? 3 : 1;
-    auto loadx3 = [&](int tap, int cb, f32x4 (&xs)[3]) {
-        const int tt = t + tap - a.pad;
-        const bool ok = tt >= 0 && tt < a.W;
-        f32x4 lo = *reinterpret_cast<const f32x4*>(xrow + tap * Fld + 16 * cb);
-        f32x4 hi = *reinterpret_cast<const f32x4*>(xrow + tap * Fld + 16 * cb + 8);
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) { lo[s4] = ok ? lo[s4] : 0.f; hi[s4] = ok ? hi[s4] : 0.f; }
-        split3(lo, hi, xs[0], xs[1], xs[2]);
-    };
     auto loadx = [&](int tap, int cb) -> f32x4 {
         const int tt = t + tap - a.pad;
         const bool ok = tt >= 0 && tt < a.W;
@@ -737,49 +708,20 @@ __global__ __launch_bounds__(256) void k_conv_lds(const ConvArgs a) {
     float vmx = 0.f;                      // largest output of this lane (outputs are >= 0: ReLU)
     for (int n0 = 0; n0 < a.NT; n0 += NTB) {
         f32x16 acc[NTB];
-#pragma unroll
-        for (int nb = 0; nb < NTB; ++nb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[nb][r] = 0.f;
+        zero_acc(acc);
         const f32x4* wq[NTB];
 #pragma unroll
         for (int nb = 0; nb < NTB; ++nb) {
             const int n = (n0 + nb < a.NT) ? n0 + nb : a.NT - 1;
-            wq[nb] = Wp + ((long)n * Q) * (64 * NP) + lane;
+            wq[nb] = Wp + ((long)n * Q) * 64 + lane;
         }
         // two register sets in turn (no copies): the weights of chunk q + 1 are in flight during the MFMAs
         // of chunk q
         int tap = 0, cb = 0;
-        if constexpr (X3) {
-            // chunk = [piece][64 lanes] words; the pieces of chunk q + 1 are requested before the MFMAs of chunk q
-            f32x4 wa[NTB][3], wb[NTB][3];
-#pragma unroll
-            for (int nb = 0; nb < NTB; ++nb)
-#pragma unroll
-                for (int pc = 0; pc < 3; ++pc) wa[nb][pc] = wq[nb][pc * 64];
-            for (int q = 0; q < Q; ++q) {
-                const int q1 = q + 1 < Q ? q + 1 : q;
-#pragma unroll
-                for (int nb = 0; nb < NTB; ++nb)
-#pragma unroll
-                    for (int pc = 0; pc < 3; ++pc) wb[nb][pc] = wq[nb][((long)q1 * 3 + pc) * 64];
-                f32x4 xs[3];
-                loadx3(tap, cb, xs);
-                if (++cb == QF) { cb = 0; ++tap; }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int nb = 0; nb < NTB; ++nb) acc[nb] = mfma_s3(wa[nb], xs, acc[nb]);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int nb = 0; nb < NTB; ++nb)
-#pragma unroll
-                    for (int pc = 0; pc < 3; ++pc) wa[nb][pc] = wb[nb][pc];
-            }
-        }
         f32x4 w0[NTB], w1[NTB];
 #pragma unroll
         for (int nb = 0; nb < NTB; ++nb) w0[nb] = wq[nb][0];
-        for (int q = 0; !X3 && q < Q; q += 2) {
+        for (int q = 0; q < Q; q += 2) {
             const int q1 = q + 1 < Q ? q + 1 : q;
 #pragma unroll
             for (int nb = 0; nb < NTB; ++nb) w1[nb] = wq[nb][(long)q1 * 64];
@@ -801,41 +743,7 @@ __global__ __launch_bounds__(256) void k_conv_lds(const ConvArgs a) {
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-#pragma unroll
-        for (int nb = 0; nb < NTB; ++nb) {
-            if (n0 + nb >= a.NT) break;
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                const int col = 32 * (n0 + nb) + 8 * m + 4 * g;
-                const f32x4 bv = *reinterpret_cast<const f32x4*>(a.bias + col);
-                f32x4 v;
-#pragma unroll
-                for (int s4 = 0; s4 < 4; ++s4) v[s4] = fmaxf(acc[nb][4 * m + s4] + bv[s4], 0.f);
-                if (row < R) {
-#pragma unroll
-                    for (int s4 = 0; s4 < 4; ++s4) vmx = (col + s4 < a.F) ? fmaxf(vmx, v[s4]) : vmx;
-                    if (a.HCAT) {   // rows of h_cat are 16-byte aligned: one store per 4 channels
-                        float* hp = a.HCAT + row * a.Dp + col;
-                        if (col + 3 < a.F) {
-                            *reinterpret_cast<f32x4*>(hp) = v;
-                        } else {
-#pragma unroll
-                            for (int s4 = 0; s4 < 4; ++s4)
-                                if (col + s4 < a.F) hp[s4] = v[s4];
-                        }
-                    }
-#pragma unroll
-                    for (int s4 = 0; s4 < 4; ++s4) {
-                        const int o = col + s4;
-                        if (o < a.F) {
-                            if (a.XC) a.XC[row * a.Fp + o] = v[s4];
-                            if (a.XCT) a.XCT[(win * a.F + o) * (long)a.Wpad + t] = v[s4];
-                            if (a.Y) a.Y[row * a.F + o] = v[s4];
-                        }
-                    }
-                }
-            }
-        }
+        vmx = fmaxf(vmx, conv_epilogue<NTB, true>(a, acc, n0, r, R, g));
     }
     if (a.vmax) {
         // range of the node values for the attention layers' fp16 operand pieces: one atomic per wave at most, and only
@@ -891,7 +799,7 @@ __global__ void __launch_bounds__(256) k_poison_nonfinite(NonFiniteArgs a) {
     const int lane = threadIdx.x & 63;
     if (w >= a.n) return;
     const long WF = (long)a.W * a.F;
-    const long at = (a.gather ? (a.starts ? a.starts[w] : a.start0 + w * a.stride) * a.F : w * WF);
+    const long at = window_offset(a, w, a.F);
     bool bad = false;
     if (a.x_bf16) {
         const unsigned short* x = reinterpret_cast<const unsigned short*>(a.X) + at;
@@ -927,8 +835,7 @@ __global__ void k_conv_scatter(const float* __restrict__ CF, const float* __rest
         for (int e = 0; e < 4; ++e)
             if (c + e < F) dst[e] = v[e];
     }
-    if (c == 0)
-        for (int k = 3 * F; k < Dp; ++k) HCAT[row * Dp + k] = 0.f;
+    if (c == 0) zero_hcat_pad(HCAT, row, F, Dp);
 }
 // transpose per window: src (B, R, C) with row stride lds -> dst (B, C, R) with row stride ldd
 __global__ void k_transpose_win(const float* __restrict__ src, long lds, float* __restrict__ dst, long ldd, long B, int R,
@@ -946,6 +853,13 @@ __global__ void k_transpose_win(const float* __restrict__ src, long lds, float* 
 static int g_gemm_lds_off = getenv("MTADGAT_ROWGEMM_NOLDS") ? 1 : 0;
 void set_gemm_lds_off(int off) { g_gemm_lds_off = off; }
 
+// gridDim.y of a launch that takes four output tiles per pass: the groups of four are spread over as many workgroups as give
+// the launch `target` of them (`grid` row blocks each), at most one group per pass
+static unsigned tile_split(int NT, unsigned grid, long target) {
+    const long groups4 = (NT + 3) / 4, want = (target + grid - 1) / grid;
+    return (unsigned)(want < 1 ? 1 : (want > groups4 ? groups4 : want));
+}
+
 template <bool XV>
 static void launch_rowgemm_xv(const RowGemmArgs& a, hipStream_t s) {
     const unsigned grid = (unsigned)((a.R + 31) / 32);
@@ -955,14 +869,10 @@ static void launch_rowgemm_xv(const RowGemmArgs& a, hipStream_t s) {
         if (XV && a.NT >= 4 && a.R >= 64 * 2048 && !s_off) {
             // plenty of rows of whole 16-byte words: 256 per workgroup, the chunk's weight words through LDS (k_rowgemm_x3s)
             const unsigned gridw = (unsigned)((a.R + 255) / 256);
-            const long want = (2048 + gridw - 1) / gridw;
-            const unsigned split = (unsigned)(want < 1 ? 1 : (want > groups4 ? groups4 : want));
-            hipLaunchKernelGGL(k_rowgemm_x3s, dim3(gridw, split), dim3(256), 0, s, a);
-        } else if (a.NT >= 4) {
-            const long want = (4096 + grid - 1) / grid;
-            const unsigned split = (unsigned)(want < 1 ? 1 : (want > groups4 ? groups4 : want));
-            hipLaunchKernelGGL((k_rowgemm_x3<4, XV>), dim3(grid, split), dim3(64), 0, s, a);
-        } else if (a.NT >= 2)
+            hipLaunchKernelGGL(k_rowgemm_x3s, dim3(gridw, tile_split(a.NT, gridw, 2048)), dim3(256), 0, s, a);
+        } else if (a.NT >= 4)
+            hipLaunchKernelGGL((k_rowgemm_x3<4, XV>), dim3(grid, tile_split(a.NT, grid, 4096)), dim3(64), 0, s, a);
+        else if (a.NT >= 2)
             hipLaunchKernelGGL((k_rowgemm_x3<2, XV>), dim3(grid), dim3(64), 0, s, a);
         else
             hipLaunchKernelGGL((k_rowgemm_x3<1, XV>), dim3(grid), dim3(64), 0, s, a);
@@ -976,11 +886,9 @@ static void launch_rowgemm_xv(const RowGemmArgs& a, hipStream_t s) {
         // registers, four waves per SIMD, instead of 172 and two) spread over gridDim.y -- 256-window forward 0.456 -> 0.429 ms
         const long groups2 = (a.NT + 1) / 2;
         hipLaunchKernelGGL((k_rowgemm<2, XV>), dim3(grid, (unsigned)groups2), dim3(64), 0, s, a);
-    } else if (a.NT >= 4) {
-        const long want = (4096 + grid - 1) / grid;                 // ~4 waves per SIMD
-        const unsigned split = (unsigned)(want < 1 ? 1 : (want > groups4 ? groups4 : want));
-        hipLaunchKernelGGL((k_rowgemm<4, XV>), dim3(grid, split), dim3(64), 0, s, a);
-    } else if (a.NT >= 2)
+    } else if (a.NT >= 4)
+        hipLaunchKernelGGL((k_rowgemm<4, XV>), dim3(grid, tile_split(a.NT, grid, 4096)), dim3(64), 0, s, a);     // ~4 waves per SIMD
+    else if (a.NT >= 2)
         hipLaunchKernelGGL((k_rowgemm<2, XV>), dim3(grid), dim3(64), 0, s, a);
     else
         hipLaunchKernelGGL((k_rowgemm<1, XV>), dim3(grid), dim3(64), 0, s, a);
@@ -1003,10 +911,6 @@ int launch_conv(const ConvArgs& a, hipStream_t s) {
     const bool staged = conv_lds_staged(a.taps, a.Fq);
     if ((a.bf16 || a.x_bf16) && !staged) return -2;
     if (staged) {                                     // >= 8 waves per CU keep their tile in LDS
-        if (lds > 64 * 1024) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_lds<2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_lds<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        }
         const unsigned wpb = (grid >= 4096 && 4 * lds <= 64 * 1024) ? 4 : 1;     // waves per workgroup
         const unsigned g4 = (grid + wpb - 1) / wpb;
         if (a.bf16) {
@@ -1023,16 +927,12 @@ int launch_conv(const ConvArgs& a, hipStream_t s) {
         if (a.vmax && hipMemsetAsync(a.vmax, 0xFF, sizeof(unsigned), s) != hipSuccess) return -3;
         if (a.Wp3) {                 // split-bf16 operands (precision mode 2, large launches: run_conv)
             const int s_off = g_gemm_lds_off;
-            if (a.NT >= 4 && R >= 64 * 2048 && (a.F & 3) == 0 && a.F >= 4 && !s_off)
-                {
-                    // groups of four output tiles spread over gridDim.y until the launch has >= 2 048 workgroups: a chunk of config 4
-                    // (229 376 rows) was 896 workgroups of four passes each on 512 slots -- 1.75 rounds of very long workgroups
-                    const unsigned gridw = (unsigned)((R + 255) / 256);
-                    const long groups4 = (a.NT + 3) / 4, want = (2048 + gridw - 1) / gridw;
-                    const unsigned split = (unsigned)(want < 1 ? 1 : (want > groups4 ? groups4 : want));
-                    hipLaunchKernelGGL(k_conv_x3s, dim3(gridw, split), dim3(256), 0, s, a);
-                }
-            else if (a.NT >= 4)
+            if (a.NT >= 4 && R >= 64 * 2048 && (a.F & 3) == 0 && a.F >= 4 && !s_off) {
+                // >= 2 048 workgroups: a chunk of config 4 (229 376 rows) was 896 workgroups of four passes each on 512 slots -- 1.75
+                // rounds of very long workgroups
+                const unsigned gridw = (unsigned)((R + 255) / 256);
+                hipLaunchKernelGGL(k_conv_x3s, dim3(gridw, tile_split(a.NT, gridw, 2048)), dim3(256), 0, s, a);
+            } else if (a.NT >= 4)
                 hipLaunchKernelGGL(k_conv_x3<4>, dim3(grid), dim3(64), 0, s, a);
             else if (a.NT >= 2)
                 hipLaunchKernelGGL(k_conv_x3<2>, dim3(grid), dim3(64), 0, s, a);
