@@ -726,6 +726,63 @@ int mtadgat_eval_window_sse(const float* preds_dev /* (batch, out_dim) */, const
 int mtadgat_eval_group_sums(const double* x_dev, int64_t n, int cols, int64_t group, double* out_dev /* (groups, cols) */,
                             void* stream);
 
+/* ---- an optimisation step on windows of a device-resident series (csrc/mtadgat_fit.hip; fitting.SeriesTrainer) -------------
+ * What surrounds mtadgat_forward_train / mtadgat_backward in a step of the reference's Trainer.fit (training.py:100-130): the
+ * window gather, the cotangents of sqrt(mse) + sqrt(mse), the gradient norm with the step's set-up, Adam.  tests/fit_refs.py is
+ * the specification.  Conventions of the calls above: handle-free, no atomics, identical calls give identical bits, status
+ * 0 / -1 / -3 / -5 with a mtadgat_last_error() message, nothing touches the device when validation fails, asynchronous on
+ * `stream`, no stream synchronisation.  starts_dev and dims_dev are the caller's to check, as in mtadgat_eval_window_sse.
+ *
+ * mtadgat_fit_gather: x_dev[w, t, :] = series_dev[starts_dev[w] + t, 0:F] for t < W; series_dev (n_rows, F) float32 with row
+ * stride ld_series >= F (rows need not be 16-byte aligned), x_dev (batch, W, F) contiguous.  1 <= batch <= 2^31 - 1,
+ * 1 <= W <= 512, 1 <= F <= 2048, n_rows >= W.
+ *
+ * mtadgat_fit_loss_grad: the cotangents of loss = rmse_f + rmse_r of one batch.  sums_dev[0], sums_dev[1] are the batch's two
+ * squared-error sums: mtadgat_eval_window_sse followed by mtadgat_eval_group_sums(group = batch) over its (batch, 2) output.
+ * With N_f = batch out_dim, N_r = batch W out_dim, in float64: rmse = sqrt(S / N), c = 1 / (N rmse);
+ *   d_preds_dev[w, d]     = float(double(preds_dev[w, d]     - series[s_w + W, dims[d]]) c_f)
+ *   d_recons_dev[w, t, d] = float(double(recons_dev[w, t, d] - series[s_w + t, dims[d]]) c_r)
+ * each difference the ONE float32 subtraction of mtadgat_eval_window_sse; rmse_dev[0] = rmse_f, rmse_dev[1] = rmse_r.
+ * Departure from torch: rmse == 0 (every residual of the head is 0) gives c = 0, a zero cotangent, where autograd's sqrt gives
+ * 0 / 0.  A sum that is not finite gives c = NaN: every cotangent of that head is NaN.  Limits of mtadgat_eval_window_sse.
+ *
+ * mtadgat_fit_prepare: the squared norm of grads_dev (n floats) as a float64 sum of double(g)^2 in a fixed order -- blocks of
+ * 4096 consecutive entries, in a block lane t of 256 adds entries t, t + 256, .. from +0.0 and the lanes meet in the halving
+ * tree of mtadgat_eval_group_sums; the blocks' sums are added the same way -- and from it the step record state_dev, 8 float64:
+ *   [0] t            steps applied so far; this call adds 1 when it applies
+ *   [1] calls        calls so far (applied or not); this call adds 1
+ *   [2] clip         min(1, max_norm / (norm + 1e-6)) (torch's clip_grad_norm_), 1 for max_norm < 0: no clipping
+ *   [3] step_size    lr / (1 - beta1^t)         b^t by squaring: r = 1; while t: (t odd: r *= b); b *= b; t >>= 1
+ *   [4] bc2s         sqrt(1 - beta2^t)
+ *   [5] applied      1, or 0 when skip_nonfinite is set and the norm, rmse_dev[0] or rmse_dev[1] is not finite: t and fields
+ *                    [2] .. [4] then stay as they were and mtadgat_fit_adam writes nothing
+ *   [6] norm^2  [7] norm
+ * The caller zeroes the record before the first step; it is all of the optimiser's scalar state.  Row (calls mod capacity) of
+ * log_dev (capacity, 4) float64 receives (rmse_f, rmse_r, norm, applied), `calls` counted before this call.
+ * Scratch: 8-byte aligned, mtadgat_fit_prepare_scratch(n) bytes (0 for a refused n), need not be initialised.
+ * lr finite and >= 0, betas in [0, 1), 1 <= capacity <= 2^31 - 1.
+ *
+ * mtadgat_fit_adam: Adam over the flat float32 buffers, per element in float64 with every product rounded (no fused
+ * multiply-add), (clip, step_size, bc2s, applied) from state_dev:
+ *   g' = g clip (+ weight_decay p);   decoupled: p' = p (1 - lr weight_decay) instead (AdamW)
+ *   m <- beta1 m + (1 - beta1) g';   v <- beta2 v + (1 - beta2) (g' g');   p <- p' - step_size (m / (sqrt(v) / bc2s + eps))
+ * p, m and v are each stored with ONE rounding to float32.  torch.optim.Adam does the same algebra in float32, rounding after
+ * every operation: its parameters differ from these in the last bits.  eps, weight_decay finite and >= 0. */
+#define MTADGAT_FIT_STATE_FIELDS 8
+int mtadgat_fit_gather(const float* series_dev, int64_t n_rows, int F, int64_t ld_series, const int64_t* starts_dev, int64_t batch,
+                       int W, float* x_dev /* (batch, W, F) */, void* stream);
+int mtadgat_fit_loss_grad(const float* preds_dev /* (batch, out_dim) */, const float* recons_dev /* (batch, W, out_dim) */,
+                          int64_t batch, int W, int out_dim, const float* series_dev, int64_t n_rows, int F, int64_t ld_series,
+                          const int64_t* starts_dev, const int32_t* dims_dev, const double* sums_dev /* 2 */, float* d_preds_dev,
+                          float* d_recons_dev, double* rmse_dev /* 2 */, void* stream);
+size_t mtadgat_fit_prepare_scratch(int64_t n);
+int mtadgat_fit_prepare(const float* grads_dev, int64_t n, const double* rmse_dev /* 2 */, double lr, double beta1, double beta2,
+                        double max_norm, int skip_nonfinite, double* state_dev /* MTADGAT_FIT_STATE_FIELDS */,
+                        double* log_dev /* (capacity, 4) */, int64_t capacity, void* scratch_dev, size_t scratch_bytes, void* stream);
+int mtadgat_fit_adam(float* params_dev, const float* grads_dev, float* exp_avg_dev, float* exp_avg_sq_dev, int64_t n,
+                     const double* state_dev, double lr, double beta1, double beta2, double eps, double weight_decay, int decoupled,
+                     void* stream);
+
 /* ---- ranking curves (csrc/mtadgat_curves.hip; evaluation.score_order, ranking_curve, ranking_metrics) -------------------
  * Conventions of the event calls above: no atomics, no library kernels, bitwise reproducible; scratch is 8-byte aligned, at
  * least what the _scratch function returns (0 for invalid sizes) and need not be initialised; status 0 / -1 / -3 / -5 with a

@@ -50,6 +50,9 @@ FRONT_SOURCES = ("windows", "windows_bf16", "series_unit", "series")
 FRONT_CONVS = ("in_gath", "k_conv_win", "shared_rows", "launch_conv")
 FRONT_LAYERS = ("none", "k_gat", "k_gath+k_gat", "rowgemm+k_gat_wide", "rowgemm+k_attend")
 FRONT_BUILDS = ("fp32", "bf16", "x3")
+# mtadgat_fit_prepare: the float64 fields of the step record and of a row of the log ring (include/mtadgat.h)
+FIT_STATE_FIELDS = ("t", "calls", "clip", "step_size", "bc2s", "applied", "norm_sq", "norm")
+FIT_LOG_FIELDS = ("rmse_forecast", "rmse_recon", "norm", "applied")
 
 _c_float_p = ctypes.POINTER(ctypes.c_float)
 
@@ -159,6 +162,13 @@ def load_library():
                                               vp, sz, vp]
     lib.mtadgat_dropout_masks.argtypes = [vp, i64, i64, f32, u64, vp, vp, vp, vp]
     lib.mtadgat_dropout_masks_rnn.argtypes = [vp, i64, i64, f32, u64, vp, vp, vp]
+    f64, ci = ctypes.c_double, ctypes.c_int
+    lib.mtadgat_fit_gather.argtypes = [vp, i64, ci, i64, vp, i64, ci, vp, vp]
+    lib.mtadgat_fit_loss_grad.argtypes = [vp, vp, i64, ci, ci, vp, i64, ci, i64, vp, vp, vp, vp, vp, vp, vp]
+    lib.mtadgat_fit_prepare_scratch.argtypes = [i64]
+    lib.mtadgat_fit_prepare_scratch.restype = sz
+    lib.mtadgat_fit_prepare.argtypes = [vp, i64, vp, f64, f64, f64, f64, ci, vp, vp, i64, vp, sz, vp]
+    lib.mtadgat_fit_adam.argtypes = [vp, vp, vp, vp, i64, vp, f64, f64, f64, f64, f64, ci, vp]
     lib.mtadgat_profile_enable.argtypes = [vp, ctypes.c_int]
     lib.mtadgat_profile_read.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i64)]
     lib.mtadgat_profile_name.argtypes = [ctypes.c_int]
@@ -205,6 +215,87 @@ def _dev_ptr(t, name, shape=None):
     if not t.is_contiguous():
         raise RuntimeError(f"{name} must be contiguous")
     return ctypes.c_void_p(t.data_ptr())
+
+
+# -- the series trainer's kernels (csrc/mtadgat_fit.hip; tests/fit_refs.py is the specification) --------------
+# Handle-free, asynchronous on the current stream of the tensors' device; none of them reads from the device.
+def _cur_stream(t):
+    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+
+def _typed(t, dtype, name, numel=None):
+    if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != dtype or not t.is_contiguous():
+        raise RuntimeError(f"{name} must be a contiguous {dtype} tensor on the GPU")
+    if numel is not None and t.numel() != numel:
+        raise RuntimeError(f"{name} holds {t.numel()} elements, expected {numel}")
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def _series_rows(series):
+    if (not isinstance(series, torch.Tensor) or series.device.type != "cuda" or series.dtype != torch.float32 or series.ndim != 2
+            or series.shape[0] < 1 or series.shape[1] < 1 or series.stride(1) != 1 or series.stride(0) < series.shape[1]):
+        raise RuntimeError("series must be a float32 (n_rows, F) tensor on the GPU whose rows are contiguous")
+    return ctypes.c_void_p(series.data_ptr()), series.shape[0], series.shape[1], series.stride(0)
+
+
+def fit_gather(series, starts, W, out=None):
+    """x[w, t, :] = series[starts[w] + t] for t < W (mtadgat_fit_gather): (len(starts), W, F) float32.  starts: int64 on the
+    GPU, every starts[w] in [0, n_rows - W] -- the caller's to check."""
+    sp, n_rows, F, ld = _series_rows(series)
+    b = starts.numel()
+    if out is None:
+        out = _empty((b, W, F), dtype=torch.float32, device=series.device)
+    with torch.cuda.device(series.device):
+        _check(load_library().mtadgat_fit_gather(sp, n_rows, F, ld, _typed(starts, torch.int64, "starts"), b, W,
+                                                 _typed(out, torch.float32, "x", b * W * F), _cur_stream(series)), "fit_gather")
+    return out
+
+
+def fit_loss_grad(preds, recons, series, starts, sums, dims=None, d_preds=None, d_recons=None, rmse=None):
+    """(d_preds, d_recons, rmse (2,) float64) of loss = rmse_forecast + rmse_recon over one batch (mtadgat_fit_loss_grad).  sums:
+    the batch's two squared-error sums on the device, mtadgat_eval_window_sse then mtadgat_eval_group_sums(group = batch).
+    dims: int32 on the GPU or None."""
+    sp, n_rows, F, ld = _series_rows(series)
+    b, W, out = recons.shape
+    dev = series.device
+    d_preds = _empty((b, out), dtype=torch.float32, device=dev) if d_preds is None else d_preds
+    d_recons = _empty((b, W, out), dtype=torch.float32, device=dev) if d_recons is None else d_recons
+    rmse = _empty(2, dtype=torch.float64, device=dev) if rmse is None else rmse
+    with torch.cuda.device(dev):
+        _check(load_library().mtadgat_fit_loss_grad(
+            _typed(preds, torch.float32, "preds", b * out), _typed(recons, torch.float32, "recons"), b, W, out, sp, n_rows, F, ld,
+            _typed(starts, torch.int64, "starts", b), None if dims is None else _typed(dims, torch.int32, "dims", out),
+            _typed(sums, torch.float64, "sums", 2), _typed(d_preds, torch.float32, "d_preds", b * out),
+            _typed(d_recons, torch.float32, "d_recons", b * W * out), _typed(rmse, torch.float64, "rmse", 2), _cur_stream(series)),
+            "fit_loss_grad")
+    return d_preds, d_recons, rmse
+
+
+def fit_prepare(grads, rmse, state, log, lr, betas, max_grad_norm=None, skip_nonfinite=False, scratch=None):
+    """The gradient norm and the step record (mtadgat_fit_prepare): state (8,) float64 -- FIT_STATE_FIELDS, zeroed before the first
+    step --, log (capacity, 4) float64 -- FIT_LOG_FIELDS.  scratch: float64, mtadgat_fit_prepare_scratch(n) bytes."""
+    lib = load_library()
+    n = grads.numel()
+    need = lib.mtadgat_fit_prepare_scratch(n)
+    if scratch is None:
+        scratch = _empty(max(1, (need + 7) // 8), dtype=torch.float64, device=grads.device)
+    with torch.cuda.device(grads.device):
+        _check(lib.mtadgat_fit_prepare(
+            _typed(grads, torch.float32, "grads"), n, _typed(rmse, torch.float64, "rmse", 2), float(lr), float(betas[0]), float(betas[1]),
+            -1.0 if max_grad_norm is None else float(max_grad_norm), int(bool(skip_nonfinite)),
+            _typed(state, torch.float64, "state", len(FIT_STATE_FIELDS)), _typed(log, torch.float64, "log"), log.numel() // 4,
+            _typed(scratch, torch.float64, "scratch"), scratch.numel() * 8, _cur_stream(grads)), "fit_prepare")
+
+
+def fit_adam(params, grads, exp_avg, exp_avg_sq, state, lr, betas, eps, weight_decay=0.0, decoupled=False):
+    """Adam / AdamW over the flat float32 buffers, in place, from the record fit_prepare left in `state` (mtadgat_fit_adam)."""
+    n = params.numel()
+    with torch.cuda.device(params.device):
+        _check(load_library().mtadgat_fit_adam(
+            _typed(params, torch.float32, "params"), _typed(grads, torch.float32, "grads", n), _typed(exp_avg, torch.float32, "exp_avg", n),
+            _typed(exp_avg_sq, torch.float32, "exp_avg_sq", n), n, _typed(state, torch.float64, "state", len(FIT_STATE_FIELDS)),
+            float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(bool(decoupled)), _cur_stream(params)),
+            "fit_adam")
 
 
 class Engine:
