@@ -28,6 +28,24 @@
  *     another (weight packs one call derives on the device are waited for by
  *     later calls on other streams; the caller still orders its own buffers
  *     and weight uploads), but not from two host threads at once.
+ *   - the model-path calls (mtadgat_forward, _forward_xbf16, _forward_series,
+ *     _attention*, _series_losses, _score_attribution, _forward_train,
+ *     _backward, _backward_input, _backward_data, the stage entries and
+ *     _dropout_masks*) read and write nothing outside the buffers they are
+ *     given: of an input or output exactly the elements of the stated shape,
+ *     of a workspace or tape exactly the byte count passed with it (the count
+ *     the matching *_bytes function reports is enough; nothing is rounded up on
+ *     the caller's behalf), and what lies in front of or behind a buffer never
+ *     influences a result.  Workspace and tape contents need not be
+ *     initialised.  Their buffers need only the alignment stated per argument:
+ *     workspace and tape 16 bytes (a too small or misaligned one is refused
+ *     with MTADGAT_ERR_WORKSPACE before anything is launched), every other
+ *     tensor of these calls the alignment of its element type -- 4 bytes for
+ *     float32, 2 for the bfloat16 windows, 8 for int64 / float64 -- and their
+ *     results do not depend on it bit for bit.  tests/test_gpu_guard_bands*.py
+ *     hold these calls to this with guard-banded, exactly sized, misaligned
+ *     buffers.  (The evaluation, preparation, fit and stream calls state the
+ *     alignment of their scratch and state buffers at their declarations.)
  *   - gfx950 only.  There is no CPU implementation behind this ABI.
  */
 #ifndef MTADGAT_H
@@ -49,7 +67,7 @@ typedef enum mtadgat_status {
     MTADGAT_ERR_UNSUPPORTED = -2,  /* shape outside what the kernels cover       */
     MTADGAT_ERR_HIP = -3,          /* a HIP runtime call failed                  */
     MTADGAT_ERR_NOWEIGHTS = -4,    /* forward before mtadgat_load_weights        */
-    MTADGAT_ERR_WORKSPACE = -5     /* workspace pointer NULL or too small        */
+    MTADGAT_ERR_WORKSPACE = -5     /* workspace NULL; workspace or tape too small or misaligned */
 } mtadgat_status;
 
 /* Model hyper-parameters: the constructor arguments of reference

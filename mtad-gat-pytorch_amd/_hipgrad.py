@@ -11,6 +11,7 @@ import warnings
 
 import torch
 
+import _native
 import _torchpath
 
 # windows per chunk of the training step: tape + workspace are ~1.6 MB per window (W=100, F=55); a batch larger
@@ -76,7 +77,7 @@ class _HipStep(torch.autograd.Function):
         eng = ctx.eng
         (x,) = ctx.saved_tensors
         offs, total = eng.grad_layout()
-        grads = torch.zeros(total, dtype=torch.float32, device=x.device)
+        grads = _native._empty(total, dtype=torch.float32, device=x.device).zero_()    # (through the allocation seam, like every buffer)
         d_preds = d_preds.contiguous().float()
         d_recons = d_recons.contiguous().float()
         want_dx = ctx.needs_input_grad[1]

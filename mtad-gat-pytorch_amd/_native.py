@@ -19,7 +19,8 @@ _POISON_VALUE = 7777.0
 
 def _empty(*shape, **kw):
     """torch.empty, poisoned under MTADGAT_POISON_SCRATCH (outputs included: a kernel that accumulates into an output it was
-    supposed to write, or leaves part of it unwritten, shows up the same way)."""
+    supposed to write, or leaves part of it unwritten, shows up the same way).  Every buffer this layer hands the library is
+    allocated here or by _empty_like: tests/arena.py replaces both to hand out exactly sized, guard-banded buffers."""
     t = torch.empty(*shape, **kw)
     if _POISON_SCRATCH and t.is_floating_point() and t.device.type == "cuda":
         t.fill_(_POISON_VALUE)

@@ -1935,7 +1935,7 @@ int backward_impl(mtadgat_handle h, const float* x, int64_t batch, int64_t windo
     plan_tape(m, batch, t);
     BwdWorkspace w;
     plan_bwd_workspace(m, batch, w);
-    if (tape_bytes < t.total * sizeof(float)) return fail(MTADGAT_ERR_WORKSPACE, "tape too small");
+    if (!aligned16(tape_) || tape_bytes < t.total * sizeof(float)) return fail(MTADGAT_ERR_WORKSPACE, "tape too small or misaligned");
     if (!aligned16(ws_) || ws_bytes < w.total * sizeof(float)) return fail(MTADGAT_ERR_WORKSPACE, "backward workspace too small or misaligned");
     hipStream_t s = (hipStream_t)stream;
     const float* T = static_cast<const float*>(tape_);
