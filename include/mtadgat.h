@@ -44,8 +44,27 @@
  *     float32, 2 for the bfloat16 windows, 8 for int64 / float64 -- and their
  *     results do not depend on it bit for bit.  tests/test_gpu_guard_bands*.py
  *     hold these calls to this with guard-banded, exactly sized, misaligned
- *     buffers.  (The evaluation, preparation, fit and stream calls state the
- *     alignment of their scratch and state buffers at their declarations.)
+ *     buffers.
+ *   - the same holds for the handle-free evaluation and preparation calls
+ *     (mtadgat_eval_*, mtadgat_spot_state_bytes / _calibrate / _run / _copy,
+ *     mtadgat_prep_fit / _transform / _inverse): of an (n, d) array with row
+ *     stride ld exactly (n - 1) ld + d elements -- the last row ends behind
+ *     its d-th element, and what lies between the rows is never read --, of
+ *     scratch exactly the bytes the matching *_scratch function reports, or,
+ *     for the calls that take no byte count (mtadgat_eval_moments,
+ *     _epsilon_table, _point_adjust and the _columns forms), the minimum
+ *     stated at their declarations; scratch and the SPOT state need the
+ *     alignment stated there (8 or 16 bytes; short or misaligned scratch is
+ *     refused with -5 before anything is launched), every other tensor the
+ *     alignment of its element type.  Results do not depend on alignment or
+ *     on what surrounds a buffer bit for bit, except the float64 sums of
+ *     mtadgat_eval_moments / _epsilon_table and their _columns forms, which
+ *     are combined with atomics and may differ in their last bits between
+ *     any two calls (their counts are exact).
+ *     tests/test_gpu_guard_bands_eval.py and _prep.py hold them to this.
+ *     (The fit and stream calls -- mtadgat_fit_*, mtadgat_stream_*,
+ *     mtadgat_prep_stream_* -- state the alignment of their scratch and state
+ *     buffers at their declarations.)
  *   - gfx950 only.  There is no CPU implementation behind this ABI.
  */
 #ifndef MTADGAT_H

@@ -183,8 +183,8 @@ def _dev2d(t, name):
         raise ValueError(f"{name} must have shape (n, d) with n, d >= 1, got {tuple(t.shape)}")
     if t.dtype != torch.float32:
         t = t.float()
-    if t.shape[0] == 1:
-        t = t.reshape(1, -1).clone()       # a single row: any row stride is legal in torch, the kernels want ld >= d
+    if t.shape[0] == 1:                    # a single row: any row stride is legal in torch, the kernels want ld >= d
+        t = t.as_strided((1, t.shape[1]), (t.shape[1], 1)) if t.shape[1] == 1 or t.stride(1) == 1 else t.reshape(1, -1).clone()
     if t.stride(1) != 1 or t.stride(0) < t.shape[1]:
         t = t.contiguous()
     return t
@@ -212,8 +212,8 @@ def anomaly_scores(preds, recons, values, window_size, target_dims=None, gamma=1
     elif actual.shape[1] != d:
         raise RuntimeError("out_dim differs from the number of features: pass target_dims")
     p, r = preds.float().contiguous(), recons.float().contiguous()
-    per_dim = torch.empty((n, d), dtype=torch.float32, device=preds.device)
-    glob = torch.empty((n,), dtype=torch.float32, device=preds.device)
+    per_dim = _native._empty((n, d), dtype=torch.float32, device=preds.device)
+    glob = _native._empty((n,), dtype=torch.float32, device=preds.device)
     with torch.cuda.device(preds.device):
         _check(lib.mtadgat_eval_scores(p.data_ptr(), r.data_ptr(), actual.data_ptr(), n, d, actual.shape[1],
                                        dims.data_ptr() if dims is not None else None, float(gamma), per_dim.data_ptr(),
@@ -278,7 +278,7 @@ def find_epsilon(errors, reg_level=1):
     lib = _lib()
     e = _dev1d(errors, torch.float32, "errors")
     n = e.numel()
-    scratch = torch.empty(64 + 4 * 64, dtype=torch.float64, device=e.device)
+    scratch = _native._empty(64 + 4 * 64, dtype=torch.float64, device=e.device)
     mom = (ctypes.c_double * 2)()
     with torch.cuda.device(e.device):
         _check(lib.mtadgat_eval_moments(e.data_ptr(), n, scratch.data_ptr(), mom, _stream(e)), "eval_moments")
@@ -432,15 +432,12 @@ def point_adjust_counts(score, label, thresholds, compare_f32=False, max_segment
     Returns an (n_thr, 6) float64 array: TP, TN, FP, FN, latency sum, detected segments."""
     lib = _lib()
     s = _dev1d(score, torch.float32, "score")
-    if label.dtype == torch.bool:
-        lab = _dev1d(label, torch.uint8, "label")
-    else:
-        lab = _dev1d((label > 0.1), torch.uint8, "label")
+    lab = _labels_u8(label, "label")
     if lab.numel() != s.numel():
         raise ValueError("score and label must have the same length")
     thr = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).reshape(-1))
     nt = thr.size
-    scratch = torch.empty(7 * nt + max_segments + 2, dtype=torch.float64, device=s.device)
+    scratch = _native._empty(7 * nt + max_segments + 2, dtype=torch.float64, device=s.device)
     out = np.zeros((nt, 6), dtype=np.float64)
     with torch.cuda.device(s.device):
         _check(lib.mtadgat_eval_point_adjust(s.data_ptr(), lab.data_ptr(), s.numel(), thr.ctypes.data_as(_c_double_p), nt,
@@ -527,6 +524,20 @@ class ScoreParts:
             put = lambda a: torch.from_numpy(a).to(device) if a.size else None
             self._on[key] = (put(self.start_host), put(self.end_host), put(self.seams_host))
         return self._on[key]
+
+    def use_tensors(self, start, end, seams=None):
+        """Hand the kernels the caller's own copies of the span arrays on their device instead of the ones tensors() would make:
+        contiguous int64 tensors holding start_host, end_host and seams_host (seams None without a seam).  Only the shapes, types
+        and devices are checked; the values are the caller's promise.  Returns self."""
+        want = (self.n_parts, self.n_parts, self.seams_host.size)
+        for t, size, name in zip((start, end, seams), want, ("start", "end", "seams")):
+            if t is None and name == "seams" and size == 0:
+                continue
+            if (not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.ndim != 1 or t.numel() != size or not t.is_contiguous()
+                    or t.device != start.device):
+                raise ValueError(f"{name} must be a contiguous int64 tensor of {size} entries on the device of start")
+        self._on[str(start.device)] = (start, end, seams if self.seams_host.size else None)
+        return self
 
     def part_of(self, i):
         """The part that owns score i (an int or an array of ints in [0, n)): an int or an int64 array."""
@@ -636,7 +647,7 @@ def part_predictions(scores, parts, thresholds):
     thr = torch.as_tensor(np.asarray(thresholds, dtype=np.float64).reshape(-1)).to(x.device)
     if thr.numel() != parts.n_parts:
         raise ValueError(f"{thr.numel()} thresholds for {parts.n_parts} parts")
-    flags = torch.empty(n, dtype=torch.uint8, device=x.device)
+    flags = _native._empty(n, dtype=torch.uint8, device=x.device)
     with torch.cuda.device(x.device):
         rc = lib.mtadgat_eval_part_flags(x.data_ptr(), n, start.data_ptr(), end.data_ptr(), parts.n_parts, thr.data_ptr(), flags.data_ptr(),
                                          _stream(x))
@@ -691,7 +702,8 @@ class SpotState:
         nbytes = lib.mtadgat_spot_state_bytes(int(n_columns), self.max_peaks)
         if nbytes == 0:
             raise ValueError(f"{n_columns} columns are refused")
-        buf = torch.zeros((nbytes + 7) // 8, dtype=torch.float64, device=self.device)
+        buf = _native._empty((nbytes + 7) // 8, dtype=torch.float64, device=self.device)
+        buf.zero_()
         with torch.cuda.device(self.device):
             rc = lib.mtadgat_spot_copy(buf.data_ptr(), int(n_columns), self.data_ptr(), 1, self.max_peaks, None, int(n_columns), 1,
                                        _stream(self.buf))
@@ -721,7 +733,8 @@ def spot_calibrate(init_scores, q=1e-3, level=0.98, max_peaks=1024, dynamic=True
     sbytes = lib.mtadgat_spot_calibrate_scratch(n, S)
     if nbytes == 0 or sbytes == 0:
         raise ValueError(f"{S} columns are refused (at most 65536 per call)")
-    buf = torch.zeros((nbytes + 7) // 8, dtype=torch.float64, device=e.device)
+    buf = _native._empty((nbytes + 7) // 8, dtype=torch.float64, device=e.device)
+    buf.zero_()
     scratch = _scratch(sbytes, e.device)
     with torch.cuda.device(e.device):
         rc = lib.mtadgat_spot_calibrate(e.data_ptr(), n, S, e.stride(0), float(q), float(level), int(max_peaks), 1 if dynamic else 0,
@@ -745,7 +758,7 @@ def spot_run(state, scores):
     if S != state.n_columns or x.device != state.device:
         raise ValueError(f"scores have {S} columns on '{x.device}', the state {state.n_columns} on '{state.device}'")
     thr = _native._empty((n, S), dtype=torch.float64, device=x.device)
-    flags = torch.empty((n, S), dtype=torch.uint8, device=x.device)
+    flags = _native._empty((n, S), dtype=torch.uint8, device=x.device)
     with torch.cuda.device(x.device):
         rc = lib.mtadgat_spot_run(state.data_ptr(), S, state.max_peaks, x.data_ptr(), n, x.stride(0), thr.data_ptr(), flags.data_ptr(), _stream(x))
     if rc != 0:
@@ -899,10 +912,11 @@ _c_int64_p = ctypes.POINTER(ctypes.c_int64)
 
 
 def _labels_u8(label, name="labels"):
-    """Labels as point_adjust_counts reads them: bool as it is, numbers as label > 0.1."""
+    """Labels as point_adjust_counts reads them: bool as it is, numbers as label > 0.1 -- which for uint8 is label != 0, what the
+    kernels test: a uint8 tensor is handed on unchanged."""
     if not isinstance(label, torch.Tensor) or label.device.type != "cuda":
         raise RuntimeError(f"{name} must be a tensor on the GPU (the evaluation kernels are HIP only)")
-    return _dev1d(label if label.dtype == torch.bool else (label > 0.1), torch.uint8, name)
+    return _dev1d(label if label.dtype in (torch.bool, torch.uint8) else (label > 0.1), torch.uint8, name)
 
 
 def _flag_source(scores, labels):
@@ -935,8 +949,8 @@ def flag_runs(scores=None, labels=None, threshold=0.0, merge_gap=0, min_length=1
     count = ctypes.c_int64(0)
     cap = int(max_runs)
     for attempt in range(2):
-        start = torch.empty(cap, dtype=torch.int64, device=src.device)
-        end = torch.empty(cap, dtype=torch.int64, device=src.device)
+        start = _native._empty(cap, dtype=torch.int64, device=src.device)
+        end = _native._empty(cap, dtype=torch.int64, device=src.device)
         with torch.cuda.device(src.device):
             rc = lib.mtadgat_eval_runs(_ptr(s), _ptr(lab), n, float(threshold), 1 if compare_f32 else 0, int(merge_gap), int(min_length), cap,
                                        scratch.data_ptr(), scratch.numel() * 8, start.data_ptr(), end.data_ptr(), ctypes.byref(count),
@@ -985,14 +999,18 @@ def run_statistics(scores, start, end, per_dim=None, feature_thresholds=None, to
                 raise ValueError(f"{thr.numel()} feature thresholds for {d} columns")
     elif feature_thresholds is not None:
         raise ValueError("feature_thresholds need per_dim")
-    out = {"peak": torch.empty(count, dtype=torch.int64, device=dev), "peak_score": _native._empty(count, dtype=torch.float32, device=dev),
-           "mean_score": _native._empty(count, dtype=torch.float32, device=dev)}
+    peak = _native._empty(count, dtype=torch.int64, device=dev)
+    peak_score = _native._empty(count, dtype=torch.float32, device=dev)
+    mean_score = _native._empty(count, dtype=torch.float32, device=dev)
+    out = {"peak": peak, "peak_score": peak_score, "mean_score": mean_score}
     if pd is not None:
-        out["feature_means"] = _native._empty((count, d), dtype=torch.float32, device=dev)
-        out["top_features"] = torch.empty((count, k), dtype=torch.int32, device=dev)
-        out["top_values"] = _native._empty((count, k), dtype=torch.float32, device=dev)
+        feature_means = _native._empty((count, d), dtype=torch.float32, device=dev)
+        top_features = _native._empty((count, k), dtype=torch.int32, device=dev)
+        top_values = _native._empty((count, k), dtype=torch.float32, device=dev)
+        out.update(feature_means=feature_means, top_features=top_features, top_values=top_values)
     if thr is not None:
-        out["feature_hits"] = torch.empty((count, d), dtype=torch.int32, device=dev)
+        feature_hits = _native._empty((count, d), dtype=torch.int32, device=dev)
+        out["feature_hits"] = feature_hits
     if count == 0:
         return out
     scratch = _scratch(lib.mtadgat_eval_run_stats_scratch(n, count, d), dev)
@@ -1013,7 +1031,7 @@ def first_hits(start, end, scores=None, labels=None, threshold=0.0, compare_f32=
     s, lab = _flag_source(scores, labels)
     src = s if s is not None else lab
     st, en = _runs(start, end, src.device)
-    first = torch.empty(st.numel(), dtype=torch.int64, device=src.device)
+    first = _native._empty(st.numel(), dtype=torch.int64, device=src.device)
     if st.numel() == 0:
         return first
     if src.numel() < 1:
@@ -1093,7 +1111,7 @@ def score_order(scores, descending=True):
     if nbytes == 0:
         raise ValueError(f"{n} scores are refused (fewer than 2**31)")
     scratch = _scratch(nbytes, s.device)
-    order = torch.empty(n, dtype=torch.int64, device=s.device)
+    order = _native._empty(n, dtype=torch.int64, device=s.device)
     with torch.cuda.device(s.device):
         rc = lib.mtadgat_eval_score_order(s.data_ptr(), n, 1 if descending else 0, scratch.data_ptr(), scratch.numel() * 8, order.data_ptr(),
                                           _stream(s))
@@ -1191,7 +1209,7 @@ def ranking_metrics(scores, labels, adjust=None):
             below = float(np.nextafter(np.float32(v), np.float32(-np.inf)))
             row = None
             if v > -math.inf:           # no float32 lies below -inf: `> below` cannot flag what `>= v` flags
-                row = point_adjust_counts(s, lab.bool(), [below], compare_f32=True, max_segments=max(65536, (s.numel() + 1) // 2))[0]
+                row = point_adjust_counts(s, lab, [below], compare_f32=True, max_segments=max(65536, (s.numel() + 1) // 2))[0]
             if row is not None and (row[0] != counts[0] or row[2] != counts[2]):
                 raise RuntimeError(f"the curve's best point (TP {counts[0]}, FP {counts[2]}) differs from point_adjust_counts' "
                                    f"(TP {row[0]}, FP {row[2]}) at threshold {below!r}")

@@ -91,8 +91,8 @@ def _rows2d(t, name):
         raise ValueError(f"{name} has {t.shape[1]} columns, the preparation covers up to 2048")
     if t.dtype != torch.float32:
         t = t.float()
-    if t.shape[0] == 1:
-        t = t.reshape(1, -1).clone()
+    if t.shape[0] == 1:                    # a single row: any row stride is legal in torch, the kernels want ld >= d
+        t = t.as_strided((1, t.shape[1]), (t.shape[1], 1)) if t.shape[1] == 1 or t.stride(1) == 1 else t.reshape(1, -1).clone()
     if t.stride(1) != 1 or t.stride(0) < t.shape[1]:
         t = t.contiguous()
     return t

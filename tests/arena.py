@@ -34,7 +34,11 @@ SKEWS = (4, 8, 12)                          # the three classes of "4-byte but n
 # The buffers the ABI wants 16-byte aligned -- workspaces and the tape --, by the names the seam gives them ("<Engine method>.<variable>";
 # Engine._buf's by its attribute).  Everything else is a data buffer and is skewed by patched(skew=True).  A scratch buffer that is
 # renamed in _native.py falls out of this list, is skewed, and the library refuses the call: the list cannot go stale silently.
-SCRATCH_BUFFERS = ("_workspace.ws", "_bws", "forward_train.tape", "_attention_ws", "score_attribution.ws", "series_losses.ws")
+SCRATCH_BUFFERS = ("_workspace.ws", "_bws", "forward_train.tape", "_attention_ws", "score_attribution.ws", "series_losses.ws",
+                   # evaluation.py / preparation.py: the _scratch helpers (8 or 16 bytes per declaration in include/mtadgat.h) and the
+                   # SPOT state (16 bytes).  (The scratch of the calls that take no byte count is float64 and asks for 8 bytes only:
+                   # a data buffer, skewed by 8.)
+                   "_scratch", "spot_calibrate.buf", "expand.buf", "spot_state.buf")  # (spot_state: the tests' copy of a calibrated state)
 ENGINE_CACHES = ("_ws", "_bws", "_train_tape", "_flat_grads")
 
 
@@ -56,6 +60,16 @@ def nbytes_of(shape, dtype):
     for s in shape:
         n *= int(s)
     return n * torch.empty(0, dtype=dtype).element_size()
+
+
+def rows_fill(x, ld, pattern):
+    """The flat ((n - 1) * ld + d,) tensor that holds the rows of x (n, d) at stride ld, the pattern's bits in the gaps (4-byte
+    elements)."""
+    n, d = x.shape
+    assert x.element_size() == 4
+    flat = torch.full(((n - 1) * ld + d,), as_int32(pattern), dtype=torch.int32, device=x.device)
+    flat.as_strided((n, d), (ld, 1)).copy_(x.contiguous().view(torch.int32))
+    return flat.view(x.dtype)
 
 
 def capacity_for(sizes):
@@ -178,6 +192,18 @@ class Arena:
         self.buffers.append(Buffer(name, start, end, end - early * item, fill is None, t, scratch))
         self.cursor = end + GUARD
         return t
+
+    def take_rows(self, x, ld, skew=0, name=None):
+        """The (n, d) tensor x as rows of stride ld >= d over exactly (n - 1) * ld + d elements: the last row is short, the guard
+        begins right behind its d-th element, and the ld - d gap elements behind every other row hold the pattern."""
+        n, d = x.shape
+        assert x.ndim == 2 and ld >= d and n >= 1
+        flat = self.take(((n - 1) * ld + d,), x.dtype, skew=skew, fill=rows_fill(x, ld, self.pattern), name=name)
+        return flat.as_strided((n, d), (ld, 1))
+
+    def span(self):
+        """[first byte, one past the last byte) of the arena's memory, guards and unused space included."""
+        return self.mem.data_ptr(), self.mem.data_ptr() + self.mem.numel()
 
     def buffer(self, name):
         return next(b for b in self.buffers if b.name == name)

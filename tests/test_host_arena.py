@@ -182,3 +182,100 @@ def test_the_seam_names_places_and_restores(monkeypatch):
     # a buffer on another device than the arena's is not the arena's business
     with a.patched(monkeypatch, eng):
         assert _native._empty(3, dtype=torch.float32, device="meta").device.type == "meta"
+
+
+# ---- the short last row and the pointer proxy (tests/test_gpu_guard_bands_eval.py, _prep.py) ------------------------------------------
+@pytest.mark.parametrize("pattern", [PATTERN_A, PATTERN_B])
+@pytest.mark.parametrize("n,d,ld,skew", [(1, 3, 6, 0), (5, 3, 6, 4), (4, 1, 4, 12), (3, 65, 68, 8)])
+def test_rows_with_a_stride_end_behind_the_last_rows_own_elements(pattern, n, d, ld, skew):
+    x = torch.arange(n * d, dtype=torch.float32).reshape(n, d) + 1.0
+    a = Arena("cpu", pattern, arena.capacity_for([((n - 1) * ld + d) * 4]))
+    t = a.take_rows(x, ld, skew=skew, name="x")
+    b = a.buffer("x")
+    assert t.shape == (n, d) and t.stride() == (ld, 1) and t.data_ptr() % 16 == skew and t.data_ptr() == a.mem.data_ptr() + b.start
+    assert b.end - b.start == ((n - 1) * ld + d) * 4 and b.guard_from == b.end      # the guard starts behind the last row's d-th element
+    assert torch.equal(t, x) and a.check() == []
+    flat = b.tensor.view(torch.int32)
+    gaps = torch.ones(flat.numel(), dtype=torch.bool)
+    gaps.as_strided((n, d), (ld, 1)).fill_(False)
+    assert int(gaps.sum()) == (n - 1) * (ld - d)
+    assert bool((flat[gaps] == arena.as_int32(pattern)).all())                       # the gap columns hold the pattern
+    if pattern == PATTERN_A and n > 1:
+        assert bool(torch.isnan(b.tensor[gaps]).all())
+    a.words[b.end // 4] = 0                                                          # the element a full last row would have had
+    assert a.check() == [dict(name="x", side="behind", offset=b.end - b.start, words=1)]
+
+
+def test_the_pointer_proxy_holds_every_device_pointer_to_the_range():
+    import ctypes
+
+    import pointer_proxy
+
+    class Fn:
+        def __init__(self, argtypes):
+            self.argtypes, self.got = argtypes, []
+
+        def __call__(self, *args):
+            self.got.append(args)
+            return 0
+
+    class Lib:
+        pass
+    vp, i64, dp = ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_double)
+    lib = Lib()
+    lib.mtadgat_eval_thing = Fn([vp, i64, vp, dp, vp])            # in, n, out, a host pointer, the stream
+    lib.mtadgat_eval_thing_scratch = Fn([i64])
+    lib.mtadgat_last_error = Fn(None)
+    lib.other = Fn([vp, vp])
+    proxy = pointer_proxy.PointerProxy(lib, 1000, 2000)
+    host = (ctypes.c_double * 2)()
+    assert proxy.mtadgat_eval_thing(1000, 7, vp(1999), host, vp(5)) == 0      # both ends of the range; the stream is not a buffer
+    assert proxy.mtadgat_eval_thing(None, 7, 0, host, None) == 0              # NULL is allowed
+    assert proxy.mtadgat_eval_thing(vp(None), 7, 1500, host, None) == 0
+    assert proxy.seen == 3 and proxy.calls == [("mtadgat_eval_thing", 2), ("mtadgat_eval_thing", 0), ("mtadgat_eval_thing", 1)]
+    for bad in (999, 2000, vp(123456)):
+        with pytest.raises(AssertionError, match="argument 2 .* outside the arena"):
+            proxy.mtadgat_eval_thing(1000, 7, bad, host, None)
+    with pytest.raises(AssertionError, match="argument 0"):
+        proxy.mtadgat_eval_thing(2000, 7, 1000, host, None)
+    assert len(lib.mtadgat_eval_thing.got) == 3                               # a refused call never reaches the library
+    with pytest.raises(AssertionError):
+        proxy.mtadgat_eval_thing(1000, 7, 1000, host)                         # an argument short
+    assert proxy.mtadgat_eval_thing_scratch(5) == 0 and proxy.mtadgat_last_error() == 0 and proxy.other(1, 2) == 0
+    proxy._bound = True                                                        # marks land on the library itself
+    assert lib._bound is True
+
+
+def test_watching_replaces_and_restores_the_loaders(monkeypatch):
+    import types
+
+    import pointer_proxy
+    lib = types.SimpleNamespace(mtadgat_x=lambda *a: 0)
+    lib.mtadgat_x.__dict__["argtypes"] = None
+    mod = types.SimpleNamespace(_lib=lambda: lib)
+    loader = mod._lib
+    with pytest.raises(AssertionError, match="no device pointer"):
+        with pointer_proxy.watching(monkeypatch, [mod], 0, 10) as proxies:
+            assert mod._lib() is proxies[0] and mod._lib().mtadgat_x() == 0
+    assert mod._lib is loader
+
+
+def test_the_seam_names_the_evaluation_buffers(monkeypatch):
+    """The scratch helpers and the SPOT state keep their alignment in the skewed run; every other buffer of evaluation.py and
+    preparation.py is a data buffer.  (The names are what Arena._empty derives from the caller's line.)"""
+    import _native
+    import evaluation
+    import preparation
+    a = Arena("cpu", PATTERN_A, arena.capacity_for([64] * 6))
+    with a.patched(monkeypatch, skew=True):
+        s0 = evaluation._scratch(20, "cpu")
+        s1 = preparation._scratch(0, "cpu")
+        scratch = _native._empty(4, dtype=torch.float64, device="cpu")
+        order = _native._empty(4, dtype=torch.int64, device="cpu")
+        flags = _native._empty(5, dtype=torch.uint8, device="cpu")
+    assert a.names() == ["_scratch", "_scratch#1", "test_the_seam_names_the_evaluation_buffers.scratch",
+                         "test_the_seam_names_the_evaluation_buffers.order", "test_the_seam_names_the_evaluation_buffers.flags"]
+    assert s0.numel() == 3 and s1.numel() == 1
+    assert [b.scratch for b in a.buffers] == [True, True, False, False, False]
+    assert s0.data_ptr() % 16 == 0 and s1.data_ptr() % 16 == 0
+    assert scratch.data_ptr() % 16 == 8 and order.data_ptr() % 16 == 8 and flags.data_ptr() % 16 != 0

@@ -141,3 +141,22 @@ def test_entry_points_validate_before_they_launch():
     assert b"halo" in lib.mtadgat_last_error()
     assert lib.mtadgat_eval_part_epsilon_table(p, 10, p, p, 1, out, 19, 49, p, 8, out, None) == -5
     assert lib.mtadgat_eval_part_flags(p, 10, p, p, 1, None, p, None) == -1
+
+
+def test_use_tensors_hands_on_the_callers_own_span_arrays():
+    """ScoreParts.use_tensors registers the caller's tensors for their device -- tensors() then returns those very tensors -- and
+    refuses wrong types, lengths and layouts."""
+    import evaluation as ev
+    sp = ev.score_parts([9, 1, 0, 65, 3], 7)
+    start, end, seams = (torch.from_numpy(a.copy()) for a in (sp.start_host, sp.end_host, sp.seams_host))
+    assert sp.use_tensors(start, end, seams) is sp
+    got = sp.tensors("cpu")
+    assert got[0] is start and got[1] is end and got[2] is seams
+    for bad in ((start.int(), end, seams), (start[:-1], end, seams), (start, end, seams[:-1]), (start, end, None),
+                (start, torch.stack([end, end], 1)[:, 0], seams), (start.tolist(), end, seams)):
+        with pytest.raises((ValueError, AttributeError)):
+            sp.use_tensors(*bad)
+    one = ev.score_parts([30], 7)                                       # no seam: None or an empty tensor, handed on as None
+    s1, e1 = torch.from_numpy(one.start_host.copy()), torch.from_numpy(one.end_host.copy())
+    assert one.use_tensors(s1, e1).tensors("cpu") == (s1, e1, None)
+    assert one.use_tensors(s1, e1, torch.zeros(0, dtype=torch.int64)).tensors("cpu")[2] is None

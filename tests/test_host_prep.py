@@ -276,3 +276,24 @@ def test_scaler_state_round_trip_and_errors():
         scaler.inverse(torch.zeros(4, 2), dims=[0, 7])
     with pytest.raises(RuntimeError):
         preparation.StreamPreparer(scaler, 4)                # GPU only
+
+
+def test_a_single_row_is_handed_on_in_place_with_a_legal_row_stride():
+    """_rows2d: a (1, d) input whose elements are contiguous is not copied -- it is re-viewed with row stride d, whatever stride torch
+    gave its one row (a row of a wider tensor, a row stride of 0 or 1) --, so its first element keeps its address; a single row whose
+    elements are strided is copied.  The values are the row's in every case."""
+    import preparation
+    wide = torch.arange(40, dtype=torch.float32).reshape(4, 10)
+    cases = [wide[2:3, 3:8], wide[1:2], torch.arange(5.0).as_strided((1, 5), (0, 1)), torch.arange(5.0).as_strided((1, 5), (1, 1)),
+             wide[3:4, 9:10], wide[0:1, ::3][:, :1], wide[0, 2:6]]
+    for t in cases:
+        got = preparation._rows2d(t, "t")
+        want = t.reshape(-1, 1) if t.ndim == 1 else t
+        assert got.shape == want.shape and torch.equal(got, want)
+        if t.ndim == 2:
+            assert got.data_ptr() == t.data_ptr() and got.stride() == (t.shape[1], 1), (t.shape, t.stride(), got.stride())
+    strided = wide[0:1, ::3]                                            # (1, 4), elements 3 apart: copied
+    got = preparation._rows2d(strided, "t")
+    assert torch.equal(got, strided) and got.data_ptr() != strided.data_ptr() and got.stride() == (4, 1)
+    multi = wide[:, 2:5]                                                # more than one row: as before, no copy
+    assert preparation._rows2d(multi, "t").data_ptr() == multi.data_ptr()
