@@ -179,9 +179,9 @@ int64_t mtadgat_selfcheck_gather_table(mtadgat_handle h, const mtadgat_params* p
  * `stream` -- the tests compare the device-side re-pack with the host packer through it. */
 int64_t mtadgat_packed_floats(mtadgat_handle h);
 /* (offset, length) pairs in floats of the image regions that are derived on the device from other regions of the image
- * (the split packs); returns their number (at most max_pairs are written).  out_pairs == NULL with max_pairs == 0 returns
+ * (the split packs); returns their number (at most max_pairs are written).  out_pairs_host == NULL with max_pairs == 0 returns
  * the number only. */
-int mtadgat_derived_regions(mtadgat_handle h, int64_t* out_pairs, int max_pairs);
+int mtadgat_derived_regions(mtadgat_handle h, int64_t* out_pairs_host, int max_pairs);
 int mtadgat_read_packed(mtadgat_handle h, float* dst_host, int64_t n_floats, void* stream);
 /* Test hook (host only: needs neither a GPU nor loaded weights): the table of steps that derive the split packs from the fp32
  * packs of the image, over all groups in group order, then step order.  A record is 10 int64:
@@ -193,10 +193,10 @@ int mtadgat_read_packed(mtadgat_handle h, float* dst_host, int64_t n_floats, voi
  *   Qs, Qd  chunks per tile of src / dst
  *   arg    SPLIT2H: words per chunk (gates); SPLIT_X: leading chunks on three bf16 pieces; SPLIT2H_GATH: embedding columns E
  *   ord    SPLIT2H_GATH: offset of the layer's column order [P8, PT, npos, 0] (ints)
- * Returns the number of steps; at most max_steps records are written (out == NULL with max_steps == 0 returns the number only).
+ * Returns the number of steps; at most max_steps records are written (out_host == NULL with max_steps == 0 returns the number only).
  * mtadgat_split_n_infer: groups [0, n_infer) are what an inference call may read (mtadgat_read_packed derives those), the rest
  * belong to the training backward. */
-int mtadgat_split_steps(mtadgat_handle h, int64_t* out, int max_steps);
+int mtadgat_split_steps(mtadgat_handle h, int64_t* out_host, int max_steps);
 int mtadgat_split_n_infer(mtadgat_handle h);
 /* Test hook: derives every stale split group, the training backward's included, on `stream` -- what the kernels' callers do lazily,
  * group by group.  Needs loaded weights.  mtadgat_read_packed afterwards shows every pack current. */
@@ -206,18 +206,18 @@ int mtadgat_derive_split_packs(mtadgat_handle h, void* stream);
  * forward); compute_units: of the device the call would run on (256 on MI355X).  The answer is the one the library's own dispatch
  * uses -- for a forward() that returns predictions and reconstructions, or a training forward -- under the handle's current
  * mtadgat_set_precision mode and "gru_kernel" option.  Writes 8 ints:
- *   out[0]  first kernel: 1 k_gru1 (window per workgroup), 2 k_gru16 (16-window groups), 3 k_gru_split (hidden-tile split),
+ *   out_host[0]  first kernel: 1 k_gru1 (window per workgroup), 2 k_gru16 (16-window groups), 3 k_gru_split (hidden-tile split),
  *           4 k_gru_split on split operands, 5 k_gru_cm (chunk-major), 6 k_gru (tile-major)
- *   out[1]  kernel launched behind it as the device-side range-guard fallback (same codes), 0 none
- *   out[2]  operand build of the k_gru_split / k_gru named in out[0] / out[1]: 0 fp32, 1 bf16, 2 / 3 split-bf16 (hidden sizes
+ *   out_host[1]  kernel launched behind it as the device-side range-guard fallback (same codes), 0 none
+ *   out_host[2]  operand build of the k_gru_split / k_gru named in out_host[0] / out_host[1]: 0 fp32, 1 bf16, 2 / 3 split-bf16 (hidden sizes
  *           above / up to 128); 0 when neither is named
- *   out[3]  k_gru takes two 32-window groups per wave
- *   out[4]  the input products of all steps are hoisted into a launch in front
- *   out[5]  the layer's split packs are needed (derived on first use after an upload)
- *   out[6]  the per-step Linear of the decoder rides inside the recurrence
- *   out[7]  the stack takes the small-batch kernels (what the heads and the training forward ask; equals out[0] in {1, 2} for layer 0)
+ *   out_host[3]  k_gru takes two 32-window groups per wave
+ *   out_host[4]  the input products of all steps are hoisted into a launch in front
+ *   out_host[5]  the layer's split packs are needed (derived on first use after an upload)
+ *   out_host[6]  the per-step Linear of the decoder rides inside the recurrence
+ *   out_host[7]  the stack takes the small-batch kernels (what the heads and the training forward ask; equals out_host[0] in {1, 2} for layer 0)
  * Returns 0, or MTADGAT_ERR_INVALID. */
-int mtadgat_gru_route(mtadgat_handle h, int stack, int layer, int64_t n, int training, int compute_units, int* out);
+int mtadgat_gru_route(mtadgat_handle h, int stack, int layer, int64_t n, int training, int compute_units, int* out_host);
 /* Test hook (host only: needs neither a GPU nor loaded weights): which kernels run the front end -- window convolution, temporal
  * and feature attention layer -- of one call on n windows (one piece of a forward()).  The answer is the one the library's own
  * dispatch uses under the handle's current mtadgat_set_precision mode and "conv_kernel" / "gat_kernel" / "conv_fused" /
@@ -229,12 +229,12 @@ int mtadgat_gru_route(mtadgat_handle h, int stack, int layer, int64_t n, int tra
  *   facts   bit 0: the node rows the fused layers read are 16-byte aligned; bit 1: their row stride is a multiple of 4 floats and
  *           at least the node columns rounded up to 4; bit 2: h_cat is 16-byte aligned (all set in the library's own calls)
  * Writes 14 ints:
- *   out[0]  convolution: 0 none (inside the temporal layer's k_gath), 1 k_conv_win on fp16 pieces, 2 shared rows of a series
+ *   out_host[0]  convolution: 0 none (inside the temporal layer's k_gath), 1 k_conv_win on fp16 pieces, 2 shared rows of a series
  *           (three launch_conv calls and the row placement), 3 launch_conv
- *   out[1]  operands of that launch_conv: 0 fp32, 1 the bf16 pack, 2 three bf16 pieces (rows too long for LDS staging)
- *   out[2]  the convolution's split packs are needed (derived on first use after an upload)
- *   out[3]  the convolution's output range is recorded for the kernels behind it
- *   out[4 .. 9) the temporal layer, out[9 .. 14) the feature layer:
+ *   out_host[1]  operands of that launch_conv: 0 fp32, 1 the bf16 pack, 2 three bf16 pieces (rows too long for LDS staging)
+ *   out_host[2]  the convolution's split packs are needed (derived on first use after an upload)
+ *   out_host[3]  the convolution's output range is recorded for the kernels behind it
+ *   out_host[4 .. 9) the temporal layer, out_host[9 .. 14) the feature layer:
  *     [0]  0 none, 1 fused k_gat alone, 2 k_gath with k_gat behind it as the device-side fallback, 3 row GEMM projection +
  *          k_gat_wide, 4 row GEMM projection + k_attend
  *     [1]  operands of the projection: 0 fp32, 1 bf16, 2 three bf16 pieces
@@ -243,24 +243,24 @@ int mtadgat_gru_route(mtadgat_handle h, int stack, int layer, int64_t n, int tra
  *     [3]  the un-fused projection is the split row GEMM
  *     [4]  the layer's split packs are needed
  * Returns 0, or MTADGAT_ERR_INVALID. */
-int mtadgat_front_route(mtadgat_handle h, int kind, int source, int64_t n, int facts, int* out);
+int mtadgat_front_route(mtadgat_handle h, int kind, int source, int64_t n, int facts, int* out_host);
 /* Test hook (host only: needs neither a GPU nor loaded weights): how a forward call of `batch` windows is cut up and where each part
  * lives in the caller's workspace.  The answer is the one the library's own forward uses under the handle's current
  * mtadgat_set_chunk_windows size, mtadgat_set_precision mode and "lanes" option.  Writes 5 + 3 * n_pieces values:
- *   out[0]  n_pieces: pieces of the call, run in this order
- *   out[1]  1 when the call is small enough to run its independent stages side by side on the handle's second stream
- *   out[2]  floats of the workspace part of lane 0 (the caller's stream), which begins at the workspace's start
- *   out[3]  floats of the part of lane 1 (the handle's second stream), which begins out[2] floats in; 0 when no piece runs there
- *   out[4]  floats of the whole workspace: mtadgat_workspace_bytes / 4
- *   out[5 + 3 i .. 8 + 3 i)  piece i: its first window, its window count, its lane
+ *   out_host[0]  n_pieces: pieces of the call, run in this order
+ *   out_host[1]  1 when the call is small enough to run its independent stages side by side on the handle's second stream
+ *   out_host[2]  floats of the workspace part of lane 0 (the caller's stream), which begins at the workspace's start
+ *   out_host[3]  floats of the part of lane 1 (the handle's second stream), which begins out_host[2] floats in; 0 when no piece runs there
+ *   out_host[4]  floats of the whole workspace: mtadgat_workspace_bytes / 4
+ *   out_host[5 + 3 i .. 8 + 3 i)  piece i: its first window, its window count, its lane
  * Returns the count of values written, or MTADGAT_ERR_INVALID (a NULL argument, batch < 1, max_n too small: nothing is written). */
-int mtadgat_forward_plan(mtadgat_handle h, int64_t batch, int64_t* out, int max_n);
+int mtadgat_forward_plan(mtadgat_handle h, int64_t batch, int64_t* out_host, int max_n);
 /* Test hook (host only: needs neither a GPU nor loaded weights): which kernels run the recurrence layers and the attention layers of
  * a training step (mtadgat_forward_train + mtadgat_backward) of n windows.  The answer is the one the library's own dispatch uses
  * under the handle's current mtadgat_set_precision mode and "gru_kernel" option; the backward's recurrence kernel is derived from
  * the forward's, whose tape it reads.  Writes 3 * (gru_n_layers + recon_n_layers) + 5 ints:
  *   per layer of the GRU stack, then per layer of the decoder, counted from the input:
- *     [0]  first kernel of the training forward (the codes of mtadgat_gru_route's out[0])
+ *     [0]  first kernel of the training forward (the codes of mtadgat_gru_route's out_host[0])
  *     [1]  kernel of the backward: 0 k_gru1_bwd (partner of k_gru1), 1 k_gru16_bwd (partner of k_gru16), 2 k_gru_bwd (partner of
  *          k_gru_split on either operand build)
  *     [2]  k_gru_bwd multiplies on three bf16 pieces per operand (its split pack is derived on first use after an upload)
@@ -271,7 +271,7 @@ int mtadgat_forward_plan(mtadgat_handle h, int64_t batch, int64_t* out, int max_
  *     [1]  the score backward is GAT (v1)'s (use_gatv2 == 0)
  * Returns the count of values written, or MTADGAT_ERR_INVALID (a NULL argument, n < 1, max_n too small: nothing is written),
  * MTADGAT_ERR_UNSUPPORTED (the configuration has no HIP backward). */
-int mtadgat_train_route(mtadgat_handle h, int64_t n, int* out, int max_n);
+int mtadgat_train_route(mtadgat_handle h, int64_t n, int* out_host, int max_n);
 /* Test hook (host only: needs neither a GPU nor loaded weights): how the weight-gradient GEMMs (d W = A^T B over the rows of the
  * call, k_wgrad_lds + one batched reduction) of a backward of n windows -- one chunk of the training step -- are laid out.  The slab
  * plan is the one the library's own dispatch launches under the handle's current mtadgat_set_precision mode and "wgrad_kernel"
@@ -289,7 +289,7 @@ int mtadgat_train_route(mtadgat_handle h, int64_t n, int* out, int max_n);
  * (Whether a site stages float4 or dword loads depends on the alignment of the call's buffers and is not reported.)
  * Returns the count of values written, or MTADGAT_ERR_INVALID (a NULL argument, n < 1, max_n too small: nothing is written),
  * MTADGAT_ERR_UNSUPPORTED (the configuration has no HIP backward). */
-int mtadgat_wgrad_plan(mtadgat_handle h, int64_t n, int64_t* out, int max_n);
+int mtadgat_wgrad_plan(mtadgat_handle h, int64_t n, int64_t* out_host, int max_n);
 /* Test hook (host only): does a row GEMM over `rows` rows take split-bf16 operands (k_rowgemm_x3) under the handle's precision mode
  * and "rowgemm_kernel" option?  has_pack: a split pack was planned for its weights; backward: a site of mtadgat_backward (there
  * "rowgemm_kernel" = 2 forces the split pack in every mode, in the forward only in the "fp32" mode).  Returns 1 / 0, negative: error. */
@@ -502,7 +502,7 @@ size_t  mtadgat_backward_workspace_bytes(mtadgat_handle h, int64_t batch);
 int64_t mtadgat_grad_floats(mtadgat_handle h);
 /* offsets (floats) of conv w,b | feature lin w,b,a,bias | temporal lin w,b,a,bias | gru w_ih,w_hh,b_ih,b_hh |
  * fc (w,b) x forecast_n_linear | decoder w_ih,w_hh,b_ih,b_hh | recon fc w,b; returns the count */
-int     mtadgat_grad_offsets(mtadgat_handle h, int64_t* offsets_out, int max_n);
+int     mtadgat_grad_offsets(mtadgat_handle h, int64_t* offsets_host, int max_n);
 int mtadgat_forward_train(mtadgat_handle h, const float* x_dev, int64_t batch, int64_t window0, float dropout_p,
                           uint64_t seed, float* preds_dev, float* recons_dev, void* tape_dev, size_t tape_bytes,
                           void* stream);
@@ -558,7 +558,7 @@ int mtadgat_dropout_masks(mtadgat_handle h, int64_t batch, int64_t window0, floa
  * (gru_n_layers - 1, batch, W, gru_hid_dim), mask_rec (recon_n_layers - 1, batch, W, recon_hid_dim); either may be NULL. */
 int mtadgat_dropout_masks_rnn(mtadgat_handle h, int64_t batch, int64_t window0, float dropout_p, uint64_t seed, float* mask_gru,
                               float* mask_rec, void* stream);
-int mtadgat_train_layout(mtadgat_handle h, int64_t batch, int64_t* offsets_out, int max_n);
+int mtadgat_train_layout(mtadgat_handle h, int64_t batch, int64_t* offsets_host, int max_n);
 
 /* ---- anomaly-score post-processing on the device (callers' data path) ------
  * The arithmetic of Predictor.get_score (prediction.py:72-91) and of the threshold evaluation
@@ -964,8 +964,8 @@ int mtadgat_spot_read(const void* state_dev, int64_t n_columns, int64_t max_peak
 int mtadgat_spot_copy(void* dst_dev, int64_t dst_columns, const void* src_dev, int64_t src_columns, int64_t max_peaks,
                       const int64_t* columns_dev, int64_t n, int init, void* stream);
 /* Host only, no GPU needed: the fit over m >= 1 positive excesses (oldest first) for n observations, Nt excesses, initial
- * threshold t and risk q, with the sums taken in the order a wave takes them.  out[3] = gamma, sigma, z. */
-int mtadgat_spot_fit_host(const double* peaks, int64_t m, int64_t n, int64_t Nt, double t, double q, double* out);
+ * threshold t and risk q, with the sums taken in the order a wave takes them.  out_host[3] = gamma, sigma, z. */
+int mtadgat_spot_fit_host(const double* peaks_host, int64_t m, int64_t n, int64_t Nt, double t, double q, double* out_host);
 /* mtadgat_stream_push / _update with each stream compared against ITS column of a SPOT state of n_streams columns (a second
  * device allocation beside the stream state), after the smoothing; the column advances with the stream.  thresholds_out_dev:
  * (n, T) float64, what each row was compared against (NaN for a stream's first W rows), or NULL. */

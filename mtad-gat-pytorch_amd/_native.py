@@ -9,6 +9,8 @@ import os
 
 import torch  # must be imported before the library: both bind libamdhip64.so.7, torch's copy wins
 
+import _abi
+
 # Debugging aid (tests/test_gpu_fuzz.py): every scratch buffer handed to the library (workspace, training tape) is
 # filled with a large finite value before each call, so a kernel that USES scratch it did not write shows up in the outputs of a
 # single call instead of depending on what the caching allocator left in the block (finite, inside the fp16 range: padding that
@@ -30,10 +32,54 @@ def _empty(*shape, **kw):
 def _empty_like(x):
     return _empty(x.shape, dtype=x.dtype, device=x.device)
 
+
+def _stream(device=None):
+    """The current HIP stream of `device` -- a tensor stands for its device, None for the current device -- as the void* the
+    library takes."""
+    if isinstance(device, torch.Tensor):
+        device = device.device
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _scratch(nbytes, device, least=0):
+    """Scratch of max(nbytes, least) bytes in 8-byte words from _empty (poisoned under MTADGAT_POISON_SCRATCH): exactly the
+    header's minimum unless the caller asks for a floor."""
+    return _empty((max(nbytes, least) + 7) // 8, dtype=torch.float64, device=device)
+
+
+def _fail(lib, rc, what):
+    raise RuntimeError(f"mtadgat {what} failed (status {rc}): {lib.mtadgat_last_error().decode('utf-8', 'replace')}")
+
+
+def _rows2d(t, name, gpu_only=False, max_columns=None):
+    """A float32 (n, d) tensor whose rows are contiguous (a column slice keeps its row stride: no copy); 1-D is one column.
+    gpu_only: the evaluation kernels' check; max_columns: the preparation's limit."""
+    if gpu_only and (not isinstance(t, torch.Tensor) or t.device.type != "cuda"):
+        raise RuntimeError(f"{name} must be a tensor on the GPU (the evaluation kernels are HIP only)")
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    t = t.detach()
+    if t.ndim == 1:
+        t = t.reshape(-1, 1)
+    if t.ndim != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError(f"{name} must have shape (n, d) with n, d >= 1, got {tuple(t.shape)}")
+    if max_columns is not None and t.shape[1] > max_columns:
+        raise ValueError(f"{name} has {t.shape[1]} columns, the preparation covers up to {max_columns}")
+    if t.dtype != torch.float32:
+        t = t.float()
+    if t.shape[0] == 1:                    # a single row: any row stride is legal in torch, the kernels want ld >= d
+        t = t.as_strided((1, t.shape[1]), (t.shape[1], 1)) if t.shape[1] == 1 or t.stride(1) == 1 else t.reshape(1, -1).clone()
+    if t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+        t = t.contiguous()
+    return t
+
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "libmtadgat.so")
-MAX_LAYERS = 8
-PROFILE_SLOTS = 6
+_HEADER = _abi.read()                  # include/mtadgat.h: the constants here, the Structures below and every declaration come from it
+ABI_VERSION = _HEADER.defines["MTADGAT_ABI_VERSION"]
+MAX_LAYERS = _HEADER.defines["MTADGAT_MAX_LAYERS"]
+PROFILE_SLOTS = _HEADER.defines["MTADGAT_PROFILE_SLOTS"]
 # mtadgat_gru_route: the integers it writes, the kernel codes (GruKernel) and operand builds (GruBuild) of csrc/mtadgat_host.h
 GRU_ROUTE_FIELDS = ("first", "fallback", "build", "two", "hoist", "split_packs", "fc_rides", "small_stack")
 GRU_KERNELS = ("none", "k_gru1", "k_gru16", "k_gru_split", "k_gru_split_x3", "k_gru_cm", "k_gru")
@@ -54,8 +100,7 @@ FRONT_BUILDS = ("fp32", "bf16", "x3")
 # mtadgat_fit_prepare: the float64 fields of the step record and of a row of the log ring (include/mtadgat.h)
 FIT_STATE_FIELDS = ("t", "calls", "clip", "step_size", "bc2s", "applied", "norm_sq", "norm")
 FIT_LOG_FIELDS = ("rmse_forecast", "rmse_recon", "norm", "applied")
-
-_c_float_p = ctypes.POINTER(ctypes.c_float)
+assert len(FIT_STATE_FIELDS) == _HEADER.defines["MTADGAT_FIT_STATE_FIELDS"]
 
 
 class Config(ctypes.Structure):
@@ -76,6 +121,13 @@ class Params(ctypes.Structure):
         + [("rec_fc_weight", ctypes.c_void_p), ("rec_fc_bias", ctypes.c_void_p)])
 
 
+class _Outputs(ctypes.Structure):
+    """mtadgat_stream_outputs (streaming.py fills it)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("scores", "flags", "per_dim", "closed_start", "closed_end", "closed_peak",
+                                                "closed_peak_score", "closed_mean")]
+
+
+_HEADER.register(mtadgat_config=Config, mtadgat_params=Params, mtadgat_stream_outputs=_Outputs)
 _lib = None
 
 
@@ -93,88 +145,8 @@ def load_library():
             f"{_LIB_PATH} is missing: the MI355X HIP extension has not been built "
             "(run `python -c 'import __graft_entry__ as g; g.build()'` or "
             "`python mtad-gat-pytorch_amd/build.py`). There is no non-HIP implementation.")
-    lib = ctypes.CDLL(_LIB_PATH)
-    vp, i64, sz = ctypes.c_void_p, ctypes.c_int64, ctypes.c_size_t
-    lib.mtadgat_abi_version.restype = ctypes.c_int
-    lib.mtadgat_last_error.restype = ctypes.c_char_p
-    lib.mtadgat_create.argtypes = [ctypes.POINTER(Config), ctypes.POINTER(vp)]
-    lib.mtadgat_destroy.argtypes = [vp]
-    lib.mtadgat_load_weights.argtypes = [vp, ctypes.POINTER(Params), vp]
-    lib.mtadgat_update_weights_device.argtypes = [vp, vp, i64, vp]
-    lib.mtadgat_params_fingerprint.argtypes = [vp, vp, ctypes.c_int, vp, vp]
-    lib.mtadgat_packed_floats.argtypes = [vp]
-    lib.mtadgat_packed_floats.restype = i64
-    lib.mtadgat_read_packed.argtypes = [vp, vp, i64, vp]
-    lib.mtadgat_derived_regions.argtypes = [vp, ctypes.POINTER(i64), ctypes.c_int]
-    lib.mtadgat_split_steps.argtypes = [vp, ctypes.POINTER(i64), ctypes.c_int]
-    lib.mtadgat_split_n_infer.argtypes = [vp]
-    lib.mtadgat_derive_split_packs.argtypes = [vp, vp]
-    lib.mtadgat_gru_route.argtypes = [vp, ctypes.c_int, ctypes.c_int, i64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
-    lib.mtadgat_front_route.argtypes = [vp, ctypes.c_int, ctypes.c_int, i64, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
-    lib.mtadgat_forward_plan.argtypes = [vp, i64, ctypes.POINTER(i64), ctypes.c_int]
-    lib.mtadgat_train_route.argtypes = [vp, i64, ctypes.POINTER(ctypes.c_int), ctypes.c_int]
-    lib.mtadgat_wgrad_plan.argtypes = [vp, i64, ctypes.POINTER(i64), ctypes.c_int]
-    lib.mtadgat_rowgemm_split.argtypes = [vp, ctypes.c_int, i64, ctypes.c_int]
-    lib.mtadgat_workspace_bytes.argtypes = [vp, i64]
-    lib.mtadgat_workspace_bytes.restype = sz
-    lib.mtadgat_set_precision.argtypes = [vp, ctypes.c_int]
-    lib.mtadgat_set_option.argtypes = [vp, ctypes.c_char_p, ctypes.c_int]
-    lib.mtadgat_last_conv_max.argtypes = [vp, vp, i64, ctypes.POINTER(ctypes.c_float), vp]
-    lib.mtadgat_bf16_ready.argtypes = [vp]
-    lib.mtadgat_chunk_windows.argtypes = [vp]
-    lib.mtadgat_chunk_windows.restype = i64
-    lib.mtadgat_set_chunk_windows.argtypes = [vp, i64]
-    lib.mtadgat_forward.argtypes = [vp, vp, i64, vp, vp, vp, vp, sz, vp]
-    lib.mtadgat_forward_xbf16.argtypes = [vp, vp, i64, vp, vp, vp, vp, sz, vp]
-    lib.mtadgat_forward_series.argtypes = [vp, vp, i64, vp, i64, i64, i64, vp, vp, vp, vp, sz, vp]
-    lib.mtadgat_conv.argtypes = [vp, vp, i64, vp, vp, sz, vp]
-    lib.mtadgat_gat.argtypes = [vp, ctypes.c_int, vp, i64, vp, vp, sz, vp]
-    lib.mtadgat_gru.argtypes = [vp, vp, i64, vp, vp, sz, vp]
-    lib.mtadgat_heads.argtypes = [vp, vp, i64, vp, vp, vp, sz, vp]
-    lib.mtadgat_attention_workspace_bytes.argtypes = [vp, i64, ctypes.c_int]
-    lib.mtadgat_attention_workspace_bytes.restype = sz
-    lib.mtadgat_attention.argtypes = [vp, vp, i64, vp, vp, vp, sz, vp]
-    lib.mtadgat_attention_mean.argtypes = [vp, vp, i64, vp, vp, vp, sz, vp]
-    lib.mtadgat_attention_series.argtypes = [vp, vp, i64, vp, i64, i64, i64, vp, vp, vp, sz, vp]
-    lib.mtadgat_attention_series_mean.argtypes = [vp, vp, i64, vp, i64, i64, i64, vp, vp, vp, sz, vp]
-    lib.mtadgat_series_losses_chunk.argtypes = [vp]
-    lib.mtadgat_series_losses_chunk.restype = i64
-    lib.mtadgat_series_losses_workspace_bytes.argtypes = [vp, i64]
-    lib.mtadgat_series_losses_workspace_bytes.restype = sz
-    lib.mtadgat_series_losses.argtypes = [vp, vp, i64, vp, i64, i64, i64, vp, vp, vp, vp, sz, vp]
-    u64, f32 = ctypes.c_uint64, ctypes.c_float
-    lib.mtadgat_backward_supported.argtypes = [vp]
-    lib.mtadgat_tape_bytes.argtypes = [vp, i64]
-    lib.mtadgat_tape_bytes.restype = sz
-    lib.mtadgat_backward_workspace_bytes.argtypes = [vp, i64]
-    lib.mtadgat_backward_input.argtypes = [vp, i64, vp, sz, vp, vp]
-    lib.mtadgat_backward_input.restype = ctypes.c_int
-    lib.mtadgat_backward_workspace_bytes.restype = sz
-    lib.mtadgat_grad_floats.argtypes = [vp]
-    lib.mtadgat_grad_floats.restype = i64
-    lib.mtadgat_grad_offsets.argtypes = [vp, ctypes.POINTER(i64), ctypes.c_int]
-    lib.mtadgat_train_layout.argtypes = [vp, i64, ctypes.POINTER(i64), ctypes.c_int]
-    lib.mtadgat_forward_train.argtypes = [vp, vp, i64, i64, f32, u64, vp, vp, vp, sz, vp]
-    lib.mtadgat_backward.argtypes = [vp, vp, i64, i64, f32, u64, vp, vp, vp, sz, vp, vp, sz, vp]
-    lib.mtadgat_backward_data.argtypes = [vp, vp, i64, i64, f32, u64, vp, vp, vp, sz, vp, vp, sz, vp]
-    lib.mtadgat_score_attribution_workspace_bytes.argtypes = [vp, i64, ctypes.c_int]
-    lib.mtadgat_score_attribution_workspace_bytes.restype = sz
-    lib.mtadgat_score_attribution.argtypes = [vp, vp, i64, vp, i64, vp, ctypes.c_int, vp, f32, ctypes.c_int, vp, ctypes.c_int, vp,
-                                              vp, sz, vp]
-    lib.mtadgat_dropout_masks.argtypes = [vp, i64, i64, f32, u64, vp, vp, vp, vp]
-    lib.mtadgat_dropout_masks_rnn.argtypes = [vp, i64, i64, f32, u64, vp, vp, vp]
-    f64, ci = ctypes.c_double, ctypes.c_int
-    lib.mtadgat_fit_gather.argtypes = [vp, i64, ci, i64, vp, i64, ci, vp, vp]
-    lib.mtadgat_fit_loss_grad.argtypes = [vp, vp, i64, ci, ci, vp, i64, ci, i64, vp, vp, vp, vp, vp, vp, vp]
-    lib.mtadgat_fit_prepare_scratch.argtypes = [i64]
-    lib.mtadgat_fit_prepare_scratch.restype = sz
-    lib.mtadgat_fit_prepare.argtypes = [vp, i64, vp, f64, f64, f64, f64, ci, vp, vp, i64, vp, sz, vp]
-    lib.mtadgat_fit_adam.argtypes = [vp, vp, vp, vp, i64, vp, f64, f64, f64, f64, f64, ci, vp]
-    lib.mtadgat_profile_enable.argtypes = [vp, ctypes.c_int]
-    lib.mtadgat_profile_read.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i64)]
-    lib.mtadgat_profile_name.argtypes = [ctypes.c_int]
-    lib.mtadgat_profile_name.restype = ctypes.c_char_p
-    if lib.mtadgat_abi_version() != 1:
+    lib = _HEADER.bind(ctypes.CDLL(_LIB_PATH))
+    if lib.mtadgat_abi_version() != ABI_VERSION:
         raise RuntimeError("libmtadgat.so ABI version mismatch")
     _lib = lib
     return lib
@@ -220,10 +192,6 @@ def _dev_ptr(t, name, shape=None):
 
 # -- the series trainer's kernels (csrc/mtadgat_fit.hip; tests/fit_refs.py is the specification) --------------
 # Handle-free, asynchronous on the current stream of the tensors' device; none of them reads from the device.
-def _cur_stream(t):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
 def _typed(t, dtype, name, numel=None):
     if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != dtype or not t.is_contiguous():
         raise RuntimeError(f"{name} must be a contiguous {dtype} tensor on the GPU")
@@ -248,7 +216,7 @@ def fit_gather(series, starts, W, out=None):
         out = _empty((b, W, F), dtype=torch.float32, device=series.device)
     with torch.cuda.device(series.device):
         _check(load_library().mtadgat_fit_gather(sp, n_rows, F, ld, _typed(starts, torch.int64, "starts"), b, W,
-                                                 _typed(out, torch.float32, "x", b * W * F), _cur_stream(series)), "fit_gather")
+                                                 _typed(out, torch.float32, "x", b * W * F), _stream(series)), "fit_gather")
     return out
 
 
@@ -267,7 +235,7 @@ def fit_loss_grad(preds, recons, series, starts, sums, dims=None, d_preds=None, 
             _typed(preds, torch.float32, "preds", b * out), _typed(recons, torch.float32, "recons"), b, W, out, sp, n_rows, F, ld,
             _typed(starts, torch.int64, "starts", b), None if dims is None else _typed(dims, torch.int32, "dims", out),
             _typed(sums, torch.float64, "sums", 2), _typed(d_preds, torch.float32, "d_preds", b * out),
-            _typed(d_recons, torch.float32, "d_recons", b * W * out), _typed(rmse, torch.float64, "rmse", 2), _cur_stream(series)),
+            _typed(d_recons, torch.float32, "d_recons", b * W * out), _typed(rmse, torch.float64, "rmse", 2), _stream(series)),
             "fit_loss_grad")
     return d_preds, d_recons, rmse
 
@@ -285,7 +253,7 @@ def fit_prepare(grads, rmse, state, log, lr, betas, max_grad_norm=None, skip_non
             _typed(grads, torch.float32, "grads"), n, _typed(rmse, torch.float64, "rmse", 2), float(lr), float(betas[0]), float(betas[1]),
             -1.0 if max_grad_norm is None else float(max_grad_norm), int(bool(skip_nonfinite)),
             _typed(state, torch.float64, "state", len(FIT_STATE_FIELDS)), _typed(log, torch.float64, "log"), log.numel() // 4,
-            _typed(scratch, torch.float64, "scratch"), scratch.numel() * 8, _cur_stream(grads)), "fit_prepare")
+            _typed(scratch, torch.float64, "scratch"), scratch.numel() * 8, _stream(grads)), "fit_prepare")
 
 
 def fit_adam(params, grads, exp_avg, exp_avg_sq, state, lr, betas, eps, weight_decay=0.0, decoupled=False):
@@ -295,7 +263,7 @@ def fit_adam(params, grads, exp_avg, exp_avg_sq, state, lr, betas, eps, weight_d
         _check(load_library().mtadgat_fit_adam(
             _typed(params, torch.float32, "params"), _typed(grads, torch.float32, "grads", n), _typed(exp_avg, torch.float32, "exp_avg", n),
             _typed(exp_avg_sq, torch.float32, "exp_avg_sq", n), n, _typed(state, torch.float64, "state", len(FIT_STATE_FIELDS)),
-            float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(bool(decoupled)), _cur_stream(params)),
+            float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(bool(decoupled)), _stream(params)),
             "fit_adam")
 
 
@@ -500,8 +468,7 @@ class Engine:
         if flat.device != device:
             return False
         with torch.cuda.device(device):
-            stream = torch.cuda.current_stream().cuda_stream
-            rc = self.lib.mtadgat_update_weights_device(self.handle, ctypes.c_void_p(flat.data_ptr()), flat.numel(), ctypes.c_void_p(stream))
+            rc = self.lib.mtadgat_update_weights_device(self.handle, ctypes.c_void_p(flat.data_ptr()), flat.numel(), _stream())
         if rc == -2:          # MTADGAT_ERR_UNSUPPORTED
             return False
         _check(rc, "update_weights_device")
@@ -521,8 +488,7 @@ class Engine:
             self._fp_cache = cache
         _, ptrs, counts, out = cache
         with torch.cuda.device(device):
-            stream = torch.cuda.current_stream().cuda_stream
-            _check(self.lib.mtadgat_params_fingerprint(ptrs, counts, n, ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(stream)), "fingerprint")
+            _check(self.lib.mtadgat_params_fingerprint(ptrs, counts, n, ctypes.c_void_p(out.data_ptr()), _stream()), "fingerprint")
         return int(out.item())
 
     def fingerprint_async(self, params, device):
@@ -569,8 +535,8 @@ class Engine:
         n = self.lib.mtadgat_packed_floats(self.handle)
         out = _empty(n, dtype=torch.float32)
         with torch.cuda.device(device):
-            stream = torch.cuda.current_stream().cuda_stream
-            _check(self.lib.mtadgat_read_packed(self.handle, ctypes.c_void_p(out.data_ptr()), n, ctypes.c_void_p(stream)), "read_packed")
+            dst = ctypes.cast(out.data_ptr(), ctypes.POINTER(ctypes.c_float))
+            _check(self.lib.mtadgat_read_packed(self.handle, dst, n, _stream()), "read_packed")
         return out
 
     def derived_regions(self):
@@ -593,8 +559,7 @@ class Engine:
         """Diagnostic: derive every split group, the backward's included, on the current stream (read_packed derives the
         inference groups only)."""
         with torch.cuda.device(device):
-            stream = torch.cuda.current_stream().cuda_stream
-            _check(self.lib.mtadgat_derive_split_packs(self.handle, ctypes.c_void_p(stream)), "derive_split_packs")
+            _check(self.lib.mtadgat_derive_split_packs(self.handle, _stream()), "derive_split_packs")
 
     def gru_route(self, stack, layer, n, training=False, compute_units=256):
         """Which kernels run recurrence layer `layer` of the GRU stack (stack 0) or the decoder (1) at n windows, under the current
@@ -697,8 +662,7 @@ class Engine:
             p.rec_b_ih[l], p.rec_b_hh[l] = ptr(f"{pre}bias_ih_l{l}").value, ptr(f"{pre}bias_hh_l{l}").value
         p.rec_fc_weight, p.rec_fc_bias = ptr("recon_model.fc.weight"), ptr("recon_model.fc.bias")
         with torch.cuda.device(device):
-            stream = torch.cuda.current_stream().cuda_stream
-            _check(self.lib.mtadgat_load_weights(self.handle, ctypes.byref(p), ctypes.c_void_p(stream)), "load_weights")
+            _check(self.lib.mtadgat_load_weights(self.handle, ctypes.byref(p), _stream()), "load_weights")
         self._keep = flat
 
     # -- scratch ------------------------------------------------------------------------------
@@ -732,8 +696,7 @@ class Engine:
             return 0.0
         out = ctypes.c_float(0.0)
         with torch.cuda.device(device):
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            _check(self.lib.mtadgat_last_conv_max(self.handle, ctypes.c_void_p(self._ws.data_ptr()), int(batch), ctypes.byref(out), stream),
+            _check(self.lib.mtadgat_last_conv_max(self.handle, ctypes.c_void_p(self._ws.data_ptr()), int(batch), ctypes.byref(out), _stream()),
                    "last_conv_max")
         return float(out.value)
 
@@ -746,8 +709,7 @@ class Engine:
 
     def _call(self, fn, what, device, *args):
         with torch.cuda.device(device):
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            _check(fn(self.handle, *args, stream), what)
+            _check(fn(self.handle, *args, _stream()), what)
 
     # -- forward ------------------------------------------------------------------------------
     def forward(self, x, want_hend=False):

@@ -4,6 +4,7 @@
 // O(N) work per threshold on 1-D arrays; the scalar bookkeeping (picking the best z / threshold, F1 from the
 // confusion counts) stays on the host in float64 exactly as the reference writes it.
 // Every kernel here is launched with 256 threads; block_sum and epsilon_tile come from mtadgat_scan.h.
+#include "../../include/mtadgat.h"      // the entry points' declarations
 #include "mtadgat_scan.h"
 
 namespace mtadgat {

@@ -17,6 +17,7 @@
 //       that composes the chunk carries in chunk order, and a pass that applies carry and closed-form denominator.  No atomics.
 //       One template, instantiated for the whole array (mtadgat_eval_ewm) and restarted at every span of a concatenated series
 //       (mtadgat_eval_ewm_parts).
+#include "../../include/mtadgat.h"      // the entry points' declarations
 #include "mtadgat_scan.h"
 
 namespace mtadgat {

@@ -10,6 +10,7 @@
 //       partial in the block's own slot; one wave per run then adds the slots in block order, so the bits depend on the data and
 //       on SPAN_RB only, not on the grid.  The top columns are top_k rounds of a wave-wide arg-max over an ordered integer key.
 //   k_eval_first_hit: the first flagged sample of every run, one wave per run, 64 samples per step, ballot + count-trailing-zeros.
+#include "../../include/mtadgat.h"      // the entry points' declarations
 #include "mtadgat_scan.h"
 
 namespace mtadgat {

@@ -20,6 +20,7 @@
 // the windows into calls (the slab count is a function of (batch, out_dim)).
 #include <algorithm>
 
+#include "../../include/mtadgat.h"      // the entry points' declarations
 #include "mtadgat_scan.h"
 
 using namespace mtadgat;

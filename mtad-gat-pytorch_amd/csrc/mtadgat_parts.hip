@@ -15,6 +15,7 @@
 //   k_part_flags                                          score_i > eps[part(i)]
 //   k_part_scale                                          (a - median) / (1 + IQR) with the quantiles of the row's part, which
 //                                                         mtadgat_eval_part_quantiles (mtadgat_evalcol.hip) selects
+#include "../../include/mtadgat.h"      // the entry points' declarations
 #include "mtadgat_scan.h"
 
 namespace mtadgat {

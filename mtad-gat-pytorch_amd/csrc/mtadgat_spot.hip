@@ -12,6 +12,7 @@
 //       and flags stored at a time, one per lane.  The state is left advanced: a second call continues where the first stopped.
 //   k_spot_copy: columns from one state to another (a clone of some columns, one column serving many streams, a reset).
 // No atomics; nothing depends on the launch geometry; every store is an ordinary vector store.
+#include "../../include/mtadgat.h"      // the entry points' declarations
 #include "mtadgat_device.h"
 #include "mtadgat_spot.h"
 

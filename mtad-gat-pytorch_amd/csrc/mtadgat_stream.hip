@@ -16,6 +16,7 @@
 //       advances that column too; the fixed-threshold instance compiles to the code it had before the variant existed.
 //   k_stream_flush: the still-open event of each selected stream, and / or the stream's reset to its initial state (ring zeroed).
 // No atomics.  A stream index outside [0, S) writes "nothing here" (NaN / -1 / 0) and touches no state.
+#include "../../include/mtadgat.h"      // the entry points' declarations
 #include "mtadgat_device.h"
 #include "mtadgat_spot.h"
 

@@ -72,78 +72,8 @@ import _native
 _c_double_p = ctypes.POINTER(ctypes.c_double)
 
 
-def _lib():
-    lib = _native.load_library()
-    if not getattr(lib, "_eval_bound", False):
-        vp, i64, f32, ci = ctypes.c_void_p, ctypes.c_int64, ctypes.c_float, ctypes.c_int
-        lib.mtadgat_eval_scores.argtypes = [vp, vp, vp, i64, ci, i64, vp, f32, vp, vp, vp]
-        lib.mtadgat_eval_moments.argtypes = [vp, i64, vp, _c_double_p, vp]
-        lib.mtadgat_eval_epsilon_table.argtypes = [vp, i64, _c_double_p, ci, ci, vp, _c_double_p, vp]
-        lib.mtadgat_eval_point_adjust.argtypes = [vp, vp, i64, _c_double_p, ci, ci, ci, vp, _c_double_p, vp]
-        sz, f64 = ctypes.c_size_t, ctypes.c_double
-        lib.mtadgat_eval_moments_columns.argtypes = [vp, i64, ci, i64, vp, _c_double_p, vp]
-        lib.mtadgat_eval_epsilon_table_columns.argtypes = [vp, i64, ci, i64, _c_double_p, ci, ci, vp, _c_double_p, vp]
-        lib.mtadgat_eval_column_quantiles_scratch.argtypes = [i64, ci, ci]
-        lib.mtadgat_eval_column_quantiles_scratch.restype = sz
-        lib.mtadgat_eval_column_quantiles.argtypes = [vp, i64, ci, i64, _c_double_p, ci, vp, sz, vp, vp]
-        lib.mtadgat_eval_ewm_scratch.argtypes = [i64]
-        lib.mtadgat_eval_ewm_scratch.restype = sz
-        lib.mtadgat_eval_ewm.argtypes = [vp, i64, f64, vp, sz, vp, vp]
-        lib.mtadgat_eval_runs_chunk.argtypes = []
-        lib.mtadgat_eval_runs_chunk.restype = ci
-        lib.mtadgat_eval_runs_scratch.argtypes = [i64]
-        lib.mtadgat_eval_runs_scratch.restype = sz
-        lib.mtadgat_eval_runs.argtypes = [vp, vp, i64, f64, ci, i64, i64, i64, vp, sz, vp, vp, ctypes.POINTER(ctypes.c_int64), vp]
-        lib.mtadgat_eval_run_stats_scratch.argtypes = [i64, i64, ci]
-        lib.mtadgat_eval_run_stats_scratch.restype = sz
-        lib.mtadgat_eval_run_stats.argtypes = [vp, i64, vp, vp, i64, vp, ci, i64, vp, ci, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
-        lib.mtadgat_eval_first_hit.argtypes = [vp, vp, i64, f64, ci, vp, vp, i64, vp, vp]
-        u64p = ctypes.POINTER(ctypes.c_double)
-        lib.mtadgat_spot_state_bytes.argtypes = [i64, i64]
-        lib.mtadgat_spot_state_bytes.restype = sz
-        lib.mtadgat_spot_calibrate_scratch.argtypes = [i64, i64]
-        lib.mtadgat_spot_calibrate_scratch.restype = sz
-        lib.mtadgat_spot_calibrate.argtypes = [vp, i64, i64, i64, f64, f64, i64, ci, vp, vp, sz, vp]
-        lib.mtadgat_spot_run.argtypes = [vp, i64, i64, vp, i64, i64, vp, vp, vp]
-        lib.mtadgat_spot_read.argtypes = [vp, i64, i64, u64p, vp]
-        lib.mtadgat_spot_copy.argtypes = [vp, i64, vp, i64, i64, vp, i64, ci, vp]
-        lib.mtadgat_spot_fit_host.argtypes = [u64p, i64, i64, i64, f64, f64, u64p]
-        lib.mtadgat_eval_order_key.argtypes = [f32, ci]
-        lib.mtadgat_eval_order_key.restype = ctypes.c_uint32
-        lib.mtadgat_eval_sort_tile.argtypes = []
-        lib.mtadgat_eval_sort_tile.restype = ci
-        lib.mtadgat_eval_sort_scan_tiles.argtypes = []
-        lib.mtadgat_eval_sort_scan_tiles.restype = ci
-        lib.mtadgat_eval_score_order_scratch.argtypes = [i64]
-        lib.mtadgat_eval_score_order_scratch.restype = sz
-        lib.mtadgat_eval_score_order.argtypes = [vp, i64, ci, vp, sz, vp, vp]
-        lib.mtadgat_eval_curve_scratch.argtypes = [i64, ci]
-        lib.mtadgat_eval_curve_scratch.restype = sz
-        lib.mtadgat_eval_curve.argtypes = [vp, vp, i64, ci, ci, vp, sz, vp, vp, vp, ctypes.POINTER(ctypes.c_int64), vp]
-        lib.mtadgat_eval_part_adjust_scratch.argtypes = [i64, ci, i64]
-        lib.mtadgat_eval_part_adjust_scratch.restype = sz
-        lib.mtadgat_eval_part_adjust.argtypes = [vp, i64, ci, i64, vp, vp, i64, vp, i64, i64, i64, ci, vp, sz, vp, i64, vp, vp]
-        lib.mtadgat_eval_ewm_parts_scratch.argtypes = [i64]
-        lib.mtadgat_eval_ewm_parts_scratch.restype = sz
-        lib.mtadgat_eval_ewm_parts.argtypes = [vp, i64, vp, vp, i64, f64, vp, sz, vp, vp]
-        lib.mtadgat_eval_part_epsilon_scratch.argtypes = [i64, i64, ci]
-        lib.mtadgat_eval_part_epsilon_scratch.restype = sz
-        lib.mtadgat_eval_part_epsilon_moments.argtypes = [vp, i64, vp, vp, i64, ci, vp, sz, _c_double_p, vp]
-        lib.mtadgat_eval_part_epsilon_table.argtypes = [vp, i64, vp, vp, i64, _c_double_p, ci, ci, vp, sz, _c_double_p, vp]
-        lib.mtadgat_eval_part_flags.argtypes = [vp, i64, vp, vp, i64, vp, vp, vp]
-        lib.mtadgat_eval_part_quantiles_scratch.argtypes = [i64, ci, i64, ci]
-        lib.mtadgat_eval_part_quantiles_scratch.restype = sz
-        lib.mtadgat_eval_part_quantiles.argtypes = [vp, i64, ci, i64, vp, vp, i64, _c_double_p, ci, vp, sz, vp, vp]
-        lib.mtadgat_eval_partq_long.argtypes = []
-        lib.mtadgat_eval_partq_long.restype = ci
-        lib.mtadgat_eval_part_scale.argtypes = [vp, i64, ci, i64, vp, vp, i64, vp, vp, i64, vp]
-        lib.mtadgat_eval_window_sse_scratch.argtypes = [i64, ci]
-        lib.mtadgat_eval_window_sse_scratch.restype = sz
-        lib.mtadgat_eval_window_sse.argtypes = [vp, vp, i64, ci, ci, vp, i64, ci, i64, vp, i64, i64, vp, ci, vp, vp, vp, sz, vp]
-        lib.mtadgat_eval_group_sums.argtypes = [vp, i64, ci, i64, vp, vp]
-        lib.mtadgat_last_error.restype = ctypes.c_char_p
-        lib._eval_bound = True
-    return lib
+_lib = _native.load_library           # (tests/pointer_proxy.py replaces it: every call below fetches the library through it)
+_stream, _scratch, _fail = _native._stream, _native._scratch, _native._fail
 
 
 def _dev1d(t, dtype, name):
@@ -155,39 +85,14 @@ def _dev1d(t, dtype, name):
     return t.contiguous()
 
 
-def _stream(t):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
 def _check(rc, what):
     if rc != 0:
         raise RuntimeError(f"mtadgat {what} failed (status {rc})")
 
 
-def _fail(lib, rc, what):
-    raise RuntimeError(f"mtadgat {what} failed (status {rc}): {lib.mtadgat_last_error().decode()}")
-
-
-def _scratch(nbytes, device):              # 8-byte words from _native._empty: poisoned under MTADGAT_POISON_SCRATCH
-    return _native._empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
-
-
 def _dev2d(t, name):
     """A float32 (n, d) GPU tensor whose rows are contiguous (a column slice keeps its row stride: no copy)."""
-    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-        raise RuntimeError(f"{name} must be a tensor on the GPU (the evaluation kernels are HIP only)")
-    t = t.detach()
-    if t.ndim == 1:
-        t = t.reshape(-1, 1)
-    if t.ndim != 2 or t.shape[0] < 1 or t.shape[1] < 1:
-        raise ValueError(f"{name} must have shape (n, d) with n, d >= 1, got {tuple(t.shape)}")
-    if t.dtype != torch.float32:
-        t = t.float()
-    if t.shape[0] == 1:                    # a single row: any row stride is legal in torch, the kernels want ld >= d
-        t = t.as_strided((1, t.shape[1]), (t.shape[1], 1)) if t.shape[1] == 1 or t.stride(1) == 1 else t.reshape(1, -1).clone()
-    if t.stride(1) != 1 or t.stride(0) < t.shape[1]:
-        t = t.contiguous()
-    return t
+    return _native._rows2d(t, name, gpu_only=True)
 
 
 def anomaly_scores(preds, recons, values, window_size, target_dims=None, gamma=1.0):

@@ -74,7 +74,7 @@ class SeriesTrainer:
         self.target_dims = target_dims
         self._dims = evaluation._target_dims(target_dims, model.out_dim, model.n_features)
         self.seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
-        self._lib = evaluation._lib()                       # libmtadgat.so with the evaluation entry points bound as well
+        self._lib = evaluation._lib()
         eng = model._sync_engine(self.device)
         model._finish_weight_check()
         if not eng.backward_supported():
@@ -127,7 +127,7 @@ class SeriesTrainer:
         eng, n = self._eng, self.params.numel()
         eng.set_precision(0 if self.model.precision == "fp32_strict" else 2)
         with torch.cuda.device(self.device):
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            stream = _native._stream()
             _native._check(self._lib.mtadgat_update_weights_device(eng.handle, ctypes.c_void_p(self.params.data_ptr()), n, stream),
                            "update_weights_device")
         # the module's own entry points re-pack from the parameters when one of them is called next
@@ -197,7 +197,7 @@ class SeriesTrainer:
         sp, stp = vp(series.data_ptr()), vp(starts.data_ptr())
         dims = None if self._dims_dev is None else vp(self._dims_dev.data_ptr())
         with torch.cuda.device(self.device):
-            stream = vp(torch.cuda.current_stream().cuda_stream)
+            stream = _native._stream()
             self.grads.zero_()
             _native._check(lib.mtadgat_fit_gather(sp, n_rows, F, ld, stp, b, W, vp(c["x"].data_ptr()), stream), "fit_gather")
             preds, recons, self._tape = eng.forward_train(c["x"], p, seed, 0, tape=self._tape)

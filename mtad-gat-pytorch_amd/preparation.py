@@ -25,7 +25,6 @@ GPU tensors run the HIP kernels of csrc/mtadgat_prep.hip (include/mtadgat.h: mta
 here for fit_scaler, transform and inverse (a scaler can be fitted where the data is loaded) whose bits are those of
 tests/prep_refs.py, the specification.  StreamPreparer is GPU only.
 """
-import ctypes
 import math
 
 import torch
@@ -38,27 +37,8 @@ _FIELDS = ("lo", "hi", "scale", "offset", "mean")
 _TINY_RANGE = 10.0 * 1.1920929e-07          # sklearn's _handle_zeros_in_scale: 10 * eps of float32
 
 
-def _lib():
-    lib = _native.load_library()
-    if not getattr(lib, "_prep_bound", False):
-        vp, i64, sz, ci = ctypes.c_void_p, ctypes.c_int64, ctypes.c_size_t, ctypes.c_int
-        lib.mtadgat_prep_rows_per_block.argtypes = []
-        lib.mtadgat_prep_rows_per_block.restype = ci
-        lib.mtadgat_prep_fit_scratch.argtypes = [i64, ci]
-        lib.mtadgat_prep_fit_scratch.restype = sz
-        lib.mtadgat_prep_fit.argtypes = [vp, i64, ci, i64, ci, vp, sz, vp, vp]
-        lib.mtadgat_prep_transform_scratch.argtypes = [i64, ci, ci, ci]
-        lib.mtadgat_prep_transform_scratch.restype = sz
-        lib.mtadgat_prep_transform.argtypes = [vp, i64, ci, i64, vp, ci, ci, vp, vp, i64, vp, sz, vp, i64, vp, vp]
-        lib.mtadgat_prep_inverse.argtypes = [vp, i64, ci, i64, vp, ci, vp, vp, i64, vp]
-        lib.mtadgat_prep_stream_state_bytes.argtypes = [i64, ci]
-        lib.mtadgat_prep_stream_state_bytes.restype = sz
-        lib.mtadgat_prep_stream_init.argtypes = [vp, i64, ci, vp]
-        lib.mtadgat_prep_stream_push.argtypes = [vp, i64, ci, vp, vp, i64, i64, vp, ci, ci, vp, vp, vp]
-        lib.mtadgat_prep_stream_reset.argtypes = [vp, i64, ci, vp, i64, vp]
-        lib.mtadgat_last_error.restype = ctypes.c_char_p
-        lib._prep_bound = True
-    return lib
+_lib = _native.load_library           # (tests/pointer_proxy.py replaces it: every call below fetches the library through it)
+_stream = _native._stream
 
 
 def rows_per_block():
@@ -67,35 +47,16 @@ def rows_per_block():
 
 
 def _fail(rc, what):
-    raise RuntimeError(f"mtadgat {what} failed (status {rc}): {_lib().mtadgat_last_error().decode('utf-8', 'replace')}")
+    _native._fail(_lib(), rc, what)
 
 
-def _stream(t):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
-def _scratch(nbytes, device):
-    return _native._empty((max(nbytes, 8) + 7) // 8, dtype=torch.float64, device=device)
+def _scratch(nbytes, device):              # (never empty: at least one 8-byte word)
+    return _native._scratch(nbytes, device, least=8)
 
 
 def _rows2d(t, name):
     """A float32 (n, d) tensor whose rows are contiguous (a column slice keeps its row stride: no copy); 1-D is one column."""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor")
-    t = t.detach()
-    if t.ndim == 1:
-        t = t.reshape(-1, 1)
-    if t.ndim != 2 or t.shape[0] < 1 or t.shape[1] < 1:
-        raise ValueError(f"{name} must have shape (n, d) with n, d >= 1, got {tuple(t.shape)}")
-    if t.shape[1] > 2048:
-        raise ValueError(f"{name} has {t.shape[1]} columns, the preparation covers up to 2048")
-    if t.dtype != torch.float32:
-        t = t.float()
-    if t.shape[0] == 1:                    # a single row: any row stride is legal in torch, the kernels want ld >= d
-        t = t.as_strided((1, t.shape[1]), (t.shape[1], 1)) if t.shape[1] == 1 or t.stride(1) == 1 else t.reshape(1, -1).clone()
-    if t.stride(1) != 1 or t.stride(0) < t.shape[1]:
-        t = t.contiguous()
-    return t
+    return _native._rows2d(t, name, max_columns=2048)
 
 
 def _fill_code(fill):

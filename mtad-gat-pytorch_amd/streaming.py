@@ -28,36 +28,15 @@ import torch
 import _native
 from evaluation import SpotState
 
-
-class _Outputs(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_void_p) for n in ("scores", "flags", "per_dim", "closed_start", "closed_end", "closed_peak",
-                                                "closed_peak_score", "closed_mean")]
-
-
+_lib = _native.load_library
+_Outputs = _native._Outputs
 _CLOSED = (("closed_start", torch.int64), ("closed_end", torch.int64), ("closed_peak", torch.int64),
            ("closed_peak_score", torch.float32), ("closed_mean", torch.float32))
 
 
-def _lib():
-    lib = _native.load_library()
-    if not getattr(lib, "_stream_bound", False):
-        vp, i64, sz, f64, ci = ctypes.c_void_p, ctypes.c_int64, ctypes.c_size_t, ctypes.c_double, ctypes.c_int
-        out_p = ctypes.POINTER(_Outputs)
-        lib.mtadgat_stream_state_bytes.argtypes = [vp, i64, i64]
-        lib.mtadgat_stream_state_bytes.restype = sz
-        lib.mtadgat_stream_init.argtypes = [vp, vp, i64, i64, f64, f64, i64, i64, vp, vp, vp, vp]
-        lib.mtadgat_stream_workspace_bytes.argtypes = [vp, i64]
-        lib.mtadgat_stream_workspace_bytes.restype = sz
-        lib.mtadgat_stream_push.argtypes = [vp, vp, i64, i64, vp, vp, i64, i64, f64, vp, out_p, vp, sz, vp]
-        lib.mtadgat_stream_update.argtypes = [vp, vp, i64, i64, vp, vp, vp, vp, i64, i64, ci, f64, vp, out_p, vp]
-        lib.mtadgat_stream_flush.argtypes = [vp, vp, i64, i64, vp, i64, ci, out_p, vp]
-        lib.mtadgat_stream_window_start.argtypes = [i64, i64, i64, i64]
-        lib.mtadgat_stream_window_start.restype = i64
-        lib.mtadgat_stream_update_spot.argtypes = [vp, vp, i64, i64, vp, vp, vp, vp, i64, i64, ci, vp, i64, vp, out_p, vp]
-        lib.mtadgat_stream_push_spot.argtypes = [vp, vp, i64, i64, vp, vp, i64, i64, vp, i64, vp, out_p, vp, sz, vp]
-        lib.mtadgat_stream_reset_spot.argtypes = [vp, vp, i64, i64, vp, vp, i64, i64, vp, i64, vp]
-        lib._stream_bound = True
-    return lib
+def _host(t, ctype):
+    """The typed host pointer of a CPU tensor (None: NULL)."""
+    return None if t is None else ctypes.cast(t.data_ptr(), ctypes.POINTER(ctype))
 
 
 def window_start(count, t, window_size, ring_rows):
@@ -151,10 +130,10 @@ class StreamScorer:
 
     # -- plumbing ------------------------------------------------------------------------------------------------------------
     def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _native._stream(self.device)
 
     def _fail(self, rc, what):
-        raise RuntimeError(f"mtadgat {what} failed (status {rc}): {_lib().mtadgat_last_error().decode('utf-8', 'replace')}")
+        _native._fail(_lib(), rc, what)
 
     def _ensure_state(self, eng):
         """The device allocation, made and initialised at the first call (the sizes come from the model's native handle)."""
@@ -168,8 +147,8 @@ class StreamScorer:
         gamma, alpha, gap, min_length, dims, center, spread = self._init_args
         with torch.cuda.device(self.device):
             rc = lib.mtadgat_stream_init(eng.handle, state.data_ptr(), self.n_streams, self.max_block, gamma, alpha, gap, min_length,
-                                         dims.data_ptr(), center.data_ptr() if center is not None else None,
-                                         spread.data_ptr() if spread is not None else None, self._stream())
+                                         _host(dims, ctypes.c_int32), _host(center, ctypes.c_float), _host(spread, ctypes.c_float),
+                                         self._stream())
         if rc != 0:
             self._fail(rc, "stream_init")
         self._state = state

@@ -61,8 +61,6 @@ def collect_shape(name, kw):
     BATCHES per combination.  The attention and attribution sizes depend on the chunk only and the training sizes on neither: they are
     queried under every mode and lanes value all the same, and recorded once after checking that the answers agree."""
     lib, h = create(kw)
-    lib.mtadgat_stream_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int64]
-    lib.mtadgat_stream_workspace_bytes.restype = ctypes.c_size_t
     out = {"kwargs": kw, "backward_supported": int(lib.mtadgat_backward_supported(h)), "workspace": {}, "stream": {}, "attention": {},
            "attribution": {}}
     bwd = out["backward_supported"] == 1

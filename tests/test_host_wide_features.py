@@ -79,7 +79,6 @@ def test_device_repack_gather_table_of_wide_feature_models(F):
     torch.manual_seed(3)
     model = MTAD_GAT(n_features=F, **dict(WIDE, out_dim=3))
     lib = _lib()
-    lib.mtadgat_selfcheck_gather_table.restype = ctypes.c_int64
     h = ctypes.c_void_p()
     assert lib.mtadgat_create(ctypes.byref(_native.Config(**model._native_cfg)), ctypes.byref(h)) == 0
     sd = {k: v.detach().float().contiguous() for k, v in model.state_dict().items()}
