@@ -476,6 +476,16 @@ size_t mtadgat_series_losses_workspace_bytes(mtadgat_handle h, int64_t batch);
 int mtadgat_series_losses(mtadgat_handle h, const float* series_dev, int64_t n_rows, const int64_t* starts_dev, int64_t start0,
                           int64_t stride, int64_t batch, const int32_t* dims_dev, double* window_sse_dev, double* dim_sse_dev,
                           void* workspace_dev, size_t workspace_bytes, void* stream);
+/* mtadgat_series_losses_masked: the same chunk loop with the reduction over observed samples only (mtadgat_fit_masked_sse below,
+ * with its age_dev (n_rows, F) int32 of row stride ld_age, and max_age): window_dev (batch, 4) float64 = (S_f, S_r, N_f, N_r) per
+ * window, dim_dev (4, out_dim) float64 the same per output dimension (may be NULL).  Everything else as mtadgat_series_losses: the
+ * chunk size, a chunk's outputs bit for bit those of mtadgat_forward_series, no state left behind, a workspace --
+ * mtadgat_series_losses_masked_workspace_bytes(h, batch) -- bounded by one chunk. */
+size_t mtadgat_series_losses_masked_workspace_bytes(mtadgat_handle h, int64_t batch);
+int mtadgat_series_losses_masked(mtadgat_handle h, const float* series_dev, int64_t n_rows, const int64_t* starts_dev, int64_t start0,
+                                 int64_t stride, int64_t batch, const int32_t* dims_dev, const int32_t* age_dev, int64_t ld_age,
+                                 int32_t max_age, double* window_dev, double* dim_dev, void* workspace_dev, size_t workspace_bytes,
+                                 void* stream);
 
 /* ---- training step --------------------------------------------------------------------------------
  * Replaces what autograd does for the reference around MTAD_GAT.forward in Trainer.fit
@@ -819,6 +829,52 @@ int mtadgat_fit_prepare(const float* grads_dev, int64_t n, const double* rmse_de
 int mtadgat_fit_adam(float* params_dev, const float* grads_dev, float* exp_avg_dev, float* exp_avg_sq_dev, int64_t n,
                      const double* state_dev, double lr, double beta1, double beta2, double eps, double weight_decay, int decoupled,
                      void* stream);
+
+/* ---- training on gappy, concatenated series (csrc/mtadgat_fitwin.hip, _losses.hip, _fit.hip; fitting.training_windows) -------
+ * The window sampler and the losses that count observed samples only.  tests/fit_mask_refs.py is the specification.
+ * Conventions of the fit calls above.  age_dev: (n_rows, F) int32 with row stride ld_age >= F, as the preparation's transform
+ * reports it -- 0 for a real sample, k for the k-th consecutive filled row; a sample is OBSERVED iff age <= max_age.
+ *
+ * mtadgat_fit_windows: the window starts a trainer may draw from.  Start s in [0, n_rows - W) reads rows s .. s + W - 1 and is asked
+ * for row s + W; it is valid iff
+ *   1. rows s .. s + W lie in one part: part p is rows [part_offsets_dev[p], part_offsets_dev[p + 1]), `parts` + 1 ascending int64
+ *      offsets from 0 to n_rows (NULL: one part);
+ *   2. row s + W has at least one observed sample among the columns dims_dev[0 .. out_dim) (NULL: 0 .. out_dim - 1);
+ *   3. rows s .. s + W - 1 hold at least min_count observed samples over all F columns.
+ * starts_dev[0 .. count) receives the valid starts in ascending order, *count_dev their number; entries from count on are not
+ * written.  age_dev NULL: every sample is observed.  All integer arithmetic, no atomics; seven launches whatever `parts` is (the
+ * part of a start is a binary search in the offsets); identical calls give identical bits.  Limits of mtadgat_fit_gather,
+ * 1 <= out_dim <= 2048 (<= F when dims_dev is NULL), W <= n_rows <= 2^31 - 1, 1 <= parts <= 2^31 - 1, min_count >= 0.  The offsets and
+ * dims_dev are the caller's to check.  Scratch: 8-byte aligned, mtadgat_fit_windows_scratch(n_rows) bytes (0 for a refused n_rows),
+ * need not be initialised; short or misaligned scratch is refused with -5 before anything is launched.
+ *
+ * mtadgat_fit_masked_sse: mtadgat_eval_window_sse over observed samples only.  window_dev[w] = (S_f, S_r, N_f, N_r): S is that
+ * call's sum with every unobserved term replaced by +0.0 -- a select, a NaN under the mask does not reach the sum --, added in that
+ * call's order, so with everything observed S equals its sums bit for bit; N counts the observed terms (float64, exact).
+ * dim_dev (4, out_dim) or NULL: the same four per output dimension over the call's windows, with mtadgat_eval_window_sse's slab
+ * scheme and its `accumulate`.  Its limits.  Scratch: 16-byte aligned, mtadgat_fit_masked_sse_scratch(batch, out_dim) bytes.
+ * mtadgat_eval_group_sums(cols = 4, group = batch) over window_dev gives the batch's four sums.
+ *
+ * mtadgat_fit_masked_loss_grad: mtadgat_fit_loss_grad from those four sums, sums_dev = (S_f, S_r, N_f, N_r).  Per head in float64:
+ * rmse = sqrt(S / N) for N > 0, else 0;  c = NaN if S is not finite, 0 if N == 0 or rmse == 0, else 1 / (N rmse).  An observed
+ * entry receives float(double(df) c) with df the ONE float32 subtraction, an unobserved one +0.0f whatever c is; rmse_dev
+ * receives the two rmse. */
+size_t mtadgat_fit_windows_scratch(int64_t n_rows);
+int mtadgat_fit_windows(const int32_t* age_dev /* (n_rows, F) or NULL */, int64_t ld_age, int32_t max_age, int64_t n_rows, int F, int W,
+                        const int32_t* dims_dev /* out_dim or NULL */, int out_dim, const int64_t* part_offsets_dev /* parts + 1 or NULL */,
+                        int64_t parts, int64_t min_count, int64_t* starts_dev /* capacity n_rows - W */, int64_t* count_dev /* 1 */,
+                        void* scratch_dev, size_t scratch_bytes, void* stream);
+size_t mtadgat_fit_masked_sse_scratch(int64_t batch, int out_dim);
+int mtadgat_fit_masked_sse(const float* preds_dev /* (batch, out_dim) */, const float* recons_dev /* (batch, W, out_dim) */, int64_t batch,
+                           int W, int out_dim, const float* series_dev, int64_t n_rows, int F, int64_t ld_series,
+                           const int64_t* starts_dev, int64_t start0, int64_t stride, const int32_t* dims_dev, const int32_t* age_dev,
+                           int64_t ld_age, int32_t max_age, int accumulate, double* window_dev /* (batch, 4) */,
+                           double* dim_dev /* (4, out_dim) or NULL */, void* scratch_dev, size_t scratch_bytes, void* stream);
+int mtadgat_fit_masked_loss_grad(const float* preds_dev /* (batch, out_dim) */, const float* recons_dev /* (batch, W, out_dim) */,
+                                 int64_t batch, int W, int out_dim, const float* series_dev, int64_t n_rows, int F, int64_t ld_series,
+                                 const int64_t* starts_dev, const int32_t* dims_dev, const int32_t* age_dev, int64_t ld_age,
+                                 int32_t max_age, const double* sums_dev /* 4 */, float* d_preds_dev, float* d_recons_dev,
+                                 double* rmse_dev /* 2 */, void* stream);
 
 /* ---- ranking curves (csrc/mtadgat_curves.hip; evaluation.score_order, ranking_curve, ranking_metrics) -------------------
  * Conventions of the event calls above: no atomics, no library kernels, bitwise reproducible; scratch is 8-byte aligned, at

@@ -267,6 +267,81 @@ def fit_adam(params, grads, exp_avg, exp_avg_sq, state, lr, betas, eps, weight_d
             "fit_adam")
 
 
+# -- training on gappy, concatenated series (csrc/mtadgat_fitwin.hip and the masked instances of _losses.hip / _fit.hip;
+#    tests/fit_mask_refs.py is the specification) ----------------------------------------------------------------------------------
+def _age_rows(age, n_rows, F, device):
+    """age: the int32 (n_rows, F) tensor of SeriesScaler.transform(..., return_age=True) on `device`, rows contiguous."""
+    if (not isinstance(age, torch.Tensor) or age.device != device or age.dtype != torch.int32 or age.ndim != 2
+            or tuple(age.shape) != (n_rows, F) or (F > 1 and age.stride(1) != 1) or (n_rows > 1 and age.stride(0) < F)):
+        raise RuntimeError(f"age must be an int32 ({n_rows}, {F}) tensor on {device} whose rows are contiguous "
+                           "(a boolean mask m of observed samples is (~m).to(torch.int32))")
+    return ctypes.c_void_p(age.data_ptr()), (age.stride(0) if n_rows > 1 else F)
+
+
+def fit_windows(n_rows, W, F, device, age=None, max_age=0, dims=None, out_dim=None, offsets=None, min_count=0):
+    """(starts, count) of mtadgat_fit_windows: starts int64 (n_rows - W,) on `device`, its first `count` entries the valid window
+    starts in ascending order, count a one-element int64 device tensor -- nothing is read from the device.  dims: int32 on the device
+    or None (then columns 0 .. out_dim - 1, out_dim defaulting to F); offsets: the P + 1 int64 part offsets on the device or None."""
+    lib = load_library()
+    device = torch.device(device)
+    n_rows, W, F = int(n_rows), int(W), int(F)
+    out_dim = (F if dims is None else dims.numel()) if out_dim is None else int(out_dim)
+    need = lib.mtadgat_fit_windows_scratch(n_rows)
+    if need == 0 or n_rows < W:
+        raise ValueError(f"fit_windows: n_rows must lie in [W, 2^31 - 1], got {n_rows} (W = {W})")
+    ap, ld = (None, 0) if age is None else _age_rows(age, n_rows, F, device)
+    starts = _empty((max(n_rows - W, 1),), dtype=torch.int64, device=device)        # (one entry where there is no start: a pointer to pass)
+    count = _empty((1,), dtype=torch.int64, device=device)
+    scratch = _scratch(need, device)
+    with torch.cuda.device(device):
+        _check(lib.mtadgat_fit_windows(
+            ap, ld, int(max_age), n_rows, F, W, None if dims is None else _typed(dims, torch.int32, "dims", out_dim), out_dim,
+            None if offsets is None else _typed(offsets, torch.int64, "offsets"), 1 if offsets is None else offsets.numel() - 1,
+            int(min_count), ctypes.c_void_p(starts.data_ptr()), _typed(count, torch.int64, "count", 1),
+            _typed(scratch, torch.float64, "scratch"), scratch.numel() * 8, _stream(device)), "fit_windows")
+    return starts[:n_rows - W], count
+
+
+def fit_masked_sse(preds, recons, series, starts, age, max_age=0, dims=None, want_dims=True):
+    """(window (b, 4) float64 = S_f, S_r, N_f, N_r per window, dim (4, out) float64 or None) of mtadgat_fit_masked_sse: the squared
+    errors of mtadgat_eval_window_sse over the observed samples (age <= max_age) and their counts."""
+    lib = load_library()
+    sp, n_rows, F, ld = _series_rows(series)
+    b, W, out = recons.shape
+    dev = series.device
+    ap, lda = _age_rows(age, n_rows, F, dev)
+    window = _empty((b, 4), dtype=torch.float64, device=dev)
+    dim = _empty((4, out), dtype=torch.float64, device=dev) if want_dims else None
+    scratch = _scratch(lib.mtadgat_fit_masked_sse_scratch(b, out), dev)
+    with torch.cuda.device(dev):
+        _check(lib.mtadgat_fit_masked_sse(
+            _typed(preds, torch.float32, "preds", b * out), _typed(recons, torch.float32, "recons"), b, W, out, sp, n_rows, F, ld,
+            _typed(starts, torch.int64, "starts", b), 0, 0, None if dims is None else _typed(dims, torch.int32, "dims", out), ap, lda,
+            int(max_age), 0, _typed(window, torch.float64, "window"), None if dim is None else _typed(dim, torch.float64, "dim"),
+            _typed(scratch, torch.float64, "scratch"), scratch.numel() * 8, _stream(series)), "fit_masked_sse")
+    return window, dim
+
+
+def fit_masked_loss_grad(preds, recons, series, starts, age, sums, max_age=0, dims=None, d_preds=None, d_recons=None, rmse=None):
+    """fit_loss_grad over observed samples (mtadgat_fit_masked_loss_grad).  sums: the batch's (S_f, S_r, N_f, N_r) on the device,
+    fit_masked_sse then mtadgat_eval_group_sums(cols = 4, group = batch).  An unobserved entry's cotangent is +0.0."""
+    sp, n_rows, F, ld = _series_rows(series)
+    b, W, out = recons.shape
+    dev = series.device
+    ap, lda = _age_rows(age, n_rows, F, dev)
+    d_preds = _empty((b, out), dtype=torch.float32, device=dev) if d_preds is None else d_preds
+    d_recons = _empty((b, W, out), dtype=torch.float32, device=dev) if d_recons is None else d_recons
+    rmse = _empty(2, dtype=torch.float64, device=dev) if rmse is None else rmse
+    with torch.cuda.device(dev):
+        _check(load_library().mtadgat_fit_masked_loss_grad(
+            _typed(preds, torch.float32, "preds", b * out), _typed(recons, torch.float32, "recons"), b, W, out, sp, n_rows, F, ld,
+            _typed(starts, torch.int64, "starts", b), None if dims is None else _typed(dims, torch.int32, "dims", out), ap, lda,
+            int(max_age), _typed(sums, torch.float64, "sums", 4), _typed(d_preds, torch.float32, "d_preds", b * out),
+            _typed(d_recons, torch.float32, "d_recons", b * W * out), _typed(rmse, torch.float64, "rmse", 2), _stream(series)),
+            "fit_masked_loss_grad")
+    return d_preds, d_recons, rmse
+
+
 class Engine:
     """One model instance on the native side: packed weights + launch plans."""
 
@@ -815,11 +890,13 @@ class Engine:
     def series_losses_workspace_bytes(self, batch):
         return int(self.lib.mtadgat_series_losses_workspace_bytes(self.handle, int(batch)))
 
-    def series_losses(self, series, starts=None, start0=0, stride=1, count=None, dims=None):
+    def series_losses(self, series, starts=None, start0=0, stride=1, count=None, dims=None, age=None, max_age=0):
         """Squared errors of the windows of forward_series() against the series itself, the (b, W, out) reconstructions never
         leaving the library's workspace: (window_sse (b, 2) float64 -- forecast against row s_w + W, reconstruction against rows
         s_w .. s_w + W - 1 --, dim_sse (2, out_dim) float64).  dims: int32 device tensor of the out_dim series columns compared
-        with (None: 0 .. out_dim - 1).  count defaults to the windows whose target row exists."""
+        with (None: 0 .. out_dim - 1).  count defaults to the windows whose target row exists.
+        age (int32 (n_rows, F) on the series' device; observed iff age <= max_age): mtadgat_series_losses_masked, the results are
+        (b, 4) = (S_f, S_r, N_f, N_r) per window and (4, out_dim) per dimension, sums and counts over the observed samples."""
         c = self.cfg
         W = c.window_size
         if starts is None and count is None:
@@ -833,13 +910,22 @@ class Engine:
         if dims is not None:
             if dims.dtype != torch.int32 or dims.device != dev or not dims.is_contiguous() or tuple(dims.shape) != (c.out_dim,):
                 raise RuntimeError(f"dims must be a contiguous int32 tensor of {c.out_dim} columns on the series' device")
-        wsse = _empty((b, 2), dtype=torch.float64, device=dev)
-        dsse = _empty((2, c.out_dim), dtype=torch.float64, device=dev)
-        need = self.series_losses_workspace_bytes(b)
+        dp = ctypes.c_void_p(dims.data_ptr()) if dims is not None else None
+        if age is None:
+            wsse = _empty((b, 2), dtype=torch.float64, device=dev)
+            dsse = _empty((2, c.out_dim), dtype=torch.float64, device=dev)
+            need = self.series_losses_workspace_bytes(b)
+            ws = _empty((need + 3) // 4, dtype=torch.float32, device=dev)
+            self._call(self.lib.mtadgat_series_losses, "series_losses", dev, sp, n_rows, stp, int(start0), int(stride), b,
+                       dp, ctypes.c_void_p(wsse.data_ptr()), ctypes.c_void_p(dsse.data_ptr()), _dev_ptr(ws, "workspace"), need)
+            return wsse, dsse
+        ap, lda = _age_rows(age, n_rows, c.n_features, dev)
+        wsse = _empty((b, 4), dtype=torch.float64, device=dev)
+        dsse = _empty((4, c.out_dim), dtype=torch.float64, device=dev)
+        need = int(self.lib.mtadgat_series_losses_masked_workspace_bytes(self.handle, b))
         ws = _empty((need + 3) // 4, dtype=torch.float32, device=dev)
-        self._call(self.lib.mtadgat_series_losses, "series_losses", dev, sp, n_rows, stp, int(start0), int(stride), b,
-                   ctypes.c_void_p(dims.data_ptr()) if dims is not None else None, ctypes.c_void_p(wsse.data_ptr()),
-                   ctypes.c_void_p(dsse.data_ptr()), _dev_ptr(ws, "workspace"), need)
+        self._call(self.lib.mtadgat_series_losses_masked, "series_losses", dev, sp, n_rows, stp, int(start0), int(stride), b,
+                   dp, ap, lda, int(max_age), ctypes.c_void_p(wsse.data_ptr()), ctypes.c_void_p(dsse.data_ptr()), _dev_ptr(ws, "workspace"), need)
         return wsse, dsse
 
     def conv(self, x):

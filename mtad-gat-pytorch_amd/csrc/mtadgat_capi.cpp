@@ -1476,23 +1476,25 @@ size_t mtadgat_series_losses_workspace_bytes(mtadgat_handle h, int64_t batch) {
     return p.total * sizeof(float);
 }
 
-int mtadgat_series_losses(mtadgat_handle h, const float* series, int64_t n_rows, const int64_t* starts, int64_t start0, int64_t stride,
-                          int64_t batch, const int32_t* dims, double* window_sse, double* dim_sse, void* ws_, size_t ws_bytes,
-                          void* stream) {
+// age == nullptr: mtadgat_series_losses (two entries per window, two kinds per dimension); else the masked call (four)
+static int series_losses_impl(mtadgat_handle h, const float* series, int64_t n_rows, const int64_t* starts, int64_t start0, int64_t stride,
+                              int64_t batch, const int32_t* dims, const int32_t* age, int64_t ld_age, int32_t max_age, double* window_out,
+                              double* dim_out, void* ws_, size_t ws_bytes, void* stream) {
     if (!h) return fail(MTADGAT_ERR_INVALID, "null handle");
     if (batch < 1 || batch > 2147483647LL) return fail(MTADGAT_ERR_INVALID, "series losses need between 1 and 2^31 - 1 windows");
     if (!h->m.have_weights) return fail(MTADGAT_ERR_NOWEIGHTS, "mtadgat_load_weights has not been called");
-    if (!series || !window_sse) return fail(MTADGAT_ERR_INVALID, "null tensor");
+    if (!series || !window_out) return fail(MTADGAT_ERR_INVALID, "null tensor");
     Model& m = h->m;
     const int W = m.W, od = m.cfg.out_dim;
     if (n_rows < (int64_t)W + 1) return fail(MTADGAT_ERR_INVALID, "series shorter than one window and its target row");
     if (!dims && od > m.F) return fail(MTADGAT_ERR_INVALID, "out_dim > n_features needs dims_dev");
+    if (age && ld_age < m.F) return fail(MTADGAT_ERR_INVALID, "ld_age < n_features");
     if (!starts && (stride < 0 || start0 < 0 || start0 + W > n_rows - 1 || (stride > 0 && batch - 1 > (n_rows - 1 - W - start0) / stride)))
         return fail(MTADGAT_ERR_INVALID, "windows start0 + w*stride .. +W and their target rows do not lie inside the series");
     if (!ws_) return fail(MTADGAT_ERR_WORKSPACE, "workspace is NULL");
     if (!aligned16(ws_)) return fail(MTADGAT_ERR_WORKSPACE, "workspace must be 16-byte aligned");
     LossPlan p;
-    plan_losses(m, batch, p);
+    plan_losses(m, batch, p, age != nullptr);
     if (ws_bytes < p.total * sizeof(float)) return fail(MTADGAT_ERR_WORKSPACE, "workspace too small");
     float* ws = static_cast<float*>(ws_);
     for (int64_t c0 = 0; c0 < batch; c0 += p.chunk) {
@@ -1503,11 +1505,36 @@ int mtadgat_series_losses(mtadgat_handle h, const float* series, int64_t n_rows,
         src.start0 = start0 + c0 * stride;
         int rc = forward_impl(h, src, n, ws + p.preds, ws + p.recons, nullptr, nullptr, ws, p.fwd_floats * sizeof(float), stream);
         if (rc) return rc;
-        rc = mtadgat_eval_window_sse(ws + p.preds, ws + p.recons, n, W, od, series, n_rows, m.F, m.F, src.starts, src.start0, stride, dims,
-                                     c0 > 0, window_sse + 2 * c0, dim_sse, ws + p.scratch, p.scratch_bytes, stream);
+        if (age)
+            rc = mtadgat_fit_masked_sse(ws + p.preds, ws + p.recons, n, W, od, series, n_rows, m.F, m.F, src.starts, src.start0, stride, dims,
+                                        age, ld_age, max_age, c0 > 0, window_out + 4 * c0, dim_out, ws + p.scratch, p.scratch_bytes, stream);
+        else
+            rc = mtadgat_eval_window_sse(ws + p.preds, ws + p.recons, n, W, od, series, n_rows, m.F, m.F, src.starts, src.start0, stride, dims,
+                                         c0 > 0, window_out + 2 * c0, dim_out, ws + p.scratch, p.scratch_bytes, stream);
         if (rc) return rc;
     }
     return 0;
+}
+
+int mtadgat_series_losses(mtadgat_handle h, const float* series, int64_t n_rows, const int64_t* starts, int64_t start0, int64_t stride,
+                          int64_t batch, const int32_t* dims, double* window_sse, double* dim_sse, void* ws_, size_t ws_bytes,
+                          void* stream) {
+    return series_losses_impl(h, series, n_rows, starts, start0, stride, batch, dims, nullptr, 0, 0, window_sse, dim_sse, ws_, ws_bytes, stream);
+}
+
+size_t mtadgat_series_losses_masked_workspace_bytes(mtadgat_handle h, int64_t batch) {
+    if (!h || batch <= 0) return 0;
+    LossPlan p;
+    plan_losses(h->m, batch, p, true);
+    return p.total * sizeof(float);
+}
+
+int mtadgat_series_losses_masked(mtadgat_handle h, const float* series, int64_t n_rows, const int64_t* starts, int64_t start0,
+                                 int64_t stride, int64_t batch, const int32_t* dims, const int32_t* age, int64_t ld_age, int32_t max_age,
+                                 double* window_out, double* dim_out, void* ws_, size_t ws_bytes, void* stream) {
+    if (!age) return fail(MTADGAT_ERR_INVALID, "null tensor");
+    return series_losses_impl(h, series, n_rows, starts, start0, stride, batch, dims, age, ld_age, max_age, window_out, dim_out, ws_, ws_bytes,
+                              stream);
 }
 
 int mtadgat_profile_enable(mtadgat_handle h, int on) {

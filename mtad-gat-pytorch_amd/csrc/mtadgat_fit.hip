@@ -8,7 +8,9 @@
 //   k_fit_loss_grad  d_preds = float(double(preds - y) c_f), d_recons = float(double(recons - x) c_r) with c = 1 / (N rmse),
 //                    rmse = sqrt(S / N) in float64 from the two batch sums S that mtadgat_eval_window_sse + mtadgat_eval_group_sums
 //                    left on the device; y and x are read from the series.  The leading workgroups take the reconstruction, the
-//                    rest the forecast; four consecutive outputs per thread as in the gather.
+//                    rest the forecast; four consecutive outputs per thread as in the gather.  The masked instance
+//                    (mtadgat_fit_masked_loss_grad; tests/fit_mask_refs.py) takes N from the batch's counts of observed terms and
+//                    writes +0.0f where the series sample is not observed.
 //   k_fit_sqnorm     per block of FIT_NORM_CHUNK gradient entries the float64 sum of double(g)^2: thread t adds entries t, t + 256, ..
 //                    of the block in that order, then block_sum (mtadgat_scan.h).
 //   k_fit_finish     one workgroup: the blocks' partials in the same order (thread t: partials t, t + 256, .., block_sum), then
@@ -17,6 +19,7 @@
 // No atomics, every sum in a fixed order: identical calls give identical bits.
 #include <algorithm>
 #include <cmath>
+#include <string>
 
 #include "../../include/mtadgat.h"      // the entry points' declarations, MTADGAT_FIT_STATE_FIELDS
 #include "mtadgat_scan.h"
@@ -93,20 +96,39 @@ __device__ __forceinline__ double cotangent_scale(double S, double N, double& rm
     return rmse == 0.0 ? 0.0 : 1.0 / (N * rmse);
 }
 
-// grid: blocks_r workgroups over the reconstruction's quads, then the forecast's
+// the masked step's scale (mtadgat_fit_masked_loss_grad): N counts the observed terms; a head without any has rmse 0 and c = 0
+__device__ __forceinline__ double masked_cotangent_scale(double S, double N, double& rmse) {
+    rmse = N > 0.0 ? sqrt(S / N) : 0.0;
+    if (!finite64(S)) return NAN;
+    return (N == 0.0 || rmse == 0.0) ? 0.0 : 1.0 / (N * rmse);
+}
+
+// What the masked instance takes on top: the samples' ages; an entry whose series sample is not observed (age > max_age) gets +0.0f
+template <bool MASK>
+struct GradMask {};
+template <>
+struct GradMask<true> {
+    const int* age;      // (n_rows, F), row stride ld
+    long ld;
+    int max_age;
+};
+
+// grid: blocks_r workgroups over the reconstruction's quads, then the forecast's.  sums: (S_f, S_r), MASK: (S_f, S_r, N_f, N_r)
+template <bool MASK>
 __global__ void __launch_bounds__(FIT_THREADS) k_fit_loss_grad(const float* __restrict__ preds, const float* __restrict__ recons, long batch,
                                                                int W, int out, const float* __restrict__ series, long ld,
                                                                const long* __restrict__ starts, const int* __restrict__ dims,
                                                                const double* __restrict__ sums, unsigned blocks_r, int vec,
                                                                float* __restrict__ d_preds, float* __restrict__ d_recons,
-                                                               double* __restrict__ rmse_out) {
+                                                               double* __restrict__ rmse_out, GradMask<MASK> mask) {
     const bool fore = blockIdx.x >= blocks_r;                          // (workgroup-uniform)
     const int T = fore ? 1 : W, t0 = fore ? W : 0;                      // the forecast is compared with row s + W
     const float* __restrict__ src = fore ? preds : recons;
     float* __restrict__ dst = fore ? d_preds : d_recons;
     const long total = batch * T * out;
-    double rmse;
-    const double c = cotangent_scale(sums[fore ? 0 : 1], (double)total, rmse);
+    double rmse, c;
+    if constexpr (MASK) c = masked_cotangent_scale(sums[fore ? 0 : 1], sums[fore ? 2 : 3], rmse);
+    else c = cotangent_scale(sums[fore ? 0 : 1], (double)total, rmse);
     const unsigned b0 = fore ? blockIdx.x - blocks_r : blockIdx.x, nb = fore ? gridDim.x - blocks_r : blocks_r;
     if (b0 == 0 && threadIdx.x == 0) rmse_out[fore ? 0 : 1] = rmse;
     const long quads = (total + 3) / 4;
@@ -127,9 +149,14 @@ __global__ void __launch_bounds__(FIT_THREADS) k_fit_loss_grad(const float* __re
 #pragma unroll
         for (int j = 0; j < 4; ++j)
             if (j < n) {
-                const float y = series[(starts[k.w] + t0 + k.t) * ld + (dims ? dims[k.c] : k.c)];
+                const long row = starts[k.w] + t0 + k.t;
+                const int col = dims ? dims[k.c] : k.c;
+                const float y = series[row * ld + col];
                 const float df = a[j] - y;                              // ONE float32 subtraction: window_sse's difference
                 a[j] = (float)((double)df * c);
+                if constexpr (MASK) {
+                    if (mask.age[row * mask.ld + col] > mask.max_age) a[j] = 0.f;      // (a select: a NaN product does not pass)
+                }
                 k.next(T, out);
             }
         if (v4) {
@@ -249,6 +276,29 @@ __global__ void __launch_bounds__(FIT_THREADS) k_fit_adam(float* __restrict__ p,
 inline bool aligned16(const void* a) { return ((uintptr_t)a & 15) == 0; }
 inline bool unit_open(double b) { return b >= 0.0 && b < 1.0; }          // (false for a NaN)
 
+// mtadgat_fit_loss_grad (MASK false) and mtadgat_fit_masked_loss_grad (MASK true)
+template <bool MASK>
+int loss_grad_call(const char* what, const float* preds_dev, const float* recons_dev, int64_t batch, int W, int out_dim,
+                   const float* series_dev, int64_t n_rows, int F, int64_t ld_series, const int64_t* starts_dev, const int32_t* dims_dev,
+                   GradMask<MASK> mask, const double* sums_dev, float* d_preds_dev, float* d_recons_dev, double* rmse_dev, void* stream) {
+    const std::string w(what);
+    auto refuse = [&](int code, const char* msg) { return record_error(code, (w + msg).c_str()); };
+    if (!preds_dev || !recons_dev || !series_dev || !starts_dev || !sums_dev || !d_preds_dev || !d_recons_dev || !rmse_dev)
+        return refuse(-1, ": null pointer");
+    if (batch < 1 || batch > N_MAX) return refuse(-1, ": batch must lie in [1, 2^31 - 1]");
+    if (out_dim < 1 || out_dim > FIT_OUT_MAX) return refuse(-1, ": out_dim must lie in [1, 2048]");
+    if (W < 1 || W > FIT_W_MAX) return refuse(-1, ": W must lie in [1, 512]");
+    if (F < 1 || ld_series < F) return refuse(-1, ": ld_series < F or F < 1");
+    if (!dims_dev && out_dim > F) return refuse(-1, ": out_dim > F needs dims_dev");
+    if (n_rows < (int64_t)W + 1) return refuse(-1, ": the series is shorter than a window and its target row");
+    const unsigned blocks_r = grid_for(((long)batch * W * out_dim + 3) / 4), blocks_f = grid_for(((long)batch * out_dim + 3) / 4);
+    const int vec = aligned16(preds_dev) && aligned16(recons_dev) && aligned16(d_preds_dev) && aligned16(d_recons_dev) ? 1 : 0;
+    hipLaunchKernelGGL(k_fit_loss_grad<MASK>, dim3(blocks_r + blocks_f), dim3(FIT_THREADS), 0, (hipStream_t)stream, preds_dev, recons_dev,
+                       (long)batch, W, out_dim, series_dev, (long)ld_series, reinterpret_cast<const long*>(starts_dev), dims_dev, sums_dev,
+                       blocks_r, vec, d_preds_dev, d_recons_dev, rmse_dev, mask);
+    return hipGetLastError() == hipSuccess ? 0 : refuse(-3, ": kernel launch failed");
+}
+
 }  // namespace
 
 extern "C" {
@@ -269,20 +319,22 @@ int mtadgat_fit_gather(const float* series_dev, int64_t n_rows, int F, int64_t l
 int mtadgat_fit_loss_grad(const float* preds_dev, const float* recons_dev, int64_t batch, int W, int out_dim, const float* series_dev,
                           int64_t n_rows, int F, int64_t ld_series, const int64_t* starts_dev, const int32_t* dims_dev,
                           const double* sums_dev, float* d_preds_dev, float* d_recons_dev, double* rmse_dev, void* stream) {
-    if (!preds_dev || !recons_dev || !series_dev || !starts_dev || !sums_dev || !d_preds_dev || !d_recons_dev || !rmse_dev)
-        return record_error(-1, "fit_loss_grad: null pointer");
-    if (batch < 1 || batch > N_MAX) return record_error(-1, "fit_loss_grad: batch must lie in [1, 2^31 - 1]");
-    if (out_dim < 1 || out_dim > FIT_OUT_MAX) return record_error(-1, "fit_loss_grad: out_dim must lie in [1, 2048]");
-    if (W < 1 || W > FIT_W_MAX) return record_error(-1, "fit_loss_grad: W must lie in [1, 512]");
-    if (F < 1 || ld_series < F) return record_error(-1, "fit_loss_grad: ld_series < F or F < 1");
-    if (!dims_dev && out_dim > F) return record_error(-1, "fit_loss_grad: out_dim > F needs dims_dev");
-    if (n_rows < (int64_t)W + 1) return record_error(-1, "fit_loss_grad: the series is shorter than a window and its target row");
-    const unsigned blocks_r = grid_for(((long)batch * W * out_dim + 3) / 4), blocks_f = grid_for(((long)batch * out_dim + 3) / 4);
-    const int vec = aligned16(preds_dev) && aligned16(recons_dev) && aligned16(d_preds_dev) && aligned16(d_recons_dev) ? 1 : 0;
-    hipLaunchKernelGGL(k_fit_loss_grad, dim3(blocks_r + blocks_f), dim3(FIT_THREADS), 0, (hipStream_t)stream, preds_dev, recons_dev, (long)batch,
-                       W, out_dim, series_dev, (long)ld_series, reinterpret_cast<const long*>(starts_dev), dims_dev, sums_dev, blocks_r, vec,
-                       d_preds_dev, d_recons_dev, rmse_dev);
-    return hipGetLastError() == hipSuccess ? 0 : record_error(-3, "fit_loss_grad: kernel launch failed");
+    return loss_grad_call<false>("fit_loss_grad", preds_dev, recons_dev, batch, W, out_dim, series_dev, n_rows, F, ld_series, starts_dev,
+                                 dims_dev, GradMask<false>{}, sums_dev, d_preds_dev, d_recons_dev, rmse_dev, stream);
+}
+
+int mtadgat_fit_masked_loss_grad(const float* preds_dev, const float* recons_dev, int64_t batch, int W, int out_dim, const float* series_dev,
+                                 int64_t n_rows, int F, int64_t ld_series, const int64_t* starts_dev, const int32_t* dims_dev,
+                                 const int32_t* age_dev, int64_t ld_age, int32_t max_age, const double* sums_dev, float* d_preds_dev,
+                                 float* d_recons_dev, double* rmse_dev, void* stream) {
+    if (!age_dev) return record_error(-1, "fit_masked_loss_grad: null pointer");
+    if (ld_age < F) return record_error(-1, "fit_masked_loss_grad: ld_age < F");
+    GradMask<true> mask;
+    mask.age = age_dev;
+    mask.ld = (long)ld_age;
+    mask.max_age = (int)max_age;
+    return loss_grad_call<true>("fit_masked_loss_grad", preds_dev, recons_dev, batch, W, out_dim, series_dev, n_rows, F, ld_series, starts_dev,
+                                dims_dev, mask, sums_dev, d_preds_dev, d_recons_dev, rmse_dev, stream);
 }
 
 size_t mtadgat_fit_prepare_scratch(int64_t n) {

@@ -428,7 +428,7 @@ struct AttPlan {
 };
 // Losses of a series (mtadgat_series_losses): chunks of `chunk` windows, each through the forward's workspace (float offset 0: the
 // larger of the plans of a full chunk and of the call's short last chunk), its preds and recons, and the scratch of
-// mtadgat_eval_window_sse (all float offsets; scratch_bytes as that call wants them).
+// mtadgat_eval_window_sse -- of mtadgat_fit_masked_sse for the masked call -- (all float offsets; scratch_bytes as that call wants them).
 struct LossPlan {
     int64_t chunk;
     size_t fwd_floats, preds, recons, scratch, scratch_bytes, total;
@@ -459,7 +459,7 @@ void plan_tape(const Model& m, int64_t n, Tape& t);
 void plan_bwd_workspace(const Model& m, int64_t n, BwdWorkspace& w);
 ForwardPlan plan_forward(const Model& m, int64_t batch);       // pieces, lanes, fork and workspace of one forward call
 void plan_attention(const Model& m, int64_t batch, bool reduce, AttPlan& p);
-void plan_losses(const Model& m, int64_t batch, LossPlan& p);
+void plan_losses(const Model& m, int64_t batch, LossPlan& p, bool masked = false);
 void plan_attribution(const Model& m, int64_t count, int steps, AttrPlan& p);
 StreamWs stream_ws(const Model& m, int64_t windows);
 int64_t default_chunk(const Model& m, double device_bytes);    // windows per chunk of a new handle (device_bytes 0: assume 16 GB)

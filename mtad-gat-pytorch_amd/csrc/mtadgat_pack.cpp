@@ -1023,7 +1023,7 @@ void plan_attention(const Model& m, int64_t batch, bool reduce, AttPlan& p) {
 
 // At most 2^26 floats of reconstructions per chunk, the bound of the attention mean's maps (MSL: 12 201 windows of 100 x 55), in whole
 // 128-window workgroups of the large-batch recurrence where a chunk holds several.  The regions do not grow with batch beyond a chunk.
-void plan_losses(const Model& m, int64_t batch, LossPlan& p) {
+void plan_losses(const Model& m, int64_t batch, LossPlan& p, bool masked) {
     const int64_t per_window = (int64_t)m.W * m.cfg.out_dim;
     p.chunk = std::min<int64_t>(m.chunk, std::max<int64_t>(1, ATT_MAPS_FLOATS / per_window));
     if (p.chunk > 128) p.chunk = p.chunk / 128 * 128;
@@ -1034,7 +1034,7 @@ void plan_losses(const Model& m, int64_t batch, LossPlan& p) {
     cv.take(p.fwd_floats);
     p.preds = cv.take((size_t)n * m.cfg.out_dim);
     p.recons = cv.take((size_t)n * per_window);
-    p.scratch_bytes = mtadgat_eval_window_sse_scratch(n, m.cfg.out_dim);
+    p.scratch_bytes = masked ? mtadgat_fit_masked_sse_scratch(n, m.cfg.out_dim) : mtadgat_eval_window_sse_scratch(n, m.cfg.out_dim);
     p.scratch = cv.take((p.scratch_bytes + sizeof(float) - 1) / sizeof(float));
     p.total = cv.off;
 }

@@ -18,6 +18,11 @@ Three departures from the reference and torch, all deliberate:
   * A head whose residuals are all zero (rmse == 0) contributes a zero gradient; autograd's sqrt gives 0 / 0 there.
   * A step takes at most one training chunk of windows (`_hipgrad._chunk_windows`, 8 192 unless the model is very wide); the
     existing route (`model(x)` + autograd) chunks larger batches.
+Series that are several parts laid end to end and hold filled gaps: `training_windows` is the sampler -- the starts whose window and
+target row lie in one part, with an observed target and enough observed samples --, and `step` / `fit` with `age` (the
+preparation's `transform(..., return_age=True)`) count observed samples only: mtadgat_fit_masked_sse and
+mtadgat_fit_masked_loss_grad take the places of mtadgat_eval_window_sse and mtadgat_fit_loss_grad.  tests/fit_mask_refs.py specifies
+both.  Without those arguments the calls and the bits are the ones above.
 (Not named training.py: the reference's train.py imports a module of that name and this package sits flat on sys.path.)"""
 import ctypes
 import math
@@ -38,6 +43,48 @@ def _mix64(z):
     z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _MASK64
     z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _MASK64
     return z ^ (z >> 31)
+
+
+def _min_count(min_observed, W, F):
+    """ceil(min_observed W F), the observed samples a window must hold, formed on the host."""
+    if not 0.0 <= float(min_observed) <= 1.0:
+        raise ValueError(f"min_observed must lie in [0, 1], got {min_observed!r}")
+    return int(math.ceil(float(min_observed) * W * F))
+
+
+def training_windows(n_rows, window_size, n_features, lengths=None, age=None, max_age=0, min_observed=0.5, target_dims=None, device=None):
+    """The window starts a trainer may draw from when the series is several parts laid end to end and has filled gaps: the int64
+    device tensor, ascending, of the starts s in [0, n_rows - W) for which
+      1. rows s .. s + W lie in one part (lengths: the parts' row counts, as SeriesScaler.transform(lengths=) and score_parts take
+         them; None: one part),
+      2. the target row s + W has an observed sample among the columns target_dims (None: all),
+      3. rows s .. s + W - 1 hold at least ceil(min_observed W F) observed samples over all columns.
+    age: int32 (n_rows, F) on the device as SeriesScaler.transform(..., return_age=True) returns it -- 0 for a real sample, k for the
+    k-th consecutive filled row; a sample is observed iff age <= max_age.  A boolean mask m of observed samples is
+    (~m).to(torch.int32).  None: every sample is observed.  One device call (mtadgat_fit_windows) and one 8-byte host read, of the
+    count.  device: where the result lives when neither age nor a device is given, the current GPU."""
+    import preparation
+    n_rows, W, F = int(n_rows), int(window_size), int(n_features)
+    min_count = _min_count(min_observed, W, F)
+    if age is not None:
+        if not isinstance(age, torch.Tensor) or age.device.type != "cuda":
+            raise RuntimeError("age must be an int32 tensor on the GPU (the window sampler is HIP only)")
+        asked = None if device is None else torch.device(device)
+        if asked is not None and (asked.type != "cuda" or asked.index not in (None, age.device.index)):
+            raise RuntimeError(f"age is on {age.device}, the windows were asked for on {device}")
+        device = age.device
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if n_rows < W + 1:
+        raise ValueError("the series is shorter than a window and its target row")
+    dims = None
+    if target_dims is not None:
+        cols = [target_dims] if isinstance(target_dims, int) else [int(d) for d in target_dims]
+        dims = torch.tensor(evaluation._target_dims(cols, len(cols), F), dtype=torch.int32, device=device)
+    offsets = None
+    if lengths is not None:
+        offsets = torch.tensor(preparation._part_offsets(lengths, n_rows), dtype=torch.int64, device=device)
+    starts, count = _native.fit_windows(n_rows, W, F, device, age=age, max_age=max_age, dims=dims, offsets=offsets, min_count=min_count)
+    return starts[:int(count.item())]
 
 
 class SeriesTrainer:
@@ -159,20 +206,37 @@ class SeriesTrainer:
                      d_recons=e((b, W, out), dtype=torch.float32, device=dev), wsse=e((b, 2), dtype=torch.float64, device=dev),
                      sums=e(2, dtype=torch.float64, device=dev), rmse=e(2, dtype=torch.float64, device=dev),
                      sse_scratch=e((need_sse + 7) // 8, dtype=torch.float64, device=dev),
+                     wsse4=None, sums4=None, sse4_scratch=None,                     # the masked step's, made when one is taken
                      norm_scratch=e(max(1, (need_norm + 7) // 8), dtype=torch.float64, device=dev))
             if len(self._bufs) >= 4:                        # a full batch and a short last one, with room for a change of batch size
                 self._bufs.pop(next(iter(self._bufs)))
             self._bufs[b] = c
         elif _native._POISON_SCRATCH:
             for t in c.values():
-                t.fill_(_native._POISON_VALUE)
+                if t is not None:
+                    t.fill_(_native._POISON_VALUE)
+        return c
+
+    def _masked_buffers(self, c, b):
+        if c["wsse4"] is None:
+            dev, e, out = self.device, _native._empty, self.model.out_dim
+            need = self._lib.mtadgat_fit_masked_sse_scratch(b, out)
+            c["wsse4"] = e((b, 4), dtype=torch.float64, device=dev)
+            c["sums4"] = e(4, dtype=torch.float64, device=dev)
+            c["sse4_scratch"] = e((need + 7) // 8, dtype=torch.float64, device=dev)
         return c
 
     # -- one step --------------------------------------------------------------------------------------------------------------------
-    def step(self, series, starts):
+    def step(self, series, starts, age=None, max_age=0):
         """One optimisation step on the windows series[s : s + W], s in `starts`, each asked to forecast row s + W.
         series: (N, n_features) float32 on the model's GPU, rows contiguous (a column slice keeps its row stride).  starts: int64 on
-        the same GPU, 1 .. one training chunk of them, every entry in [0, N - W - 1] -- not checked: that would read the device."""
+        the same GPU, 1 .. one training chunk of them, every entry in [0, N - W - 1] -- not checked: that would read the device.
+        age: int32 (N, n_features) on the same GPU, as SeriesScaler.transform(..., return_age=True) returns it (a boolean mask m of
+        observed samples is (~m).to(torch.int32)): the loss is sqrt(S_f / N_f) + sqrt(S_r / N_r) over the observed samples only,
+        age <= max_age -- a filled value is neither a target of the forecast nor of the reconstruction, and its cotangent is 0.
+        The step runs mtadgat_fit_masked_sse, mtadgat_eval_group_sums(cols 4) and mtadgat_fit_masked_loss_grad in place of the
+        three loss calls; a head without an observed sample in the batch logs rmse 0 and contributes no gradient.  Without age the
+        calls and the bits are what they were."""
         m, lib = self.model, self._lib
         W, F, out = m.window_size, m.n_features, m.out_dim
         if not isinstance(series, torch.Tensor) or series.device != self.device or series.dtype != torch.float32 or series.ndim != 2 \
@@ -183,6 +247,9 @@ class SeriesTrainer:
         if not isinstance(starts, torch.Tensor) or starts.device != self.device or starts.dtype != torch.int64 or starts.ndim != 1 \
                 or not starts.is_contiguous():
             raise RuntimeError(f"starts must be a contiguous 1-D int64 tensor on {self.device}")
+        agep = None
+        if age is not None:
+            agep, ld_age = _native._age_rows(age, series.shape[0], F, self.device)
         eng = self._ready()
         b = starts.numel()
         limit = _hipgrad._chunk_windows(eng, self.device)
@@ -201,13 +268,27 @@ class SeriesTrainer:
             self.grads.zero_()
             _native._check(lib.mtadgat_fit_gather(sp, n_rows, F, ld, stp, b, W, vp(c["x"].data_ptr()), stream), "fit_gather")
             preds, recons, self._tape = eng.forward_train(c["x"], p, seed, 0, tape=self._tape)
-            _native._check(lib.mtadgat_eval_window_sse(vp(preds.data_ptr()), vp(recons.data_ptr()), b, W, out, sp, n_rows, F, ld, stp, 0, 0,
-                                                       dims, 0, vp(c["wsse"].data_ptr()), None, vp(c["sse_scratch"].data_ptr()),
-                                                       c["sse_scratch"].numel() * 8, stream), "eval_window_sse")
-            _native._check(lib.mtadgat_eval_group_sums(vp(c["wsse"].data_ptr()), b, 2, b, vp(c["sums"].data_ptr()), stream), "eval_group_sums")
-            _native._check(lib.mtadgat_fit_loss_grad(vp(preds.data_ptr()), vp(recons.data_ptr()), b, W, out, sp, n_rows, F, ld, stp, dims,
-                                                     vp(c["sums"].data_ptr()), vp(c["d_preds"].data_ptr()), vp(c["d_recons"].data_ptr()),
-                                                     vp(c["rmse"].data_ptr()), stream), "fit_loss_grad")
+            if agep is not None:
+                c = self._masked_buffers(c, b)
+                _native._check(lib.mtadgat_fit_masked_sse(vp(preds.data_ptr()), vp(recons.data_ptr()), b, W, out, sp, n_rows, F, ld, stp, 0, 0,
+                                                          dims, agep, ld_age, int(max_age), 0, vp(c["wsse4"].data_ptr()), None,
+                                                          vp(c["sse4_scratch"].data_ptr()), c["sse4_scratch"].numel() * 8, stream),
+                               "fit_masked_sse")
+                _native._check(lib.mtadgat_eval_group_sums(vp(c["wsse4"].data_ptr()), b, 4, b, vp(c["sums4"].data_ptr()), stream),
+                               "eval_group_sums")
+                _native._check(lib.mtadgat_fit_masked_loss_grad(vp(preds.data_ptr()), vp(recons.data_ptr()), b, W, out, sp, n_rows, F, ld, stp,
+                                                                dims, agep, ld_age, int(max_age), vp(c["sums4"].data_ptr()),
+                                                                vp(c["d_preds"].data_ptr()), vp(c["d_recons"].data_ptr()),
+                                                                vp(c["rmse"].data_ptr()), stream), "fit_masked_loss_grad")
+            else:
+                _native._check(lib.mtadgat_eval_window_sse(vp(preds.data_ptr()), vp(recons.data_ptr()), b, W, out, sp, n_rows, F, ld, stp, 0, 0,
+                                                           dims, 0, vp(c["wsse"].data_ptr()), None, vp(c["sse_scratch"].data_ptr()),
+                                                           c["sse_scratch"].numel() * 8, stream), "eval_window_sse")
+                _native._check(lib.mtadgat_eval_group_sums(vp(c["wsse"].data_ptr()), b, 2, b, vp(c["sums"].data_ptr()), stream),
+                               "eval_group_sums")
+                _native._check(lib.mtadgat_fit_loss_grad(vp(preds.data_ptr()), vp(recons.data_ptr()), b, W, out, sp, n_rows, F, ld, stp, dims,
+                                                         vp(c["sums"].data_ptr()), vp(c["d_preds"].data_ptr()), vp(c["d_recons"].data_ptr()),
+                                                         vp(c["rmse"].data_ptr()), stream), "fit_loss_grad")
             eng.backward(c["x"], p, seed, c["d_preds"], c["d_recons"], self._tape, self.grads, 0)
             _native.fit_prepare(self.grads, c["rmse"], self.state, self.log, self.lr, self.betas, self.max_grad_norm, self.skip_nonfinite,
                                 scratch=c["norm_scratch"])
@@ -229,17 +310,39 @@ class SeriesTrainer:
         log = self.log.cpu().numpy()
         return log[[(self._calls - k + i) % cap for i in range(k)]]
 
-    def fit(self, train_series, val_series=None, epochs=1, batch_size=256, shuffle=True):
+    def fit(self, train_series, val_series=None, epochs=1, batch_size=256, shuffle=True, lengths=None, age=None, val_lengths=None,
+            val_age=None, max_age=0, min_observed=0.5):
         """The reference's Trainer.fit over a device series: per epoch the windows 0 .. N - W - 1 in consecutive batches of
         `batch_size` (the short last batch kept) of a device `torch.randperm` (shuffle) or in order.  The epoch's losses are the
         reference's sqrt(mean over the batches of rmse^2) per head, read from the log once per epoch; validation, when val_series is
         given, is model.series_losses(val_series, target_dims=, batch_size=).  Returns the dict of lists of Trainer.losses:
-        train_forecast, train_recon, train_total, val_forecast, val_recon, val_total."""
+        train_forecast, train_recon, train_total, val_forecast, val_recon, val_total.
+        lengths (the row counts of the parts laid end to end in train_series) and / or age (int32 (N, F), as
+        SeriesScaler.transform(..., return_age=True) returns it; a boolean mask m of observed samples is (~m).to(torch.int32)): the
+        windows are training_windows(N, W, F, lengths, age, max_age, min_observed, target_dims), found once per call -- none
+        straddles two parts, asks for an unobserved target row or holds fewer than min_observed of its samples observed --, an
+        epoch's order is windows[randperm(count)] or the windows in order, its step count follows their number, and every step
+        takes `age`: filled samples count for nothing in either loss.  val_lengths / val_age: the same for val_series, whose losses
+        are then model.series_losses(val_series, starts=<its windows>, age=val_age, max_age=)."""
         W = self.model.window_size
-        n = train_series.shape[0] - W
         batch_size = int(batch_size)
+        windows = None
+        if lengths is not None or age is not None:
+            windows = training_windows(train_series.shape[0], W, self.model.n_features, lengths, age, max_age, min_observed,
+                                       self.target_dims, self.device)
+            n = windows.numel()
+            if n < 1:
+                raise ValueError("fit: no window lies in one part with an observed target row and enough observed samples")
+        else:
+            n = train_series.shape[0] - W
         if n < 1 or batch_size < 1:
             raise ValueError("fit needs at least one window with a target row and batch_size >= 1")
+        val_windows = None
+        if val_series is not None and (val_lengths is not None or val_age is not None):
+            val_windows = training_windows(val_series.shape[0], W, self.model.n_features, val_lengths, val_age, max_age, min_observed,
+                                           self.target_dims, self.device)
+            if val_windows.numel() < 1:
+                raise ValueError("fit: no validation window lies in one part with an observed target row and enough observed samples")
         steps = (n + batch_size - 1) // batch_size
         if steps > self.log.shape[0]:
             raise ValueError(f"an epoch of {steps} steps does not fit the log (log_capacity={self.log.shape[0]})")
@@ -249,8 +352,13 @@ class SeriesTrainer:
                 order = torch.randperm(n, device=self.device, generator=self._generator)
             else:
                 order = torch.arange(n, device=self.device)
+            if windows is not None:
+                order = windows[order]
             for lo in range(0, n, batch_size):
-                self.step(train_series, order[lo:lo + batch_size])
+                if age is None:
+                    self.step(train_series, order[lo:lo + batch_size])
+                else:
+                    self.step(train_series, order[lo:lo + batch_size], age=age, max_age=max_age)
             rows = self.losses(last=steps)
             with np.errstate(over="ignore", invalid="ignore"):
                 f, r = (float(np.sqrt(np.mean(rows[:, j] ** 2))) for j in (0, 1))
@@ -258,7 +366,11 @@ class SeriesTrainer:
             out["train_recon"].append(r)
             out["train_total"].append(f + r)
             if val_series is not None:
-                vf, vr, vt = self.model.series_losses(val_series, target_dims=self.target_dims, batch_size=batch_size)
+                if val_windows is None:
+                    vf, vr, vt = self.model.series_losses(val_series, target_dims=self.target_dims, batch_size=batch_size)
+                else:
+                    vf, vr, vt = self.model.series_losses(val_series, target_dims=self.target_dims, batch_size=batch_size,
+                                                          starts=val_windows, age=val_age, max_age=max_age)
                 out["val_forecast"].append(vf)
                 out["val_recon"].append(vr)
                 out["val_total"].append(vt)

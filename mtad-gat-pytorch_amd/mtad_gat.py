@@ -651,7 +651,7 @@ class MTAD_GAT(nn.Module):
             return self._checked(dev, False, lambda eng: eng.score_attribution(vf, idx_d, dims_d, w_d, gamma, m, baseline))
 
     # -- the validation pass: forecast and reconstruction losses of a series ------------------------------------------------------
-    def series_losses(self, values, target_dims=None, batch_size=None, starts=None, start=0, stride=1, count=None):
+    def series_losses(self, values, target_dims=None, batch_size=None, starts=None, start=0, stride=1, count=None, age=None, max_age=0):
         """What the reference's `Trainer.evaluate` (training.py:188-228) computes over `SlidingWindowDataset(values, W)`, in one
         call on a series (N, F): window w = values[s_w : s_w + W] (s_w = starts[w] or start + w*stride; default the N - W windows
         0 .. N-W-1, the dataset's length) is run through the model, its forecast compared with row s_w + W and its reconstruction
@@ -668,7 +668,12 @@ class MTAD_GAT(nn.Module):
         validation pass in the middle of training does not have to flip modes.  GPU tensors run the HIP library
         (mtadgat_series_losses): the (n, W, out_dim) reconstructions pass through its workspace a chunk at a time and the group
         sums are formed on the device, one small host copy per call.  CPU tensors run the torch-op forward over batches of
-        `batch_size` windows (256 when None) -- the calls the reference's loader would make."""
+        `batch_size` windows (256 when None) -- the calls the reference's loader would make.
+        age (GPU tensors only; int32 (N, F) on values' device, as SeriesScaler.transform(..., return_age=True) returns it -- a
+        boolean mask m of observed samples is (~m).to(torch.int32)): only observed samples, age <= max_age, are compared
+        (mtadgat_series_losses_masked).  Per group of batch_size windows (all of them when None) mse = S_g / N_g over its observed
+        terms; a group without any is left out of the mean, and no group left gives NaN.  window_sse holds the sums over the
+        observed terms, window_count (n, 2) float64 their numbers (None without age), dim_mse is S / N per dimension, NaN where N == 0."""
         import evaluation
         W, F = self.window_size, self.n_features
         if values.dim() != 2 or values.shape[1] != F:
@@ -692,6 +697,8 @@ class MTAD_GAT(nn.Module):
         if n < 1:
             raise RuntimeError("series_losses needs at least one window whose target row lies inside the series")
         group = n if batch_size is None else int(batch_size)
+        if age is not None:
+            return self._series_losses_masked(values, age, max_age, target_dims, dims, starts, start, stride, n, group)
         with torch.no_grad():
             if dev.type == "cuda":
                 vf = values.detach().contiguous().float()
@@ -704,6 +711,29 @@ class MTAD_GAT(nn.Module):
         f, r, t = evaluation.group_losses(sums, n, W, self.out_dim, batch_size)
         terms = torch.tensor([[n], [n * W]], dtype=torch.float64, device=dsse.device)
         return SeriesLosses(f, r, t, wsse, dsse / terms, n)
+
+    def _series_losses_masked(self, values, age, max_age, target_dims, dims, starts, start, stride, n, group):
+        """series_losses over observed samples: the device's (n, 4) sums and counts, their group sums, one small host copy."""
+        import numpy as np
+        import evaluation
+        dev = values.device
+        if dev.type != "cuda":
+            raise RuntimeError("series_losses(age=) runs on the GPU only: the masked reduction is a HIP kernel, there is no CPU route")
+        with torch.no_grad():
+            vf = values.detach().contiguous().float()
+            dims_d = None if target_dims is None else torch.tensor(dims, dtype=torch.int32, device=dev)
+            st = None if starts is None else starts.to(dev).contiguous()
+            w4, d4 = self._checked(dev, self._use_bf16(values),
+                                   lambda eng: eng.series_losses(vf, st, start, stride, n, dims_d, age=age, max_age=max_age))
+            sums = evaluation.group_sums(w4, group).cpu().numpy()
+        with np.errstate(all="ignore"):
+            losses = []
+            for j in (0, 1):
+                seen = sums[:, 2 + j] > 0
+                losses.append(float(np.sqrt((sums[seen, j] / sums[seen, 2 + j]).mean())) if seen.any() else float("nan"))
+        f, r = losses
+        dim_mse = torch.where(d4[2:] > 0, d4[:2] / d4[2:], torch.full_like(d4[:2], float("nan")))
+        return SeriesLosses(f, r, f + r, w4[:, :2], dim_mse, n, window_count=w4[:, 2:])
 
     def _series_losses_cpu(self, values, starts, start, stride, n, dims, batch):
         """(window_sse, dim_sse) from torch-op forwards over loader batches, with evaluation.window_sse's arithmetic in numpy."""
@@ -732,11 +762,12 @@ class MTAD_GAT(nn.Module):
 
 class SeriesLosses:
     """Result of MTAD_GAT.series_losses: Trainer.evaluate's three floats, and the per-window / per-dimension errors behind them."""
-    __slots__ = ("forecast_loss", "recon_loss", "total_loss", "window_sse", "dim_mse", "n_windows")
+    __slots__ = ("forecast_loss", "recon_loss", "total_loss", "window_sse", "dim_mse", "n_windows", "window_count")
 
-    def __init__(self, forecast_loss, recon_loss, total_loss, window_sse, dim_mse, n_windows):
+    def __init__(self, forecast_loss, recon_loss, total_loss, window_sse, dim_mse, n_windows, window_count=None):
         self.forecast_loss, self.recon_loss, self.total_loss = forecast_loss, recon_loss, total_loss
         self.window_sse, self.dim_mse, self.n_windows = window_sse, dim_mse, n_windows
+        self.window_count = window_count          # (n, 2) float64: the observed terms behind window_sse; None for the unmasked call
 
     def __iter__(self):                   # forecast_loss, recon_loss, total_loss = model.series_losses(...): Trainer.evaluate's return
         return iter((self.forecast_loss, self.recon_loss, self.total_loss))
