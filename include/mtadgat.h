@@ -610,6 +610,67 @@ int mtadgat_eval_column_quantiles(const float* a_dev, int64_t n, int d, int64_t 
 size_t mtadgat_eval_ewm_scratch(int64_t n);
 int mtadgat_eval_ewm(const float* x_dev, int64_t n, double alpha, void* scratch_dev, size_t scratch_bytes, float* out_dev,
                      void* stream);
+/* ---- scores of a gappy series (csrc/mtadgat_evalmask.hip, the VALID select of csrc/mtadgat_evalcol.hip; evaluation.scored_rows,
+ * anomaly_scores(age=), the skip_nan arguments) -- tests/score_mask_refs.py is the specification -------------------------------
+ * A score exists exactly where mtadgat_fit_windows (below) would have drawn a training window: score i belongs to window start i
+ * and target row i + W.  NaN means "no score": the calls here write the canonical quiet NaN 0x7fc00000 and skip every NaN
+ * they read, whatever its sign or payload; +-inf is a value, not a gap.  Conventions of the two calls above: no atomics on
+ * floating-point values, no library kernels, bitwise reproducible; status 0 / -1 / -3 / -5 with a mtadgat_last_error() message;
+ * nothing is launched when validation fails; scratch need not be initialised.  n <= 2^31 - 1, d <= 2048.
+ *
+ * mtadgat_eval_mark_rows: keep_dev[i] (uint8, n entries) = 1 for i in starts_dev[0 .. *count_dev) and 0 elsewhere; the count is read
+ * on the device (cut to [0, n]; a start outside [0, n) is ignored), so mtadgat_fit_windows followed by this call gives "which scores
+ * exist" without a host read.  Asynchronous on `stream`.
+ *
+ * mtadgat_eval_scores_masked: mtadgat_eval_scores over observed samples.  age_dev points at the age row of score 0 (row W of the
+ * series' (N, F) int32 ages, row stride ld_age) and is indexed by the same column -- dims_dev[k] or k -- as actual_dev; a target
+ * sample is observed iff age <= max_age.  per_dim[i][k] is mtadgat_eval_scores' expression in its float32 arithmetic where the sample
+ * is observed and keep_dev[i] != 0 (NULL: all kept), else NaN.  global[i] is the float32 sum over those entries in k order -- a
+ * select, not a multiply: a NaN or inf of `actual` under the mask does not reach it -- divided by (float)count, NaN for count = 0;
+ * count_dev[i] (int32, may be NULL) is their number.  per_dim_dev and global_dev may be NULL.  With everything observed and kept the
+ * outputs equal mtadgat_eval_scores' bit for bit.  Asynchronous on `stream`.
+ *
+ * mtadgat_eval_row_means_valid: global_dev[i] = the float32 sum of the non-NaN entries of row i of a_dev, (n, d) with row stride ld,
+ * in column order, divided by (float) their number; NaN for a row without one; count_dev[i] (int32, may be NULL) their number: the
+ * mean of mtadgat_eval_scores_masked for per-dimension scores that were scaled after masking.  Asynchronous on `stream`.
+ *
+ * mtadgat_eval_column_quantiles_valid: mtadgat_eval_column_quantiles over the m non-NaN entries of each column
+ * (np.nanpercentile(..., method="linear")): pos = q (m - 1), the two exact order statistics, float64 interpolation, rounded once;
+ * m = 0 gives NaN.  A count pass leaves m per column on the device (integer sums, independent of their order), the select's ranks
+ * are set per column from it, and every NaN takes the one key above +inf, which no rank below m reaches.  count_dev (d) int64,
+ * may be NULL, receives m.  Limits, scratch alignment (16 bytes) and status of mtadgat_eval_column_quantiles.
+ *
+ * mtadgat_eval_ewm_valid: the exponentially weighted mean over observed rows; a NaN input is an unobserved row.  In float64, with
+ * b = 1 - alpha: N_t = (obs ? x_t : 0) + b N_{t-1}, D_t = (obs ? 1 : 0) + b D_{t-1}, out[t] = float(N_t / D_t) at an observed row
+ * (D_t >= 1 there: no 0 / 0) and NaN at an unobserved one -- pandas' ewm(span, adjust=True, ignore_na=False).mean() at the observed
+ * rows; pandas repeats the previous mean at an unobserved row, here that row has no score.  A blocked scan on (N, D) pairs in a
+ * fixed order; across a long gap b^gap may underflow to 0 and the history is forgotten, as in the sequential recursion.  out_dev
+ * may be x_dev.  Scratch: 8-byte aligned, mtadgat_eval_ewm_valid_scratch(n) bytes.  Asynchronous on `stream`.
+ *
+ * mtadgat_eval_moments_valid: out_host (d, 3) float64 = per column the sum, the sum of squares and the count of the non-NaN entries
+ * of an (n, d) array with row stride ld: per-block partials by a fixed tree, then one wave per column that adds them in block
+ * order -- no atomics, two calls give the same bits (unlike mtadgat_eval_moments_columns).  Synchronises the stream.  Scratch: 8-byte
+ * aligned, mtadgat_eval_moments_valid_scratch(n, d) bytes.
+ * The z table needs no call of its own: mtadgat_eval_epsilon_table(_columns) compares x < eps and x >= eps, both false for a NaN, so
+ * a missing row enters neither the pruned sums and count nor the hot flags; it IS counted in the dilated count when it lies inside
+ * a hot row's halo. */
+int mtadgat_eval_mark_rows(const int64_t* starts_dev, const int64_t* count_dev, int64_t n, uint8_t* keep_dev, void* stream);
+int mtadgat_eval_scores_masked(const float* preds_dev, const float* recons_dev, const float* actual_dev, int64_t n, int d,
+                               int64_t ld_actual, const int32_t* dims_dev, float gamma, const int32_t* age_dev, int64_t ld_age,
+                               int32_t max_age, const uint8_t* keep_dev /* n or NULL */, float* per_dim_dev, float* global_dev,
+                               int32_t* count_dev /* n or NULL */, void* stream);
+int mtadgat_eval_row_means_valid(const float* a_dev, int64_t n, int d, int64_t ld, float* global_dev, int32_t* count_dev /* n or NULL */,
+                                 void* stream);
+size_t mtadgat_eval_column_quantiles_valid_scratch(int64_t n, int d, int nq);
+int mtadgat_eval_column_quantiles_valid(const float* a_dev, int64_t n, int d, int64_t ld, const double* q_host, int nq,
+                                        void* scratch_dev, size_t scratch_bytes, float* out_dev, int64_t* count_dev /* d or NULL */,
+                                        void* stream);
+size_t mtadgat_eval_ewm_valid_scratch(int64_t n);
+int mtadgat_eval_ewm_valid(const float* x_dev, int64_t n, double alpha, void* scratch_dev, size_t scratch_bytes, float* out_dev,
+                           void* stream);
+size_t mtadgat_eval_moments_valid_scratch(int64_t n, int d);
+int mtadgat_eval_moments_valid(const float* e_dev, int64_t n, int d, int64_t ld, void* scratch_dev, size_t scratch_bytes,
+                               double* out_host /* (d, 3) */, void* stream);
 /* ---- from thresholded scores to events (csrc/mtadgat_events.hip; evaluation.anomaly_events) ----------------------------
  * Conventions of the two calls above: no float atomics, no library kernels, nothing sorted, bitwise reproducible; scratch
  * is 8-byte aligned, at least what the _scratch function returns (0 for invalid sizes), and need not be initialised;

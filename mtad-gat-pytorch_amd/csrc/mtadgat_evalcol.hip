@@ -7,6 +7,9 @@
 //       order-preserving 32-bit key of the float, all columns and all 2 nq ranks per pass.  Histograms are built with integer
 //       atomics in LDS and merged with integer atomics in memory -- integer sums do not depend on their order, so two runs give
 //       the same bits -- and the digit of every (column, rank) is chosen on the device between the passes.  Nothing is sorted.
+//   k_colqv_* and the VALID instantiation of k_eval_colq_hist: the same select over the non-NaN entries of every column
+//       (mtadgat_eval_column_quantiles_valid, np.nanpercentile): a count pass gives every column's number of valid entries, the ranks
+//       are set per column from it, and every NaN takes one key above +inf that no such rank reaches.
 //   k_partq_* and the segmented instantiations of k_eval_colq_hist / _pick: the same select for every (part, column) of a
 //       concatenated series (mtadgat_eval_part_quantiles), by two routes chosen per part on the device.  A part of at most PARTQ_LONG
 //       rows is selected inside one workgroup, bins, prefixes and ranks in LDS (k_partq_short).  A longer part runs the four passes
@@ -30,6 +33,8 @@ constexpr int CQ_ROWS = 256 / CQ_CT;
 // the select's key: the order bits as they stand, so -0.0 sorts just below +0.0 (both are 0 in the interpolation)
 __device__ __forceinline__ unsigned colq_key(float v) { return float_order_bits(v); }
 __device__ __forceinline__ float colq_value(unsigned k) { return float_from_order_bits(k); }
+// the key of the select that skips NaN: +inf is 0xff800000, so 0xffffffff (the bits 0x7fffffff, itself a NaN) lies above every number
+__device__ __forceinline__ unsigned colq_valid_key(float v) { return v != v ? 0xffffffffu : float_order_bits(v); }
 // position of probability q among n sorted values: lo = floor(q (n - 1)) in float64, the weight of s[lo + 1] returned in *frac
 __device__ __forceinline__ unsigned colq_rank(double q, long n, double* frac) {
     const double pos = __dmul_rn(q, (double)(n - 1));     // rounded product: a fused pos - lo would use the unrounded one
@@ -83,7 +88,10 @@ constexpr int PARTQ_LONG = 16 * SPAN_RB;     // a part longer than this many row
 // One radix pass over the rows first, first + step, .. below `last` of the workgroup's CQ_CT columns: for every (column, rank) the
 // histogram of digit (key >> shift) & 255 over the keys whose higher digits equal the rank's prefix, built in `h` and merged into
 // `hist`.  state / hist start at the cell of (column 0, rank 0), nanflag at column 0.  Every thread of the workgroup calls it
-// (barriers inside; one more before `h` is used again).
+// (barriers inside; one more before `h` is used again).  VALID: the select over the non-NaN entries -- every NaN, whatever its sign
+// or payload, takes the one key above +inf (colq_valid_key), which no rank below the column's valid count can reach; nanflag is
+// not touched.
+template <bool VALID>
 __device__ __forceinline__ void colq_hist_rows(const float* __restrict__ a, int d, long ld, int R, int shift, long first, long last, long step,
                                                const unsigned* __restrict__ state, unsigned* __restrict__ hist,
                                                unsigned* __restrict__ nanflag, unsigned* h) {
@@ -102,14 +110,15 @@ __device__ __forceinline__ void colq_hist_rows(const float* __restrict__ a, int 
         bool seen_nan = false;
         for (long row = first; row < last; row += step) {
             const float v = a[row * ld + col];
-            seen_nan = seen_nan || (v != v);
-            const unsigned key = colq_key(v);
+            if constexpr (!VALID) seen_nan = seen_nan || (v != v);
+            const unsigned key = VALID ? colq_valid_key(v) : colq_key(v);
             const unsigned bin = (key >> shift) & 255u;
 #pragma unroll
             for (int r = 0; r < CQ_RT; ++r)
                 if (r < nr && ((key ^ pfx[r]) & high) == 0u) atomicAdd(&h[(r * CQ_CT + c) * 256 + bin], 1u);
         }
-        if (seen_nan && shift == 24 && blockIdx.z == 0) atomicOr(&nanflag[col], 1u);
+        if constexpr (!VALID)
+            if (seen_nan && shift == 24 && blockIdx.z == 0) atomicOr(&nanflag[col], 1u);
     }
     __syncthreads();
     for (int i = tid; i < nr * CQ_CT * 256; i += 256) {
@@ -119,11 +128,11 @@ __device__ __forceinline__ void colq_hist_rows(const float* __restrict__ a, int 
     }
 }
 
-// One pass, instantiated twice.  !SEG: the whole column, grid = (column tiles, row slices, rank groups), the rows walked grid-stride;
-// no span array is read.  SEG: grid = (column tiles, chunks of PARTQ_LONG rows, rank groups); a chunk meets at most two long parts --
+// One pass, instantiated three times (VALID, with !SEG only: the column's non-NaN entries, see colq_hist_rows).  !SEG: the whole
+// column, grid = (column tiles, row slices, rank groups), the rows walked grid-stride; no span array is read.  SEG: grid = (column tiles, chunks of PARTQ_LONG rows, rank groups); a chunk meets at most two long parts --
 // the one that covers its first row and the one that starts inside it, which is the owner of slot `chunk` -- and adds its rows of
 // each to that part's bins.  Chunks that meet no long part leave at once.
-template <bool SEG>
+template <bool SEG, bool VALID = false>
 __global__ void __launch_bounds__(256) k_eval_colq_hist(const float* __restrict__ a, long n, int d, long ld, int R, int shift,
                                                          const unsigned* __restrict__ state, unsigned* __restrict__ hist,
                                                          unsigned* __restrict__ nanflag, const long* __restrict__ start,
@@ -131,7 +140,7 @@ __global__ void __launch_bounds__(256) k_eval_colq_hist(const float* __restrict_
     __shared__ unsigned h[CQ_RT * CQ_CT * 256];
     const long sub = threadIdx.x >> 3;                    // CQ_ROWS rows at a time
     if constexpr (!SEG) {
-        colq_hist_rows(a, d, ld, R, shift, (long)blockIdx.y * CQ_ROWS + sub, n, (long)gridDim.y * CQ_ROWS, state, hist, nanflag, h);
+        colq_hist_rows<VALID>(a, d, ld, R, shift, (long)blockIdx.y * CQ_ROWS + sub, n, (long)gridDim.y * CQ_ROWS, state, hist, nanflag, h);
     } else {
         const long cells = (long)d * R;
         for (long b = blockIdx.y; b <= n / PARTQ_LONG; b += gridDim.y) {
@@ -148,7 +157,7 @@ __global__ void __launch_bounds__(256) k_eval_colq_hist(const float* __restrict_
                 if (e - s <= PARTQ_LONG || (which == 1 && s == c0)) continue;      // short; or met as the part that covers c0
                 const long slot = s / PARTQ_LONG;
                 const long lo = s > c0 ? s : c0, hi = e < c1 ? e : c1;
-                colq_hist_rows(a, d, ld, R, shift, lo + sub, hi, (long)CQ_ROWS, state + 2 * slot * cells, hist + slot * cells * 256,
+                colq_hist_rows<false>(a, d, ld, R, shift, lo + sub, hi, (long)CQ_ROWS, state + 2 * slot * cells, hist + slot * cells * 256,
                                nanflag + p * d, h);
                 __syncthreads();
             }
@@ -199,6 +208,75 @@ __global__ void __launch_bounds__(64) k_eval_colq_pick(unsigned* __restrict__ st
             if (shift == 0) ord[at] = colq_value(key);
         }
     }
+}
+
+// ---- quantiles of the non-NaN entries (mtadgat_eval_column_quantiles_valid) ---------------------------------------------------------
+// The select above with VALID keys and the ranks of every column taken from the column's own count m of non-NaN entries:
+//   k_colqv_init    clears the bins and the counts (and writes inline probabilities to q);
+//   k_colqv_count   m[col]: integer sums in LDS and memory, independent of their order;
+//   k_colqv_ranks   lo = floor(q (m - 1)), hi = min(lo + 1, m - 1) per (column, probability); rank 0 for m = 0 (never interpolated);
+//   k_colqv_interp  as k_eval_colq_interp with m in the place of n; NaN for m = 0; the counts as int64.
+__global__ void k_colqv_init(double* __restrict__ q, ColqProbs pv, int inl, int nq, int d, unsigned* __restrict__ m,
+                             unsigned* __restrict__ hist) {
+    if (inl && blockIdx.x == 0 && threadIdx.x < nq) q[threadIdx.x] = pv.v[threadIdx.x];
+    const long nhist = (long)d * 2 * nq * 256;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nhist; i += (long)gridDim.x * blockDim.x) {
+        hist[i] = 0u;
+        if (i < d) m[i] = 0u;
+    }
+}
+
+// grid = (column tiles, row slices): thread (row group, column) walks its rows grid-stride
+__global__ void __launch_bounds__(256) k_colqv_count(const float* __restrict__ a, long n, int d, long ld, unsigned* __restrict__ m) {
+    __shared__ unsigned cnt[CQ_CT];
+    const int tid = threadIdx.x, c = tid & (CQ_CT - 1);
+    const int col = blockIdx.x * CQ_CT + c;
+    if (tid < CQ_CT) cnt[tid] = 0u;
+    __syncthreads();
+    unsigned mine = 0u;
+    if (col < d)
+        for (long row = (long)blockIdx.y * CQ_ROWS + (tid >> 3); row < n; row += (long)gridDim.y * CQ_ROWS) {
+            const float v = a[row * ld + col];
+            mine += v == v ? 1u : 0u;
+        }
+    if (mine) atomicAdd(&cnt[c], mine);
+    __syncthreads();
+    if (tid < CQ_CT && col < d && cnt[tid]) atomicAdd(&m[col], cnt[tid]);
+}
+
+__global__ void k_colqv_ranks(const double* __restrict__ q, ColqProbs pv, int inl, int nq, int d, const unsigned* __restrict__ m,
+                              unsigned* __restrict__ state) {
+    const int R = 2 * nq;
+    const long nstate = (long)d * R;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nstate; i += (long)gridDim.x * blockDim.x) {
+        const int r = (int)(i % R);
+        const long mm = (long)m[i / R];
+        unsigned rank = 0u;
+        if (mm > 0) {
+            const unsigned lo = colq_rank(inl ? pv.v[r >> 1] : q[r >> 1], mm, nullptr);
+            const unsigned hi = (long)lo + 1 < mm ? lo + 1 : (unsigned)(mm - 1);
+            rank = (r & 1) ? hi : lo;
+        }
+        state[2 * i] = 0u;
+        state[2 * i + 1] = rank;
+    }
+}
+
+__global__ void k_colqv_interp(const float* __restrict__ ord, const double* __restrict__ q, const unsigned* __restrict__ m, int d, int nq,
+                               float* __restrict__ out, long* __restrict__ count) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)nq * d) return;
+    const int qi = (int)(i / d), col = (int)(i % d);
+    const long mm = (long)m[col];
+    if (count && qi == 0) count[col] = mm;
+    float r = __builtin_bit_cast(float, 0x7fc00000u);
+    if (mm > 0) {
+        double frac;
+        colq_rank(q[qi], mm, &frac);
+        const double lo = ord[((long)col * nq + qi) * 2], hi = ord[((long)col * nq + qi) * 2 + 1];
+        r = (float)(lo + (hi - lo) * frac);
+    }
+    out[i] = r;
 }
 
 // ---- quantiles per part ----------------------------------------------------------------------------------------------------------
@@ -496,6 +574,7 @@ ColqScratch colq_scratch(ScratchCarver& c, int64_t d, int64_t nq) {
 }
 
 // the four digit passes of the select for R ranks per column, on an initialised state
+template <bool VALID>
 void colq_passes(const float* a_dev, long n, int d, long ld, int R, unsigned* state, unsigned* hist, unsigned* nanflag, float* ord,
                  hipStream_t s) {
     // bounded grid: about 1024 workgroups in all, each walking at least four row groups
@@ -505,7 +584,7 @@ void colq_passes(const float* a_dev, long n, int d, long ld, int R, unsigned* st
     const long cap = 1024 / ((long)tiles * groups) > 0 ? 1024 / ((long)tiles * groups) : 1;
     if (slices > cap) slices = cap;
     for (int shift = 24; shift >= 0; shift -= 8) {
-        hipLaunchKernelGGL(k_eval_colq_hist<false>, dim3(tiles, (unsigned)slices, groups), dim3(256), 0, s, a_dev, (long)n, d, (long)ld, R, shift,
+        hipLaunchKernelGGL((k_eval_colq_hist<false, VALID>), dim3(tiles, (unsigned)slices, groups), dim3(256), 0, s, a_dev, (long)n, d, (long)ld, R, shift,
                            (const unsigned*)state, hist, nanflag, (const long*)nullptr, (const long*)nullptr, 0L, (const int*)nullptr);
         hipLaunchKernelGGL(k_eval_colq_pick<false>, dim3((unsigned)cells), dim3(64), 0, s, state, hist, shift, ord, cells, 1L, (const int*)nullptr);
     }
@@ -572,7 +651,7 @@ int launch_column_rank(const float* a_dev, long n, int d, long ld, long rank, vo
     const long init_blocks = ((long)d * 256 + 255) / 256;
     hipLaunchKernelGGL(k_eval_colq_init_rank, dim3((unsigned)(init_blocks < 2048 ? init_blocks : 2048)), dim3(256), 0, s, (unsigned)rank, d, l.state,
                        l.nanflag, l.hist);
-    colq_passes(a_dev, n, d, ld, 1, l.state, l.hist, l.nanflag, l.ord, s);
+    colq_passes<false>(a_dev, n, d, ld, 1, l.state, l.hist, l.nanflag, l.ord, s);
     *ord_dev = l.ord;
     return (int)hipGetLastError();
 }
@@ -613,11 +692,56 @@ int mtadgat_eval_column_quantiles(const float* a_dev, int64_t n, int d, int64_t 
     const long init_blocks = (cells * 256 + 255) / 256;
     hipLaunchKernelGGL(k_eval_colq_init, dim3((unsigned)(init_blocks < 2048 ? init_blocks : 2048)), dim3(256), 0, s, l.q, pv, inl, nq, (long)n, d,
                        l.state, l.nanflag, l.hist);
-    colq_passes(a_dev, (long)n, d, (long)ld, R, l.state, l.hist, l.nanflag, l.ord, s);
+    colq_passes<false>(a_dev, (long)n, d, (long)ld, R, l.state, l.hist, l.nanflag, l.ord, s);
     const long outs = (long)nq * d;
     hipLaunchKernelGGL(k_eval_colq_interp, dim3((unsigned)((outs + 255) / 256)), dim3(256), 0, s, (const float*)l.ord, (const double*)l.q,
                        (const unsigned*)l.nanflag, (long)n, d, nq, out_dev);
     return hipGetLastError() == hipSuccess ? 0 : record_error(-3, "column_quantiles: kernel launch failed");
+}
+
+size_t mtadgat_eval_column_quantiles_valid_scratch(int64_t n, int d, int nq) { return mtadgat_eval_column_quantiles_scratch(n, d, nq); }
+
+// the layout of mtadgat_eval_column_quantiles; its NaN flags hold the columns' valid counts
+int mtadgat_eval_column_quantiles_valid(const float* a_dev, int64_t n, int d, int64_t ld, const double* q_host, int nq, void* scratch_dev,
+                                        size_t scratch_bytes, float* out_dev, int64_t* count_dev, void* stream) {
+    if (!a_dev || !q_host || !scratch_dev || !out_dev) return record_error(-1, "column_quantiles_valid: null pointer");
+    if (n < 1 || n > 2147483647LL) return record_error(-1, "column_quantiles_valid: n must lie in [1, 2^31 - 1]");
+    if (d < 1 || d > 2048) return record_error(-1, "column_quantiles_valid: d must lie in [1, 2048]");
+    if (ld < d) return record_error(-1, "column_quantiles_valid: ld < d");
+    if (nq < 1 || nq > 4096) return record_error(-1, "column_quantiles_valid: nq must lie in [1, 4096]");
+    for (int i = 0; i < nq; ++i)
+        if (!(q_host[i] >= 0.0 && q_host[i] <= 1.0)) return record_error(-1, "column_quantiles_valid: q outside [0, 1]");
+    ScratchCarver carver(scratch_dev);
+    const ColqScratch l = colq_scratch(carver, d, nq);
+    if (scratch_bytes < carver.bytes())
+        return record_error(-5, "column_quantiles_valid: scratch too small (see mtadgat_eval_column_quantiles_valid_scratch)");
+    if ((uintptr_t)scratch_dev & 15) return record_error(-5, "column_quantiles_valid: scratch must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const int R = 2 * nq;
+    const long cells = (long)d * R;
+    ColqProbs pv = {};
+    const int inl = nq <= CQ_INLINE;
+    if (inl) {
+        for (int i = 0; i < nq; ++i) pv.v[i] = q_host[i];
+    } else if (hipMemcpyAsync(l.q, q_host, nq * sizeof(double), hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+        return record_error(-3, "column_quantiles_valid: copy of q failed");
+    }
+    unsigned* m = l.nanflag;
+    const long init_blocks = (cells * 256 + 255) / 256;
+    hipLaunchKernelGGL(k_colqv_init, dim3((unsigned)(init_blocks < 2048 ? init_blocks : 2048)), dim3(256), 0, s, l.q, pv, inl, nq, d, m, l.hist);
+    const int tiles = (d + CQ_CT - 1) / CQ_CT;
+    long slices = (n + 4 * CQ_ROWS - 1) / (4 * CQ_ROWS);
+    const long cap = 1024 / tiles > 0 ? 1024 / tiles : 1;
+    if (slices > cap) slices = cap;
+    hipLaunchKernelGGL(k_colqv_count, dim3(tiles, (unsigned)slices), dim3(256), 0, s, a_dev, (long)n, d, (long)ld, m);
+    const long rank_blocks = (cells + 255) / 256;
+    hipLaunchKernelGGL(k_colqv_ranks, dim3((unsigned)(rank_blocks < 2048 ? rank_blocks : 2048)), dim3(256), 0, s, (const double*)l.q, pv, inl, nq,
+                       d, (const unsigned*)m, l.state);
+    colq_passes<true>(a_dev, (long)n, d, (long)ld, R, l.state, l.hist, (unsigned*)nullptr, l.ord, s);
+    const long outs = (long)nq * d;
+    hipLaunchKernelGGL(k_colqv_interp, dim3((unsigned)((outs + 255) / 256)), dim3(256), 0, s, (const float*)l.ord, (const double*)l.q,
+                       (const unsigned*)m, d, nq, out_dev, reinterpret_cast<long*>(count_dev));
+    return hipGetLastError() == hipSuccess ? 0 : record_error(-3, "column_quantiles_valid: kernel launch failed");
 }
 
 int mtadgat_eval_partq_long(void) { return PARTQ_LONG; }

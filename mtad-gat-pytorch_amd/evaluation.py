@@ -58,6 +58,17 @@ is the specification):
                                     from, and the same squares per output dimension: float32 differences, float64 sums, fixed order
   group_sums / group_losses         sums over consecutive loader batches of windows, and the reference's epoch losses from them
                                     (MTAD_GAT.series_losses runs the forward and these without the reconstructions leaving the library)
+Series with filled sensor gaps (csrc/mtadgat_evalmask.hip and the NaN-skipping instantiation of the column select in
+csrc/mtadgat_evalcol.hip; tests/test_gpu_score_mask.py; tests/score_mask_refs.py is the specification).  A score exists exactly where
+fitting.training_windows would have drawn a training window; NaN means "no score", +-inf is a value:
+  scored_rows                       which scores exist, from the ages the preparation reports: mtadgat_fit_windows and a marking
+                                    kernel, the count never leaving the device
+  anomaly_scores(age=, keep=)       the score arithmetic over observed target samples only, with the number of them per row
+  column_quantiles / scale_scores / np.nanpercentile from the exact select with per-column ranks, the exponentially weighted mean
+  moving_average / find_epsilon*    over scored rows as a two-component scan, fixed-order moments with counts: all with
+  (skip_nan=True)                   skip_nan=True; not together with parts=
+  predict_anomalies(mask=)          the above inside the one-call pipeline.  Not covered: masks in streams, per-part masked scoring,
+                                    SPOT and ranking curves on unscored rows
 The fit follows the paper, not the reference's vendored spot.py (its optimiser-based root search cannot be reproduced bit for
 bit): tests/spot_refs.py is the specification, csrc/mtadgat_spot.h spells it out.
 """
@@ -95,10 +106,53 @@ def _dev2d(t, name):
     return _native._rows2d(t, name, gpu_only=True)
 
 
-def anomaly_scores(preds, recons, values, window_size, target_dims=None, gamma=1.0):
-    """a_i[d] = |y_hat_i[d] - x_{i+W}[d]| + gamma |recon_i[d] - x_{i+W}[d]| and its mean over d
-    (prediction.py:72-91, before the optional per-dimension scaling).  Returns (global (n,), per_dim (n, d))."""
+def scored_rows(n_rows, window_size, n_features, age, max_age=0, min_observed=0.5, target_dims=None, lengths=None):
+    """Which scores of a gappy series exist: a uint8 (n_rows - W,) device tensor, 1 exactly where fitting.training_windows would have
+    drawn a training window.  Score i belongs to window start i and target row i + W; it exists iff
+      1. rows i .. i + W lie in one part (lengths: the parts' row counts; None: one part),
+      2. the target row i + W has an observed sample among the columns target_dims (None: all),
+      3. rows i .. i + W - 1 hold at least ceil(min_observed W F) observed samples over all columns.
+    age: int32 (n_rows, F) on the device as SeriesScaler.transform(..., return_age=True) returns it; a sample is observed iff
+    age <= max_age.  Arguments are checked as training_windows checks them.  Two device calls (mtadgat_fit_windows,
+    mtadgat_eval_mark_rows); the number of valid starts stays on the device: nothing is read back."""
+    import fitting
+    import preparation
     lib = _lib()
+    n_rows, W, F = int(n_rows), int(window_size), int(n_features)
+    min_count = fitting._min_count(min_observed, W, F)
+    if not isinstance(age, torch.Tensor) or age.device.type != "cuda":
+        raise RuntimeError("age must be an int32 tensor on the GPU (the window sampler is HIP only)")
+    device = age.device
+    if n_rows < W + 1:
+        raise ValueError("the series is shorter than a window and its target row")
+    dims = None
+    if target_dims is not None:
+        cols = [target_dims] if isinstance(target_dims, int) else [int(d) for d in target_dims]
+        dims = torch.tensor(_target_dims(cols, len(cols), F), dtype=torch.int32, device=device)
+    offsets = None
+    if lengths is not None:
+        offsets = torch.tensor(preparation._part_offsets(lengths, n_rows), dtype=torch.int64, device=device)
+    starts, count = _native.fit_windows(n_rows, W, F, device, age=age, max_age=max_age, dims=dims, offsets=offsets, min_count=min_count)
+    n = n_rows - W
+    keep = _native._empty((n,), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        rc = lib.mtadgat_eval_mark_rows(starts.data_ptr(), count.data_ptr(), n, keep.data_ptr(), _stream(device))
+    if rc != 0:
+        _fail(lib, rc, "eval_mark_rows")
+    return keep
+
+
+def anomaly_scores(preds, recons, values, window_size, target_dims=None, gamma=1.0, age=None, max_age=0, keep=None):
+    """a_i[d] = |y_hat_i[d] - x_{i+W}[d]| + gamma |recon_i[d] - x_{i+W}[d]| and its mean over d
+    (prediction.py:72-91, before the optional per-dimension scaling).  Returns (global (n,), per_dim (n, d)).
+    With age -- the whole series' (N, F) int32 ages of SeriesScaler.transform(..., return_age=True) -- a filled sample is not scored:
+    per_dim[i][d] is NaN where the target sample is unobserved (age > max_age) or keep[i] == 0 (keep: uint8 (n,) on the device as
+    scored_rows returns it, None: all rows kept), global is the mean over the row's remaining entries (NaN when there is none), and
+    the result is (global, per_dim, count) with count (n,) int32 their number.  With everything observed and kept global and per_dim
+    are the plain call's bit for bit."""
+    lib = _lib()
+    if age is None and keep is not None:
+        raise ValueError("keep needs age")
     n, d = preds.shape
     if values.ndim != 2 or values.shape[0] < window_size + n:
         raise ValueError(f"values must hold at least window_size + n = {window_size + n} rows (the series the {n} windows were cut "
@@ -119,11 +173,42 @@ def anomaly_scores(preds, recons, values, window_size, target_dims=None, gamma=1
     p, r = preds.float().contiguous(), recons.float().contiguous()
     per_dim = _native._empty((n, d), dtype=torch.float32, device=preds.device)
     glob = _native._empty((n,), dtype=torch.float32, device=preds.device)
+    if age is not None:
+        N, F = values.shape
+        _native._age_rows(age, N, F, preds.device)
+        rows = age[window_size:window_size + n]
+        if keep is not None and (not isinstance(keep, torch.Tensor) or keep.dtype != torch.uint8 or keep.device != preds.device
+                                 or keep.ndim != 1 or keep.numel() != n or not keep.is_contiguous()):
+            raise ValueError(f"keep must be a contiguous uint8 ({n},) tensor on {preds.device}")
+        count = _native._empty((n,), dtype=torch.int32, device=preds.device)
+        with torch.cuda.device(preds.device):
+            rc = lib.mtadgat_eval_scores_masked(p.data_ptr(), r.data_ptr(), actual.data_ptr(), n, d, actual.shape[1],
+                                                dims.data_ptr() if dims is not None else None, float(gamma), rows.data_ptr(),
+                                                age.stride(0) if N > 1 else F, int(max_age), _ptr(keep), per_dim.data_ptr(),
+                                                glob.data_ptr(), count.data_ptr(), _stream(preds))
+        if rc != 0:
+            _fail(lib, rc, "eval_scores_masked")
+        return glob, per_dim, count
     with torch.cuda.device(preds.device):
         _check(lib.mtadgat_eval_scores(p.data_ptr(), r.data_ptr(), actual.data_ptr(), n, d, actual.shape[1],
                                        dims.data_ptr() if dims is not None else None, float(gamma), per_dim.data_ptr(),
                                        glob.data_ptr(), _stream(preds)), "eval_scores")
     return glob, per_dim
+
+
+def row_means_valid(per_dim):
+    """The mean over the non-NaN entries of every row of an (n, d) float32 GPU tensor, added in column order in float32 and divided
+    by their number: (n,) float32, NaN for a row without one.  What anomaly_scores(age=) returns as its global score, for
+    per-dimension scores that were scaled after the mask was applied."""
+    lib = _lib()
+    a = _dev2d(per_dim, "per_dim")
+    n, d = a.shape
+    glob = _native._empty((n,), dtype=torch.float32, device=a.device)
+    with torch.cuda.device(a.device):
+        rc = lib.mtadgat_eval_row_means_valid(a.data_ptr(), n, d, a.stride(0), glob.data_ptr(), None, _stream(a))
+    if rc != 0:
+        _fail(lib, rc, "eval_row_means_valid")
+    return glob
 
 
 def _choose_epsilon(n, mean, sd, eps, tab, reg_level):
@@ -178,8 +263,11 @@ def _chosen_epsilons(counts, means, sds, eps, tab, reg_level):
             for p in range(len(eps))]
 
 
-def find_epsilon(errors, reg_level=1):
-    """Threshold of Hundman et al. as the reference computes it (eval_methods.py:189-236)."""
+def find_epsilon(errors, reg_level=1, skip_nan=False):
+    """Threshold of Hundman et al. as the reference computes it (eval_methods.py:189-236).
+    skip_nan: a NaN is a row without a score (find_epsilon_columns(skip_nan=True) of the one column)."""
+    if skip_nan:
+        return find_epsilon_columns(_dev1d(errors, torch.float32, "errors"), reg_level, skip_nan=True)[0]
     lib = _lib()
     e = _dev1d(errors, torch.float32, "errors")
     n = e.numel()
@@ -196,21 +284,44 @@ def find_epsilon(errors, reg_level=1):
     return float(e.max().item()) if best is None else best
 
 
-def find_epsilon_columns(errors, reg_level=1):
+def moments_valid(errors):
+    """Per column of an (n,) or (n, d) float32 GPU tensor the float64 sum, sum of squares and count of its non-NaN entries: a (d, 3)
+    float64 numpy array.  Added in a fixed order (mtadgat_eval_moments_valid): two calls give the same bits."""
+    lib = _lib()
+    e = _dev2d(errors, "errors")
+    n, d = e.shape
+    scratch = _scratch(lib.mtadgat_eval_moments_valid_scratch(n, d), e.device)
+    mom = np.empty((d, 3), dtype=np.float64)
+    with torch.cuda.device(e.device):
+        rc = lib.mtadgat_eval_moments_valid(e.data_ptr(), n, d, e.stride(0), scratch.data_ptr(), scratch.numel() * 8,
+                                            mom.ctypes.data_as(_c_double_p), _stream(e))
+    if rc != 0:
+        _fail(lib, rc, "eval_moments_valid")
+    return mom
+
+
+def find_epsilon_columns(errors, reg_level=1, skip_nan=False):
     """find_epsilon of every column of an (n, d) array (the per-feature thresholds of prediction.py:140-147): the moments
     and the z table of all columns in one launch each.  Returns a list of d floats; a column where no z qualifies gets its
-    maximum, as in find_epsilon."""
+    maximum, as in find_epsilon.
+    skip_nan: a NaN is a row without a score.  Mean, sd and the counts are those of the column's non-NaN entries (moments_valid);
+    in the z table a NaN row is neither pruned nor hot -- both comparisons are false -- but counts as dilated inside a hot row's
+    halo; the fallback is the maximum over the non-NaN entries; a column without one gets a NaN threshold, which flags nothing."""
     lib = _lib()
     e = _dev2d(errors, "errors")
     n, d = e.shape
     ld = e.stride(0)
     nz = len(_EPSILON_ZS)
     scratch = _native._empty(max(2 * d, 5 * d * nz), dtype=torch.float64, device=e.device)
-    mom = np.empty((d, 2), dtype=np.float64)
-    with torch.cuda.device(e.device):
-        _check(lib.mtadgat_eval_moments_columns(e.data_ptr(), n, d, ld, scratch.data_ptr(), mom.ctypes.data_as(_c_double_p), _stream(e)),
-               "eval_moments_columns")
-    counts = [n] * d
+    if skip_nan:
+        mom = moments_valid(e)
+        counts = [int(c) for c in mom[:, 2]]
+    else:
+        mom = np.empty((d, 2), dtype=np.float64)
+        with torch.cuda.device(e.device):
+            _check(lib.mtadgat_eval_moments_columns(e.data_ptr(), n, d, ld, scratch.data_ptr(), mom.ctypes.data_as(_c_double_p), _stream(e)),
+                   "eval_moments_columns")
+        counts = [n] * d
     means, sds, eps = _epsilon_thresholds(mom[:, 0], mom[:, 1], counts)
     tab = np.empty((d, 4 * nz), dtype=np.float64)
     with torch.cuda.device(e.device):
@@ -219,21 +330,36 @@ def find_epsilon_columns(errors, reg_level=1):
                "eval_epsilon_table_columns")
     out = _chosen_epsilons(counts, means, sds, eps, tab, reg_level)
     if None in out:
-        col_max = e.max(dim=0).values.cpu()
+        # (the valid maximum: the q = 1 order statistic of the non-NaN entries, NaN for a column without one)
+        col_max = (column_quantiles(e, [1.0], skip_nan=True)[0] if skip_nan else e.max(dim=0).values).cpu()
         out = [float(col_max[c]) if best is None else best for c, best in enumerate(out)]
     return out
 
 
-def column_quantiles(a, qs):
+def column_quantiles(a, qs, skip_nan=False, return_counts=False):
     """np.percentile(a, 100 * qs, axis=0) for an (n, d) float32 GPU tensor, (len(qs), d) float32 on the device: the "linear"
     definition, interpolated in float64 between the two exact order statistics and rounded once.  A column that holds a NaN
-    gives NaN, as in numpy.  A column slice of a wider tensor is read in place.  Bitwise reproducible."""
+    gives NaN, as in numpy.  A column slice of a wider tensor is read in place.  Bitwise reproducible.
+    skip_nan: np.nanpercentile -- the same definition over the m non-NaN entries of each column, NaN for m = 0; with return_counts
+    the result is (quantiles, m (d,) int64 on the device)."""
     lib = _lib()
     a = _dev2d(a, "a")
     n, d = a.shape
     q = np.ascontiguousarray(np.asarray(qs, dtype=np.float64).reshape(-1))
     if q.size < 1 or not np.all((q >= 0.0) & (q <= 1.0)):
         raise ValueError(f"quantile probabilities must lie in [0, 1], got {qs!r}")
+    if return_counts and not skip_nan:
+        raise ValueError("return_counts needs skip_nan")
+    if skip_nan:
+        scratch = _scratch(lib.mtadgat_eval_column_quantiles_valid_scratch(n, d, q.size), a.device)
+        out = _native._empty((q.size, d), dtype=torch.float32, device=a.device)
+        counts = _native._empty((d,), dtype=torch.int64, device=a.device)
+        with torch.cuda.device(a.device):
+            rc = lib.mtadgat_eval_column_quantiles_valid(a.data_ptr(), n, d, a.stride(0), q.ctypes.data_as(_c_double_p), q.size,
+                                                         scratch.data_ptr(), scratch.numel() * 8, out.data_ptr(), counts.data_ptr(), _stream(a))
+        if rc != 0:
+            _fail(lib, rc, "eval_column_quantiles_valid")
+        return (out, counts) if return_counts else out
     scratch = _scratch(lib.mtadgat_eval_column_quantiles_scratch(n, d, q.size), a.device)
     out = _native._empty((q.size, d), dtype=torch.float32, device=a.device)
     with torch.cuda.device(a.device):
@@ -268,13 +394,17 @@ def part_quantiles(a, qs, parts):
     return out
 
 
-def scale_scores(per_dim, parts=None):
+def scale_scores(per_dim, parts=None, skip_nan=False):
     """(a - median) / (1 + IQR) per column (prediction.py:84-88), quantiles from column_quantiles.
     With parts (a ScoreParts with parts.n == len(per_dim)) every part's rows are scaled by the part's own median and IQR
     (part_quantiles), in float32 with every operation rounded on its own: one noisy part no longer sets the scale of the others.
+    skip_nan: median and IQR are those of the column's non-NaN entries (column_quantiles(skip_nan=True)); NaN stays NaN.  Not
+    together with parts (ValueError): per-part masked scoring is not covered.
     Returns a new float32 tensor of the input's shape."""
+    if skip_nan and parts is not None:
+        raise ValueError("skip_nan together with parts= is not supported: per-part masked scoring is not covered")
     if parts is None:
-        q = column_quantiles(per_dim, [0.25, 0.5, 0.75])
+        q = column_quantiles(per_dim, [0.25, 0.5, 0.75], skip_nan=skip_nan)
         return (per_dim - q[1]) / (1.0 + (q[2] - q[0]))
     lib = _lib()
     one_d = isinstance(per_dim, torch.Tensor) and per_dim.ndim == 1
@@ -291,13 +421,18 @@ def scale_scores(per_dim, parts=None):
     return out.reshape(-1) if one_d else out
 
 
-def moving_average(scores, span, parts=None):
+def moving_average(scores, span, parts=None, skip_nan=False):
     """pandas.DataFrame(scores).ewm(span=span).mean() (prediction.py:99-103) of a 1-D GPU tensor: (n,) float32.
     Accumulated in float64 on the device, stored as float32; bitwise reproducible.
     With parts (a ScoreParts with parts.n == len(scores)) the average restarts at the first score of every part, so that no part is
-    smoothed into the next: ewm(span).mean() of every part's slice on its own.  The reference smooths across the seams."""
+    smoothed into the next: ewm(span).mean() of every part's slice on its own.  The reference smooths across the seams.
+    skip_nan: a NaN is a row without a score: it adds nothing to the weighted sum or to the weights, which both decay across it
+    (pandas' ewm(span, adjust=True, ignore_na=False).mean() at the scored rows), and stays NaN, where pandas repeats the previous
+    mean.  Not together with parts (ValueError)."""
     if not span >= 1:
         raise ValueError(f"span must be >= 1, got {span!r}")
+    if skip_nan and parts is not None:
+        raise ValueError("skip_nan together with parts= is not supported: per-part masked scoring is not covered")
     lib = _lib()
     x = _dev1d(scores, torch.float32, "scores")
     n = x.numel()
@@ -306,7 +441,7 @@ def moving_average(scores, span, parts=None):
     alpha = 2.0 / (float(span) + 1.0)
     out = _native._empty((n,), dtype=torch.float32, device=x.device)
     if parts is None:
-        what, spans = "eval_ewm", ()
+        what, spans = ("eval_ewm_valid" if skip_nan else "eval_ewm"), ()
     else:
         start, end, _ = _parts_on(parts, x, n)
         what, spans = "eval_ewm_parts", (start.data_ptr(), end.data_ptr(), parts.n_parts)
@@ -318,13 +453,14 @@ def moving_average(scores, span, parts=None):
     return out
 
 
-def feature_predictions(train_per_dim, test_per_dim, reg_level=1):
+def feature_predictions(train_per_dim, test_per_dim, reg_level=1, skip_nan=False):
     """Per-feature thresholds and predictions (prediction.py:140-154): eps_i = find_epsilon(train_per_dim[:, i]) and
     preds[:, i] = test_per_dim[:, i] >= eps_i.  The comparison is `>=`: the reference tree was not at hand to pin the
     operator, so this package fixes it -- a score equal to its threshold counts as anomalous.
+    skip_nan: the thresholds from find_epsilon_columns(skip_nan=True); a NaN score or a NaN threshold flags nothing.
     Returns (thresholds (d,) float64 on the host, preds (n_test, d) uint8 on the device)."""
     test = _dev2d(test_per_dim, "test_per_dim")
-    thr = find_epsilon_columns(train_per_dim, reg_level)
+    thr = find_epsilon_columns(train_per_dim, reg_level, skip_nan=skip_nan)
     if test.shape[1] != len(thr):
         raise ValueError(f"train has {len(thr)} columns, test has {test.shape[1]}")
     # compared in float64 like a float32 array against Python floats in numpy
@@ -366,9 +502,10 @@ def _result(counts, threshold, **extra):
     return out
 
 
-def epsilon_eval(train_scores, test_scores, test_labels, reg_level=1):
-    """Threshold from the training scores (find_epsilon), point-adjusted metrics on the test scores (eval_methods.py:164-186)."""
-    eps = find_epsilon(train_scores, reg_level)
+def epsilon_eval(train_scores, test_scores, test_labels, reg_level=1, skip_nan=False):
+    """Threshold from the training scores (find_epsilon), point-adjusted metrics on the test scores (eval_methods.py:164-186).
+    skip_nan: find_epsilon(skip_nan=True); a test row without a score (NaN) is never above the threshold."""
+    eps = find_epsilon(train_scores, reg_level, skip_nan=skip_nan)
     if test_labels is None:
         return {"threshold": eps, "reg_level": reg_level}
     return _result(point_adjust_counts(test_scores, test_labels, [eps])[0], eps, reg_level=reg_level)
@@ -694,7 +831,7 @@ def pot_eval(init_scores, scores, labels, q=1e-3, level=0.98, dynamic=False, max
 
 
 def predict_anomalies(model, train, test, labels=None, target_dims=None, gamma=1.0, scale_scores=False, use_mov_av=False, reg_level=1,
-                      bf_search=None, events=None, pot=None, curves=None, parts=None, prepare=None):
+                      bf_search=None, events=None, pot=None, curves=None, parts=None, prepare=None, mask=None):
     """What Predictor.predict_anomalies (prediction.py:106-165) derives from a train and a test series, with every score array
     staying on the device.  train, test: device-resident (N, F) series; labels: the test labels for rows window_size.. (one
     per score) or None; bf_search: (start, end, step_num) for the best-F1 sweep, run when labels are given too.
@@ -732,9 +869,42 @@ def predict_anomalies(model, train, test, labels=None, target_dims=None, gamma=1
     prepare=dict(fill=, clip=, gaps=) (any subset; defaults "zero", False, "zero": the reference's normalize_data) takes train and
     test as RAW series: a preparation.SeriesScaler is fitted on train (fit_scaler(train, gaps)) and both series go through its
     transform(fill=, clip=) before anything else, a "hold" fill stopping at the seams of parts' train_lengths / test_lengths when
-    those are given; the result gains "scaler".  Without prepare nothing changes."""
+    those are given; the result gains "scaler".  Without prepare nothing changes.
+    mask=dict(max_age=, min_observed=) (any subset; defaults 0 and 0.5) keeps filled samples out of scores and thresholds.  It
+    needs prepare=: both transforms then run with return_age=True, train and test scores come from
+    model.anomaly_scores(..., age=, max_age=, min_observed=) -- a score exists exactly where a training window would have been drawn,
+    NaN elsewhere --, and every threshold is computed with skip_nan.  The result gains train_scored and test_scored, uint8 on the
+    device: 1 where the score exists.  mask without prepare, or together with parts, pot or curves, raises ValueError: per-part
+    masked scoring is not covered, and SPOT's and the ranking sort's treatment of unscored rows is not defined.  With events=: a NaN
+    is never flagged, so an unscored row ends a run unless merge_gap bridges it; and by run_statistics' rule a run that contains an
+    unscored row has a NaN mean_score."""
+    mask_opts = None
+    if mask is not None:
+        unknown = set(mask) - {"max_age", "min_observed"}
+        if unknown:
+            raise ValueError(f"mask takes max_age and min_observed, got {sorted(unknown)}")
+        if prepare is None:
+            raise ValueError("mask needs prepare=: the ages of the filled samples come from the preparation's transform")
+        for name, other in (("parts", parts), ("pot", pot), ("curves", curves)):
+            if other is not None:
+                raise ValueError(f"mask together with {name}= is not supported: " + (
+                    "per-part masked scoring is not covered" if name == "parts" else
+                    "SPOT's treatment of unscored rows is not defined" if name == "pot" else
+                    "the ranking curves' treatment of unscored rows is not defined"))
+        mask_opts = dict(max_age=0, min_observed=0.5)
+        mask_opts.update(mask)
     scaler = None
-    if prepare is not None:
+    if prepare is not None and mask_opts is not None:
+        import preparation
+        unknown = set(prepare) - {"fill", "clip", "gaps"}
+        if unknown:
+            raise ValueError(f"prepare takes fill, clip and gaps, got {sorted(unknown)}")
+        prep_opts = dict(fill="zero", clip=False, gaps="zero")
+        prep_opts.update(prepare)
+        scaler = preparation.fit_scaler(train, gaps=prep_opts["gaps"])
+        train, train_age = scaler.transform(train, fill=prep_opts["fill"], clip=prep_opts["clip"], return_age=True)
+        test, test_age = scaler.transform(test, fill=prep_opts["fill"], clip=prep_opts["clip"], return_age=True)
+    elif prepare is not None:
         import preparation
         unknown = set(prepare) - {"fill", "clip", "gaps"}
         if unknown:
@@ -759,7 +929,11 @@ def predict_anomalies(model, train, test, labels=None, target_dims=None, gamma=1
         if part_opts["thresholds"] not in ("global", "per_part"):
             raise ValueError(f"parts' thresholds must be 'global' or 'per_part', got {part_opts['thresholds']!r}")
     score_kw = dict(target_dims=target_dims, gamma=gamma, scale_scores=scale_scores, use_mov_av=use_mov_av)
-    if part_opts is None:
+    skip = mask_opts is not None
+    if skip:
+        train_scores, train_per_dim = model.anomaly_scores(train, age=train_age, **mask_opts, **score_kw)
+        test_scores, test_per_dim = model.anomaly_scores(test, age=test_age, **mask_opts, **score_kw)
+    elif part_opts is None:
         train_scores, train_per_dim = model.anomaly_scores(train, **score_kw)
         test_scores, test_per_dim = model.anomaly_scores(test, **score_kw)
     else:
@@ -773,15 +947,19 @@ def predict_anomalies(model, train, test, labels=None, target_dims=None, gamma=1
         test_scores, test_per_dim = model.anomaly_scores(test, parts=test_parts, normalize_parts=part_opts["normalize"], **score_kw)
     eps_result = bf_result = None
     if labels is not None:
-        eps_result = epsilon_eval(train_scores, test_scores, labels, reg_level)
+        eps_result = epsilon_eval(train_scores, test_scores, labels, reg_level, **({"skip_nan": True} if skip else {}))
         if bf_search is not None:
             start, end, step_num = bf_search
             bf_result = _sweep(test_scores, labels, start, end, step_num)
-    thr, preds = feature_predictions(train_per_dim, test_per_dim, reg_level)
+    thr, preds = feature_predictions(train_per_dim, test_per_dim, reg_level, **({"skip_nan": True} if skip else {}))
     out = {"epsilon_result": eps_result, "bf_result": bf_result, "feature_thresholds": thr, "train_scores": train_scores,
            "test_scores": test_scores, "test_per_dim": test_per_dim, "feature_preds": preds}
     if scaler is not None:
         out["scaler"] = scaler
+    if skip:
+        # (a score is NaN exactly where it does not exist: finite model outputs give finite scores at the rows that are kept)
+        out["train_scored"] = scored_rows(train.shape[0], model.window_size, train.shape[1], train_age, target_dims=target_dims, **mask_opts)
+        out["test_scored"] = scored_rows(test.shape[0], model.window_size, test.shape[1], test_age, target_dims=target_dims, **mask_opts)
     if part_opts is not None and part_opts["thresholds"] == "per_part":
         same = train_parts.n_parts == test_parts.n_parts
         part_thr = find_epsilon_parts(train_scores, train_parts, reg_level) if same else find_epsilon_parts(test_scores, test_parts, reg_level)
@@ -805,7 +983,7 @@ def predict_anomalies(model, train, test, labels=None, target_dims=None, gamma=1
         unknown = set(events) - {"merge_gap", "min_length", "top_k"}
         if unknown:
             raise ValueError(f"events takes merge_gap, min_length and top_k, got {sorted(unknown)}")
-        eps = eps_result["threshold"] if eps_result is not None else find_epsilon(train_scores, reg_level)
+        eps = eps_result["threshold"] if eps_result is not None else find_epsilon(train_scores, reg_level, **({"skip_nan": True} if skip else {}))
         out["events"] = anomaly_events(test_scores, eps, per_dim=test_per_dim, feature_thresholds=thr, labels=labels, **events)
     return out
 

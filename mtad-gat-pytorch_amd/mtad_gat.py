@@ -523,7 +523,7 @@ class MTAD_GAT(nn.Module):
         return p[:n], last[1:n + 1]
 
     def anomaly_scores(self, values, target_dims=None, gamma=1.0, scale_scores=False, use_mov_av=False, smoothing_span=None, parts=None,
-                       normalize_parts=True):
+                       normalize_parts=True, age=None, max_age=0, min_observed=0.5, lengths=None):
         """The per-timestamp anomaly score of `Predictor.get_score` (reference prediction.py:65-103) for a
         whole series (N, F), computed on the device from `score_series`:
             a_i[d] = |y_hat_i[d] - x_{i+W}[d]| + gamma * |recon_i[d] - x_{i+W}[d]|
@@ -543,7 +543,25 @@ class MTAD_GAT(nn.Module):
         its meaning -- the quantiles of the whole series -- with or without `parts`; "per_part" without `parts`, and any other
         string, raise ValueError.
         Returns (scores (N-W,), per-dimension scores (N-W, out_dim)), both on the device; the per-dimension
-        scores are never smoothed, as in the reference."""
+        scores are never smoothed, as in the reference.
+        `age` (GPU only) scores a series with filled gaps: the int32 (N, F) tensor SeriesScaler.transform(..., return_age=True)
+        returns with the series -- 0 for a real sample, k for the k-th consecutive filled row; a sample is observed iff
+        age <= max_age.  A score exists exactly where fitting.training_windows would have drawn a training window: score i
+        belongs to window start i and target row i + W, and exists iff
+          1. rows i .. i + W lie in one part (`lengths`: the parts' row counts, for a concatenated series, so that the windows over
+             a seam are unscored; None: one part),
+          2. the target row i + W has an observed sample among the columns target_dims (None: all),
+          3. rows i .. i + W - 1 hold at least ceil(min_observed W F) observed samples over all columns
+        (evaluation.scored_rows).  Everywhere else the score is NaN, and so is the per-dimension score of an unobserved target
+        sample: a held value is not scored as if it had been measured.  The steps are those above with the missing entries
+        left out: the masked score kernel (evaluation.anomaly_scores(age=, keep=)), scale_scores by the median and IQR of every
+        column's existing entries, the mean over the row's existing entries, the moving average over the scored rows
+        (evaluation.moving_average(skip_nan=True): an unscored row stays NaN).  `age` with `parts` or scale_scores="per_part", and
+        `lengths` without `age`, raise ValueError."""
+        if age is not None and (parts is not None or scale_scores == "per_part"):
+            raise ValueError("age together with parts= or scale_scores='per_part' is not supported: per-part masked scoring is not covered")
+        if lengths is not None and age is None:
+            raise ValueError("lengths needs age (without age, parts= describes a concatenated series)")
         if isinstance(scale_scores, str) and scale_scores != "per_part":
             raise ValueError(f"scale_scores must be False, True or 'per_part', got {scale_scores!r}")
         if isinstance(scale_scores, str) and parts is None:
@@ -554,6 +572,20 @@ class MTAD_GAT(nn.Module):
             if not span >= 1:
                 raise ValueError(f"the smoothing span must be >= 1, got {span!r}")
         preds, recons = self.score_series(values)
+        if age is not None:
+            import evaluation
+            if values.device.type != "cuda":
+                raise RuntimeError("anomaly_scores(age=) runs on the GPU only (the masked score kernels are HIP only)")
+            keep = evaluation.scored_rows(values.shape[0], self.window_size, values.shape[1], age, max_age=max_age,
+                                          min_observed=min_observed, target_dims=target_dims, lengths=lengths)
+            scores, a, _ = evaluation.anomaly_scores(preds, recons, values, self.window_size, target_dims=target_dims, gamma=gamma,
+                                                     age=age, max_age=max_age, keep=keep)
+            if scale_scores:
+                a = evaluation.scale_scores(a, skip_nan=True)
+                scores = evaluation.row_means_valid(a)
+            if use_mov_av:
+                scores = evaluation.moving_average(scores, span, skip_nan=True)
+            return scores, a
         actual = values[self.window_size:].float()
         if target_dims is not None:
             dims = [target_dims] if isinstance(target_dims, int) else list(target_dims)
