@@ -610,8 +610,9 @@ int mtadgat_eval_column_quantiles(const float* a_dev, int64_t n, int d, int64_t 
 size_t mtadgat_eval_ewm_scratch(int64_t n);
 int mtadgat_eval_ewm(const float* x_dev, int64_t n, double alpha, void* scratch_dev, size_t scratch_bytes, float* out_dev,
                      void* stream);
-/* ---- scores of a gappy series (csrc/mtadgat_evalmask.hip, the VALID select of csrc/mtadgat_evalcol.hip; evaluation.scored_rows,
- * anomaly_scores(age=), the skip_nan arguments) -- tests/score_mask_refs.py is the specification -------------------------------
+/* ---- scores of a gappy series (csrc/mtadgat_evalmask.hip; the VALID select and the VALID exponentially weighted scan of
+ * csrc/mtadgat_evalcol.hip; evaluation.scored_rows, anomaly_scores(age=), the skip_nan arguments) -- tests/score_mask_refs.py is
+ * the specification ------------------------------------------------------------------------------------------------------------
  * A score exists exactly where mtadgat_fit_windows (below) would have drawn a training window: score i belongs to window start i
  * and target row i + W.  NaN means "no score": the calls here write the canonical quiet NaN 0x7fc00000 and skip every NaN
  * they read, whatever its sign or payload; +-inf is a value, not a gap.  Conventions of the two calls above: no atomics on

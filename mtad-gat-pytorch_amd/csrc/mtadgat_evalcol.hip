@@ -18,8 +18,10 @@
 //       number n / PARTQ_LONG + 1 whatever the number of parts.
 //   k_ewm_chunk / _carry / _apply: pandas' ewm(span).mean() (adjust=True) as a blocked scan in float64: chunk-local scans, one wave
 //       that composes the chunk carries in chunk order, and a pass that applies carry and closed-form denominator.  No atomics.
-//       One template, instantiated for the whole array (mtadgat_eval_ewm) and restarted at every span of a concatenated series
-//       (mtadgat_eval_ewm_parts).
+//       One template, instantiated for the whole array (mtadgat_eval_ewm), restarted at every span of a concatenated series
+//       (mtadgat_eval_ewm_parts) and over the observed rows of a gappy series, on (N, D) pairs (mtadgat_eval_ewm_valid).
+#include <string>
+
 #include "../../include/mtadgat.h"      // the entry points' declarations
 #include "mtadgat_scan.h"
 
@@ -415,24 +417,50 @@ __global__ void k_eval_colq_interp(const float* __restrict__ ord, const double* 
 }
 
 // ---- exponentially weighted mean -------------------------------------------------------------------------------------------------
-// One scan, instantiated twice.  SEG: the mean restarts at the start of every span [start, end) (disjoint and ascending,
-// mtadgat_scan.h; a score outside every span is a span of its own and gives NaN): the scan carries (sum, "a span started inside")
-// pairs, so a part never sees its predecessor's sum -- nothing is subtracted.  !SEG: one span [0, n) -- no span arrays are read,
-// every flag is a compile-time false and F is never touched; the arithmetic, and so the bits, are those of SEG with that one span.
+// One scan, instantiated three times.
+// SEG: the mean restarts at the start of every span [start, end) (disjoint and ascending, mtadgat_scan.h; a score outside every span
+// is a span of its own and gives NaN): the scan carries (sum, "a span started inside") pairs, so a part never sees its predecessor's
+// sum -- nothing is subtracted.  !SEG: one span [0, n) -- no span arrays are read, every flag is a compile-time false and F is never
+// touched; the arithmetic, and so the bits, are those of SEG with that one span.
+// VALID: the mean over observed rows, a NaN input being an unobserved row.  The scan carries (N, D), N_t = (obs ? x_t : 0) + b N_{t-1},
+// D_t = (obs ? 1 : 0) + b D_{t-1}; the result is N_t / D_t at an observed row (D_t >= 1 there) and the canonical NaN elsewhere.
+// !VALID: the scan carries N alone and D_t is the closed form (1 - b^(t - s + 1)) / alpha; nothing of D is read, shuffled or stored.
+// Either way N goes through the same float64 operations in the same order, and D, where it is carried, through N's.
+// <false, false> is mtadgat_eval_ewm, <true, false> mtadgat_eval_ewm_parts, <false, true> mtadgat_eval_ewm_valid.  <true, true> has no
+// caller and is not instantiated: a span start resets N and D alike and a row outside every span stores NaN, so it takes one more
+// instantiation of launch_ewm and an entry point, nothing here.
 constexpr int EWM_L = 1024;      // elements per chunk: 256 threads x 4
 
-// this thread's four elements: the value, whether a span starts there and the start of its span (-1: outside every span)
-template <bool SEG>
+struct EwmSum {
+    double n, d;                 // d: VALID only
+};
+
+// the terms of one sample: x, and with VALID (x, 1) at an observed row and (0, 0) at a NaN
+template <bool VALID>
+__device__ __forceinline__ void ewm_terms(float f, double& v, double& o) {
+    if constexpr (VALID) {
+        const bool obs = f == f;
+        v = obs ? (double)f : 0.0;
+        o = obs ? 1.0 : 0.0;
+    } else {
+        v = (double)f;
+    }
+}
+
+// this thread's four elements: the terms of N and D, whether a span starts there and the start of its span (-1: outside every span);
+// an index beyond n is an unobserved row
+template <bool SEG, bool VALID>
 __device__ __forceinline__ void ewm_load(const float* __restrict__ x, long n, long base, const long* __restrict__ start,
-                                         const long* __restrict__ end, long count, double (&v)[4], bool (&rs)[4], long (&st)[4]) {
+                                         const long* __restrict__ end, long count, double (&v)[4], double (&o)[4], bool (&rs)[4],
+                                         long (&st)[4]) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const long i = base + j;
-        v[j] = 0.0; rs[j] = false; st[j] = 0;
+        v[j] = 0.0; o[j] = 0.0; rs[j] = false; st[j] = 0;
         if constexpr (!SEG) {
-            v[j] = i < n ? (double)x[i] : 0.0;
+            ewm_terms<VALID>(i < n ? x[i] : (VALID ? __builtin_nanf("") : 0.f), v[j], o[j]);
         } else if (i < n) {
-            v[j] = (double)x[i];
+            ewm_terms<VALID>(x[i], v[j], o[j]);
             long s = 0;
             const long p = span_find(start, end, count, i, s);
             rs[j] = p < 0 || i == s;
@@ -441,113 +469,156 @@ __device__ __forceinline__ void ewm_load(const float* __restrict__ x, long n, lo
     }
 }
 
-// N just before this thread's four elements for N_t = x_t + b N_{t-1}, N = 0 before a span start, started from `carry` before the
-// chunk.  Wave scan by shuffles (factor b^(4 off) at distance off) on (sum, flag) pairs -- a piece in which a span starts ignores
+// (N, D) just before this thread's four elements for N_t = x_t + b N_{t-1}, N = 0 before a span start, started from `carry` before
+// the chunk.  Wave scan by shuffles (factor b^(4 off) at distance off) on (sums, flag) -- a piece in which a span starts ignores
 // what precedes it -- then the four wave totals composed in order.  *any: a span starts somewhere in the chunk.
-// sm: 4 doubles, smf: 4 ints (SEG only).
-template <bool SEG>
-__device__ __forceinline__ double ewm_prefix(const double (&x)[4], const bool (&rs)[4], double b, double carry, double* sm, int* smf,
-                                             bool* any) {
+// sm: 4 doubles, 8 with VALID (N and D of a wave side by side); smf: 4 ints (SEG only).
+template <bool SEG, bool VALID>
+__device__ __forceinline__ EwmSum ewm_prefix(const double (&x)[4], const double (&o)[4], const bool (&rs)[4], double b, EwmSum carry,
+                                             double* sm, int* smf, bool* any) {
+    constexpr int NC = VALID ? 2 : 1;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double s = x[0];
+    double s = x[0], d = o[0];
     int fl = SEG && rs[0];
 #pragma unroll
     for (int j = 1; j < 4; ++j) {
         s = (SEG && rs[j] ? 0.0 : s) * b + x[j];
+        if constexpr (VALID) d = (SEG && rs[j] ? 0.0 : d) * b + o[j];
         fl |= SEG && rs[j];
     }
     double f = (b * b) * (b * b);
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
         const double t = __shfl_up(s, off);
+        const double td = VALID ? __shfl_up(d, off) : 0.0;
         const int tf = SEG ? __shfl_up(fl, off) : 0;
         if (lane >= off) {
             if (!fl) s = t * f + s;
+            if constexpr (VALID)
+                if (!fl) d = td * f + d;
             fl |= tf;
         }
         f *= f;
     }                                                   // f = b^256
     if (lane == 63) {
-        sm[wave] = s;
+        sm[NC * wave] = s;
+        if constexpr (VALID) sm[NC * wave + 1] = d;
         if constexpr (SEG) smf[wave] = fl;
     }
     double ex = __shfl_up(s, 1);
+    double exd = VALID ? __shfl_up(d, 1) : 0.0;
     int exf = SEG ? __shfl_up(fl, 1) : 0;
-    if (lane == 0) { ex = 0.0; exf = 0; }
+    if (lane == 0) { ex = 0.0; exd = 0.0; exf = 0; }
     __syncthreads();
-    double in = carry;
-    for (int w = 0; w < wave; ++w) in = (SEG && smf[w] ? 0.0 : in) * f + sm[w];
+    EwmSum in = carry;
+    for (int w = 0; w < wave; ++w) {
+        in.n = (SEG && smf[w] ? 0.0 : in.n) * f + sm[NC * w];
+        if constexpr (VALID) in.d = (SEG && smf[w] ? 0.0 : in.d) * f + sm[NC * w + 1];
+    }
     *any = SEG && (smf[0] | smf[1] | smf[2] | smf[3]) != 0;
-    return ex + (exf ? 0.0 : in) * pow(b, (double)(4 * lane));
+    EwmSum r;
+    r.n = ex + (exf ? 0.0 : in.n) * pow(b, (double)(4 * lane));
+    r.d = VALID ? exd + (exf ? 0.0 : in.d) * pow(b, (double)(4 * lane)) : 0.0;
+    return r;
 }
 
-// S[c] = N at the end of chunk c when nothing precedes it, F[c] = a span starts inside chunk c (SEG only)
-template <bool SEG>
+// S[c] = N at the end of chunk c when nothing precedes it -- with VALID S[2 c], S[2 c + 1] = (N, D) --, F[c] = a span starts inside
+// chunk c (SEG only)
+template <bool SEG, bool VALID>
 __global__ void __launch_bounds__(256) k_ewm_chunk(const float* __restrict__ x, long n, const long* __restrict__ start,
                                                     const long* __restrict__ end, long count, double b, double* __restrict__ S,
                                                     int* __restrict__ F) {
-    __shared__ double sm[4];
+    constexpr int NC = VALID ? 2 : 1;
+    __shared__ double sm[4 * NC];
     __shared__ int smf[4];
-    double v[4];
+    double v[4], o[4];
     bool rs[4], any;
     long st[4];
-    ewm_load<SEG>(x, n, (long)blockIdx.x * EWM_L + 4 * threadIdx.x, start, end, count, v, rs, st);
-    double s = ewm_prefix<SEG>(v, rs, b, 0.0, sm, smf, &any);
+    ewm_load<SEG, VALID>(x, n, (long)blockIdx.x * EWM_L + 4 * threadIdx.x, start, end, count, v, o, rs, st);
+    EwmSum s = ewm_prefix<SEG, VALID>(v, o, rs, b, EwmSum{0.0, 0.0}, sm, smf, &any);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) s = (rs[j] ? 0.0 : s) * b + v[j];
+    for (int j = 0; j < 4; ++j) {
+        s.n = (rs[j] ? 0.0 : s.n) * b + v[j];
+        if constexpr (VALID) s.d = (rs[j] ? 0.0 : s.d) * b + o[j];
+    }
     if (threadIdx.x == 255) {
-        S[blockIdx.x] = s;
+        S[NC * blockIdx.x] = s.n;
+        if constexpr (VALID) S[NC * blockIdx.x + 1] = s.d;
         if constexpr (SEG) F[blockIdx.x] = any ? 1 : 0;
     }
 }
 
-// carry[c] = N just before chunk c: carry[c] = (F[c-1] ? 0 : carry[c-1] b^L) + S[c-1], 64 chunks per step of one wave, in chunk order
-template <bool SEG>
+// carry[c] = N (with VALID (N, D), laid out as S) just before chunk c: carry[c] = (F[c-1] ? 0 : carry[c-1] b^L) + S[c-1], 64 chunks
+// per step of one wave, in chunk order
+template <bool SEG, bool VALID>
 __global__ void __launch_bounds__(64) k_ewm_carry(const double* __restrict__ S, const int* __restrict__ F, long nchunks, double fL,
                                                    double* __restrict__ carry) {
+    constexpr int NC = VALID ? 2 : 1;
     const int lane = threadIdx.x;
     const double fl = pow(fL, (double)lane);
-    double run = 0.0;
+    double run = 0.0, rund = 0.0;
     for (long base = 0; base < nchunks; base += 64) {
         const long i = base + lane;
-        double s = i < nchunks ? S[i] : 0.0;
+        double s = i < nchunks ? S[NC * i] : 0.0;
+        double d = VALID && i < nchunks ? S[NC * i + 1] : 0.0;
         int g = SEG && i < nchunks ? F[i] : 0;
         double f = fL;
 #pragma unroll
         for (int off = 1; off < 64; off <<= 1) {
             const double t = __shfl_up(s, off);
+            const double td = VALID ? __shfl_up(d, off) : 0.0;
             const int tg = SEG ? __shfl_up(g, off) : 0;
             if (lane >= off) {
                 if (!g) s = t * f + s;
+                if constexpr (VALID)
+                    if (!g) d = td * f + d;
                 g |= tg;
             }
             f *= f;
         }                                               // f = fL^64
         double ex = __shfl_up(s, 1);
+        double exd = VALID ? __shfl_up(d, 1) : 0.0;
         int exg = SEG ? __shfl_up(g, 1) : 0;
-        if (lane == 0) { ex = 0.0; exg = 0; }
-        if (i < nchunks) carry[i] = (exg ? 0.0 : run) * fl + ex;
-        run = (SEG && __shfl(g, 63) ? 0.0 : run) * f + __shfl(s, 63);
+        if (lane == 0) { ex = 0.0; exd = 0.0; exg = 0; }
+        if (i < nchunks) {
+            carry[NC * i] = (exg ? 0.0 : run) * fl + ex;
+            if constexpr (VALID) carry[NC * i + 1] = (exg ? 0.0 : rund) * fl + exd;
+        }
+        const bool reset = SEG && __shfl(g, 63);
+        run = (reset ? 0.0 : run) * f + __shfl(s, 63);
+        if constexpr (VALID) rund = (reset ? 0.0 : rund) * f + __shfl(d, 63);
     }
 }
 
-// y[t] = N_t / D_t, D_t = (1 - b^(t - s + 1)) / alpha with s the start of t's span; NaN outside every span.  y may be x.
-template <bool SEG>
+// y[t] = N_t / D_t, NaN outside every span.  !VALID: D_t = (1 - b^(t - s + 1)) / alpha with s the start of t's span.  VALID: the
+// scanned D_t, and the canonical NaN at an unobserved row.  y may be x: a thread reads its four elements before it writes them, and
+// no other thread touches them.
+template <bool SEG, bool VALID>
 __global__ void __launch_bounds__(256) k_ewm_apply(const float* x, long n, const long* __restrict__ start, const long* __restrict__ end,
                                                     long count, double b, double alpha, const double* __restrict__ carry, float* y) {
-    __shared__ double sm[4];
+    constexpr int NC = VALID ? 2 : 1;
+    __shared__ double sm[4 * NC];
     __shared__ int smf[4];
-    double v[4];
+    double v[4], o[4];
     bool rs[4], any;
     long st[4];
     const long base = (long)blockIdx.x * EWM_L + 4 * threadIdx.x;
-    ewm_load<SEG>(x, n, base, start, end, count, v, rs, st);
-    double s = ewm_prefix<SEG>(v, rs, b, carry[blockIdx.x], sm, smf, &any);
+    ewm_load<SEG, VALID>(x, n, base, start, end, count, v, o, rs, st);
+    EwmSum c;
+    c.n = carry[NC * blockIdx.x];
+    c.d = VALID ? carry[NC * blockIdx.x + 1] : 0.0;
+    EwmSum s = ewm_prefix<SEG, VALID>(v, o, rs, b, c, sm, smf, &any);
+    const float none = __builtin_bit_cast(float, 0x7fc00000u);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        s = (rs[j] ? 0.0 : s) * b + v[j];
-        if (base + j < n)
-            y[base + j] = st[j] < 0 ? __builtin_nanf("") : (float)(s / ((1.0 - pow(b, (double)(base + j - st[j] + 1))) / alpha));
+        s.n = (rs[j] ? 0.0 : s.n) * b + v[j];
+        if constexpr (VALID) s.d = (rs[j] ? 0.0 : s.d) * b + o[j];
+        if (base + j < n) {
+            if constexpr (VALID)
+                y[base + j] = st[j] >= 0 && o[j] != 0.0 ? (float)(s.n / s.d) : none;
+            else
+                y[base + j] = st[j] < 0 ? none : (float)(s.n / ((1.0 - pow(b, (double)(base + j - st[j] + 1))) / alpha));
+        }
     }
 }
 
@@ -611,32 +682,55 @@ PartqScratch partq_scratch(ScratchCarver& c, int64_t n, int64_t d, int64_t count
 
 constexpr int64_t N_MAX = 2147483647LL;
 
-// S and carry: one double per chunk each (mtadgat_eval_ewm: 16 bytes per chunk); the segmented scan adds one int per chunk
+// S and carry: per chunk one element each, its components side by side (mtadgat_eval_ewm: 16 bytes per chunk, mtadgat_eval_ewm_valid:
+// 32); the segmented scan adds one int per chunk
 struct EwmScratch {
     double *S, *carry;
     int* F;
     long nchunks;
 };
-EwmScratch ewm_scratch(ScratchCarver& c, int64_t n, bool seg) {
+EwmScratch ewm_scratch(ScratchCarver& c, int64_t n, bool seg, bool valid) {
     EwmScratch l;
     l.nchunks = (long)((n + EWM_L - 1) / EWM_L);
-    l.S = c.take<double>(l.nchunks);
-    l.carry = c.take<double>(l.nchunks);
+    const size_t doubles = (size_t)l.nchunks * (valid ? 2 : 1);
+    l.S = c.take<double>(doubles);
+    l.carry = c.take<double>(doubles);
     l.F = seg ? c.take<int>(l.nchunks) : nullptr;
     return l;
 }
 
 // chunk-local scans, one wave that composes the chunk carries, the pass that applies carry and denominator; false: a launch failed
-template <bool SEG>
+template <bool SEG, bool VALID>
 bool launch_ewm(const float* x, int64_t n, const long* st, const long* en, long count, double alpha, const EwmScratch& l, float* out,
                 hipStream_t s) {
     const double b = 1.0 - alpha;
-    hipLaunchKernelGGL(k_ewm_chunk<SEG>, dim3((unsigned)l.nchunks), dim3(256), 0, s, x, (long)n, st, en, count, b, l.S, l.F);
-    hipLaunchKernelGGL(k_ewm_carry<SEG>, dim3(1), dim3(64), 0, s, (const double*)l.S, (const int*)l.F, l.nchunks, pow(b, (double)EWM_L),
-                       l.carry);
-    hipLaunchKernelGGL(k_ewm_apply<SEG>, dim3((unsigned)l.nchunks), dim3(256), 0, s, x, (long)n, st, en, count, b, alpha,
+    hipLaunchKernelGGL((k_ewm_chunk<SEG, VALID>), dim3((unsigned)l.nchunks), dim3(256), 0, s, x, (long)n, st, en, count, b, l.S, l.F);
+    hipLaunchKernelGGL((k_ewm_carry<SEG, VALID>), dim3(1), dim3(64), 0, s, (const double*)l.S, (const int*)l.F, l.nchunks,
+                       pow(b, (double)EWM_L), l.carry);
+    hipLaunchKernelGGL((k_ewm_apply<SEG, VALID>), dim3((unsigned)l.nchunks), dim3(256), 0, s, x, (long)n, st, en, count, b, alpha,
                        (const double*)l.carry, out);
     return hipGetLastError() == hipSuccess;
+}
+
+// The checks, the carving and the launches of the three entry points, which differ in `who` (the prefix of the error texts and the
+// name of the scratch query) and in the spans: SEG takes start, end and count, the others pass none.
+int ewm_fail(int code, const char* who, const std::string& what) { return record_error(code, (std::string(who) + ": " + what).c_str()); }
+
+template <bool SEG, bool VALID>
+int run_ewm(const char* who, const float* x_dev, int64_t n, const int64_t* start_dev, const int64_t* end_dev, int64_t count, double alpha,
+            void* scratch_dev, size_t scratch_bytes, float* out_dev, void* stream) {
+    if (!x_dev || (SEG && (!start_dev || !end_dev)) || !scratch_dev || !out_dev) return ewm_fail(-1, who, "null pointer");
+    if (n < 1 || n > N_MAX) return ewm_fail(-1, who, "n must lie in [1, 2^31 - 1]");
+    if (SEG && (count < 1 || count > N_MAX)) return ewm_fail(-1, who, "count must lie in [1, 2^31 - 1]");
+    if (!(alpha > 0.0 && alpha <= 1.0)) return ewm_fail(-1, who, "alpha outside (0, 1]");
+    ScratchCarver carver(scratch_dev);
+    const EwmScratch l = ewm_scratch(carver, n, SEG, VALID);
+    if (scratch_bytes < carver.bytes()) return ewm_fail(-5, who, std::string("scratch too small (see mtadgat_eval_") + who + "_scratch)");
+    if ((uintptr_t)scratch_dev & 7) return ewm_fail(-5, who, "scratch must be 8-byte aligned");
+    const long *st = reinterpret_cast<const long*>(start_dev), *en = reinterpret_cast<const long*>(end_dev);
+    if (!launch_ewm<SEG, VALID>(x_dev, n, st, en, (long)count, alpha, l, out_dev, (hipStream_t)stream))
+        return ewm_fail(-3, who, "kernel launch failed");
+    return 0;
 }
 
 }  // namespace
@@ -798,39 +892,30 @@ int mtadgat_eval_part_quantiles(const float* a_dev, int64_t n, int d, int64_t ld
 
 size_t mtadgat_eval_ewm_scratch(int64_t n) {
     if (n < 1) return 0;
-    return scratch_bytes_of([&](ScratchCarver& c) { ewm_scratch(c, n, false); });
+    return scratch_bytes_of([&](ScratchCarver& c) { ewm_scratch(c, n, false, false); });
 }
 
 int mtadgat_eval_ewm(const float* x_dev, int64_t n, double alpha, void* scratch_dev, size_t scratch_bytes, float* out_dev, void* stream) {
-    if (!x_dev || !scratch_dev || !out_dev) return record_error(-1, "ewm: null pointer");
-    if (n < 1 || n > N_MAX) return record_error(-1, "ewm: n must lie in [1, 2^31 - 1]");
-    if (!(alpha > 0.0 && alpha <= 1.0)) return record_error(-1, "ewm: alpha outside (0, 1]");
-    ScratchCarver carver(scratch_dev);
-    const EwmScratch l = ewm_scratch(carver, n, false);
-    if (scratch_bytes < carver.bytes()) return record_error(-5, "ewm: scratch too small (see mtadgat_eval_ewm_scratch)");
-    if ((uintptr_t)scratch_dev & 7) return record_error(-5, "ewm: scratch must be 8-byte aligned");
-    if (!launch_ewm<false>(x_dev, n, nullptr, nullptr, 0, alpha, l, out_dev, (hipStream_t)stream)) return record_error(-3, "ewm: kernel launch failed");
-    return 0;
+    return run_ewm<false, false>("ewm", x_dev, n, nullptr, nullptr, 0, alpha, scratch_dev, scratch_bytes, out_dev, stream);
 }
 
 size_t mtadgat_eval_ewm_parts_scratch(int64_t n) {
     if (n < 1 || n > N_MAX) return 0;
-    return scratch_bytes_of([&](ScratchCarver& c) { ewm_scratch(c, n, true); });
+    return scratch_bytes_of([&](ScratchCarver& c) { ewm_scratch(c, n, true, false); });
 }
 
 int mtadgat_eval_ewm_parts(const float* x_dev, int64_t n, const int64_t* start_dev, const int64_t* end_dev, int64_t count, double alpha,
                            void* scratch_dev, size_t scratch_bytes, float* out_dev, void* stream) {
-    if (!x_dev || !start_dev || !end_dev || !scratch_dev || !out_dev) return record_error(-1, "ewm_parts: null pointer");
-    if (n < 1 || n > N_MAX) return record_error(-1, "ewm_parts: n must lie in [1, 2^31 - 1]");
-    if (count < 1 || count > N_MAX) return record_error(-1, "ewm_parts: count must lie in [1, 2^31 - 1]");
-    if (!(alpha > 0.0 && alpha <= 1.0)) return record_error(-1, "ewm_parts: alpha outside (0, 1]");
-    ScratchCarver carver(scratch_dev);
-    const EwmScratch l = ewm_scratch(carver, n, true);
-    if (scratch_bytes < carver.bytes()) return record_error(-5, "ewm_parts: scratch too small (see mtadgat_eval_ewm_parts_scratch)");
-    if ((uintptr_t)scratch_dev & 7) return record_error(-5, "ewm_parts: scratch must be 8-byte aligned");
-    const long *st = reinterpret_cast<const long*>(start_dev), *en = reinterpret_cast<const long*>(end_dev);
-    if (!launch_ewm<true>(x_dev, n, st, en, (long)count, alpha, l, out_dev, (hipStream_t)stream)) return record_error(-3, "ewm_parts: kernel launch failed");
-    return 0;
+    return run_ewm<true, false>("ewm_parts", x_dev, n, start_dev, end_dev, count, alpha, scratch_dev, scratch_bytes, out_dev, stream);
+}
+
+size_t mtadgat_eval_ewm_valid_scratch(int64_t n) {
+    if (n < 1 || n > N_MAX) return 0;
+    return scratch_bytes_of([&](ScratchCarver& c) { ewm_scratch(c, n, false, true); });
+}
+
+int mtadgat_eval_ewm_valid(const float* x_dev, int64_t n, double alpha, void* scratch_dev, size_t scratch_bytes, float* out_dev, void* stream) {
+    return run_ewm<false, true>("ewm_valid", x_dev, n, nullptr, nullptr, 0, alpha, scratch_dev, scratch_bytes, out_dev, stream);
 }
 
 }  // extern "C"

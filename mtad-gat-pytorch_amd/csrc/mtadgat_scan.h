@@ -1,6 +1,8 @@
-// Scan, rank, reduction and layout primitives of the evaluation kernels (mtadgat_eval.hip, mtadgat_evalcol.hip, mtadgat_events.hip,
-// mtadgat_curves.hip, mtadgat_parts.hip): what at least two of their kernels or entry points share.  Everything runs in a fixed
-// order -- no atomics -- so a result is a function of the input alone.
+// Scan, rank, reduction and layout primitives of the evaluation kernels (mtadgat_eval.hip, mtadgat_evalcol.hip, mtadgat_evalmask.hip,
+// mtadgat_events.hip, mtadgat_curves.hip, mtadgat_parts.hip): what at least two of their kernels or entry points share.  The
+// primitives here run in a fixed order -- no atomics -- so what they return is a function of the input alone.  Two callers do not
+// keep that up to their result: k_eval_moments and k_eval_epsilon (mtadgat_eval.hip) add their per-workgroup sums with float64
+// atomicAdd, in whatever order the workgroups finish (evaluation._choose_epsilon carries a 1e-9 margin for it).
 //
 //   blocked scan of counts: per-chunk totals (chunk_rank), one wave that turns the totals into the chunks' starting ranks in
 //       chunk order (k_scan_carry), and a pass that recomputes the predicate and places every item at start + rank inside the

@@ -8,8 +8,9 @@ two builds of the library.
             moving_average(skip_nan) / moving_average, span 1280, on the (n,) global score; find_epsilon_columns(skip_nan) /
             find_epsilon_columns (whose moments are moments_valid / mtadgat_eval_moments_columns); MTAD_GAT.anomaly_scores(age=,
             scale_scores=True, use_mov_av=True) / the same without age, on a (MODEL_ROWS x 38) series
-  --plain   only the plain calls, one line of medians as JSON: run once per process with the package of either build first on
-            sys.path (--package DIR), the two builds alternately, to see whether a plain call changed
+  --plain   only the plain calls, and moving_average(skip_nan) and moving_average(parts=) (PARTS equal parts) beside the plain moving
+            average, one line of medians as JSON: run once per process with the package of either build first on sys.path
+            (--package DIR), the two builds alternately, to see whether a call changed
 Usage: python profiles/score_mask_bench.py [--out FILE] [--cases N:D ...] [--plain] [--package DIR]"""
 import argparse
 import json
@@ -23,7 +24,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 
-WARMUP, RUNS, ROUNDS, MODEL_ROWS = 3, 10, 3, 1 << 16
+WARMUP, RUNS, ROUNDS, MODEL_ROWS, PARTS = 3, 10, 3, 1 << 16, 27
 
 
 def one_ms(fn):
@@ -94,9 +95,15 @@ def main():
         a = torch.from_numpy((rng.random((n, d), dtype=np.float32) * 3.0)).to(dev)
         glob = a[:, 0].contiguous()
         if args.plain:
+            gappy = torch.where(torch.from_numpy(rng.random(n) < 0.15).to(dev), torch.full_like(glob, float("nan")), glob)
+            lengths = np.full(PARTS, (n + W) // PARTS, dtype=np.int64)
+            lengths[0] += (n + W) % PARTS
+            parts = ev.score_parts(lengths, W, device=dev)
             res = compare(lambda: ev.column_quantiles(a, [0.25, 0.5, 0.75]), lambda: ev.moving_average(glob, 1280),
+                          lambda: ev.moving_average(gappy, 1280, skip_nan=True), lambda: ev.moving_average(glob, 1280, parts=parts),
                           lambda: ev.find_epsilon_columns(a))
-            for name, r in zip(("column_quantiles", "moving_average", "find_epsilon_columns"), res):
+            names = ("column_quantiles", "moving_average", "moving_average(skip_nan)", "moving_average(parts=)", "find_epsilon_columns")
+            for name, r in zip(names, res):
                 plain[f"{name} {n}x{d}"] = r[0]
             continue
         import fitting

@@ -28,7 +28,7 @@ from test_host_score_mask import planted
 
 pytestmark = pytest.mark.gpu
 
-CHUNK = 1024                 # CHUNK_L / EWMV_L of the scans
+CHUNK = 1024                 # CHUNK_L / EWM_L of the scans
 TRIP = 256 * 256             # rows of k_momv_blocks per trip of its grid
 W = 7
 

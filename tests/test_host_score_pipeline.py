@@ -110,6 +110,21 @@ def test_scratch_queries_grow_monotonically(lib):
         assert cq(65536, 38, a) < cq(65536, 38, b)
 
 
+def test_ewm_scratch_queries_are_the_documented_bytes(lib):
+    """With c = ceil(n / 1024) chunks: S and carry, a double per chunk each; the per-part scan adds an int per chunk, its region
+    rounded up to 8 bytes; the scan over observed rows carries two doubles where the plain one carries one."""
+    plain, parts, valid = lib.mtadgat_eval_ewm_scratch, lib.mtadgat_eval_ewm_parts_scratch, lib.mtadgat_eval_ewm_valid_scratch
+    for n in (1, 1024, 1025, 65536, 65537, (1 << 31) - 1):
+        c = (n + 1023) // 1024
+        assert plain(n) == 16 * c, n
+        assert parts(n) == 16 * c + (4 * c + 7) // 8 * 8, n
+        assert valid(n) == 32 * c, n
+    for n in (0, -1):
+        assert plain(n) == 0 and parts(n) == 0 and valid(n) == 0, n
+    assert parts(1 << 31) == 0 and valid(1 << 31) == 0
+    assert plain(1 << 31) == 16 * (1 << 21)           # the plain query alone leaves n > 2^31 - 1 to the call, which rejects it
+
+
 def test_reference_moving_average_equals_pandas():
     pd = pytest.importorskip("pandas")
     rng = np.random.default_rng(11)
